@@ -4,7 +4,11 @@
 Metric (BASELINE.json): Mrays/s (+ Msamples/s) on a ~1M-triangle Mitsuba-style
 scene at 1920x1080, on 1/2/4/8 MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the line
+(`value`, `ms_per_step` = milliseconds per timed step, `config`).  --full adds what the headline does not need:
+`roofline` (with its untimed traversal-statistics pass), `cpu_baseline` and config.other_workloads, described below.
 
 * One "step" = `--spp-per-step` (default 64) samples per pixel over the whole 1920x1080
   frame of the generated bathroom2 stand-in (gpuspectral_amd.scenes.interior,
@@ -18,7 +22,7 @@ scene at 1920x1080, on 1/2/4/8 MI355X.
 * Timed region: barrier + device sync on both sides, max over ranks.
 * Scene upload and BVH build are outside the timed region (reported separately).
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel, k_trace<ExtendIO> (closest-hit BVH traversal).
+Rank 0 prints ONE JSON line.  With --full, `roofline` describes the dominant kernel, k_trace<ExtendIO> (closest-hit BVH traversal).
 No dense contraction: MFMA unused; HBM at about a third of its peak.  `bound` / `achieved` / `peak` / `frac` name the LARGEST of the three
 datasheet fractions this kernel can run against, picked from the data (r06; r05 hard-coded VALU issue):
   valu_issue   wave64 VALU instructions per second (rocprofv3 SQ_INSTS_VALU of exactly the timed launches, from the committed PMC
@@ -165,6 +169,28 @@ def kernel_rates(c, ms, launches, coalesced_read_bytes):
     return r
 
 
+DUMP_FULL_MAX_PIXELS = 3_000_000  # --dump-outputs: a larger frame is written as a sample of ...
+DUMP_SAMPLE_PIXELS = 2_000_000  # ... this many pixels (16 B each + an 8-B index: 48 MB, under the 64 MB budget)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(frame, out_dir):
+    """--dump-outputs: what the timed path hands its caller after the last step, the HDR frame (height x width x RGBA), as
+    out_dir/frame.npy in float32 (1920 x 1080: 33 MB).  A frame of more than DUMP_FULL_MAX_PIXELS pixels is written as a
+    fixed, seeded sample of DUMP_SAMPLE_PIXELS of them in pixel order (frame_sample.npy, float32, n x 4) with their flat
+    pixel indices (frame_sample_ids.npy, float64).  -> the list of files written"""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    npix = frame.shape[0] * frame.shape[1]
+    if npix <= DUMP_FULL_MAX_PIXELS:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return ["frame.npy"]
+    ids = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(npix, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), frame.reshape(-1, 4)[ids])
+    np.save(os.path.join(out_dir, "frame_sample_ids.npy"), ids.astype(np.float64))
+    return ["frame_sample.npy", "frame_sample_ids.npy"]
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks of the job (default: WORLD_SIZE, or 1 without a launcher)")
@@ -175,10 +201,17 @@ def parse():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--tris", type=int, default=1_000_000)
     ap.add_argument("--scene", default="interior", choices=["interior", "materials", "caustics", "cornell"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip BASELINE's other configs after the timed region (N = 1)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: skip BASELINE's other configs after the timed region (N = 1)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the CPU baseline sample (--full)")
     ap.add_argument("--dump", default="", help="write the gathered frame as .npy (rank 0)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (rank 0): frame.npy = the HDR "
+                         "frame (height x width x RGBA, float32) the caller receives after the last step (a seeded sample "
+                         "of its pixels above 3 M pixels)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: `roofline` (an untimed traversal-statistics "
+                         "pass + the committed PMC files), `cpu_baseline` and config.other_workloads (N = 1)")
     ap.add_argument("--force-dist", action="store_true",
                     help="with one rank and no launcher: still create the process group and run the gather through it "
                          "(RCCL initialisation + torch / HIP-runtime coexistence smoke run on a one-GPU box)")
@@ -405,20 +438,23 @@ def _main():
     for _ in range(args.warmup):
         ctx.render(spp=S, first_timestamp=ts)
         ts += S
-    # untimed statistics pass: BVH node / triangle reads per extension ray (for the roofline)
+    # one untimed sample per pixel behind the warm-up.  With --full it is the statistics pass: BVH node / triangle reads per
+    # extension ray (for the roofline).  A plain run renders the same sample without statistics, so that the timed steps
+    # continue from the same timestamp and the frame is the same with and without --full
     ctx.reset_stats()
-    ctx.render(spp=1, first_timestamp=ts, collect_traversal_stats=1)
+    ctx.render(spp=1, first_timestamp=ts, collect_traversal_stats=1 if args.full else 0)
     ts += 1
-    st = ctx.stats()
-    nodes_per_ray = st["nodes_visited"] / max(1, st["stat_rays"])
-    tris_per_ray = st["tris_tested"] / max(1, st["stat_rays"])
-    # requests on the vector-memory path per ray ("lane loads": one lane's 16-B load = one request): a node record read from
-    # HBM / L2 is 4 of them, one read from the block's LDS copy of the top of the tree is none, a triangle packet 3, the
-    # ray's own record 2
-    lds_nodes_per_ray = st["nodes_from_lds"] / max(1, st["stat_rays"])
-    ext_lane_loads = 4.0 * (nodes_per_ray - lds_nodes_per_ray) + 3.0 * tris_per_ray + 2.0
-    sh_n = max(1, st["shadow_stat_rays"])
-    sh_lane_loads = 4.0 * (st["shadow_nodes_visited"] - st["shadow_nodes_from_lds"]) / sh_n + 3.0 * st["shadow_tris_tested"] / sh_n + 2.0 + st["shadow_stat_occluded"] / sh_n  # (+ the occluded ray's commit load)
+    if args.full:
+        st = ctx.stats()
+        nodes_per_ray = st["nodes_visited"] / max(1, st["stat_rays"])
+        tris_per_ray = st["tris_tested"] / max(1, st["stat_rays"])
+        # requests on the vector-memory path per ray ("lane loads": one lane's 16-B load = one request): a node record read from
+        # HBM / L2 is 4 of them, one read from the block's LDS copy of the top of the tree is none, a triangle packet 3, the
+        # ray's own record 2
+        lds_nodes_per_ray = st["nodes_from_lds"] / max(1, st["stat_rays"])
+        ext_lane_loads = 4.0 * (nodes_per_ray - lds_nodes_per_ray) + 3.0 * tris_per_ray + 2.0
+        sh_n = max(1, st["shadow_stat_rays"])
+        sh_lane_loads = 4.0 * (st["shadow_nodes_visited"] - st["shadow_nodes_from_lds"]) / sh_n + 3.0 * st["shadow_tris_tested"] / sh_n + 2.0 + st["shadow_stat_occluded"] / sh_n  # (+ the occluded ray's commit load)
     ctx.reset_stats()
 
     local_t = None
@@ -490,6 +526,8 @@ def _main():
         tot = local
     if rank == 0 and args.dump:
         np.save(args.dump, frame.cpu().numpy().reshape(H, W, 4) if frame is not None else host_frame)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(frame.cpu().numpy().reshape(H, W, 4) if frame is not None else host_frame, args.dump_outputs)
 
     if rank == 0:
         ext_rays, sh_rays, samples = tot[1], tot[2], tot[3]
@@ -498,16 +536,6 @@ def _main():
         # shoots the same camera ray for every sample of a pixel) are left out, the one trace of each camera ray is in
         traced_ext = ext_rays - memoised + memo_build
         rays = traced_ext + sh_rays
-        # ---- roofline of the dominant kernel (rank 0's launches): this run's HIP-event time, the committed counters
-        b_ray = 32.0 + 16.0 + 64.0 * nodes_per_ray + 48.0 * tris_per_ray  # ray + hit + node / triangle records
-        ext_ms = st["extend_kernel_ms"]
-        launches = max(1, st["extend_launches"])
-        # rays rank 0's closest-hit launches traced in the timed region (the one trace of each camera ray for the memo included)
-        ext_traced0 = st["extension_rays"] - st["memoised_rays"] + st["memo_build_rays"]
-        alg_bytes = ext_traced0 * b_ray
-        cfg_key = {"workload": scene_name, "triangles": int(st["num_triangles"]), "resolution": "%dx%d" % (W, H), "spp_per_step": S,
-                   "steps": args.steps, "warmup": args.warmup, "primary_memo": bool(st["memoised_rays"] > 0),
-                   "launch_shape": {"extension_rays": int(traced_ext), "shadow_rays": int(sh_rays)}}
         digest = g.pt.build_info()["digest"]
         # class tables + the digest of the render kernels' instruction streams, written next to the library by csrc/Makefile
         mixf = os.path.join(os.path.dirname(g.lib_path()), "valu_mix.json")
@@ -518,100 +546,112 @@ def _main():
                 vmix, kernel_digest = vm["kernels"], vm.get("kernel_digest")
         except (OSError, ValueError):
             pass
-        pmc, pmc_src = pmc_for_run(cfg_key, int(st["extend_launches"]), digest, kernel_digest) if world == 1 else (None, "N > 1: counters are a single-GPU measurement")
-        vertices = float(tot[8])
-        ext = kernel_rates((pmc or {}).get("k_trace_extend"), ext_ms, launches, 32.0 * ext_traced0)
-        # k_trace<ConnectIO> streams the 32-B shadow ray in (an occluded one loads 16 B more at its commit: a gather);
-        # k_shade streams the hit + the path record in (80 B per vertex)
-        con = kernel_rates((pmc or {}).get("k_trace_connect"), st["connect_kernel_ms"], launches, 32.0 * st["shadow_rays"])
-        shd = kernel_rates((pmc or {}).get("k_shade"), st["shade_kernel_ms"], launches, 80.0 * vertices)
-        # k_shade's compulsory queue traffic: hit + path record in, the survivor's record and the 48-B shadow record out
-        shade_bytes = 80.0 * vertices + 64.0 * max(0.0, st["extension_rays"] - samples) + 48.0 * st["shadow_rays"]
-        shd["queue_bytes_per_vertex"] = shade_bytes / max(1.0, vertices)
-        shd["queue_gbs"] = shade_bytes / (st["shade_kernel_ms"] * 1e-3) / 1e9 if st["shade_kernel_ms"] > 0 else None
-        shd["queue_frac_of_hbm_peak"] = shd["queue_gbs"] / HBM_PEAK_GBS if shd["queue_gbs"] else None
+        roof = None
+        if args.full:
+            # ---- roofline of the dominant kernel (rank 0's launches): this run's HIP-event time, the committed counters
+            b_ray = 32.0 + 16.0 + 64.0 * nodes_per_ray + 48.0 * tris_per_ray  # ray + hit + node / triangle records
+            ext_ms = st["extend_kernel_ms"]
+            launches = max(1, st["extend_launches"])
+            # rays rank 0's closest-hit launches traced in the timed region (the one trace of each camera ray for the memo included)
+            ext_traced0 = st["extension_rays"] - st["memoised_rays"] + st["memo_build_rays"]
+            alg_bytes = ext_traced0 * b_ray
+            cfg_key = {"workload": scene_name, "triangles": int(st["num_triangles"]), "resolution": "%dx%d" % (W, H), "spp_per_step": S,
+                       "steps": args.steps, "warmup": args.warmup, "primary_memo": bool(st["memoised_rays"] > 0),
+                       "launch_shape": {"extension_rays": int(traced_ext), "shadow_rays": int(sh_rays)}}
+            pmc, pmc_src = pmc_for_run(cfg_key, int(st["extend_launches"]), digest, kernel_digest) if world == 1 else (None, "N > 1: counters are a single-GPU measurement")
+            vertices = float(tot[8])
+            ext = kernel_rates((pmc or {}).get("k_trace_extend"), ext_ms, launches, 32.0 * ext_traced0)
+            # k_trace<ConnectIO> streams the 32-B shadow ray in (an occluded one loads 16 B more at its commit: a gather);
+            # k_shade streams the hit + the path record in (80 B per vertex)
+            con = kernel_rates((pmc or {}).get("k_trace_connect"), st["connect_kernel_ms"], launches, 32.0 * st["shadow_rays"])
+            shd = kernel_rates((pmc or {}).get("k_shade"), st["shade_kernel_ms"], launches, 80.0 * vertices)
+            # k_shade's compulsory queue traffic: hit + path record in, the survivor's record and the 48-B shadow record out
+            shade_bytes = 80.0 * vertices + 64.0 * max(0.0, st["extension_rays"] - samples) + 48.0 * st["shadow_rays"]
+            shd["queue_bytes_per_vertex"] = shade_bytes / max(1.0, vertices)
+            shd["queue_gbs"] = shade_bytes / (st["shade_kernel_ms"] * 1e-3) / 1e9 if st["shade_kernel_ms"] > 0 else None
+            shd["queue_frac_of_hbm_peak"] = shd["queue_gbs"] / HBM_PEAK_GBS if shd["queue_gbs"] else None
 
-        def ceilings(k, kname, lane_loads_per_ray, rays, ms):
-            """adds the request-path and class-weighted issue figures to a kernel_rates() dict"""
-            c = (pmc or {}).get(kname) or {}
-            k["lane_loads_per_ray"] = lane_loads_per_ray
-            k["lane_loads_g_s"] = lane_loads_per_ray * rays / (ms * 1e-3) / 1e9 if ms > 0 else None
-            k["l1_request_frac"] = k["lane_loads_g_s"] / L1_REQUEST_PEAK_G if k["lane_loads_g_s"] else None
-            tab = vmix.get(kname) or {}
-            cyc_static = tab.get("mean_issue_cycles")
-            # DYNAMIC class mix: the hardware's class counters of the same launches x the issue cost of each class
-            cyc, shares = None, None
-            if tab.get("classes") and c.get("SQ_INSTS_VALU", 0) > 0 and "SQ_INSTS_VALU_FMA_F32" in c:
-                from scripts import valu_mix as _vm
+            def ceilings(k, kname, lane_loads_per_ray, rays, ms):
+                """adds the request-path and class-weighted issue figures to a kernel_rates() dict"""
+                c = (pmc or {}).get(kname) or {}
+                k["lane_loads_per_ray"] = lane_loads_per_ray
+                k["lane_loads_g_s"] = lane_loads_per_ray * rays / (ms * 1e-3) / 1e9 if ms > 0 else None
+                k["l1_request_frac"] = k["lane_loads_g_s"] / L1_REQUEST_PEAK_G if k["lane_loads_g_s"] else None
+                tab = vmix.get(kname) or {}
+                cyc_static = tab.get("mean_issue_cycles")
+                # DYNAMIC class mix: the hardware's class counters of the same launches x the issue cost of each class
+                cyc, shares = None, None
+                if tab.get("classes") and c.get("SQ_INSTS_VALU", 0) > 0 and "SQ_INSTS_VALU_FMA_F32" in c:
+                    from scripts import valu_mix as _vm
 
-                dyn = {cl: c.get("SQ_INSTS_VALU_" + cl, 0.0) for cl in _vm.HW_CLASSES[:-1]}
-                cyc, shares = _vm.dynamic_mean_cost(tab["classes"], dyn, c["SQ_INSTS_VALU"])
-            k["valu_mean_issue_cycles_static"] = cyc_static
-            k["valu_mean_issue_cycles"] = cyc
-            k["valu_class_shares"] = shares
-            k["issue_frac_weighted_static"] = k["valu_ginstr_s"] / (1024 * 2.4 / cyc_static) if (cyc_static and k["valu_ginstr_s"]) else None
-            k["valu_weighted_peak_ginstr_s"] = 1024 * 2.4 / cyc if cyc else None
-            k["issue_frac_weighted"] = k["valu_ginstr_s"] / k["valu_weighted_peak_ginstr_s"] if (cyc and k["valu_ginstr_s"]) else None
-            # ... and against the same ceiling at the clock the chip actually held (informational: `frac` stays on the nominal peak)
-            k["issue_frac_weighted_at_clock"] = (k["valu_ginstr_s"] / (1024 * k["shader_clock_ghz"] / cyc)
-                                                 if (cyc and k["valu_ginstr_s"] and k.get("shader_clock_ghz")) else None)
-            fr = {"valu_issue": k["issue_frac"], "l1_request": k["l1_request_frac"], "hbm": k["hbm_frac"]}
-            fr = {a_: b_ for a_, b_ in fr.items() if b_ is not None}
-            k["bound"] = max(fr, key=fr.get) if fr else None  # (of the three datasheet ceilings; the weighted figures are secondaries)
-            return k
+                    dyn = {cl: c.get("SQ_INSTS_VALU_" + cl, 0.0) for cl in _vm.HW_CLASSES[:-1]}
+                    cyc, shares = _vm.dynamic_mean_cost(tab["classes"], dyn, c["SQ_INSTS_VALU"])
+                k["valu_mean_issue_cycles_static"] = cyc_static
+                k["valu_mean_issue_cycles"] = cyc
+                k["valu_class_shares"] = shares
+                k["issue_frac_weighted_static"] = k["valu_ginstr_s"] / (1024 * 2.4 / cyc_static) if (cyc_static and k["valu_ginstr_s"]) else None
+                k["valu_weighted_peak_ginstr_s"] = 1024 * 2.4 / cyc if cyc else None
+                k["issue_frac_weighted"] = k["valu_ginstr_s"] / k["valu_weighted_peak_ginstr_s"] if (cyc and k["valu_ginstr_s"]) else None
+                # ... and against the same ceiling at the clock the chip actually held (informational: `frac` stays on the nominal peak)
+                k["issue_frac_weighted_at_clock"] = (k["valu_ginstr_s"] / (1024 * k["shader_clock_ghz"] / cyc)
+                                                     if (cyc and k["valu_ginstr_s"] and k.get("shader_clock_ghz")) else None)
+                fr = {"valu_issue": k["issue_frac"], "l1_request": k["l1_request_frac"], "hbm": k["hbm_frac"]}
+                fr = {a_: b_ for a_, b_ in fr.items() if b_ is not None}
+                k["bound"] = max(fr, key=fr.get) if fr else None  # (of the three datasheet ceilings; the weighted figures are secondaries)
+                return k
 
-        ceilings(ext, "k_trace_extend", ext_lane_loads, ext_traced0, ext_ms)
-        ceilings(con, "k_trace_connect", sh_lane_loads, st["shadow_rays"], st["connect_kernel_ms"])
-        ceilings(shd, "k_shade", 9.0, vertices, st["shade_kernel_ms"])  # 5 coalesced record quads + the 4 quads of the shading packet
-        survey_gbs = alg_bytes / (ext_ms * 1e-3) / 1e9 if ext_ms > 0 else None
-        roof = {
-            "kernel": "k_trace<ExtendIO> (closest-hit traversal of the wide BVH)",
-            # bound / achieved / peak / frac: the LARGEST of the three datasheet ceilings this kernel can run against (no MFMA
-            # by design), picked from the data -- VALU issue, the vector-memory request path, HBM; all three stay in `fractions`
-            "bound": None, "achieved": None, "peak": None, "unit": None, "frac": None,
-            "fractions": {"valu_issue": ext["issue_frac"], "valu_issue_weighted": ext["issue_frac_weighted"],
-                          "valu_issue_weighted_static": ext["issue_frac_weighted_static"],
-                          "valu_issue_weighted_at_clock": ext["issue_frac_weighted_at_clock"],
-                          "l1_request": ext["l1_request_frac"], "hbm": ext["hbm_frac"]},
-            "largest_datasheet_fraction": ext["bound"],
-            "shader_clock_ghz": ext["shader_clock_ghz"],
-            "valu_ginstr_s": ext["valu_ginstr_s"], "valu_peak_ginstr_s": VALU_PEAK_GINST,
-            "valu_weighted_peak_ginstr_s": ext["valu_weighted_peak_ginstr_s"], "valu_mean_issue_cycles": ext["valu_mean_issue_cycles"],
-            "valu_mean_issue_cycles_static": ext["valu_mean_issue_cycles_static"], "valu_class_shares": ext["valu_class_shares"],
-            "lane_loads_per_ray": ext_lane_loads, "lds_nodes_per_ray": lds_nodes_per_ray, "lane_loads_g_s": ext["lane_loads_g_s"],
-            "l1_request_peak_g_s": L1_REQUEST_PEAK_G,
-            "lanes_per_instr": ext["lanes_per_instr"],
-            # work-normalised: a build that issues MORE instructions per ray scores higher on `frac`; these do not
-            "effective": ext["effective"],
-            "valu_instr_per_ray": None, "valu_lane_instr_per_ray": None,
-            "wait_share": ext["wait_share"],
-            "traffic": ext["traffic"], "hbm_gbs": ext["hbm_gbs"], "hbm_frac": ext["hbm_frac"], "l2_hit_rate": ext["l2_hit_rate"],
-            # SURVEY 8(d)'s byte model: what the traversal ASKS of the memory hierarchy if every record came from HBM.  Not a
-            # bound (LDS serves half of the node visits, L2 most of the rest): above the HBM peak by construction
-            "survey_byte_model": {"bytes_per_ray": b_ray, "bytes_per_launch": alg_bytes / launches, "gbs_if_all_from_hbm": survey_gbs,
-                                  "note": "not a roofline: the top of the tree is read from LDS and L2"},
-            "traffic_over_survey_model": (ext["traffic"] / (alg_bytes / launches)) if (ext["traffic"] and alg_bytes > 0) else None,
-            "nodes_per_ray": nodes_per_ray, "tris_per_ray": tris_per_ray,
-            "launches": int(launches), "avg_launch_ms": ext_ms / launches,
-            "extend_ms": ext_ms, "shade_ms": st["shade_kernel_ms"], "connect_ms": st["connect_kernel_ms"],
-            "other_kernels": {"k_trace<ConnectIO>": con, "k_shade": shd},
-            # the counters were NOT measured in this run (they cannot be read in-process): they are the committed rocprofv3
-            # passes over the same command line and the same device code; the times they are divided by ARE this run's
-            "counters_from": ("committed PMC file " + pmc_src) if pmc else None,
-            "pmc": pmc_src,
-        }
-        rows = {"valu_issue": (ext["valu_ginstr_s"], VALU_PEAK_GINST, "G wave64 VALU instr/s", ext["issue_frac"]),
-                "l1_request": (ext["lane_loads_g_s"], L1_REQUEST_PEAK_G, "G 16-B lane loads/s", ext["l1_request_frac"]),
-                "hbm": (ext["hbm_gbs"], HBM_PEAK_GBS, "GB/s", ext["hbm_frac"])}
-        if ext["bound"] in rows:
-            roof["bound"] = ext["bound"]
-            roof["achieved"], roof["peak"], roof["unit"], roof["frac"] = rows[ext["bound"]]
-        if pmc and pmc.get("k_trace_extend") and ext_traced0 > 0:
-            c = pmc["k_trace_extend"]
-            if "SQ_INSTS_VALU" in c:
-                roof["valu_instr_per_ray"] = c["SQ_INSTS_VALU"] / ext_traced0
-            if "SQ_THREAD_CYCLES_VALU" in c:
-                roof["valu_lane_instr_per_ray"] = c["SQ_THREAD_CYCLES_VALU"] / ext_traced0
+            ceilings(ext, "k_trace_extend", ext_lane_loads, ext_traced0, ext_ms)
+            ceilings(con, "k_trace_connect", sh_lane_loads, st["shadow_rays"], st["connect_kernel_ms"])
+            ceilings(shd, "k_shade", 9.0, vertices, st["shade_kernel_ms"])  # 5 coalesced record quads + the 4 quads of the shading packet
+            survey_gbs = alg_bytes / (ext_ms * 1e-3) / 1e9 if ext_ms > 0 else None
+            roof = {
+                "kernel": "k_trace<ExtendIO> (closest-hit traversal of the wide BVH)",
+                # bound / achieved / peak / frac: the LARGEST of the three datasheet ceilings this kernel can run against (no MFMA
+                # by design), picked from the data -- VALU issue, the vector-memory request path, HBM; all three stay in `fractions`
+                "bound": None, "achieved": None, "peak": None, "unit": None, "frac": None,
+                "fractions": {"valu_issue": ext["issue_frac"], "valu_issue_weighted": ext["issue_frac_weighted"],
+                              "valu_issue_weighted_static": ext["issue_frac_weighted_static"],
+                              "valu_issue_weighted_at_clock": ext["issue_frac_weighted_at_clock"],
+                              "l1_request": ext["l1_request_frac"], "hbm": ext["hbm_frac"]},
+                "largest_datasheet_fraction": ext["bound"],
+                "shader_clock_ghz": ext["shader_clock_ghz"],
+                "valu_ginstr_s": ext["valu_ginstr_s"], "valu_peak_ginstr_s": VALU_PEAK_GINST,
+                "valu_weighted_peak_ginstr_s": ext["valu_weighted_peak_ginstr_s"], "valu_mean_issue_cycles": ext["valu_mean_issue_cycles"],
+                "valu_mean_issue_cycles_static": ext["valu_mean_issue_cycles_static"], "valu_class_shares": ext["valu_class_shares"],
+                "lane_loads_per_ray": ext_lane_loads, "lds_nodes_per_ray": lds_nodes_per_ray, "lane_loads_g_s": ext["lane_loads_g_s"],
+                "l1_request_peak_g_s": L1_REQUEST_PEAK_G,
+                "lanes_per_instr": ext["lanes_per_instr"],
+                # work-normalised: a build that issues MORE instructions per ray scores higher on `frac`; these do not
+                "effective": ext["effective"],
+                "valu_instr_per_ray": None, "valu_lane_instr_per_ray": None,
+                "wait_share": ext["wait_share"],
+                "traffic": ext["traffic"], "hbm_gbs": ext["hbm_gbs"], "hbm_frac": ext["hbm_frac"], "l2_hit_rate": ext["l2_hit_rate"],
+                # SURVEY 8(d)'s byte model: what the traversal ASKS of the memory hierarchy if every record came from HBM.  Not a
+                # bound (LDS serves half of the node visits, L2 most of the rest): above the HBM peak by construction
+                "survey_byte_model": {"bytes_per_ray": b_ray, "bytes_per_launch": alg_bytes / launches, "gbs_if_all_from_hbm": survey_gbs,
+                                      "note": "not a roofline: the top of the tree is read from LDS and L2"},
+                "traffic_over_survey_model": (ext["traffic"] / (alg_bytes / launches)) if (ext["traffic"] and alg_bytes > 0) else None,
+                "nodes_per_ray": nodes_per_ray, "tris_per_ray": tris_per_ray,
+                "launches": int(launches), "avg_launch_ms": ext_ms / launches,
+                "extend_ms": ext_ms, "shade_ms": st["shade_kernel_ms"], "connect_ms": st["connect_kernel_ms"],
+                "other_kernels": {"k_trace<ConnectIO>": con, "k_shade": shd},
+                # the counters were NOT measured in this run (they cannot be read in-process): they are the committed rocprofv3
+                # passes over the same command line and the same device code; the times they are divided by ARE this run's
+                "counters_from": ("committed PMC file " + pmc_src) if pmc else None,
+                "pmc": pmc_src,
+            }
+            rows = {"valu_issue": (ext["valu_ginstr_s"], VALU_PEAK_GINST, "G wave64 VALU instr/s", ext["issue_frac"]),
+                    "l1_request": (ext["lane_loads_g_s"], L1_REQUEST_PEAK_G, "G 16-B lane loads/s", ext["l1_request_frac"]),
+                    "hbm": (ext["hbm_gbs"], HBM_PEAK_GBS, "GB/s", ext["hbm_frac"])}
+            if ext["bound"] in rows:
+                roof["bound"] = ext["bound"]
+                roof["achieved"], roof["peak"], roof["unit"], roof["frac"] = rows[ext["bound"]]
+            if pmc and pmc.get("k_trace_extend") and ext_traced0 > 0:
+                c = pmc["k_trace_extend"]
+                if "SQ_INSTS_VALU" in c:
+                    roof["valu_instr_per_ray"] = c["SQ_INSTS_VALU"] / ext_traced0
+                if "SQ_THREAD_CYCLES_VALU" in c:
+                    roof["valu_lane_instr_per_ray"] = c["SQ_THREAD_CYCLES_VALU"] / ext_traced0
         out = {
             "metric": "Mrays/s (traced rays: extension + shadow; memoised camera segments excluded), ~1M-tri Mitsuba-style scene at 1080p",
             "value": rays / elapsed / 1e6,
@@ -653,12 +693,13 @@ def _main():
                               "kernel_ms": float(v[4]), "launches": int(v[5]), "device_bytes": int(v[6]),
                               "render_call_s": float(v[7]), "scene_upload_s": float(v[8]), "gather_s": float(v[9])} for r, v in enumerate(per_rank)],
             },
-            "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if roof is not None:  # (--full)
+            out["roofline"] = roof
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sc, args, scene_name)
         ctx.close()  # (the other workloads size their own path pools from free memory)
-        if world == 1 and not args.no_other_workloads:
+        if args.full and world == 1 and not args.no_other_workloads:
             # after the timed region, outside `value`: BASELINE's configs 2, 3 and 5 (rank-0 share), ~1 s of rendering each
             out["config"]["other_workloads"] = other_workloads(g)
         print(json.dumps(out), flush=True)

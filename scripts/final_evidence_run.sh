@@ -12,8 +12,8 @@ bash scripts/pmc_bench.sh ${TAG}_s20_w5 --steps 20 --warmup 5 > $O/pmc_s20_w5.lo
 cp gpurun_out/pmc_${TAG}_s4_w1/pmc_bench.json profiles/pmc_bench_s4_w1.json
 cp gpurun_out/pmc_${TAG}_s20_w5/pmc_bench.json profiles/pmc_bench_s20_w5.json
 cp profiles/pmc_bench_s4_w1.json profiles/pmc_bench_s20_w5.json $O/
-timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_s20_w5.json 2> $O/bench_n1_s20_w5.err
+timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_s20_w5.json 2> $O/bench_n1_s20_w5.err
 cp gpurun_out/pmc_${TAG}_s4_w1/summary.txt $O/pmc_summary_s4_w1.txt
 cp gpurun_out/pmc_${TAG}_s20_w5/summary.txt $O/pmc_summary_s20_w5.txt
 cp gpurun_out/pmc_${TAG}_s4_w1/valu_mix_dynamic.json $O/valu_mix_s4_w1.json      # dynamic VALU class mix of the timed launches

@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 100 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/p -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline $* > $OUT/p.log 2>&1
+timeout -s KILL 100 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/p -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline $* > $OUT/p.log 2>&1
 echo "rc=$?"
 python3 - <<PY
 import csv,glob,collections

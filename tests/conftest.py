@@ -86,6 +86,19 @@ def coffee_xml(tmp_path_factory):
 
 
 @pytest.fixture(scope="session")
+def living_room_xml(tmp_path_factory):
+    """The reference's 'The Modern Living Room' scene (scene.xml, its OBJ meshes and textures, CC-BY), unpacked from the
+    three committed archives (each under 1 MiB) into one tree."""
+    import tarfile
+
+    d = tmp_path_factory.mktemp("ref_living_room")
+    for part in (1, 2, 3):
+        with tarfile.open(os.path.join(GOLDEN, "ref_scenes", "living-room_%d.tar.xz" % part)) as t:
+            t.extractall(str(d))
+    return os.path.join(str(d), "living-room", "scene.xml")
+
+
+@pytest.fixture(scope="session")
 def materials_scene():
     from gpuspectral_amd import scenes
 

@@ -4,6 +4,7 @@
 #include "Loader.h"
 #include "Scene.h"
 #include <cstdio>
+#include <filesystem>
 #include <fstream>
 #include <iterator>
 #include <vector>
@@ -63,9 +64,11 @@ int main(int argc, char** argv) {
                        "<scene><sensor><transform name='toWorld'><matrix value='1 2 3'/></transform></sensor></scene>",
                        "<scene><shape type='rectangle'><emitter type='area'><rgb name='radiance' value='x'/></emitter></shape></scene>",
                        "<<<>>>", "<scene><bsdf type='twosided'><bsdf type='twosided'></bsdf></bsdf></scene>"};
+  // (the files go to the working directory the test gives this program)
+  const std::string cwd = std::filesystem::current_path().string();
   int i = 0;
   for (const char* txt : bad) {
-    std::string p = "/tmp/bad_" + std::to_string(i++) + ".xml";
+    std::string p = cwd + "/bad_" + std::to_string(i++) + ".xml";
     std::ofstream(p) << txt;
     try {
       Scene s = loadScene(p, R);
@@ -75,9 +78,9 @@ int main(int argc, char** argv) {
     }
   }
   // malformed OBJ
-  std::ofstream("/tmp/bad.obj") << "v 1 2\nv a b c\nf 1 2 3\nf 1/2/3 9999 -7\nvn\nf\n";
-  std::ofstream("/tmp/bad_obj.xml") << "<scene><shape type='obj'><string name='filename' value='/tmp/bad.obj'/></shape></scene>";
-  try { Scene s = loadScene("/tmp/bad_obj.xml", R); printf("bad obj loaded: %zu objects\n", s.renderObjects.size()); }
+  std::ofstream(cwd + "/bad.obj") << "v 1 2\nv a b c\nf 1 2 3\nf 1/2/3 9999 -7\nvn\nf\n";
+  std::ofstream(cwd + "/bad_obj.xml") << "<scene><shape type='obj'><string name='filename' value='" << cwd << "/bad.obj'/></shape></scene>";
+  try { Scene s = loadScene(cwd + "/bad_obj.xml", R); printf("bad obj loaded: %zu objects\n", s.renderObjects.size()); }
   catch (const std::exception& e) { printf("bad obj: error ok: %.70s\n", e.what()); }
   puts("loader asan ok");
 }

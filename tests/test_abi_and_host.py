@@ -401,9 +401,6 @@ def test_write_pfm_roundtrip(tmp_path):
     assert np.array_equal(data, img[:, :, :3])
 
 
-REF_SCENES = "/root/reference/src/GPUSpectral/assets/scenes"
-
-
 def _check_reference_scene(xml, name):
     from gpuspectral_amd import host
     from oracle import mitsuba_loader as ml
@@ -432,13 +429,15 @@ def test_cpp_loader_on_staircase2(staircase2_xml):
 
 
 @pytest.mark.parametrize("name", ["coffee", "living-room"])
-def test_cpp_loader_on_reference_scenes(name):
-    """The larger shipped scenes (`conductor material=none`, disk/sphere/hair shapes, missing OBJ blobs), where the
-    reference tree is mounted (build container only; staircase2 above runs everywhere)."""
-    xml = os.path.join(REF_SCENES, name, "scene.xml")
-    if not os.path.exists(xml):
-        pytest.skip("reference tree not available")
-    _check_reference_scene(xml, name)
+def test_cpp_loader_on_reference_scenes(name, request):
+    """The larger shipped scenes (`conductor material=none`, disk/sphere/hair shapes, missing OBJ blobs), from their
+    committed archives: the C++ loader, the numpy restatement and the arrays the GPU tests use agree."""
+    from gpuspectral_amd import abi
+
+    xml = request.getfixturevalue({"coffee": "coffee_xml", "living-room": "living_room_xml"}[name])
+    a = _check_reference_scene(xml, name)
+    cached = abi.SceneArrays.load(os.path.join(os.path.dirname(os.path.dirname(CORNELL_XML)), "ref_scenes", name + ".npz"))
+    same_scene(a, cached)
 
 
 def test_builtin_disk_and_sphere_meshes():
@@ -498,15 +497,13 @@ def test_cpp_loader_builtin_shapes_on_staircase2(staircase2_xml):
     assert d.arrays().num_triangles == 30927 and sum("disk.obj" in w for w in d.warnings) == 5
 
 
-def test_cpp_loader_builtin_shapes_on_living_room():
+def test_cpp_loader_builtin_shapes_on_living_room(living_room_xml):
     """'The Modern Living Room' with its sphere light BUILT (radius 0.164 about `center`): 512 triangles and lights more;
-    C++ loader == numpy restatement == the GPU tests' fixture.  Needs the reference tree (build container)."""
+    C++ loader == numpy restatement == the GPU tests' fixture."""
     from gpuspectral_amd import abi, host
     from oracle import mitsuba_loader as ml
 
-    xml = os.path.join(REF_SCENES, "living-room", "scene.xml")
-    if not os.path.exists(xml):
-        pytest.skip("reference tree not available")
+    xml = living_room_xml
     s = host.Scene(xml, builtin_shapes=True)
     a, b = s.arrays(), ml.load_scene(xml, builtin_shapes=True)
     same_scene(a, b)

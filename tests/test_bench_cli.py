@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -121,6 +122,40 @@ def test_gpus_defaults_to_world_size(monkeypatch, capsys):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     args = b.parse()
     assert args.gpus is None
+
+
+def test_plain_run_is_lean_by_default(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline only: the roofline, the CPU baseline and the
+    other workloads need --full; --dump-outputs names the directory the timed path's outputs go to."""
+    b = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = b.parse()
+    assert args.full is False and args.dump_outputs == "" and (args.steps, args.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = b.parse()
+    assert args.full is True and args.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_frame_or_a_seeded_sample(tmp_path):
+    """--dump-outputs: a frame of up to 3 M pixels is written whole (float32); a larger one as the same seeded sample of 2 M
+    pixels on every run, in pixel order, with float64 pixel indices -- under 64 MB in all."""
+    b = _load_bench()
+    small = np.random.RandomState(1).rand(240, 416, 4).astype(np.float32)
+    assert b.dump_outputs(small.astype(np.float64), str(tmp_path / "s")) == ["frame.npy"]
+    got = np.load(str(tmp_path / "s" / "frame.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    W, H = 2048, 1600  # 3.3 M pixels
+    big = np.arange(W * H * 4, dtype=np.float32).reshape(H, W, 4)
+    for run in ("a", "b"):
+        d = tmp_path / run
+        assert b.dump_outputs(big, str(d)) == ["frame_sample.npy", "frame_sample_ids.npy"]
+        assert sum(f.stat().st_size for f in d.iterdir()) < 64e6
+    ids, ids_b = np.load(str(tmp_path / "a" / "frame_sample_ids.npy")), np.load(str(tmp_path / "b" / "frame_sample_ids.npy"))
+    px, px_b = np.load(str(tmp_path / "a" / "frame_sample.npy")), np.load(str(tmp_path / "b" / "frame_sample.npy"))
+    assert ids.dtype == np.float64 and px.dtype == np.float32 and px.shape == (2_000_000, 4)
+    assert np.array_equal(ids, ids_b) and np.array_equal(px, px_b)
+    assert (np.diff(ids) > 0).all() and ids[0] >= 0 and ids[-1] < W * H
+    assert np.array_equal(px, big.reshape(-1, 4)[ids.astype(np.int64)])
 
 
 def test_nccl_ranks_beyond_the_visible_gpus_are_refused(monkeypatch, capsys):

@@ -157,7 +157,7 @@ def test_bench_one_rank_through_nccl(tmp_path):
     execution of this path is not the 8-GPU scaling run.  Frame and ray counts equal the plain single-rank run's."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     common = ["--steps", "1", "--warmup", "1", "--spp-per-step", "4", "--tris", "60000", "--width", "416", "--height", "240",
-              "--no-cpu-baseline"]
+              "--no-cpu-baseline", "--full"]
     f1, f2 = str(tmp_path / "plain.npy"), str(tmp_path / "nccl.npy")
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump", f1] + common, env=env,
                         capture_output=True, text=True, timeout=600)
@@ -177,6 +177,37 @@ def test_bench_one_rank_through_nccl(tmp_path):
     assert j1["config"]["extension_rays"] == j2["config"]["extension_rays"] and j1["config"]["shadow_rays"] == j2["config"]["shadow_rays"]
     a, b = np.load(f1), np.load(f2)
     assert a.shape == (240, 416, 4) and np.array_equal(a.reshape(-1, 4), b.reshape(-1, 4))
+
+
+def test_bench_plain_run_and_full_run_compute_the_same_frame(tmp_path):
+    """A plain bench run times the steps and prints the headline line only; --full adds `roofline`, `cpu_baseline` and
+    config.other_workloads behind the same timed steps.  Both compute the same frame, and --dump-outputs writes it."""
+    common = ["--steps", "2", "--warmup", "1", "--spp-per-step", "4", "--tris", "60000", "--width", "416", "--height", "240"]
+    runs = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-other-workloads"])):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(d),
+                            "--dump", str(tmp_path / (name + ".npy"))] + common + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        runs[name] = (json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]), np.load(str(d / "frame.npy")))
+        assert sorted(os.listdir(str(d))) == ["frame.npy"]
+        assert np.array_equal(runs[name][1], np.load(str(tmp_path / (name + ".npy"))))
+    (jp, fp), (jf, ff) = runs["plain"], runs["full"]
+    assert "roofline" not in jp and "cpu_baseline" not in jp and "other_workloads" not in jp["config"]
+    assert jf["roofline"]["launches"] > 0 and "cpu_baseline" not in jf
+    for j in (jp, jf):
+        assert j["steps"] == 2 and j["warmup"] == 1 and j["unit"] == "Mrays/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert j["value"] > 0 and j["ms_per_step"] > 0 and j["config"]["spp_timed"] == 8
+    assert jp["config"]["extension_rays"] == jf["config"]["extension_rays"] and jp["config"]["shadow_rays"] == jf["config"]["shadow_rays"]
+    assert fp.dtype == np.float32 and fp.shape == (240, 416, 4) and np.isfinite(fp).all() and fp[..., :3].max() > 0
+    assert np.array_equal(fp, ff)
+    # ... and it is the frame of one 13-spp render from timestamp 0 (warm-up 4 + the untimed sample + 2 x 4 timed), bit for
+    # bit the CPU oracle's: the timed steps continue the sample sequence exactly as before the plain run became lean
+    from gpuspectral_amd import scenes
+    from oracle import oracle as orc
+
+    ref, _ = orc.Oracle(scenes.interior(60000, seed=7)).render(416, 240, spp=13, threads=orc.usable_cpus())
+    assert np.array_equal(fp.reshape(-1, 4), ref.reshape(-1, 4)), int((fp.reshape(-1, 4) != ref.reshape(-1, 4)).any(axis=1).sum())
 
 
 def _read_pfm(path):

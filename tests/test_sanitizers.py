@@ -6,20 +6,16 @@ import pytest
 
 from conftest import CORNELL_XML, ROOT
 
-REF_ASSETS = "/root/reference/src/GPUSpectral/assets"
 
-
-def test_cpp_loader_under_asan_ubsan(tmp_path, staircase2_xml):
+def test_cpp_loader_under_asan_ubsan(tmp_path, staircase2_xml, coffee_xml, living_room_xml):
     host = os.path.join(ROOT, "gpuspectral_amd", "host")
     exe = str(tmp_path / "asan_loader")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-I", host, "-o", exe,
                            os.path.join(ROOT, "tests", "emu", "asan_loader.cpp"), os.path.join(host, "Loader.cpp"),
                            os.path.join(host, "Image.cpp")])
-    scenes = [CORNELL_XML, staircase2_xml]
+    # the reference's scenes from the committed fixtures, the same on every machine
+    scenes = [CORNELL_XML, staircase2_xml, coffee_xml, living_room_xml]
     assets = os.path.dirname(os.path.dirname(CORNELL_XML))
-    if os.path.isdir(REF_ASSETS):  # the reference's large scenes, where the tree is mounted
-        assets = REF_ASSETS
-        scenes = [os.path.join(REF_ASSETS, "scenes", n, "scene.xml") for n in ("cornell-box", "coffee", "staircase2", "living-room")]
     # image readers of the dormant features: intact files + 400 damaged copies of each
     images = []
     try:
