@@ -8,7 +8,8 @@ import ctypes as C
 
 import numpy as np
 
-GSP_ABI_VERSION = 8
+GSP_ABI_VERSION = 9
+ADAPTIVE_LUMINANCE_FLOOR = 1e-3  # GSP_ADAPTIVE_LUMINANCE_FLOOR
 
 BSDF_DIFFUSE = 0
 BSDF_SMOOTH_DIELECTRIC = 1
@@ -139,6 +140,10 @@ class RenderParams(C.Structure):
         ("collect_traversal_stats", C.c_uint32),
         ("collect_kernel_times", C.c_uint32),
         ("disable_nee", C.c_uint32),  # (ABI 7) RenderParams.nee inverted, PathTracer.h:36-41; 0 = the shipped shader (`#define NEE true`)
+        # (ABI 9) adaptive sampling: 0 = off; > 0 = stop a pixel once its relative standard error is at most this (gpuspectral_pt.h)
+        ("adaptive_threshold", C.c_float),
+        ("adaptive_min_spp", C.c_uint32),  # first checkpoint, 0 = 16
+        ("adaptive_step", C.c_uint32),  # samples between checkpoints, 0 = 16
     ]
 
 
@@ -234,6 +239,8 @@ class Stats(C.Structure):
         ("shadow_stat_no_triangle", C.c_uint64),  # (ABI 7)
         ("scene_drains", C.c_uint64),  # (ABI 7)
         ("scene_splits", C.c_uint64),  # (ABI 7)
+        ("adaptive_rounds", C.c_uint64),  # (ABI 9)
+        ("adaptive_active_pixels", C.c_uint64),  # (ABI 9) 0 = the adaptive frame has converged
     ]
 
     def as_dict(self):

@@ -23,6 +23,7 @@
 // calls last milliseconds to minutes).  The same device may appear more than once in `devices` (several shares on
 // one GPU): that is how the single-GPU test box exercises partition + gather + scatter.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -412,6 +413,12 @@ int gsp_multi_render(gsp_multi* m, const gsp_render_params* params) {
   if (!m) return GSP_ERR_INVALID;
   if (!params) {
     m->err = "gsp_multi_render: null parameters";
+    return GSP_ERR_INVALID;
+  }
+  // (ABI 9) adaptive sampling is single-context for now: every share would stop its own pixels correctly, but nothing gathers
+  // or reports the per-share state yet -- refused rather than half supported
+  if (params->struct_size >= offsetof(gsp_render_params, adaptive_threshold) + sizeof(float) && params->adaptive_threshold != 0.0f) {
+    m->err = "gsp_multi_render: adaptive sampling (adaptive_threshold != 0) is not supported over several shares";
     return GSP_ERR_INVALID;
   }
   return for_each_share(m, [&](size_t r) { return gsp_render(m->ctx[r], params); });

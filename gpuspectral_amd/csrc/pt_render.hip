@@ -199,6 +199,17 @@ struct gsp_context {
     uint64_t holes_in = 0;     // ... of which filler records of k_shade's chunked reservation (no paths, no rays)
     std::vector<uint32_t> h_live;      // host mirror of the slots' live counters
     std::vector<uint32_t> live_since;  // per slot: iteration whose read-back is the first to show the slot's current batch
+    // adaptive frame (ABI 9): only the pixels of active[act] are sampled (lane-local owned indices, increasing); k_converge
+    // writes the survivors of a checkpoint into the other buffer
+    bool adaptive = false;
+    DevBuf<uint32_t> active[2];
+    uint32_t act = 0;
+    uint64_t num_active = 0;
+    DevBuf<uint64_t> conv_masks;   // k_converge: "keeps going" ballot per wave
+    DevBuf<uint32_t> conv_blocks;  // ... kept pixels per block, then their offsets; the new count behind them
+    uint32_t h_num_active = 0;
+    // pixels the pipeline samples: the owned pixels, or the active list of an adaptive frame (the memo keeps the owned count)
+    uint64_t work_pixels() const { return adaptive ? num_active : num_pixels; }
   };
   static constexpr int kMaxLanes = 2;
   Lane lanes[kMaxLanes];
@@ -209,6 +220,18 @@ struct gsp_context {
   bool primary_memo = true;         // gsp_ctx_options.primary_memo = 2: every sample traces its camera ray
   double memory_share = 0.4;        // of the free device memory, for the path pool + result ring (gsp_ctx_options.memory_share)
   bool pipe_active = false;
+  // adaptive sampling (ABI 9): what the first gsp_render of the frame decided, the samples every still-sampled pixel holds, and
+  // per owned pixel (compact, allocated by the first adaptive call) m2 and the samples folded
+  enum FrameMode { kFrameUndecided = 0, kFrameUniform = 1, kFrameAdaptive = 2 };
+  int frame_mode = kFrameUndecided;
+  uint32_t adaptive_n = 0;
+  DevBuf<float> pix_m2;
+  DevBuf<uint32_t> pix_spp;
+  uint64_t active_pixels() const {
+    uint64_t n = 0;
+    for (uint32_t l = 0; l < num_lanes; ++l) n += lanes[l].adaptive ? lanes[l].num_active : 0;
+    return n;
+  }
 
   // oldest table version a sample in flight may carry (= tab.ver when none is)
   uint32_t oldest_live_version() const {

@@ -730,6 +730,145 @@ __global__ __launch_bounds__(kBlock) void k_resolve(uint32_t num_pixels, uint32_
   }
 }
 
+// ---- adaptive sampling (include/gpuspectral_pt.h, ABI 9) ----------------------------------------------------------------
+// An adaptive frame samples only the pixels of each lane's ACTIVE LIST: lane-local owned indices l (owned pixel l * lanes + lane)
+// in increasing order, so that the camera rays of a launch stay as coherent as the uniform frame's.  k_generate_active /
+// k_resolve_active are k_generate / k_resolve with path i mapped to (timestamp k, active[a]) instead of (k, l); they are kernels
+// of their own so that the uniform frame's launches -- their arguments and their code -- are exactly what they were.
+__global__ __launch_bounds__(kBlock) void k_generate_active(RenderConsts rc, uint32_t num_active, uint32_t K, uint32_t first_timestamp,
+                                                            const uint32_t* __restrict__ pixel_ids, const uint32_t* __restrict__ active,
+                                                            PathQueue q, uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
+                                                            q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
+  const uint64_t total = (uint64_t)num_active * K;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t k = (uint32_t)(i / num_active), l = active[i % num_active];
+    const uint32_t lp = l * lanes + lane;
+    const uint32_t gid = pixel_ids ? pixel_ids[lp] : lp;
+    const uint32_t sid = sid_base + (uint32_t)i;
+    PathState p;
+    generate_path(rc, gid, first_timestamp + k, sid, p);
+    p.flags |= ver_bits;
+    const uint64_t j = offset + i;
+    qst(&q.P0[j], mkq(p.o.x, p.o.y, p.o.z, p.d.x));
+    qst(&q.P1[j], mkq(p.d.y, p.d.z, ub(p.seed), ub(p.sid)));
+    qst(&q.P2[j], mkq(p.weight.x, p.weight.y, p.weight.z, p.directWeight));
+    qst(&q.P3[j], mkq(0.0f, 0.0f, 0.0f, ub(p.flags)));
+    if (memo) qst(&hits[j], memo[l]);  // (the memo holds every owned pixel of the lane)
+  }
+}
+
+// the second moment of an adaptive pixel: running mean of Y^2 over its samples, with the recurrence and the NaN rule of
+// resolve_sample (a sample whose colour mix is NaN leaves the colour, and so m2, as they were).  Called BEFORE resolve_sample
+// folds the same sample: the mix it tests is of the previous mean.
+__device__ __forceinline__ void fold_second_moment(uint32_t timestamp, q4 sample, const q4& accum, float& m2) {
+  f3 c = mk3(sample.x, sample.y, sample.z);
+  const float a = 1.0f / (float)(timestamp + 1u);
+  if (timestamp > 0) c = mk3(accum.x, accum.y, accum.z) * (1.0f - a) + c * a;
+  if (gisnan(c.x) || gisnan(c.y) || gisnan(c.z)) return;
+  const float y = 0.2126f * sample.x + 0.7152f * sample.y + 0.0722f * sample.z;
+  m2 = timestamp > 0 ? m2 * (1.0f - a) + (y * y) * a : y * y;
+}
+
+__global__ __launch_bounds__(kBlock) void k_resolve_active(uint32_t num_active, uint32_t K, uint32_t first_timestamp,
+                                                           const uint32_t* __restrict__ active, const q4* __restrict__ result,
+                                                           q4* __restrict__ accum, float* __restrict__ m2, uint32_t* __restrict__ count,
+                                                           uint32_t lane, uint32_t lanes) {
+  for (uint32_t a = blockIdx.x * kBlock + threadIdx.x; a < num_active; a += gridDim.x * kBlock) {
+    const uint64_t lp = (uint64_t)active[a] * lanes + lane;
+    q4 acc = accum[lp];
+    float m = m2[lp];
+    for (uint32_t k = 0; k < K; ++k) {
+      const q4 s = result[(uint64_t)k * num_active + a];
+      fold_second_moment(first_timestamp + k, s, acc, m);
+      resolve_sample(first_timestamp + k, s, acc);  // (the colour: the uniform frame's fold, unchanged)
+    }
+    accum[lp] = acc;
+    m2[lp] = m;
+    count[lp] = first_timestamp + K;
+  }
+}
+
+// The stopping rule of include/gpuspectral_pt.h, in double from the float32 buffers.
+struct ConvergeIO {
+  const q4* accum;
+  const float* m2;
+  const uint32_t* count;
+  double threshold;
+  uint32_t lane, lanes;
+};
+__device__ __forceinline__ bool adaptive_stops(const ConvergeIO& io, uint64_t lp) {
+  const uint32_t n = io.count[lp];
+  if (n < 2) return false;
+  const q4 mean = io.accum[lp];
+  const double yb = 0.2126 * (double)mean.x + 0.7152 * (double)mean.y + 0.0722 * (double)mean.z;
+  const double var = fmax((double)io.m2[lp] - yb * yb, 0.0) * (double)n / (double)(n - 1u);
+  const double err = sqrt(var / (double)n);
+  return err <= io.threshold * fmax(yb, (double)GSP_ADAPTIVE_LUMINANCE_FLOOR);
+}
+
+// k_converge, once per checkpoint and lane: a STABLE compaction of the active list to the pixels that go on, in three launches
+// and no atomics.  (1) k_converge: the rule per pixel, one wave64 ballot of "keeps going" per wave -> masks, the block's count
+// -> blocks[b]; (2) k_converge_scan: one block turns the counts into exclusive offsets and writes the total behind them;
+// (3) k_converge_compact: every kept pixel goes to blocks[b] + the popcounts of the waves before it + its rank in its wave.
+__global__ __launch_bounds__(kBlock) void k_converge(uint32_t num_active, const uint32_t* __restrict__ active, ConvergeIO io,
+                                                     uint64_t* __restrict__ masks, uint32_t* __restrict__ blocks) {
+  __shared__ uint32_t s_cnt[kBlock / 64];
+  const uint32_t a = blockIdx.x * kBlock + threadIdx.x;
+  const bool keep = a < num_active && !adaptive_stops(io, (uint64_t)active[a] * io.lanes + io.lane);
+  const uint64_t m = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) {
+    masks[a / 64] = m;
+    s_cnt[threadIdx.x / 64] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t c = 0;
+    for (int w = 0; w < kBlock / 64; ++w) c += s_cnt[w];
+    blocks[blockIdx.x] = c;
+  }
+}
+
+constexpr int kScanBlock = 1024;
+__global__ __launch_bounds__(kScanBlock) void k_converge_scan(uint32_t num_blocks, uint32_t* __restrict__ blocks) {
+  __shared__ uint32_t s[kScanBlock];
+  const uint32_t per = (num_blocks + kScanBlock - 1) / kScanBlock;
+  const uint32_t b0 = threadIdx.x * per, b1 = min(num_blocks, b0 + per);
+  uint32_t sum = 0;
+  for (uint32_t b = b0; b < b1; ++b) sum += blocks[b];
+  s[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t off = 1; off < (uint32_t)kScanBlock; off <<= 1) {  // inclusive scan of the per-thread sums
+    const uint32_t v = threadIdx.x >= off ? s[threadIdx.x - off] : 0u;
+    __syncthreads();
+    s[threadIdx.x] += v;
+    __syncthreads();
+  }
+  uint32_t run = s[threadIdx.x] - sum;
+  for (uint32_t b = b0; b < b1; ++b) {
+    const uint32_t c = blocks[b];
+    blocks[b] = run;
+    run += c;
+  }
+  if (threadIdx.x == kScanBlock - 1) blocks[num_blocks] = s[kScanBlock - 1];  // the new active count
+}
+
+__global__ __launch_bounds__(kBlock) void k_converge_compact(uint32_t num_active, const uint32_t* __restrict__ active,
+                                                             const uint64_t* __restrict__ masks, const uint32_t* __restrict__ blocks,
+                                                             uint32_t* __restrict__ out) {
+  const uint32_t a = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x / 64;
+  const uint64_t m = masks[a / 64];
+  if (a < num_active && ((m >> lane) & 1ull)) {
+    uint32_t pos = blocks[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    for (uint32_t w = 0; w < wave; ++w) pos += (uint32_t)__popcll(masks[blockIdx.x * (kBlock / 64) + w]);
+    out[pos] = active[a];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_iota(uint32_t n, uint32_t* __restrict__ out) {
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) out[i] = i;
+}
+
 // ---- resident table records ---------------------------------------------------------------------------------------------
 // once per gsp_upload_scene / gsp_update_tables: what a vertex would compute from its light / diffuse record alone (pt_shading.h)
 struct BakeTables {  // the resident BSDF tables: records of type t at rec[t] (stride rec_bytes[t]), their derived quads in front (derived_of)

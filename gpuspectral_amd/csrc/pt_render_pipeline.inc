@@ -67,7 +67,8 @@ static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderCons
   gsp_context::Pipeline& P = L.pipe;
   hipStream_t st = L.stream;
   const gsp_render_params* rp = &ctx->pipe_params;
-  const uint64_t npix = L.num_pixels;
+  const uint64_t npix = L.num_pixels;     // owned pixels of the lane (the primary-hit memo)
+  const uint64_t wpix = L.work_pixels();  // ... of which the samples go to (all of them unless the frame is adaptive)
   const uint64_t batch_paths = P.batch_paths;
   const bool stats_mode = rp->collect_traversal_stats != 0;
   const bool timing = rp->collect_kernel_times != 0;  // per-kernel HIP event timing (bench)
@@ -195,8 +196,14 @@ static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderCons
           slot = s2;
           break;
         }
-      const uint64_t paths = (uint64_t)kb * npix;
+      const uint64_t paths = (uint64_t)kb * wpix;
       if (slot == P.num_slots || n + inj + paths + slack > P.cap) break;
+      if (L.adaptive)  // (adaptive frame: the lane's active pixels only)
+        hipLaunchKernelGGL(k_generate_active, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)wpix, kb, P.next_ts,
+                           ctx->subset ? ctx->pixel_ids.p : nullptr, (const uint32_t*)L.active[L.act].p, Q[cur ^ 1], (uint32_t)inj,
+                           (uint32_t)(slot * batch_paths), use_memo ? L.memo.p : (const q4*)nullptr, L.hits[cur ^ 1].p, L.index,
+                           ctx->num_lanes, gen_ver_bits);
+      else
       hipLaunchKernelGGL(k_generate, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)npix, kb, P.next_ts,
                          ctx->subset ? ctx->pixel_ids.p : nullptr, Q[cur ^ 1], (uint32_t)inj, (uint32_t)(slot * batch_paths),
                          use_memo ? L.memo.p : (const q4*)nullptr, L.hits[cur ^ 1].p, L.index, ctx->num_lanes, gen_ver_bits);
@@ -354,12 +361,18 @@ static int lane_collect(gsp_context* ctx, gsp_context::Lane& L) {
   while (!P.inflight.empty() && L.h_live[P.inflight.front().slot] == 0) {
     const gsp_context::Batch b = P.inflight.front();
     P.inflight.pop_front();
+    const uint64_t wpix = L.work_pixels();
+    if (L.adaptive)
+      hipLaunchKernelGGL(k_resolve_active, dim3(ctx->grid_for(wpix)), dim3(kBlock), 0, st, (uint32_t)wpix, b.kb, b.t0,
+                         (const uint32_t*)L.active[L.act].p, L.result.p + (uint64_t)b.slot * P.batch_paths, ctx->accum.p,
+                         ctx->pix_m2.p, ctx->pix_spp.p, L.index, ctx->num_lanes);
+    else
     hipLaunchKernelGGL(k_resolve, dim3(ctx->grid_for(L.num_pixels)), dim3(kBlock), 0, st, (uint32_t)L.num_pixels, b.kb, b.t0,
                        L.result.p + (uint64_t)b.slot * P.batch_paths, ctx->accum.p, L.index, ctx->num_lanes);
     CTX_TRY(ctx, hipGetLastError());
     P.slot_used[b.slot] = 0;
     P.folded_end = b.t0 + b.kb;
-    ctx->stats.samples += (uint64_t)b.kb * L.num_pixels;
+    ctx->stats.samples += (uint64_t)b.kb * wpix;
   }
   if (L.queued == 0 && P.n == 0 && P.remaining == 0 && !P.inflight.empty()) {
     ctx->err = "internal error: paths exhausted with unresolved sample batches";
@@ -434,6 +447,9 @@ static int pipeline_run(gsp_context* ctx, bool drain) {
 // Completes everything gsp_render has queued.
 static int pipeline_drain(gsp_context* ctx) { return pipeline_run(ctx, true); }
 
+static int render_enqueue(gsp_context* ctx, const gsp_render_params* rp);
+static int render_adaptive(gsp_context* ctx, const gsp_render_params* rp);
+
 int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
   if (!ctx || !rp_host) return GSP_ERR_INVALID;
   // ABI 8: the host's struct may be shorter than this library's (an older header of ABI >= 8): the fields it does not have are 0,
@@ -461,6 +477,25 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
   }
   CTX_TRY(ctx, hipSetDevice(ctx->device));
   if (rp->spp == 0 || ctx->num_pixels == 0) return GSP_OK;
+  if (!(rp->adaptive_threshold >= 0.0f) || std::isinf(rp->adaptive_threshold)) {
+    ctx->err = "adaptive_threshold must be 0 (off) or a finite positive value";
+    return GSP_ERR_INVALID;
+  }
+  // the first render of a frame decides whether it is adaptive (include/gpuspectral_pt.h, "Adaptive sampling")
+  const bool adaptive = rp->adaptive_threshold > 0.0f;
+  if (ctx->frame_mode != gsp_context::kFrameUndecided && (ctx->frame_mode == gsp_context::kFrameAdaptive) != adaptive) {
+    ctx->err = adaptive ? "adaptive_threshold > 0 in a frame that began uniform: call gsp_frame_begin first"
+                        : "adaptive_threshold == 0 in an adaptive frame: call gsp_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  if (adaptive) return render_adaptive(ctx, rp);
+  ctx->frame_mode = gsp_context::kFrameUniform;
+  return render_enqueue(ctx, rp);
+}
+
+// Queues rp->spp samples of every pixel the lanes sample (all owned pixels, or an adaptive frame's active lists) without waiting
+// for them (pipeline_run(ctx, false)).
+static int render_enqueue(gsp_context* ctx, const gsp_render_params* rp) {
   // A running pipeline is continued when the integrator constants and the batch size are unchanged
   // (paths in flight carry no copy of them); otherwise it is drained first.
   if (ctx->pipe_active &&
@@ -504,8 +539,8 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
       gsp_context::Pipeline& P = L.pipe;
       P = gsp_context::Pipeline{};
       P.folded_end = ctx->folded_idle;
-      const uint64_t npix = L.num_pixels;
-      if (npix == 0) continue;  // fewer pixels than lanes
+      const uint64_t npix = L.work_pixels();
+      if (npix == 0) continue;  // fewer pixels than lanes (or, adaptive, no pixel of this lane left)
       uint64_t Kb = rp->timestamps_in_flight;
       if (Kb == 0) Kb = std::max<uint64_t>(1, (1ull << 20) / npix);
       while (Kb > 1 && Kb * npix >= (1ull << 30)) --Kb;
@@ -548,6 +583,16 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
       const uint64_t want_slots = 24 * ((P.pool_target + P.batch_paths - 1) / P.batch_paths);
       const uint64_t fit_slots = ring_bytes / ctx->num_lanes / (P.batch_paths * sizeof(q4));
       P.num_slots = (uint32_t)std::min<uint64_t>(kMaxSlots, std::max<uint64_t>(4, std::min(want_slots, fit_slots)));
+      if (L.adaptive) {
+        // an adaptive round re-derives the batch from a shrinking pixel count: it works in the pool and the ring the frame's first
+        // round allocated rather than re-allocating them (a 16-GB ring freed and allocated again: 0.45-0.88 s per call in the first probe run)
+        if (P.cap > L.pool_cap && L.pool_cap >= 3 * P.batch_paths) {
+          P.pool_target = (L.pool_cap - P.batch_paths) / 2;
+          P.cap = L.pool_cap;
+        }
+        if ((uint64_t)P.num_slots * P.batch_paths > L.result_cap && L.result_cap >= 4 * P.batch_paths)
+          P.num_slots = (uint32_t)std::min<uint64_t>(kMaxSlots, L.result_cap / P.batch_paths);
+      }
       if (P.cap >= (1ull << 32) || (uint64_t)P.num_slots * P.batch_paths >= (1ull << 32)) {
         ctx->err = "frame too large for 32-bit path indices";
         return GSP_ERR_INVALID;
@@ -579,6 +624,115 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
     P.remaining += rp->spp;
   }
   return pipeline_run(ctx, false);
+}
+
+// ---- adaptive sampling (ABI 9) ----------------------------------------------------------------------------------------------
+// The first adaptive gsp_render of a frame: m2 and the per-pixel counts (zero), every lane's active list = all its owned pixels.
+static int adaptive_begin(gsp_context* ctx) {
+  CTX_TRY(ctx, ctx->pix_m2.ensure(ctx->num_pixels, &ctx->bytes));
+  CTX_TRY(ctx, ctx->pix_spp.ensure(ctx->num_pixels, &ctx->bytes));
+  CTX_TRY(ctx, hipMemsetAsync(ctx->pix_m2.p, 0, ctx->num_pixels * sizeof(float), ctx->stream));
+  CTX_TRY(ctx, hipMemsetAsync(ctx->pix_spp.p, 0, ctx->num_pixels * sizeof(uint32_t), ctx->stream));
+  for (uint32_t l = 0; l < ctx->num_lanes; ++l) {
+    gsp_context::Lane& L = ctx->lanes[l];
+    const uint64_t n = L.num_pixels, nb = (n + kBlock - 1) / kBlock;
+    CTX_TRY(ctx, L.active[0].ensure(n, &ctx->bytes));
+    CTX_TRY(ctx, L.active[1].ensure(n, &ctx->bytes));
+    CTX_TRY(ctx, L.conv_masks.ensure(nb * (kBlock / 64), &ctx->bytes));
+    CTX_TRY(ctx, L.conv_blocks.ensure(nb + 1, &ctx->bytes));
+    if (n) {
+      hipLaunchKernelGGL(k_iota, dim3(ctx->grid_for(n)), dim3(kBlock), 0, ctx->stream, (uint32_t)n, L.active[0].p);
+      CTX_TRY(ctx, hipGetLastError());
+    }
+    L.act = 0;
+    L.num_active = n;
+    L.adaptive = true;
+  }
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->adaptive_n = 0;
+  ctx->frame_mode = gsp_context::kFrameAdaptive;
+  return GSP_OK;
+}
+
+// At a checkpoint (nothing in flight): every lane's active list loses the pixels the rule stops, order kept (k_converge).  One
+// 4-byte read-back per lane.
+static int adaptive_converge(gsp_context* ctx, float threshold) {
+  for (uint32_t l = 0; l < ctx->num_lanes; ++l) {
+    gsp_context::Lane& L = ctx->lanes[l];
+    if (!L.adaptive || L.num_active == 0) continue;
+    const uint32_t n = (uint32_t)L.num_active, nb = (n + kBlock - 1) / kBlock;
+    const ConvergeIO io{ctx->accum.p, ctx->pix_m2.p, ctx->pix_spp.p, (double)threshold, L.index, ctx->num_lanes};
+    hipLaunchKernelGGL(k_converge, dim3(nb), dim3(kBlock), 0, L.stream, n, (const uint32_t*)L.active[L.act].p, io, L.conv_masks.p,
+                       L.conv_blocks.p);
+    hipLaunchKernelGGL(k_converge_scan, dim3(1), dim3(kScanBlock), 0, L.stream, nb, L.conv_blocks.p);
+    hipLaunchKernelGGL(k_converge_compact, dim3(nb), dim3(kBlock), 0, L.stream, n, (const uint32_t*)L.active[L.act].p,
+                       (const uint64_t*)L.conv_masks.p, (const uint32_t*)L.conv_blocks.p, L.active[L.act ^ 1].p);
+    CTX_TRY(ctx, hipGetLastError());
+    CTX_TRY(ctx, hipMemcpyAsync(&L.h_num_active, L.conv_blocks.p + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream));
+  }
+  for (uint32_t l = 0; l < ctx->num_lanes; ++l) {
+    gsp_context::Lane& L = ctx->lanes[l];
+    if (!L.adaptive || L.num_active == 0) continue;
+    CTX_TRY(ctx, hipStreamSynchronize(L.stream));
+    L.act ^= 1;
+    L.num_active = L.h_num_active;
+  }
+  return GSP_OK;
+}
+
+// An adaptive gsp_render: rounds that end at the checkpoints and at the end of the call, each drained; k_converge at every
+// checkpoint.  Decisions happen only at checkpoints, so the split of the samples over calls does not change the result.
+static int render_adaptive(gsp_context* ctx, const gsp_render_params* rp) {
+  if (ctx->frame_mode != gsp_context::kFrameAdaptive) {
+    int rc = pipeline_drain(ctx);  // (nothing of this frame is in flight; a pipeline of an earlier frame would have been drained)
+    if (rc == GSP_OK) rc = adaptive_begin(ctx);
+    if (rc != GSP_OK) return rc;
+  }
+  if (ctx->active_pixels() == 0) return GSP_OK;  // every pixel has stopped: nothing to add
+  if (rp->first_timestamp != ctx->adaptive_n) {
+    ctx->err = "adaptive frame: first_timestamp " + std::to_string(rp->first_timestamp) + " must equal the samples the pixels still sampled hold (" +
+               std::to_string(ctx->adaptive_n) + ")";
+    return GSP_ERR_INVALID;
+  }
+  const uint64_t min_spp = rp->adaptive_min_spp ? rp->adaptive_min_spp : 16u, step = rp->adaptive_step ? rp->adaptive_step : 16u;
+  uint32_t remaining = rp->spp;
+  while (remaining > 0 && ctx->active_pixels() > 0) {
+    const uint64_t n = ctx->adaptive_n;
+    const uint64_t next = n < min_spp ? min_spp : min_spp + ((n - min_spp) / step + 1) * step;  // the next checkpoint
+    const uint32_t k = (uint32_t)std::min<uint64_t>(remaining, next - n);
+    gsp_render_params r = *rp;
+    r.spp = k;
+    r.first_timestamp = (uint32_t)n;
+    int rc = render_enqueue(ctx, &r);
+    if (rc == GSP_OK) rc = pipeline_drain(ctx);
+    if (rc != GSP_OK) return rc;
+    ctx->adaptive_n = (uint32_t)(n + k);
+    remaining -= k;
+    ++ctx->stats.adaptive_rounds;
+    if (n + k == next) {
+      const auto t0 = std::chrono::steady_clock::now();
+      rc = adaptive_converge(ctx, rp->adaptive_threshold);
+      if (rc != GSP_OK) return rc;
+      ctx->stats.render_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+  }
+  return GSP_OK;
+}
+
+int gsp_download_pixel_stats(gsp_context* ctx, float* second_moment, uint32_t* spp) {
+  if (!ctx || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  {
+    int rc_ = pipeline_drain(ctx);
+    if (rc_ != GSP_OK) return rc_;
+  }
+  if (ctx->frame_mode != gsp_context::kFrameAdaptive) {
+    ctx->err = "gsp_download_pixel_stats: the frame is not adaptive (no gsp_render with adaptive_threshold > 0 since gsp_frame_begin)";
+    return GSP_ERR_INVALID;
+  }
+  if (second_moment) CTX_TRY(ctx, hipMemcpy(second_moment, ctx->pix_m2.p, ctx->num_pixels * sizeof(float), hipMemcpyDeviceToHost));
+  if (spp) CTX_TRY(ctx, hipMemcpy(spp, ctx->pix_spp.p, ctx->num_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return GSP_OK;
 }
 
 #ifdef GSP_SHADE_PROFILE
@@ -742,6 +896,10 @@ extern "C" {
 
 int gsp_upload_accum(gsp_context* ctx, const float* rgba, uint64_t num_pixels) {
   if (!ctx || !rgba || !ctx->have_frame || num_pixels != ctx->num_pixels) return GSP_ERR_INVALID;
+  if (ctx->frame_mode == gsp_context::kFrameAdaptive) {
+    ctx->err = "gsp_upload_accum: not available in an adaptive frame (its per-pixel m2 and counts cannot be restored)";
+    return GSP_ERR_INVALID;
+  }
   CTX_TRY(ctx, hipSetDevice(ctx->device));
   {
     int rc_ = pipeline_drain(ctx);
@@ -781,6 +939,7 @@ int gsp_get_stats(gsp_context* ctx, gsp_stats* out) {
   ctx->stats.num_bvh_nodes = ctx->bvh.num_nodes + (ctx->split ? ctx->dyn.num_nodes : 0u);
   ctx->stats.bvh_depth = std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u);
   ctx->stats.device_bytes = ctx->bytes;
+  ctx->stats.adaptive_active_pixels = ctx->frame_mode == gsp_context::kFrameAdaptive ? ctx->active_pixels() : 0u;
   ctx->stats.algorithmic_bytes = 48ull * ctx->stats.stat_rays + (uint64_t)kNodeBytes * ctx->stats.nodes_visited + 48ull * ctx->stats.tris_tested +
                                  32ull * ctx->stats.shadow_stat_rays + 36ull * ctx->stats.shadow_stat_occluded +
                                  (uint64_t)kNodeBytes * ctx->stats.shadow_nodes_visited + 48ull * ctx->stats.shadow_tris_tested;

@@ -889,7 +889,13 @@ int gsp_frame_begin(gsp_context* ctx, uint32_t width, uint32_t height, const uin
     return GSP_ERR_INVALID;
   }
   ctx->have_frame = false;
-  for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
+  for (gsp_context::Lane& L : ctx->lanes) {
+    L.memo_valid = false;
+    L.adaptive = false;  // (the next gsp_render decides whether the new frame is adaptive)
+    L.num_active = 0;
+  }
+  ctx->frame_mode = gsp_context::kFrameUndecided;
+  ctx->adaptive_n = 0;
   ctx->subset = pixel_ids != nullptr;
   if (pixel_ids) {
     for (uint64_t i = 0; i < num_pixels; ++i) {

@@ -6,6 +6,8 @@
 //   may repeat.  --dormant-features: LoadOptions::dormantFeatures (bitmap / checkerboard textures, envmap emitter);
 //   --builtin-shapes: LoadOptions::builtinShapes (`disk` / `sphere` shapes are tessellated instead of skipped);
 //   --no-nee: gsp_render_params.disable_nee = 1 (RenderParams.nee = false); --memory-share / --pool-paths: gsp_ctx_options (how much device memory the path pool takes)
+//   --adaptive T [--adaptive-min N] [--adaptive-step N]: adaptive sampling (gsp_render_params.adaptive_*): spp is then the most a
+//   pixel gets; a pixel stops at the first checkpoint where its relative standard error is <= T
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +25,8 @@ int main(int argc, char** argv) {
   gsp_ctx_options ctxOptions;
   gsp_default_ctx_options(&ctxOptions);
   bool nee = true;
+  float adaptive = 0.0f;
+  uint32_t adaptiveMin = 0, adaptiveStep = 0;
   while (argc > 1 && argv[1][0] == '-' && argv[1][1] == '-') {
     const std::string flag = argv[1];
     int used = 1;
@@ -31,6 +35,9 @@ int main(int argc, char** argv) {
     else if (flag == "--no-nee") nee = false;
     else if (flag == "--memory-share" && argc > 2) ctxOptions.memory_share = std::atof(argv[2]), used = 2;
     else if (flag == "--pool-paths" && argc > 2) ctxOptions.pool_paths = std::strtoull(argv[2], nullptr, 10), used = 2;
+    else if (flag == "--adaptive" && argc > 2) adaptive = (float)std::atof(argv[2]), used = 2;
+    else if (flag == "--adaptive-min" && argc > 2) adaptiveMin = (uint32_t)std::strtoul(argv[2], nullptr, 10), used = 2;
+    else if (flag == "--adaptive-step" && argc > 2) adaptiveStep = (uint32_t)std::strtoul(argv[2], nullptr, 10), used = 2;
     else {
       std::fprintf(stderr, "gsp_render: unknown option '%s'\n", argv[1]);
       return 2;
@@ -39,7 +46,7 @@ int main(int argc, char** argv) {
     argv += used;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -81,6 +88,9 @@ int main(int argc, char** argv) {
     if (devices.size() == 1) {
       PathTracer pt(width, height, devices[0], {}, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
+      pt.params.adaptive_threshold = adaptive;
+      pt.params.adaptive_min_spp = adaptiveMin;
+      pt.params.adaptive_step = adaptiveStep;
       auto t0 = std::chrono::steady_clock::now();
       pt.render(scene, spp);
       img = pt.download();
@@ -89,6 +99,7 @@ int main(int argc, char** argv) {
     } else {
       MultiGpuPathTracer pt(width, height, devices, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
+      pt.params.adaptive_threshold = adaptive;  // (gsp_multi_render refuses adaptive sampling: reported as an error)
       auto t0 = std::chrono::steady_clock::now();
       pt.render(scene, spp);
       img = pt.download();
@@ -101,6 +112,10 @@ int main(int argc, char** argv) {
     std::printf("%llu triangles, %ux%u x %u spp in %.3f s: %.1f Mrays/s, %.2f Msamples/s (BVH build %.1f ms)\n",
                 (unsigned long long)st.num_triangles, width, height, spp, s,
                 (st.extension_rays + st.shadow_rays) / s / 1e6, st.samples / s / 1e6, st.bvh_build_ms);
+    if (adaptive > 0.0f)
+      std::printf("adaptive %g: %llu samples taken (%.2f per pixel of at most %u), %llu pixels still active, %llu rounds\n", adaptive,
+                  (unsigned long long)st.samples, (double)st.samples / ((double)width * height), spp,
+                  (unsigned long long)st.adaptive_active_pixels, (unsigned long long)st.adaptive_rounds);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "error: %s\n", e.what());
     return 1;

@@ -29,6 +29,7 @@ EXPORTS = (
     "gsp_update_tables",
     "gsp_frame_begin",
     "gsp_render",
+    "gsp_download_pixel_stats",
     "gsp_sync",
     "gsp_download",
     "gsp_download_compact",
@@ -101,6 +102,7 @@ def load():
     L.gsp_upload_scene.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_frame_begin.argtypes = [vp, u32, u32, vp, u64]
     L.gsp_render.argtypes = [vp, C.POINTER(abi.RenderParams)]
+    L.gsp_download_pixel_stats.argtypes = [vp, vp, vp]
     L.gsp_sync.argtypes = [vp]
     L.gsp_download.argtypes = [vp, vp]
     L.gsp_download_compact.argtypes = [vp, vp]
@@ -297,6 +299,14 @@ class Context:
         folded = C.c_uint32(0)
         self._check(self._L.gsp_peek_to_device(self._h, device_ptr, nbytes, C.byref(folded)), "gsp_peek_to_device")
         return int(folded.value)
+
+    def pixel_stats(self):
+        """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of
+        Y^2 over each pixel's samples and the samples folded into it (gsp_download_pixel_stats)."""
+        m2 = np.zeros(self.num_pixels, np.float32)
+        spp = np.zeros(self.num_pixels, np.uint32)
+        self._check(self._L.gsp_download_pixel_stats(self._h, m2.ctypes.data, spp.ctypes.data), "gsp_download_pixel_stats")
+        return m2, spp
 
     def upload_accum(self, rgba):
         rgba = np.ascontiguousarray(rgba, np.float32).reshape(-1, 4)

@@ -57,12 +57,14 @@
 extern "C" {
 #endif
 
-#define GSP_ABI_VERSION 8 /* 8: gsp_render_params.struct_size (first field); 2: gsp_multi_*, gsp_tile_partition, gsp_stats.algorithmic_bytes; 4: gsp_stats.memoised_rays, memo_build_rays, bvh_depth;
+#define GSP_ABI_VERSION 9 /* 8: gsp_render_params.struct_size (first field); 2: gsp_multi_*, gsp_tile_partition, gsp_stats.algorithmic_bytes; 4: gsp_stats.memoised_rays, memo_build_rays, bvh_depth;
                              5: gsp_update_camera / _instances / _tables (+ gsp_multi_*), gsp_ctx_options + gsp_ctx_create_ex /
                                 gsp_multi_create_ex, gsp_render_params.nee, gsp_stats.scene_updates;
                              6: gsp_update_instances refits the tree (gsp_ctx_options.refit_growth, gsp_stats.scene_refits);
                              7: gsp_render_params.nee -> disable_nee (a zeroed struct is the reference as shipped),
-                                gsp_stats.shadow_stat_no_triangle */
+                                gsp_stats.shadow_stat_no_triangle;
+                             9: adaptive sampling: gsp_render_params.adaptive_threshold / _min_spp / _step,
+                                gsp_download_pixel_stats, gsp_stats.adaptive_rounds / adaptive_active_pixels */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -257,7 +259,16 @@ typedef struct gsp_render_params {
                                branches (rayhit.rchit:733,763-768): no shadow ray, every emitter met counts with full weight,
                                directWeight stays 1; the light sample is still DRAWN (rayhit.rchit:720 is outside the branch),
                                so the random streams of the two settings coincide */
+  /* (ABI 9) Adaptive sampling.  0 (default, and what a zero-initialised struct or an older host says) = off: every owned pixel
+     gets spp samples per call, exactly as before.  > 0: a pixel stops being sampled once its relative standard error is at
+     most this value; see "Adaptive sampling" at gsp_render. */
+  float adaptive_threshold;
+  uint32_t adaptive_min_spp; /* first checkpoint; 0 = 16 */
+  uint32_t adaptive_step;    /* samples between checkpoints; 0 = 16 */
 } gsp_render_params;
+
+/* (ABI 9) Luminance below which the stopping rule measures the error against this floor instead of the pixel's own luminance. */
+#define GSP_ADAPTIVE_LUMINANCE_FLOOR 1e-3
 
 typedef struct gsp_stats {
   uint64_t extension_rays;
@@ -307,6 +318,9 @@ typedef struct gsp_stats {
   uint64_t scene_splits;     /* (ABI 7) of scene_updates: gsp_update_instances calls that built the scene as TWO trees -- the instances
                                 edited so far and the rest (the first edit that arrives while samples are in flight, and every later
                                 one that touches an instance not edited before); edits of those instances then refit the small tree */
+  uint64_t adaptive_rounds;        /* (ABI 9) rounds run by adaptive gsp_render calls (each ends at a checkpoint or at the end of a call) */
+  uint64_t adaptive_active_pixels; /* (ABI 9) owned pixels the adaptive frame still samples (0 = converged: a viewer is done; 0 on a
+                                      uniform frame).  `samples` keeps its meaning: samples folded, the sum over pixels of N_p */
 } gsp_stats;
 
 typedef struct gsp_context gsp_context;
@@ -434,6 +448,33 @@ int gsp_frame_begin(gsp_context* ctx, uint32_t width, uint32_t height,
  * the download / copy / upload_accum calls, gsp_get_stats, gsp_reset_stats,
  * gsp_frame_begin, gsp_upload_scene and gsp_ctx_destroy complete them first. */
 int gsp_render(gsp_context* ctx, const gsp_render_params* params);
+/*
+ * (ABI 9) Adaptive sampling: params->adaptive_threshold > 0.
+ *   Checkpoints are at n = min_spp + j * step samples (j >= 0).  At a checkpoint every pixel still sampled is tested and stops
+ *   when err <= threshold * max(Ybar, GSP_ADAPTIVE_LUMINANCE_FLOOR).  The rule is evaluated in double from the float32 buffers:
+ *     Y    = 0.2126 r + 0.7152 g + 0.0722 b
+ *     Ybar = Y of the pixel's accumulate-buffer mean
+ *     m2   = running mean of Y^2 over the pixel's folded samples, with the colour's recurrence: sample t enters with weight
+ *            1 / (t + 1) (Y and Y^2 of a sample formed in float32); a sample whose colour mix is NaN leaves m2 alone, as it
+ *            leaves the colour
+ *     var  = max(m2 - Ybar^2, 0) * n / (n - 1),   err = sqrt(var / n)      (n = 1: the pixel does not stop)
+ *   It is an estimator: whether a pixel stops depends on the noise it measures, so the adaptive image carries a small stopping
+ *   bias that the uniform renderer does not have.  A pixel that stops after N_p samples holds exactly the uniform image of that
+ *   pixel at N_p samples, bit for bit.
+ * Frame rules.  The first gsp_render after gsp_frame_begin decides whether the frame is adaptive; later calls of the frame must
+ *   agree (threshold > 0 or not), else GSP_ERR_INVALID.  first_timestamp must equal the samples the still-sampled pixels hold
+ *   (0 for the first call; not checked once no pixel is left).  A call adds up to spp samples to every pixel still sampled, in
+ *   ROUNDS that end at the checkpoints and at the end of the call.  A stop is decided only at a checkpoint, so the result does
+ *   not depend on how the samples are split over calls, on timestamps_in_flight or on gsp_ctx_options.lanes.  Stopped pixels
+ *   stay stopped until the next gsp_frame_begin; scene edits leave them (and the accumulate buffer) alone.  An adaptive
+ *   gsp_render returns DRAINED: every sample it added has been folded.  gsp_peek's samples_folded is the count of the pixels
+ *   still sampled (the largest per-pixel count).  gsp_multi_render and gsp_upload_accum refuse adaptive frames
+ *   (GSP_ERR_INVALID).  The per-pixel state: gsp_download_pixel_stats.
+ */
+
+/* (ABI 9) The owned pixels' m2 (see above) and folded sample counts after adaptive gsp_render calls, compact (pixel_ids
+ * order), num_pixels entries each; either pointer may be NULL.  GSP_ERR_INVALID on a frame that is not adaptive. */
+int gsp_download_pixel_stats(gsp_context* ctx, float* second_moment, uint32_t* spp);
 
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
