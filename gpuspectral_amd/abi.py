@@ -144,7 +144,15 @@ class RenderParams(C.Structure):
         ("adaptive_threshold", C.c_float),
         ("adaptive_min_spp", C.c_uint32),  # first checkpoint, 0 = 16
         ("adaptive_step", C.c_uint32),  # samples between checkpoints, 0 = 16
+        # pixel filter (added at the end under the struct_size rule, ABI still 9): FILTER_*; 0 = the reference as shipped
+        ("pixel_filter", C.c_uint32),
+        ("pixel_filter_param", C.c_float),  # tent radius (0 = 1.0) / Gaussian standard deviation (0 = 0.5), in pixels
     ]
+
+
+# gsp_render_params.pixel_filter (GSP_FILTER_*, include/gpuspectral_pt.h "Pixel filter")
+FILTER_NONE, FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN = 0, 1, 2, 3
+FILTER_NAMES = {"none": FILTER_NONE, "box": FILTER_BOX, "tent": FILTER_TENT, "gaussian": FILTER_GAUSSIAN}
 
 
 def default_render_params(spp=1, first_timestamp=0):

@@ -86,7 +86,8 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 // ---- generate ------------------------------------------------------------------
 // Appends K timestamps x num_pixels new paths to the queue at `offset`; their sample slots start
 // at `sid_base` in the result ring.
-__global__ __launch_bounds__(kBlock) void k_generate(RenderConsts rc, uint32_t num_pixels, uint32_t K,
+template <bool FILTER, class RC>
+__device__ __forceinline__ void generate_body(RC rc, uint32_t num_pixels, uint32_t K,
                                                       uint32_t first_timestamp,
                                                       const uint32_t* __restrict__ pixel_ids, PathQueue q,
                                                       uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void k_generate(RenderConsts rc, uint32_t n
     const uint32_t gid = pixel_ids ? pixel_ids[lp] : lp;
     const uint32_t sid = sid_base + (uint32_t)i;
     PathState p;
-    generate_path(rc, gid, first_timestamp + k, sid, p);
+    generate_path_t<FILTER>(rc, gid, first_timestamp + k, sid, p);
     p.flags |= ver_bits;  // the version of the BSDF / light tables this sample belongs to (pt_stages.h kVerMask)
     const uint64_t j = offset + i;
     qst(&q.P0[j], mkq(p.o.x, p.o.y, p.o.z, p.d.x));
@@ -109,6 +110,24 @@ __global__ __launch_bounds__(kBlock) void k_generate(RenderConsts rc, uint32_t n
     // hit record is copied instead of traced again; the extend launch skips these leading entries of the queue
     if (memo) qst(&hits[j], memo[i % num_pixels]);
   }
+}
+
+__global__ __launch_bounds__(kBlock) void k_generate(RenderConstsBase rc, uint32_t num_pixels, uint32_t K,
+                                                      uint32_t first_timestamp,
+                                                      const uint32_t* __restrict__ pixel_ids, PathQueue q,
+                                                      uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
+                                                      q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
+  generate_body<false>(rc, num_pixels, K, first_timestamp, pixel_ids, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
+}
+// ... with a pixel filter (include/gpuspectral_pt.h): every sample's camera ray goes through its own sub-pixel offset, so the
+// launch gets memo = nullptr and the extend launch traces these entries like every other.  A kernel of its own so that the
+// unfiltered launch runs the code it ran before.
+__global__ __launch_bounds__(kBlock) void k_generate_filtered(RenderConsts rc, uint32_t num_pixels, uint32_t K,
+                                                      uint32_t first_timestamp,
+                                                      const uint32_t* __restrict__ pixel_ids, PathQueue q,
+                                                      uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
+                                                      q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
+  generate_body<true>(rc, num_pixels, K, first_timestamp, pixel_ids, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
 }
 
 // ---- extend / connect / test hook: ray sources and result sinks of k_trace -----------------
@@ -139,14 +158,14 @@ struct ExtendIO {  // raygen.rgen:53-58: tmin 0, tmax 1e10, closest hit
 struct MemoIO {
   static constexpr float kTmin = 0.0f, kTmax = 1e10f;
   static constexpr bool kVersioned = false, kSplit = false;
-  RenderConsts rc;
+  RenderConstsBase rc;
   const uint32_t* pixel_ids;
   uint32_t lane, lanes;
   q4* memo;
   __device__ __forceinline__ void load(uint32_t i, f3& o, f3& d, float& tmin, float& tmax, uint32_t& pay) const {
     const uint32_t lp = i * lanes + lane;
     PathState p;
-    generate_path(rc, pixel_ids ? pixel_ids[lp] : lp, 0u, 0u, p);
+    generate_path_t<false>(rc, pixel_ids ? pixel_ids[lp] : lp, 0u, 0u, p);  // (a filtered frame never uses the memo)
     o = p.o;
     d = p.d;
     tmin = 0.0f;
@@ -309,7 +328,7 @@ constexpr int kShadeWaves = kShadeBlock / 64;
 // path carries, from HBM / L2 (no LDS copy: it would have to hold every live version) -- unless the versions in flight differ only
 // in their GEOMETRY (gsp_update_instances): then the one live version of the tables is staged as usual (SceneView::ver_stride == 0)
 template <bool TEX, bool VER>
-__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(SceneView S, RenderConsts rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
+__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(SceneView S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
                                                         const q4* __restrict__ hits, PathQueue nxt, ShadowQueue sq,
                                                         q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                         uint32_t* __restrict__ live,
@@ -614,7 +633,7 @@ struct FinishStack {
 };
 
 template <bool TEX, bool VER>
-__global__ __launch_bounds__(kBlock) void k_finish(SceneView S, RenderConsts rc, uint32_t n, PathQueue q,
+__global__ __launch_bounds__(kBlock) void k_finish(SceneView S, RenderConstsBase rc, uint32_t n, PathQueue q,
                                                     q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                     uint32_t* __restrict__ live,
                                                     uint32_t slot_paths, DevStats* __restrict__ stats) {
@@ -735,7 +754,8 @@ __global__ __launch_bounds__(kBlock) void k_resolve(uint32_t num_pixels, uint32_
 // in increasing order, so that the camera rays of a launch stay as coherent as the uniform frame's.  k_generate_active /
 // k_resolve_active are k_generate / k_resolve with path i mapped to (timestamp k, active[a]) instead of (k, l); they are kernels
 // of their own so that the uniform frame's launches -- their arguments and their code -- are exactly what they were.
-__global__ __launch_bounds__(kBlock) void k_generate_active(RenderConsts rc, uint32_t num_active, uint32_t K, uint32_t first_timestamp,
+template <bool FILTER, class RC>
+__device__ __forceinline__ void generate_active_body(RC rc, uint32_t num_active, uint32_t K, uint32_t first_timestamp,
                                                             const uint32_t* __restrict__ pixel_ids, const uint32_t* __restrict__ active,
                                                             PathQueue q, uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
                                                             q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
@@ -746,7 +766,7 @@ __global__ __launch_bounds__(kBlock) void k_generate_active(RenderConsts rc, uin
     const uint32_t gid = pixel_ids ? pixel_ids[lp] : lp;
     const uint32_t sid = sid_base + (uint32_t)i;
     PathState p;
-    generate_path(rc, gid, first_timestamp + k, sid, p);
+    generate_path_t<FILTER>(rc, gid, first_timestamp + k, sid, p);
     p.flags |= ver_bits;
     const uint64_t j = offset + i;
     qst(&q.P0[j], mkq(p.o.x, p.o.y, p.o.z, p.d.x));
@@ -755,6 +775,18 @@ __global__ __launch_bounds__(kBlock) void k_generate_active(RenderConsts rc, uin
     qst(&q.P3[j], mkq(0.0f, 0.0f, 0.0f, ub(p.flags)));
     if (memo) qst(&hits[j], memo[l]);  // (the memo holds every owned pixel of the lane)
   }
+}
+__global__ __launch_bounds__(kBlock) void k_generate_active(RenderConstsBase rc, uint32_t num_active, uint32_t K, uint32_t first_timestamp,
+                                                            const uint32_t* __restrict__ pixel_ids, const uint32_t* __restrict__ active,
+                                                            PathQueue q, uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
+                                                            q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
+  generate_active_body<false>(rc, num_active, K, first_timestamp, pixel_ids, active, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
+}
+__global__ __launch_bounds__(kBlock) void k_generate_active_filtered(RenderConsts rc, uint32_t num_active, uint32_t K, uint32_t first_timestamp,
+                                                            const uint32_t* __restrict__ pixel_ids, const uint32_t* __restrict__ active,
+                                                            PathQueue q, uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
+                                                            q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
+  generate_active_body<true>(rc, num_active, K, first_timestamp, pixel_ids, active, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
 }
 
 // the second moment of an adaptive pixel: running mean of Y^2 over its samples, with the recurrence and the NaN rule of

@@ -47,6 +47,11 @@ static RenderConsts render_consts(const gsp_context* ctx) {
   rcst.cam_origin[0] = ctx->camera.to_world[12];  // Camera::getPosition, Camera.cpp:41-45
   rcst.cam_origin[1] = ctx->camera.to_world[13];
   rcst.cam_origin[2] = ctx->camera.to_world[14];
+  // pixel filter: the id and the parameter with its default resolved (include/gpuspectral_pt.h)
+  rcst.pixel_filter = rp->pixel_filter;
+  rcst.pixel_filter_param = rp->pixel_filter == GSP_FILTER_TENT       ? (rp->pixel_filter_param != 0.0f ? rp->pixel_filter_param : 1.0f)
+                            : rp->pixel_filter == GSP_FILTER_GAUSSIAN ? (rp->pixel_filter_param != 0.0f ? rp->pixel_filter_param : 0.5f)
+                                                                      : 0.0f;
   return rcst;
 }
 
@@ -123,7 +128,10 @@ static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderCons
   const uint32_t gen_stamp = ctx->geo.phys(ctx->geo.ver + ctx->geo.slots() - ctx->geo.base);
 
   CTX_TRY(ctx, hipMemsetAsync(tails_out, 0, kTailSet * sizeof(uint32_t), st));
-  const bool use_memo = ctx->primary_memo && !stats_mode;
+  // (a filtered sample's camera ray is its own: nothing to memoise.  L.memo / L.memo_valid are left as they are -- the memo holds
+  // the UNJITTERED camera rays' hits and stays true for a later unfiltered call as long as scene, camera and frame do)
+  const bool filtered = rcst.pixel_filter != GSP_FILTER_NONE;
+  const bool use_memo = ctx->primary_memo && !stats_mode && !filtered;
   if (use_memo && !L.memo_valid && P.remaining > 0) {  // once per scene / camera / frame: trace the camera rays
     CTX_TRY(ctx, L.memo.ensure(npix, &ctx->bytes));
     CTX_TRY(ctx, hipMemsetAsync(L.counters.p + C_WORK_EXT, 0, kWorkShards * kWorkStride * sizeof(uint32_t), st));
@@ -198,7 +206,15 @@ static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderCons
         }
       const uint64_t paths = (uint64_t)kb * wpix;
       if (slot == P.num_slots || n + inj + paths + slack > P.cap) break;
-      if (L.adaptive)  // (adaptive frame: the lane's active pixels only)
+      if (L.adaptive && filtered)
+        hipLaunchKernelGGL(k_generate_active_filtered, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)wpix, kb, P.next_ts,
+                           ctx->subset ? ctx->pixel_ids.p : nullptr, (const uint32_t*)L.active[L.act].p, Q[cur ^ 1], (uint32_t)inj,
+                           (uint32_t)(slot * batch_paths), (const q4*)nullptr, L.hits[cur ^ 1].p, L.index, ctx->num_lanes, gen_ver_bits);
+      else if (filtered)
+        hipLaunchKernelGGL(k_generate_filtered, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)npix, kb, P.next_ts,
+                           ctx->subset ? ctx->pixel_ids.p : nullptr, Q[cur ^ 1], (uint32_t)inj, (uint32_t)(slot * batch_paths),
+                           (const q4*)nullptr, L.hits[cur ^ 1].p, L.index, ctx->num_lanes, gen_ver_bits);
+      else if (L.adaptive)  // (adaptive frame: the lane's active pixels only)
         hipLaunchKernelGGL(k_generate_active, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)wpix, kb, P.next_ts,
                            ctx->subset ? ctx->pixel_ids.p : nullptr, (const uint32_t*)L.active[L.act].p, Q[cur ^ 1], (uint32_t)inj,
                            (uint32_t)(slot * batch_paths), use_memo ? L.memo.p : (const q4*)nullptr, L.hits[cur ^ 1].p, L.index,
@@ -479,6 +495,14 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
   if (rp->spp == 0 || ctx->num_pixels == 0) return GSP_OK;
   if (!(rp->adaptive_threshold >= 0.0f) || std::isinf(rp->adaptive_threshold)) {
     ctx->err = "adaptive_threshold must be 0 (off) or a finite positive value";
+    return GSP_ERR_INVALID;
+  }
+  if (rp->pixel_filter > GSP_FILTER_GAUSSIAN) {
+    ctx->err = "pixel_filter " + std::to_string(rp->pixel_filter) + " is not a GSP_FILTER_* value";
+    return GSP_ERR_INVALID;
+  }
+  if (!(rp->pixel_filter_param >= 0.0f) || std::isinf(rp->pixel_filter_param)) {
+    ctx->err = "pixel_filter_param must be 0 (the filter's default) or a finite positive value";
     return GSP_ERR_INVALID;
   }
   // the first render of a frame decides whether it is adaptive (include/gpuspectral_pt.h, "Adaptive sampling")

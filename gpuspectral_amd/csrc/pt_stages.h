@@ -26,7 +26,9 @@ GSP_HD uint32_t pack_material(uint32_t bsdf, uint32_t twofaced) {
   return (bsdf & 0x7fffffffu) | (twofaced == 1u ? 0x80000000u : 0u);
 }
 
-struct RenderConsts {
+// What every stage reads.  k_shade, k_finish and the unfiltered k_generate take this struct: its size is part of their kernel
+// argument layout, and so of their instruction streams (the committed counter files belong to those, profiles/pmc_bench_*.json).
+struct RenderConstsBase {
   uint32_t width, height;
   uint32_t max_depth, rr_start_depth;
   float clamp;
@@ -34,6 +36,14 @@ struct RenderConsts {
   float zplane;        // (max(W,H)/2) / tan(fov/2), raygen.rgen:22 (tan evaluated on the host)
   float cam_origin[3]; // camera.eye = toWorld[3]
   float cam_to_world[16];
+};
+
+// ... plus what only the generation of a FILTERED sample reads (k_generate_filtered, k_generate_active_filtered, generate_path):
+// the pixel filter (include/gpuspectral_pt.h, "Pixel filter"): GSP_FILTER_* and the RESOLVED parameter (tent radius / Gaussian
+// standard deviation, never 0 for those two).  0 = the reference as shipped: the ray through the integer pixel coordinate
+struct RenderConsts : RenderConstsBase {
+  uint32_t pixel_filter = 0;
+  float pixel_filter_param = 0.0f;
 };
 
 struct SceneView {
@@ -104,21 +114,63 @@ struct ShadowRay {
   int32_t next;   // index of the continuing path in the next queue, -1 if the path ended here
 };
 
-// raygen.rgen:20-25,31-48
-GSP_HD void generate_path(const RenderConsts& rc, uint32_t gid, uint32_t timestamp, uint32_t sid, PathState& p) {
-  const uint32_t px = gid % rc.width, py = gid / rc.width;
-  const float x = (float)px - (float)rc.width / 2.0f;
-  const float y = (float)py - (float)rc.height / 2.0f;
+// Sub-pixel offset of one sample, drawn from the pixel filter's own density (filter importance sampling: the sample then counts
+// with weight 1 in its own pixel).  The formulas are fixed in include/gpuspectral_pt.h; log / sin / cos are the deterministic
+// ones of pt_math.h, so host and device agree bit for bit.  Always two draws: the streams of all filters coincide afterwards.
+GSP_HD void filter_offset(uint32_t filter, float param, uint32_t& rng, float& ox, float& oy) {
+  const float u1 = rand_uniform(rng);
+  const float u2 = rand_uniform(rng);
+  if (filter == 2u) {  // GSP_FILTER_TENT: inverse CDF of the tent on [-1, 1], scaled by the radius
+    const float t1 = u1 < 0.5f ? gsqrt(2.0f * u1) - 1.0f : 1.0f - gsqrt(2.0f - 2.0f * u1);
+    const float t2 = u2 < 0.5f ? gsqrt(2.0f * u2) - 1.0f : 1.0f - gsqrt(2.0f - 2.0f * u2);
+    ox = 0.5f + param * t1;
+    oy = 0.5f + param * t2;
+  } else if (filter == 3u) {  // GSP_FILTER_GAUSSIAN: Box-Muller, radius cut at 4 sigma
+    const float rho = gmin(param * gsqrt(-2.0f * det_logf(gmax(1.0f - u1, 2.3283064365386962890625e-10f))), 4.0f * param);
+    float sn, cs;
+    det_sincosf((2.0f * kPi) * u2, sn, cs);
+    ox = 0.5f + rho * cs;
+    oy = 0.5f + rho * sn;
+  } else {  // GSP_FILTER_BOX: the reference's dormant line, raygen.rgen:38
+    ox = u1;
+    oy = u2;
+  }
+}
+
+// rayDir(size, fragCoord, fov) + the camera transform + the y flip, raygen.rgen:20-25,41-45
+GSP_HD f3 camera_dir(const RenderConstsBase& rc, float fx, float fy) {
+  const float x = fx - (float)rc.width / 2.0f;
+  const float y = fy - (float)rc.height / 2.0f;
   f3 dl = normalize(mk3(-x, y, rc.zplane));
   f3 dir = xform_dir(rc.cam_to_world, dl);
   dir.y = dir.y * -1.0f;
+  return dir;
+}
+
+// raygen.rgen:31-48.  FILTER = false is the reference as shipped (the jitter of raygen.rgen:38 commented out), instruction
+// for instruction what it was before pixel filters existed; FILTER = true draws the offset at the position of that line.
+template <bool FILTER, class RC>
+GSP_HD void generate_path_t(const RC& rc, uint32_t gid, uint32_t timestamp, uint32_t sid, PathState& p) {
+  const uint32_t px = gid % rc.width, py = gid / rc.width;
+  uint32_t rng = pcg_hash(tea(rc.width * py + px, timestamp));
+  float fx = (float)px, fy = (float)py;  // fragCoord
+  if constexpr (FILTER) {
+    float ox, oy;
+    filter_offset(rc.pixel_filter, rc.pixel_filter_param, rng, ox, oy);
+    fx = fx + ox;
+    fy = fy + oy;
+  }
   p.o = mk3(rc.cam_origin[0], rc.cam_origin[1], rc.cam_origin[2]);
-  p.d = dir;
+  p.d = camera_dir(rc, fx, fy);
   p.weight = splat(1.0f);
   p.directWeight = 1.0f;
-  p.seed = pcg_hash(tea(rc.width * py + px, timestamp));
+  p.seed = rng;
   p.flags = pack_flags(0, 0, 1);
   p.sid = sid;
+}
+GSP_HD void generate_path(const RenderConsts& rc, uint32_t gid, uint32_t timestamp, uint32_t sid, PathState& p) {
+  if (rc.pixel_filter != 0u) generate_path_t<true>(rc, gid, timestamp, sid, p);
+  else generate_path_t<false>(rc, gid, timestamp, sid, p);
 }
 
 // firefly test + add, raygen.rgen:60-63
@@ -144,7 +196,7 @@ struct ShadeOut {
 // VER: tables of several versions are live (an edit through gsp_update_tables while samples were in flight): the vertex reads
 // the version its path carries.  VER = false is the code of a scene that is not being edited, instruction for instruction.
 template <bool TEX = false, bool VER = false>
-GSP_HD void shade_vertex(const SceneView& S, const RenderConsts& rc, const PathState& in, const HitRec& hit,
+GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
                          ShadeOut& out) {
   uint32_t rng = in.seed;                                                 // rchit:668
   BsdfTables Tv;  // (VER only: this lane's version of the tables)

@@ -57,6 +57,8 @@ def load():
     L.gsph_scene_reflatten.argtypes = [vp]
     L.gsph_pathtracer_render_files_same_slot.argtypes = [vp, C.POINTER(C.c_char_p), C.c_char_p, u32, u32, vp, vp]
     L.gsph_tracker_remember.argtypes = [vp]
+    L.gsph_scene_pixel_filter.restype = u32
+    L.gsph_scene_pixel_filter.argtypes = [vp, C.POINTER(C.c_float)]
     L.gsph_tracker_diff.argtypes = [vp]
     L.gsph_tracker_probe.argtypes = [vp, vp]
     L.gsph_pathtracer_create.restype = vp
@@ -91,14 +93,16 @@ def _view(ptr, count, dtype):
 class Scene:
     """A C++ GPUSpectral::Scene produced by loadScene (S/engine/Loader.cpp:253-349)."""
 
-    def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False):
+    def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False):
         """dormant_features: LoadOptions::dormantFeatures (textures / environment map, SURVEY 8(f).3); builtin_shapes:
         LoadOptions::builtinShapes (`disk` and `sphere` shapes are built instead of skipped, SURVEY 8(f).1); the defaults are
-        the reference's behaviour."""
+        the reference's behaviour.  read_filter: LoadOptions::readFilter (the film's <rfilter> becomes `pixel_filter`, which
+        PathTracer.render applies unless its params name a filter of their own)."""
         self._L = load()
         ad = asset_dir.encode() if asset_dir else None
-        if builtin_shapes:
-            self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) | 4)
+        if builtin_shapes or read_filter:
+            self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) |
+                                                   (4 if builtin_shapes else 0) | (8 if read_filter else 0))
         elif dormant_features:
             self._h = self._L.gsph_load_scene_ex(path.encode(), ad, 1, 1 if srgb_textures else 0)
         else:
@@ -120,6 +124,13 @@ class Scene:
     @property
     def warnings(self):
         return [self._L.gsph_scene_warning(self._h, i).decode() for i in range(self._L.gsph_scene_num_warnings(self._h))]
+
+    @property
+    def pixel_filter(self):
+        """(abi.FILTER_*, parameter) the loader read from the film's <rfilter>; (0, 0.0) without read_filter."""
+        param = C.c_float(0.0)
+        f = self._L.gsph_scene_pixel_filter(self._h, C.byref(param))
+        return int(f), float(param.value)
 
     @property
     def num_materials(self):

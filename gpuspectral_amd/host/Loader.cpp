@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -751,6 +752,29 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
       float fov = obj->number("fov");
       outScene.camera.setFov((float)(fov * M_PI / 180.f));
       outScene.camera.setToWorld(transpose(make_mat4(rowMajor)));
+      if (options.readFilter) {  // <sensor><film><rfilter type=... /></film></sensor>
+        auto each = [](const Object& o, const std::string& kind, const std::function<void(const Object&)>& f) {
+          for (auto& c : o.children)
+            if (c && c->kind == kind) f(*c);
+          for (auto& nc : o.named)
+            if (nc.second && nc.second->kind == kind) f(*nc.second);
+        };
+        each(*obj, "film", [&](const Object& film) {
+          each(film, "rfilter", [&](const Object& rf) {
+            const bool hasParam = rf.plugin == "tent" ? rf.has("radius") : rf.has("stddev");
+            const float param = rf.plugin == "tent" ? rf.number("radius") : rf.number("stddev");
+            if (rf.plugin == "box") outScene.pixelFilter = GSP_FILTER_BOX;
+            else if (rf.plugin == "tent") outScene.pixelFilter = GSP_FILTER_TENT;
+            else if (rf.plugin == "gaussian") outScene.pixelFilter = GSP_FILTER_GAUSSIAN;
+            else
+              throw std::runtime_error("rfilter type '" + rf.plugin + "' is not supported: box, tent and gaussian can be importance-sampled "
+                                       "with weight 1, filters with negative lobes cannot");
+            outScene.pixelFilterParam = outScene.pixelFilter != GSP_FILTER_BOX && hasParam ? param : 0.0f;
+            if (!(outScene.pixelFilterParam >= 0.0f) || std::isinf(outScene.pixelFilterParam))
+              throw std::runtime_error("rfilter type '" + rf.plugin + "': radius / stddev must be finite and not negative");
+          });
+        });
+      }
     } else if (obj->kind == "emitter") {
       if (!options.dormantFeatures || obj->plugin != "envmap") {
         outScene.warnings.push_back("top-level emitter (envmap) ignored, as in the reference (Loader.cpp:338-346)");

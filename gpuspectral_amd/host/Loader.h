@@ -25,6 +25,13 @@ struct LoadOptions {
   // (no libm: oracle/mitsuba_loader.py builds the same floats).  `to_world` and `center` as for every shape
   // (Loader.cpp:284-293); `radius` -- which the reference never reads -- scales the sphere.
   bool builtinShapes = false;
+  // Every scene the reference ships declares `<rfilter type="tent" />` in its film, and its loader never looks at it.
+  // readFilter = true reads it: `box`, `tent` (optional float `radius`) and `gaussian` (optional float `stddev`) under the
+  // sensor's film become Scene::pixelFilter / pixelFilterParam (GSP_FILTER_*, include/gpuspectral_pt.h "Pixel filter"; an
+  // absent parameter stays 0 = the filter's default), which PathTracer::render hands to the device.  Any other type
+  // (mitchell, catmullrom, lanczos: negative lobes, which cannot be importance-sampled with weight 1) is a load error.
+  // false (default): the film is ignored and the scene renders unfiltered, as in the reference.
+  bool readFilter = false;
 };
 
 // assetDir: where rect.obj / box.obj / disk.obj live (Engine::assetPath); "" = the

@@ -163,6 +163,10 @@ void PathTracer::render(const Scene& scene, uint32_t spp) {
   gsp_render_params p = params;
   p.spp = spp;
   p.first_timestamp = (uint32_t)timestamp;  // renderState.params.timestamp, PathTracer.cpp:91
+  if (p.pixel_filter == GSP_FILTER_NONE && scene.pixelFilter != GSP_FILTER_NONE) {  // the film's <rfilter> (LoadOptions::readFilter)
+    p.pixel_filter = scene.pixelFilter;
+    p.pixel_filter_param = scene.pixelFilterParam;
+  }
   check(gsp_render(ctx, &p), "gsp_render");
   timestamp += (int)spp;                    // PathTracer.cpp:92
 }
@@ -241,6 +245,10 @@ void MultiGpuPathTracer::render(const Scene& scene, uint32_t spp) {
   gsp_render_params p = params;
   p.spp = spp;
   p.first_timestamp = (uint32_t)timestamp;
+  if (p.pixel_filter == GSP_FILTER_NONE && scene.pixelFilter != GSP_FILTER_NONE) {
+    p.pixel_filter = scene.pixelFilter;
+    p.pixel_filter_param = scene.pixelFilterParam;
+  }
   check(gsp_multi_render(multi, &p), "gsp_multi_render");
   timestamp += (int)spp;
 }

@@ -81,7 +81,9 @@ class PathTracer : public RenderPassCreator {
   void reset();  // timestamp = 0, accumulate buffer cleared
   int getTimestamp() const { return timestamp; }
   gsp_stats stats();
-  gsp_render_params params;  // reference literals by default (MAX_DEPTH 50, RR > 10, clamp 20)
+  // reference literals by default (MAX_DEPTH 50, RR > 10, clamp 20).  params.pixel_filter != GSP_FILTER_NONE overrides the
+  // filter a scene carries (Scene::pixelFilter, LoadOptions::readFilter); NONE leaves the choice to the scene
+  gsp_render_params params;
 
  private:
   void check(int rc, const char* what);

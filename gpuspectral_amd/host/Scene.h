@@ -184,6 +184,10 @@ struct Scene {
   std::vector<RoughFloorBSDF> roughFloorBSDFs;
   std::vector<RoughPlasticBSDF> roughPlasticBSDFs;
   std::vector<std::string> warnings;  // what the loader skipped (the reference printed these to stdout)
+  // the film's <rfilter>, read only with LoadOptions::readFilter: GSP_FILTER_* and its parameter (0 = the filter's default).
+  // 0 = none: the renderer's own params decide.  PathTracer::render uses these when its params.pixel_filter is GSP_FILTER_NONE
+  uint32_t pixelFilter = 0;
+  float pixelFilterParam = 0.0f;
 
   // dormant features: filled only by loadScene(..., LoadOptions{.dormantFeatures = true}); a BSDF record's hasTexture is
   // 1 + the index into `textures`

@@ -63,7 +63,8 @@ void* gsph_load_scene_ex(const char* path, const char* asset_dir, int dormant, i
   }
   return b;
 }
-// flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere)
+// flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere),
+// 8 = readFilter (the film's <rfilter>)
 void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned flags) {
   SceneBox* b = nullptr;
   int rc = guard([&] {
@@ -72,6 +73,7 @@ void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned fla
     opt.dormantFeatures = (flags & 1u) != 0;
     opt.srgbTextures = (flags & 2u) != 0;
     opt.builtinShapes = (flags & 4u) != 0;
+    opt.readFilter = (flags & 8u) != 0;
     b->scene = loadScene(path, asset_dir ? asset_dir : "", opt);
     flattenScene(b->scene, b->flat);
   });
@@ -105,6 +107,10 @@ int gsph_load_hdr_bitmap(const char* path, uint32_t* width, uint32_t* height, fl
 const gsp_scene_desc* gsph_scene_desc(void* s) { return &((SceneBox*)s)->flat.desc; }
 uint32_t gsph_scene_num_warnings(void* s) { return (uint32_t)((SceneBox*)s)->scene.warnings.size(); }
 const char* gsph_scene_warning(void* s, uint32_t i) { return ((SceneBox*)s)->scene.warnings[i].c_str(); }
+uint32_t gsph_scene_pixel_filter(void* s, float* param) {
+  if (param) *param = ((SceneBox*)s)->scene.pixelFilterParam;
+  return ((SceneBox*)s)->scene.pixelFilter;
+}
 uint32_t gsph_scene_num_materials(void* s) { return (uint32_t)((SceneBox*)s)->scene.materials.size(); }
 
 // ---- scene edits between frames (what a host application does to its Scene; the tests drive PathTracer::prepareScene's

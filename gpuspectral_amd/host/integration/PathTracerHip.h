@@ -36,11 +36,17 @@ class PathTracerHip : public RenderPassCreator {
     gsp_default_render_params(&p);          // MAX_DEPTH 50, RR > 10, clamp 20, NEE on
     p.spp = 1;
     p.first_timestamp = (uint32_t)timestamp++;  // renderState.params.timestamp, PathTracer.cpp:91-92
+    p.pixel_filter = pixelFilter;               // GSP_FILTER_NONE by default: the reference as shipped (raygen.rgen:38 dormant)
+    p.pixel_filter_param = pixelFilterParam;
     check(gsp_render(ctx, &p));
   }
   void download(float* rgba) { check(gsp_download(ctx, rgba)); }  // what the DrawTexture blit sampled, once every path has ended
   // ... and as it stands this frame, into the device memory the blit reads (PathTracer.cpp:41-55): no wait, no trip through the host
   void blitSource(void* deviceRgba, uint64_t bytes, uint32_t* samples = nullptr) { check(gsp_peek_to_device(ctx, deviceRgba, bytes, samples)); }
+  // anti-aliasing, opt-in (gpuspectral_pt.h "Pixel filter"): e.g. GSP_FILTER_TENT, 0 = the <rfilter type="tent"/> of the shipped
+  // scenes; call restart() after a change, or the running mean mixes filtered and unfiltered samples
+  uint32_t pixelFilter = GSP_FILTER_NONE;
+  float pixelFilterParam = 0.0f;
   void restart() {                                                // a viewer that wants a fresh running mean after an edit
     timestamp = 0;
     check(gsp_frame_begin(ctx, width, height, nullptr, 0));

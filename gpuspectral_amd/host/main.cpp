@@ -8,6 +8,8 @@
 //   --no-nee: gsp_render_params.disable_nee = 1 (RenderParams.nee = false); --memory-share / --pool-paths: gsp_ctx_options (how much device memory the path pool takes)
 //   --adaptive T [--adaptive-min N] [--adaptive-step N]: adaptive sampling (gsp_render_params.adaptive_*): spp is then the most a
 //   pixel gets; a pixel stops at the first checkpoint where its relative standard error is <= T
+//   --filter none|box|tent[:r]|gaussian[:s]: pixel filter (gsp_render_params.pixel_filter / _param: anti-aliasing by sub-pixel
+//   jitter drawn from the filter); --scene-filter: LoadOptions::readFilter (the film's <rfilter>; --filter other than none wins)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +29,8 @@ int main(int argc, char** argv) {
   bool nee = true;
   float adaptive = 0.0f;
   uint32_t adaptiveMin = 0, adaptiveStep = 0;
+  uint32_t filter = GSP_FILTER_NONE;
+  float filterParam = 0.0f;
   while (argc > 1 && argv[1][0] == '-' && argv[1][1] == '-') {
     const std::string flag = argv[1];
     int used = 1;
@@ -38,7 +42,30 @@ int main(int argc, char** argv) {
     else if (flag == "--adaptive" && argc > 2) adaptive = (float)std::atof(argv[2]), used = 2;
     else if (flag == "--adaptive-min" && argc > 2) adaptiveMin = (uint32_t)std::strtoul(argv[2], nullptr, 10), used = 2;
     else if (flag == "--adaptive-step" && argc > 2) adaptiveStep = (uint32_t)std::strtoul(argv[2], nullptr, 10), used = 2;
-    else {
+    else if (flag == "--scene-filter") options.readFilter = true;
+    else if (flag == "--filter" && argc > 2) {
+      const std::string v = argv[2];
+      const size_t colon = v.find(':');
+      const std::string name = v.substr(0, colon);
+      filterParam = 0.0f;
+      if (name == "none") filter = GSP_FILTER_NONE;
+      else if (name == "box") filter = GSP_FILTER_BOX;
+      else if (name == "tent") filter = GSP_FILTER_TENT;
+      else if (name == "gaussian") filter = GSP_FILTER_GAUSSIAN;
+      else {
+        std::fprintf(stderr, "gsp_render: bad filter '%s' (expected none, box, tent[:radius] or gaussian[:stddev])\n", argv[2]);
+        return 2;
+      }
+      if (colon != std::string::npos) {
+        char* e = nullptr;
+        filterParam = std::strtof(v.c_str() + colon + 1, &e);
+        if (e == v.c_str() + colon + 1 || *e != 0 || !(filterParam >= 0.0f) || filter == GSP_FILTER_NONE || filter == GSP_FILTER_BOX) {
+          std::fprintf(stderr, "gsp_render: bad filter '%s' (expected none, box, tent[:radius] or gaussian[:stddev])\n", argv[2]);
+          return 2;
+        }
+      }
+      used = 2;
+    } else {
       std::fprintf(stderr, "gsp_render: unknown option '%s'\n", argv[1]);
       return 2;
     }
@@ -46,7 +73,7 @@ int main(int argc, char** argv) {
     argv += used;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -91,6 +118,8 @@ int main(int argc, char** argv) {
       pt.params.adaptive_threshold = adaptive;
       pt.params.adaptive_min_spp = adaptiveMin;
       pt.params.adaptive_step = adaptiveStep;
+      pt.params.pixel_filter = filter;
+      pt.params.pixel_filter_param = filterParam;
       auto t0 = std::chrono::steady_clock::now();
       pt.render(scene, spp);
       img = pt.download();
@@ -100,6 +129,8 @@ int main(int argc, char** argv) {
       MultiGpuPathTracer pt(width, height, devices, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
       pt.params.adaptive_threshold = adaptive;  // (gsp_multi_render refuses adaptive sampling: reported as an error)
+      pt.params.pixel_filter = filter;
+      pt.params.pixel_filter_param = filterParam;
       auto t0 = std::chrono::steady_clock::now();
       pt.render(scene, spp);
       img = pt.download();

@@ -262,6 +262,8 @@ class Context:
         self.width, self.height = width, height
 
     def render(self, spp=1, first_timestamp=0, params=None, **overrides):
+        """gsp_render.  Keyword arguments set single fields of gsp_render_params: adaptive_threshold=..., pixel_filter=abi.FILTER_TENT,
+        pixel_filter_param=1.5 (anti-aliasing, gpuspectral_pt.h "Pixel filter"), timestamps_in_flight=..., ..."""
         p = params or abi.default_render_params()
         p.spp, p.first_timestamp = spp, first_timestamp
         for k, v in overrides.items():
@@ -411,6 +413,7 @@ class MultiContext:
         self.width, self.height = width, height
 
     def render(self, spp=1, first_timestamp=0, params=None, **overrides):
+        """gsp_multi_render: as Context.render (pixel_filter= / pixel_filter_param= included; adaptive sampling is refused)."""
         p = params or abi.default_render_params()
         p.spp, p.first_timestamp = spp, first_timestamp
         for k, v in overrides.items():

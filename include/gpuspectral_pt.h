@@ -265,7 +265,45 @@ typedef struct gsp_render_params {
   float adaptive_threshold;
   uint32_t adaptive_min_spp; /* first checkpoint; 0 = 16 */
   uint32_t adaptive_step;    /* samples between checkpoints; 0 = 16 */
+  /* Pixel filter (see "Pixel filter" below).  Added at the end under the struct_size rule of ABI 8, WITHOUT a new ABI version: a
+     host built against the earlier ABI-9 header passes a shorter struct_size, the library takes both fields as 0, and 0 =
+     GSP_FILTER_NONE = the reference as shipped. */
+  uint32_t pixel_filter;     /* GSP_FILTER_* */
+  float pixel_filter_param;  /* tent: radius in pixels, 0 = 1.0; Gaussian: standard deviation in pixels, 0 = 0.5; else ignored */
 } gsp_render_params;
+
+/*
+ * Pixel filter: opt-in anti-aliasing by filter importance sampling.
+ *
+ * The reference shoots every sample of a pixel through the integer pixel coordinate; its sub-pixel jitter is the dormant line
+ * raygen.rgen:38 and the <rfilter> of its scenes is ignored.  With pixel_filter != GSP_FILTER_NONE each sample's camera ray goes
+ * through fragCoord = vec2(pixel) + offset, the offset drawn from the filter's own density, and the sample is accumulated into
+ * its own pixel with weight 1, exactly as without a filter.  Samples are never splatted across pixels, so pixels stay
+ * independent: tile shares, adaptive sampling and progressive accumulation mean what they meant.
+ *
+ *   u1 = randUniform(), then u2 = randUniform(), drawn from rngState directly after pcgHash(tea(W*y + x, timestamp)) (the
+ *   position of raygen.rgen:38); prd.seed is the state AFTER the two draws.  Every filter other than NONE draws exactly two
+ *   variates, so the random streams of all filtered modes coincide from the first bounce on.  NONE draws nothing.
+ *
+ *   NONE      offset = (0, 0), no draw: the reference as shipped, bit for bit.  The parameter is ignored.
+ *   BOX       offset = (u1, u2): the reference's dormant line.
+ *   TENT      r = param, 0 = 1.0 (Mitsuba's default).  Per axis offset = 0.5 + r * t(u),
+ *             t(u) = u < 0.5 ? sqrt(2u) - 1 : 1 - sqrt(2 - 2u).
+ *   GAUSSIAN  sigma = param, 0 = 0.5 (Mitsuba's default).  rho = min(sigma * sqrt(-2 log(max(1 - u1, 2^-32))), 4 sigma),
+ *             offset = 0.5 + rho * (cos 2 pi u2, sin 2 pi u2).
+ *
+ * All arithmetic is float32 in the order written; log, sin and cos are the library's deterministic functions, sqrt is correctly
+ * rounded.  fragCoord enters rayDir unchanged, so a pixel's footprint is [p, p + 1): BOX, TENT and GAUSSIAN are centred on
+ * p + 0.5 while NONE samples the corner p, i.e. a filtered image is moved by half a pixel against the unfiltered one.
+ *
+ * A filtered call traces every camera ray (the primary-hit memo answers only the unjittered ray): gsp_stats.memoised_rays does
+ * not grow.  The filter may change from call to call; it composes with adaptive sampling and with gsp_multi_render.  An unknown
+ * filter id, or a negative or non-finite parameter: GSP_ERR_INVALID.  gsp_trace is not affected.
+ */
+#define GSP_FILTER_NONE 0u
+#define GSP_FILTER_BOX 1u
+#define GSP_FILTER_TENT 2u
+#define GSP_FILTER_GAUSSIAN 3u
 
 /* (ABI 9) Luminance below which the stopping rule measures the error against this floor instead of the pixel's own luminance. */
 #define GSP_ADAPTIVE_LUMINANCE_FLOOR 1e-3
