@@ -150,6 +150,22 @@ class RenderParams(C.Structure):
     ]
 
 
+class Lens(C.Structure):
+    """gsp_lens (include/gpuspectral_pt.h "Thin lens"): context state set with gsp_set_lens; radius 0 = the pinhole."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("radius", C.c_float),
+        ("focus_distance", C.c_float),
+        ("blades", C.c_uint32),  # 0 = circle, 3..16 = polygon
+        ("rotation", C.c_float),  # radians
+    ]
+
+
+def lens(radius=0.0, focus_distance=0.0, blades=0, rotation=0.0):
+    return Lens(C.sizeof(Lens), radius, focus_distance, blades, rotation)
+
+
 # gsp_render_params.pixel_filter (GSP_FILTER_*, include/gpuspectral_pt.h "Pixel filter")
 FILTER_NONE, FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN = 0, 1, 2, 3
 FILTER_NAMES = {"none": FILTER_NONE, "box": FILTER_BOX, "tent": FILTER_TENT, "gaussian": FILTER_GAUSSIAN}

@@ -1,7 +1,30 @@
 // pt_hostmath.h -- host-side float32 linear algebra of gsp_upload_scene.
 #pragma once
+#include <cmath>
+#include <cstring>
+
+#include "../../include/gpuspectral_pt.h"
 
 namespace gsp {
+
+// gsp_set_lens: the host's struct under the struct_size rule (fields it does not have are 0; NULL = pinhole), validated as
+// include/gpuspectral_pt.h "Thin lens" says.  Returns nullptr and the lens in `out`, or the text for gsp_last_error.
+inline const char* resolve_lens(const gsp_lens* host, gsp_lens& out) {
+  gsp_lens l;
+  std::memset(&l, 0, sizeof(l));
+  if (host) {
+    if (host->struct_size < sizeof(uint32_t)) return "gsp_lens.struct_size is smaller than the field itself: set it to sizeof(gsp_lens)";
+    std::memcpy(&l, host, host->struct_size < sizeof(l) ? host->struct_size : sizeof(l));
+  }
+  if (!(l.radius >= 0.0f) || std::isinf(l.radius)) return "gsp_lens.radius must be 0 (pinhole) or a finite positive value";
+  if (l.radius > 0.0f && (!(l.focus_distance > 0.0f) || std::isinf(l.focus_distance)))
+    return "gsp_lens.focus_distance must be finite and positive when radius > 0";
+  if (l.blades != 0u && (l.blades < 3u || l.blades > 16u)) return "gsp_lens.blades must be 0 (circular aperture) or 3..16";
+  if (!std::isfinite(l.rotation)) return "gsp_lens.rotation must be finite";
+  l.struct_size = (uint32_t)sizeof(gsp_lens);
+  out = l;
+  return nullptr;
+}
 
 // ---- host-side linear algebra for PathTracer::prepareScene (PathTracer.cpp:62) ------
 // glm::inverse(glm::transpose(M)); cofactor expansion in glm's order so the

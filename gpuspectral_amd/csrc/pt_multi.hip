@@ -346,6 +346,11 @@ int gsp_multi_update_camera(gsp_multi* m, const gsp_camera* camera) {
   return for_each_share(m, [&](size_t r) { return gsp_update_camera(m->ctx[r], camera); });
 }
 
+int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens) {  // (NULL = pinhole, as for gsp_set_lens)
+  if (!m) return GSP_ERR_INVALID;
+  return for_each_share(m, [&](size_t r) { return gsp_set_lens(m->ctx[r], lens); });
+}
+
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances) {
   if (!m) return GSP_ERR_INVALID;
   if (!instances && num_instances) {

@@ -100,6 +100,7 @@ struct gsp_context {
   DevBuf<uint32_t> s2g_all;            // slot counted through both trees -> scene triangle index (gsp_trace)
   bool s2g_all_valid = false;
   gsp_camera camera{};
+  gsp_lens lens{};  // gsp_set_lens; radius 0 = the pinhole.  Context state like the camera: render_consts reads it at every gsp_render
   double bvh_build_ms = 0.0;
   // what gsp_upload_scene leaves resident for the per-frame edits (gsp_update_instances re-bakes from it, as the reference
   // keeps the BLAS of a mesh and rebuilds the TLAS, Renderer.cpp:122-131 / PathTracer.cpp:10-19): the object-space

@@ -86,7 +86,8 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 // ---- generate ------------------------------------------------------------------
 // Appends K timestamps x num_pixels new paths to the queue at `offset`; their sample slots start
 // at `sid_base` in the result ring.
-template <bool FILTER, class RC>
+// MODE: 0 = the reference's pinhole ray, 1 = with a pixel filter, 2 = through a thin lens (the filter by a runtime branch)
+template <int MODE, class RC>
 __device__ __forceinline__ void generate_body(RC rc, uint32_t num_pixels, uint32_t K,
                                                       uint32_t first_timestamp,
                                                       const uint32_t* __restrict__ pixel_ids, PathQueue q,
@@ -99,7 +100,8 @@ __device__ __forceinline__ void generate_body(RC rc, uint32_t num_pixels, uint32
     const uint32_t gid = pixel_ids ? pixel_ids[lp] : lp;
     const uint32_t sid = sid_base + (uint32_t)i;
     PathState p;
-    generate_path_t<FILTER>(rc, gid, first_timestamp + k, sid, p);
+    if constexpr (MODE == 2) generate_path_lens(rc, gid, first_timestamp + k, sid, p);
+    else generate_path_t<MODE != 0>(rc, gid, first_timestamp + k, sid, p);
     p.flags |= ver_bits;  // the version of the BSDF / light tables this sample belongs to (pt_stages.h kVerMask)
     const uint64_t j = offset + i;
     qst(&q.P0[j], mkq(p.o.x, p.o.y, p.o.z, p.d.x));
@@ -128,6 +130,15 @@ __global__ __launch_bounds__(kBlock) void k_generate_filtered(RenderConsts rc, u
                                                       uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
                                                       q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
   generate_body<true>(rc, num_pixels, K, first_timestamp, pixel_ids, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
+}
+// ... through a thin lens (include/gpuspectral_pt.h, "Thin lens"): every sample leaves from its own point of the aperture, so this
+// launch too gets memo = nullptr.  The queue stores are generate_body's, non-temporal hint included.
+__global__ __launch_bounds__(kBlock) void k_generate_lens(RenderConstsLens rc, uint32_t num_pixels, uint32_t K,
+                                                      uint32_t first_timestamp,
+                                                      const uint32_t* __restrict__ pixel_ids, PathQueue q,
+                                                      uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
+                                                      q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
+  generate_body<2>(rc, num_pixels, K, first_timestamp, pixel_ids, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
 }
 
 // ---- extend / connect / test hook: ray sources and result sinks of k_trace -----------------
@@ -754,7 +765,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve(uint32_t num_pixels, uint32_
 // in increasing order, so that the camera rays of a launch stay as coherent as the uniform frame's.  k_generate_active /
 // k_resolve_active are k_generate / k_resolve with path i mapped to (timestamp k, active[a]) instead of (k, l); they are kernels
 // of their own so that the uniform frame's launches -- their arguments and their code -- are exactly what they were.
-template <bool FILTER, class RC>
+template <int MODE, class RC>
 __device__ __forceinline__ void generate_active_body(RC rc, uint32_t num_active, uint32_t K, uint32_t first_timestamp,
                                                             const uint32_t* __restrict__ pixel_ids, const uint32_t* __restrict__ active,
                                                             PathQueue q, uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
@@ -766,7 +777,8 @@ __device__ __forceinline__ void generate_active_body(RC rc, uint32_t num_active,
     const uint32_t gid = pixel_ids ? pixel_ids[lp] : lp;
     const uint32_t sid = sid_base + (uint32_t)i;
     PathState p;
-    generate_path_t<FILTER>(rc, gid, first_timestamp + k, sid, p);
+    if constexpr (MODE == 2) generate_path_lens(rc, gid, first_timestamp + k, sid, p);
+    else generate_path_t<MODE != 0>(rc, gid, first_timestamp + k, sid, p);
     p.flags |= ver_bits;
     const uint64_t j = offset + i;
     qst(&q.P0[j], mkq(p.o.x, p.o.y, p.o.z, p.d.x));
@@ -787,6 +799,12 @@ __global__ __launch_bounds__(kBlock) void k_generate_active_filtered(RenderConst
                                                             PathQueue q, uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
                                                             q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
   generate_active_body<true>(rc, num_active, K, first_timestamp, pixel_ids, active, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
+}
+__global__ __launch_bounds__(kBlock) void k_generate_active_lens(RenderConstsLens rc, uint32_t num_active, uint32_t K, uint32_t first_timestamp,
+                                                            const uint32_t* __restrict__ pixel_ids, const uint32_t* __restrict__ active,
+                                                            PathQueue q, uint32_t offset, uint32_t sid_base, const q4* __restrict__ memo,
+                                                            q4* __restrict__ hits, uint32_t lane, uint32_t lanes, uint32_t ver_bits) {
+  generate_active_body<2>(rc, num_active, K, first_timestamp, pixel_ids, active, q, offset, sid_base, memo, hits, lane, lanes, ver_bits);
 }
 
 // the second moment of an adaptive pixel: running mean of Y^2 over its samples, with the recurrence and the NaN rule of

@@ -32,9 +32,9 @@ static int ensure_pool(gsp_context* ctx, gsp_context::Lane& L, uint64_t cap, uin
   return GSP_OK;
 }
 
-static RenderConsts render_consts(const gsp_context* ctx) {
+static RenderConstsLens render_consts(const gsp_context* ctx) {
   const gsp_render_params* rp = &ctx->pipe_params;
-  RenderConsts rcst;
+  RenderConstsLens rcst;
   rcst.width = ctx->width;
   rcst.height = ctx->height;
   rcst.max_depth = rp->max_depth;
@@ -52,6 +52,7 @@ static RenderConsts render_consts(const gsp_context* ctx) {
   rcst.pixel_filter_param = rp->pixel_filter == GSP_FILTER_TENT       ? (rp->pixel_filter_param != 0.0f ? rp->pixel_filter_param : 1.0f)
                             : rp->pixel_filter == GSP_FILTER_GAUSSIAN ? (rp->pixel_filter_param != 0.0f ? rp->pixel_filter_param : 0.5f)
                                                                       : 0.0f;
+  set_lens_consts(rcst, ctx->lens);  // thin lens (gsp_set_lens)
   return rcst;
 }
 
@@ -68,7 +69,7 @@ static_assert(kPipeDepth >= 1 && kPipeDepth <= 2, "two tail sets / read-back buf
 //                   on the device; survivors are appended behind the injected paths
 //   copy of the counter words to the host buffer of this parity + an event
 // `exact` = no iteration is in flight, so P.n is the true queue size (and 0 means there is nothing to trace).
-static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderConsts& rcst, const SceneView& view, bool drain) {
+static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderConstsLens& rcst, const SceneView& view, bool drain) {
   gsp_context::Pipeline& P = L.pipe;
   hipStream_t st = L.stream;
   const gsp_render_params* rp = &ctx->pipe_params;
@@ -131,7 +132,8 @@ static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderCons
   // (a filtered sample's camera ray is its own: nothing to memoise.  L.memo / L.memo_valid are left as they are -- the memo holds
   // the UNJITTERED camera rays' hits and stays true for a later unfiltered call as long as scene, camera and frame do)
   const bool filtered = rcst.pixel_filter != GSP_FILTER_NONE;
-  const bool use_memo = ctx->primary_memo && !stats_mode && !filtered;
+  const bool lens = rcst.lens_radius > 0.0f;  // (... and so is a sample's through a lens: the same bypass)
+  const bool use_memo = ctx->primary_memo && !stats_mode && !filtered && !lens;
   if (use_memo && !L.memo_valid && P.remaining > 0) {  // once per scene / camera / frame: trace the camera rays
     CTX_TRY(ctx, L.memo.ensure(npix, &ctx->bytes));
     CTX_TRY(ctx, hipMemsetAsync(L.counters.p + C_WORK_EXT, 0, kWorkShards * kWorkStride * sizeof(uint32_t), st));
@@ -206,7 +208,15 @@ static int lane_enqueue(gsp_context* ctx, gsp_context::Lane& L, const RenderCons
         }
       const uint64_t paths = (uint64_t)kb * wpix;
       if (slot == P.num_slots || n + inj + paths + slack > P.cap) break;
-      if (L.adaptive && filtered)
+      if (L.adaptive && lens)
+        hipLaunchKernelGGL(k_generate_active_lens, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)wpix, kb, P.next_ts,
+                           ctx->subset ? ctx->pixel_ids.p : nullptr, (const uint32_t*)L.active[L.act].p, Q[cur ^ 1], (uint32_t)inj,
+                           (uint32_t)(slot * batch_paths), (const q4*)nullptr, L.hits[cur ^ 1].p, L.index, ctx->num_lanes, gen_ver_bits);
+      else if (lens)
+        hipLaunchKernelGGL(k_generate_lens, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)npix, kb, P.next_ts,
+                           ctx->subset ? ctx->pixel_ids.p : nullptr, Q[cur ^ 1], (uint32_t)inj, (uint32_t)(slot * batch_paths),
+                           (const q4*)nullptr, L.hits[cur ^ 1].p, L.index, ctx->num_lanes, gen_ver_bits);
+      else if (L.adaptive && filtered)
         hipLaunchKernelGGL(k_generate_active_filtered, dim3(ctx->grid_for(paths)), dim3(kBlock), 0, st, rcst, (uint32_t)wpix, kb, P.next_ts,
                            ctx->subset ? ctx->pixel_ids.p : nullptr, (const uint32_t*)L.active[L.act].p, Q[cur ^ 1], (uint32_t)inj,
                            (uint32_t)(slot * batch_paths), (const q4*)nullptr, L.hits[cur ^ 1].p, L.index, ctx->num_lanes, gen_ver_bits);
@@ -405,7 +415,7 @@ static int lane_collect(gsp_context* ctx, gsp_context::Lane& L) {
 static int pipeline_run(gsp_context* ctx, bool drain) {
   if (!ctx->pipe_active) return GSP_OK;
   const auto t_begin = std::chrono::steady_clock::now();
-  const RenderConsts rcst = render_consts(ctx);
+  const RenderConstsLens rcst = render_consts(ctx);
   const SceneView view = ctx->view();
   auto has_work = [&](const gsp_context::Lane& L) {
     const gsp_context::Pipeline& P = L.pipe;
@@ -989,6 +999,52 @@ int gsp_reset_stats(gsp_context* ctx) {
     CTX_TRY(ctx, hipMemsetAsync(ctx->dstats.p, 0, sizeof(DevStats), ctx->stream));
     CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return GSP_OK;
+}
+
+// ---- thin lens (include/gpuspectral_pt.h, "Thin lens") ----
+int gsp_set_lens(gsp_context* ctx, const gsp_lens* lens_host) {
+  if (!ctx) return GSP_ERR_INVALID;
+  gsp_lens l;
+  if (const char* why = resolve_lens(lens_host, l)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  ctx->lens = l;  // no drain, and the memo stays: it holds the pinhole rays' hits, which a lens call does not read
+  return GSP_OK;
+}
+
+int gsp_focus_distance(gsp_context* ctx, uint32_t width, uint32_t height, float fx, float fy, float* out) {
+  if (!ctx || !out) return GSP_ERR_INVALID;
+  if (!ctx->have_scene) {
+    ctx->err = "gsp_focus_distance needs gsp_upload_scene first";
+    return GSP_ERR_INVALID;
+  }
+  if (width == 0 || height == 0 || !std::isfinite(fx) || !std::isfinite(fy)) {
+    ctx->err = "gsp_focus_distance: width and height must be positive, fx and fy finite";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  {  // (a one-off query: the samples already queued finish first, so the traversal below has the device to itself)
+    int rc_ = pipeline_drain(ctx);
+    if (rc_ != GSP_OK) return rc_;
+  }
+  // the pinhole ray of fragCoord (fx, fy), as generate_path forms it (camera_dir), and the cosine of its angle to the local z
+  RenderConstsBase rc{};
+  rc.width = width;
+  rc.height = height;
+  rc.zplane = (std::max((float)width, (float)height) / 2.0f) / tanf(ctx->camera.fov / 2.0f);
+  for (int i = 0; i < 16; ++i) rc.cam_to_world[i] = ctx->camera.to_world[i];
+  const f3 d = camera_dir(rc, fx, fy);
+  const float cosz = normalize(mk3(-(fx - (float)width / 2.0f), fy - (float)height / 2.0f, rc.zplane)).z;
+  const float ray[8] = {ctx->camera.to_world[12], ctx->camera.to_world[13], ctx->camera.to_world[14], 0.0f, d.x, d.y, d.z, 1e10f};
+  struct {
+    float t, u, v;
+    int32_t prim;
+  } hit;
+  int rc_ = gsp_trace(ctx, ray, 1, 0, &hit);
+  if (rc_ != GSP_OK) return rc_;
+  *out = hit.prim < 0 ? 0.0f : hit.t * cosz;
   return GSP_OK;
 }
 

@@ -46,6 +46,26 @@ struct RenderConsts : RenderConstsBase {
   float pixel_filter_param = 0.0f;
 };
 
+// ... plus what only the generation of a sample through a THIN LENS reads (k_generate_lens, k_generate_active_lens): the lens
+// of include/gpuspectral_pt.h, "Thin lens", resolved on the host.  lens_radius == 0 = the pinhole: never handed to those kernels
+struct RenderConstsLens : RenderConsts {
+  float lens_radius = 0.0f;
+  float lens_focus = 0.0f;     // gsp_lens.focus_distance
+  float lens_s = 0.0f;         // focus_distance / zplane, formed once on the host like zplane
+  uint32_t lens_blades = 0;    // 0 = circle, 3..16 = polygon
+  float lens_rotation = 0.0f;  // radians
+};
+
+// (host) the lens of a context into the constants; zplane must be set.  s is formed here, once, like zplane
+inline void set_lens_consts(RenderConstsLens& rc, const gsp_lens& lens) {
+  if (!(lens.radius > 0.0f)) return;  // pinhole: the fields stay 0 whatever the lens holds
+  rc.lens_radius = lens.radius;
+  rc.lens_focus = lens.focus_distance;
+  rc.lens_s = lens.focus_distance / rc.zplane;
+  rc.lens_blades = lens.blades;
+  rc.lens_rotation = lens.rotation;
+}
+
 struct SceneView {
   const q4* nodes;
   const q4* tri_isect;  // 3 quads per slot
@@ -147,9 +167,71 @@ GSP_HD f3 camera_dir(const RenderConstsBase& rc, float fx, float fy) {
   return dir;
 }
 
+// Point on the aperture, uniform over it, in camera space (include/gpuspectral_pt.h, "Thin lens").  Always two draws.
+// Circle: the concentric map of sample_cosine_hemisphere (pt_shading.h, rayhit.rchit:89-111), operation for operation, times the
+// radius.  Polygon: u3 picks the triangle (centre, v_k, v_k+1) and, stretched, the square-root coordinate inside it.
+GSP_HD void lens_vertex(float radius, uint32_t blades, float rotation, uint32_t j, float& vx, float& vy) {
+  float sn, cs;
+  det_sincosf(rotation + ((2.0f * kPi) * (float)j) / (float)blades, sn, cs);
+  vx = radius * cs;
+  vy = radius * sn;
+}
+GSP_HD void lens_point(float radius, uint32_t blades, float rotation, uint32_t& rng, float& lx, float& ly) {
+  const float u3 = rand_uniform(rng);
+  const float u4 = rand_uniform(rng);
+  if (blades == 0u) {
+    const float ux = 2.0f * u3 - 1.0f;
+    const float uy = 2.0f * u4 - 1.0f;
+    float dx = 0.0f, dy = 0.0f;
+    if (!(ux == 0.0f && uy == 0.0f)) {
+      float r, th;
+      if (gabs(ux) > gabs(uy)) {
+        r = ux;
+        th = (kPi / 4.0f) * (uy / ux);
+      } else {
+        r = uy;
+        th = kPi / 2.0f - (kPi / 4.0f) * (ux / uy);
+      }
+      float s, c;
+      det_sincosf(th, s, c);
+      dx = r * c;
+      dy = r * s;
+    }
+    lx = dx * radius;
+    ly = dy * radius;
+  } else {
+    const float t = u3 * (float)blades;
+    const uint32_t k = (uint32_t)t < blades - 1u ? (uint32_t)t : blades - 1u;
+    const float a = gsqrt(t - (float)k);
+    const float b = u4;
+    float x0, y0, x1, y1;
+    lens_vertex(radius, blades, rotation, k, x0, y0);
+    lens_vertex(radius, blades, rotation, k + 1u == blades ? 0u : k + 1u, x1, y1);  // (vertex n is vertex 0: the polygon closes exactly)
+    lx = a * ((1.0f - b) * x0 + b * x1);
+    ly = a * ((1.0f - b) * y0 + b * y1);
+  }
+}
+
+// The camera ray of fragCoord (fx, fy) through the lens point l = (lx, ly, 0): towards the point where the pinhole ray of that
+// fragCoord crosses the plane of focus.  Offset and direction go through the same linear map (xform_dir, then the y flip)
+GSP_HD void camera_ray_lens(const RenderConstsLens& rc, float fx, float fy, float lx, float ly, f3& o, f3& d) {
+  const float x = fx - (float)rc.width / 2.0f;
+  const float y = fy - (float)rc.height / 2.0f;
+  const f3 pf = mk3(-x * rc.lens_s, y * rc.lens_s, rc.lens_focus);
+  const f3 l = mk3(lx, ly, 0.0f);
+  f3 dir = xform_dir(rc.cam_to_world, normalize(pf - l));
+  dir.y = dir.y * -1.0f;
+  f3 off = xform_dir(rc.cam_to_world, l);
+  off.y = off.y * -1.0f;
+  o = mk3(rc.cam_origin[0], rc.cam_origin[1], rc.cam_origin[2]) + off;
+  d = dir;
+}
+
 // raygen.rgen:31-48.  FILTER = false is the reference as shipped (the jitter of raygen.rgen:38 commented out), instruction
 // for instruction what it was before pixel filters existed; FILTER = true draws the offset at the position of that line.
-template <bool FILTER, class RC>
+// LENS = true (RC = RenderConstsLens, radius > 0): the lens point is drawn right behind the filter's two variates and the ray
+// leaves from it; LENS = false is the pinhole, instruction for instruction what it was before the lens existed.
+template <bool FILTER, bool LENS = false, class RC>
 GSP_HD void generate_path_t(const RC& rc, uint32_t gid, uint32_t timestamp, uint32_t sid, PathState& p) {
   const uint32_t px = gid % rc.width, py = gid / rc.width;
   uint32_t rng = pcg_hash(tea(rc.width * py + px, timestamp));
@@ -160,8 +242,14 @@ GSP_HD void generate_path_t(const RC& rc, uint32_t gid, uint32_t timestamp, uint
     fx = fx + ox;
     fy = fy + oy;
   }
-  p.o = mk3(rc.cam_origin[0], rc.cam_origin[1], rc.cam_origin[2]);
-  p.d = camera_dir(rc, fx, fy);
+  if constexpr (LENS) {
+    float lx, ly;
+    lens_point(rc.lens_radius, rc.lens_blades, rc.lens_rotation, rng, lx, ly);
+    camera_ray_lens(rc, fx, fy, lx, ly, p.o, p.d);
+  } else {
+    p.o = mk3(rc.cam_origin[0], rc.cam_origin[1], rc.cam_origin[2]);
+    p.d = camera_dir(rc, fx, fy);
+  }
   p.weight = splat(1.0f);
   p.directWeight = 1.0f;
   p.seed = rng;
@@ -171,6 +259,15 @@ GSP_HD void generate_path_t(const RC& rc, uint32_t gid, uint32_t timestamp, uint
 GSP_HD void generate_path(const RenderConsts& rc, uint32_t gid, uint32_t timestamp, uint32_t sid, PathState& p) {
   if (rc.pixel_filter != 0u) generate_path_t<true>(rc, gid, timestamp, sid, p);
   else generate_path_t<false>(rc, gid, timestamp, sid, p);
+}
+// ... through a lens of radius > 0 (the filter by the same runtime branch), and the entry that takes either camera
+GSP_HD void generate_path_lens(const RenderConstsLens& rc, uint32_t gid, uint32_t timestamp, uint32_t sid, PathState& p) {
+  if (rc.pixel_filter != 0u) generate_path_t<true, true>(rc, gid, timestamp, sid, p);
+  else generate_path_t<false, true>(rc, gid, timestamp, sid, p);
+}
+GSP_HD void generate_path(const RenderConstsLens& rc, uint32_t gid, uint32_t timestamp, uint32_t sid, PathState& p) {
+  if (rc.lens_radius > 0.0f) generate_path_lens(rc, gid, timestamp, sid, p);
+  else generate_path(static_cast<const RenderConsts&>(rc), gid, timestamp, sid, p);
 }
 
 // firefly test + add, raygen.rgen:60-63

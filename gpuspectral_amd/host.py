@@ -59,6 +59,10 @@ def load():
     L.gsph_tracker_remember.argtypes = [vp]
     L.gsph_scene_pixel_filter.restype = u32
     L.gsph_scene_pixel_filter.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gsph_scene_lens.restype = None
+    L.gsph_scene_lens.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    L.gsph_scene_set_lens.restype = None
+    L.gsph_scene_set_lens.argtypes = [vp, C.c_float, C.c_float, u32, C.c_float]
     L.gsph_tracker_diff.argtypes = [vp]
     L.gsph_tracker_probe.argtypes = [vp, vp]
     L.gsph_pathtracer_create.restype = vp
@@ -93,16 +97,18 @@ def _view(ptr, count, dtype):
 class Scene:
     """A C++ GPUSpectral::Scene produced by loadScene (S/engine/Loader.cpp:253-349)."""
 
-    def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False):
+    def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False,
+                 read_lens=False):
         """dormant_features: LoadOptions::dormantFeatures (textures / environment map, SURVEY 8(f).3); builtin_shapes:
         LoadOptions::builtinShapes (`disk` and `sphere` shapes are built instead of skipped, SURVEY 8(f).1); the defaults are
         the reference's behaviour.  read_filter: LoadOptions::readFilter (the film's <rfilter> becomes `pixel_filter`, which
-        PathTracer.render applies unless its params name a filter of their own)."""
+        PathTracer.render applies unless its params name a filter of their own).  read_lens: LoadOptions::readLens (a `thinlens`
+        sensor's aperture_radius / focus_distance become the camera's lens, which PathTracer hands to the device)."""
         self._L = load()
         ad = asset_dir.encode() if asset_dir else None
-        if builtin_shapes or read_filter:
+        if builtin_shapes or read_filter or read_lens:
             self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) |
-                                                   (4 if builtin_shapes else 0) | (8 if read_filter else 0))
+                                                   (4 if builtin_shapes else 0) | (8 if read_filter else 0) | (16 if read_lens else 0))
         elif dormant_features:
             self._h = self._L.gsph_load_scene_ex(path.encode(), ad, 1, 1 if srgb_textures else 0)
         else:
@@ -131,6 +137,17 @@ class Scene:
         param = C.c_float(0.0)
         f = self._L.gsph_scene_pixel_filter(self._h, C.byref(param))
         return int(f), float(param.value)
+
+    @property
+    def lens(self):
+        """(aperture radius, focus distance, blades, rotation) of the scene's camera; all 0 without read_lens / set_lens."""
+        out = (C.c_float * 4)()
+        self._L.gsph_scene_lens(self._h, C.byref(out))
+        return float(out[0]), float(out[1]), int(out[2]), float(out[3])
+
+    def set_lens(self, radius, focus_distance, blades=0, rotation=0.0):
+        """Camera::setLens: the tracer sends it with the next pass (gsp_set_lens) when its value changed."""
+        self._L.gsph_scene_set_lens(self._h, radius, focus_distance, blades, rotation)
 
     @property
     def num_materials(self):

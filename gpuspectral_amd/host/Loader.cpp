@@ -752,6 +752,15 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
       float fov = obj->number("fov");
       outScene.camera.setFov((float)(fov * M_PI / 180.f));
       outScene.camera.setToWorld(transpose(make_mat4(rowMajor)));
+      if (options.readLens && obj->plugin == "thinlens") {
+        const float radius = obj->has("aperture_radius") ? obj->number("aperture_radius") : obj->number("apertureRadius");
+        const float focus = obj->has("focus_distance") ? obj->number("focus_distance") : obj->number("focusDistance");
+        if (!(radius >= 0.0f) || std::isinf(radius))
+          throw std::runtime_error("thinlens sensor: aperture_radius must be finite and not negative");
+        if (radius > 0.0f && (!(focus > 0.0f) || std::isinf(focus)))
+          throw std::runtime_error("thinlens sensor: focus_distance must be finite and positive when aperture_radius > 0");
+        outScene.camera.setLens(radius, focus);
+      }
       if (options.readFilter) {  // <sensor><film><rfilter type=... /></film></sensor>
         auto each = [](const Object& o, const std::string& kind, const std::function<void(const Object&)>& f) {
           for (auto& c : o.children)

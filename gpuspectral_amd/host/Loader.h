@@ -32,6 +32,12 @@ struct LoadOptions {
   // (mitchell, catmullrom, lanczos: negative lobes, which cannot be importance-sampled with weight 1) is a load error.
   // false (default): the film is ignored and the scene renders unfiltered, as in the reference.
   bool readFilter = false;
+  // The reference treats every <sensor> as `perspective`.  readLens = true reads a `thinlens` sensor's float `aperture_radius`
+  // (or `apertureRadius`) and `focus_distance` (or `focusDistance`) into the camera (Camera::setLens; circular aperture), which
+  // PathTracer hands to the device (gsp_set_lens, include/gpuspectral_pt.h "Thin lens").  A negative or non-finite radius, or a
+  // radius > 0 without a finite positive focus distance, is a load error.  Other sensor types are not affected.
+  // false (default): the sensor plugin is ignored and the camera is a pinhole, as in the reference.
+  bool readLens = false;
 };
 
 // assetDir: where rect.obj / box.obj / disk.obj live (Engine::assetPath); "" = the

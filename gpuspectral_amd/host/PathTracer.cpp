@@ -53,7 +53,25 @@ gsp_camera cameraOf(const Scene& s) {
   c.fov = s.camera.getFov();
   return c;
 }
+gsp_lens lensOf(const Scene& s) {
+  gsp_lens l{};
+  l.struct_size = (uint32_t)sizeof(gsp_lens);
+  l.radius = s.camera.getApertureRadius();
+  if (l.radius != 0.0f) {  // (a pinhole is a pinhole whatever the other fields say: one value, so no resend)
+    l.focus_distance = s.camera.getFocusDistance();
+    l.blades = s.camera.getApertureBlades();
+    l.rotation = s.camera.getApertureRotation();
+  }
+  return l;
+}
 }  // namespace
+
+bool SceneTracker::lensChanged(const Scene& scene, gsp_lens& out) const {
+  out = lensOf(scene);
+  gsp_lens mine = lens;
+  mine.struct_size = out.struct_size;
+  return std::memcmp(&mine, &out, sizeof(out)) != 0;
+}
 
 unsigned SceneTracker::diff(const Scene& scene, std::vector<gsp_instance>& inst) const {
   flattenInstances(scene, inst);
@@ -125,6 +143,11 @@ void PathTracer::reset() {
 // re-bake from the resident meshes + refit of the tree (a rebuild when it has degraded) for an edited transform or material, everything for another object list.
 // Tables go before instances: an instance may name a BSDF the new tables add.
 void PathTracer::prepareScene(const Scene& scene) {
+  gsp_lens lens;
+  if (tracker.lensChanged(scene, lens)) {  // (context state: no scene needed, no drain)
+    check(gsp_set_lens(ctx, &lens), "gsp_set_lens");
+    tracker.rememberLens(lens);
+  }
   std::vector<gsp_instance> inst;
   const unsigned change = tracker.diff(scene, inst);
   if (change == SceneTracker::None) return;
@@ -169,6 +192,13 @@ void PathTracer::render(const Scene& scene, uint32_t spp) {
   }
   check(gsp_render(ctx, &p), "gsp_render");
   timestamp += (int)spp;                    // PathTracer.cpp:92
+}
+
+float PathTracer::focusDistance(const Scene& scene, float fx, float fy) {
+  prepareScene(scene);
+  float d = 0.0f;
+  check(gsp_focus_distance(ctx, width, height, fx, fy, &d), "gsp_focus_distance");
+  return d;
 }
 
 // PathTracer.cpp:9-56: one traceRays(W, H) = one sample per pixel
@@ -217,6 +247,11 @@ void MultiGpuPathTracer::reset() {
 }
 
 void MultiGpuPathTracer::prepareScene(const Scene& scene) {
+  gsp_lens lens;
+  if (tracker.lensChanged(scene, lens)) {
+    check(gsp_multi_set_lens(multi, &lens), "gsp_multi_set_lens");
+    tracker.rememberLens(lens);
+  }
   std::vector<gsp_instance> inst;
   const unsigned change = tracker.diff(scene, inst);
   if (change == SceneTracker::None) return;

@@ -29,11 +29,15 @@ namespace GPUSpectral {
 // date.  Mesh identity is the MeshPtr itself, HELD here: while the tracker holds it no other Mesh can be constructed at
 // that address, so a different scene built in the same stack slot can never be mistaken for the uploaded one.
 struct SceneTracker {
-  enum Change : unsigned { None = 0, CameraChanged = 1, TablesChanged = 2, InstancesChanged = 4, Everything = 8 };
+  enum Change : unsigned { None = 0, CameraChanged = 1, TablesChanged = 2, InstancesChanged = 4, Everything = 8, LensChanged = 16 };
   // what differs between `scene` and the snapshot (Everything: other meshes / object list / textures: a full upload)
   unsigned diff(const Scene& scene, std::vector<gsp_instance>& instances) const;
   void remember(const Scene& scene, const std::vector<gsp_instance>& instances);
   void forget() { valid = false; meshes.clear(); }
+  // the camera's thin lens (Camera::setLens) against the one last sent; context state of its own (gsp_set_lens), so it is
+  // tracked beside the snapshot: a full upload does not resend it, a changed value does
+  bool lensChanged(const Scene& scene, gsp_lens& out) const;
+  void rememberLens(const gsp_lens& l) { lens = l; }
 
  private:
   bool valid = false;
@@ -41,6 +45,7 @@ struct SceneTracker {
   std::vector<gsp_instance> instances;  // transform, emission, bsdf, twofaced, vertex range per object
   std::vector<unsigned char> tables;    // counts + the eight BSDF arrays + the lights, back to back
   gsp_camera camera{};
+  gsp_lens lens{};                      // (zeroed = pinhole = a fresh context's state)
   std::vector<uint64_t> assets;         // dormant features: texture / environment-map sizes, flags, envmap transform
 };
 
@@ -67,6 +72,9 @@ class PathTracer : public RenderPassCreator {
   // Brings the device up to date with `scene` as it is NOW (the reference re-reads it every frame): nothing when nothing
   // changed, gsp_update_camera / _tables / _instances for edits, a full flatten + upload + BVH build for another object list.
   void prepareScene(const Scene& scene);
+  // Autofocus (gsp_focus_distance): brings the device up to date with `scene`, then the camera-space depth of what the pinhole
+  // ray through fragCoord (fx, fy) hits, 0 on a miss: the value for Camera::setLens's focus distance
+  float focusDistance(const Scene& scene, float fx, float fy);
   // Forget what was uploaded: the next pass uploads everything.  Needed only after texel CONTENTS of a texture or
   // environment map were rewritten in place (dormant features; sizes and flags are tracked, contents are not).
   void invalidateScene() { tracker.forget(); }

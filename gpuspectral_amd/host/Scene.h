@@ -139,10 +139,25 @@ class Camera {
   vec3 getPosition() const noexcept { return vec3{toWorld[3][0], toWorld[3][1], toWorld[3][2]}; }
   const mat4& getToWorld() const noexcept { return toWorld; }
   float getFov() const noexcept { return fov; }
+  // thin lens, opt-in (gpuspectral_pt.h "Thin lens"; the reference's camera is a pinhole): aperture radius in camera-space units
+  // (0 = pinhole), distance of the plane of focus along the local z, 0 = circular aperture or 3..16 blades, rotation in radians
+  void setLens(float radius, float focus, uint32_t blades = 0, float rotation = 0.0f) {
+    apertureRadius = radius;
+    focusDistance = focus;
+    apertureBlades = blades;
+    apertureRotation = rotation;
+  }
+  float getApertureRadius() const noexcept { return apertureRadius; }
+  float getFocusDistance() const noexcept { return focusDistance; }
+  uint32_t getApertureBlades() const noexcept { return apertureBlades; }
+  float getApertureRotation() const noexcept { return apertureRotation; }
 
  private:
   mat4 toWorld = mat4::identity();
   float fov = 0.5f;
+  float apertureRadius = 0.0f, focusDistance = 0.0f;
+  uint32_t apertureBlades = 0;
+  float apertureRotation = 0.0f;
 };
 
 struct Scene {

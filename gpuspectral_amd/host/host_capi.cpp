@@ -64,7 +64,7 @@ void* gsph_load_scene_ex(const char* path, const char* asset_dir, int dormant, i
   return b;
 }
 // flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere),
-// 8 = readFilter (the film's <rfilter>)
+// 8 = readFilter (the film's <rfilter>), 16 = readLens (a thinlens sensor's aperture_radius / focus_distance)
 void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned flags) {
   SceneBox* b = nullptr;
   int rc = guard([&] {
@@ -74,6 +74,7 @@ void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned fla
     opt.srgbTextures = (flags & 2u) != 0;
     opt.builtinShapes = (flags & 4u) != 0;
     opt.readFilter = (flags & 8u) != 0;
+    opt.readLens = (flags & 16u) != 0;
     b->scene = loadScene(path, asset_dir ? asset_dir : "", opt);
     flattenScene(b->scene, b->flat);
   });
@@ -110,6 +111,17 @@ const char* gsph_scene_warning(void* s, uint32_t i) { return ((SceneBox*)s)->sce
 uint32_t gsph_scene_pixel_filter(void* s, float* param) {
   if (param) *param = ((SceneBox*)s)->scene.pixelFilterParam;
   return ((SceneBox*)s)->scene.pixelFilter;
+}
+// out4 = {aperture radius, focus distance, blades, rotation} of the scene's camera (Camera::setLens)
+void gsph_scene_lens(void* s, float* out4) {
+  const Camera& c = ((SceneBox*)s)->scene.camera;
+  out4[0] = c.getApertureRadius();
+  out4[1] = c.getFocusDistance();
+  out4[2] = (float)c.getApertureBlades();
+  out4[3] = c.getApertureRotation();
+}
+void gsph_scene_set_lens(void* s, float radius, float focus, uint32_t blades, float rotation) {
+  ((SceneBox*)s)->scene.camera.setLens(radius, focus, blades, rotation);
 }
 uint32_t gsph_scene_num_materials(void* s) { return (uint32_t)((SceneBox*)s)->scene.materials.size(); }
 

@@ -47,6 +47,18 @@ class PathTracerHip : public RenderPassCreator {
   // scenes; call restart() after a change, or the running mean mixes filtered and unfiltered samples
   uint32_t pixelFilter = GSP_FILTER_NONE;
   float pixelFilterParam = 0.0f;
+  // depth of field, opt-in (gpuspectral_pt.h "Thin lens"): context state like the camera -- it holds until changed and needs no
+  // wait; radius 0 = the reference's pinhole.  autofocus() = the camera-space depth under fragCoord (fx, fy), 0 on a miss: the
+  // value for setLens's focus distance.  Call restart() after a change, or the running mean mixes sharp and defocused samples
+  void setLens(float radius, float focusDistance, uint32_t blades = 0, float rotation = 0.0f) {
+    gsp_lens l{(uint32_t)sizeof(gsp_lens), radius, focusDistance, blades, rotation};
+    check(gsp_set_lens(ctx, &l));
+  }
+  float autofocus(float fx, float fy) {
+    float d = 0.0f;
+    check(gsp_focus_distance(ctx, width, height, fx, fy, &d));
+    return d;
+  }
   void restart() {                                                // a viewer that wants a fresh running mean after an edit
     timestamp = 0;
     check(gsp_frame_begin(ctx, width, height, nullptr, 0));

@@ -10,10 +10,15 @@
 //   pixel gets; a pixel stops at the first checkpoint where its relative standard error is <= T
 //   --filter none|box|tent[:r]|gaussian[:s]: pixel filter (gsp_render_params.pixel_filter / _param: anti-aliasing by sub-pixel
 //   jitter drawn from the filter); --scene-filter: LoadOptions::readFilter (the film's <rfilter>; --filter other than none wins)
+//   --aperture R --focus-distance D | --focus-pixel X,Y [--blades N[:rot_deg]]: thin lens (gsp_set_lens; depth of field).
+//   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
+//   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -31,6 +36,14 @@ int main(int argc, char** argv) {
   uint32_t adaptiveMin = 0, adaptiveStep = 0;
   uint32_t filter = GSP_FILTER_NONE;
   float filterParam = 0.0f;
+  float aperture = -1.0f, focusDistance = -1.0f, focusX = 0.0f, focusY = 0.0f, bladeRotation = 0.0f;  // (-1 = not given)
+  bool focusPixel = false;
+  int blades = -1;
+  auto parseFloat = [](const char* s, float& out) {
+    char* e = nullptr;
+    out = std::strtof(s, &e);
+    return e != s && *e == 0 && std::isfinite(out);
+  };
   while (argc > 1 && argv[1][0] == '-' && argv[1][1] == '-') {
     const std::string flag = argv[1];
     int used = 1;
@@ -43,6 +56,43 @@ int main(int argc, char** argv) {
     else if (flag == "--adaptive-min" && argc > 2) adaptiveMin = (uint32_t)std::strtoul(argv[2], nullptr, 10), used = 2;
     else if (flag == "--adaptive-step" && argc > 2) adaptiveStep = (uint32_t)std::strtoul(argv[2], nullptr, 10), used = 2;
     else if (flag == "--scene-filter") options.readFilter = true;
+    else if (flag == "--scene-lens") options.readLens = true;
+    else if (flag == "--aperture" && argc > 2) {
+      if (!parseFloat(argv[2], aperture) || aperture < 0.0f) {
+        std::fprintf(stderr, "gsp_render: bad aperture '%s' (expected a radius >= 0)\n", argv[2]);
+        return 2;
+      }
+      used = 2;
+    } else if (flag == "--focus-distance" && argc > 2) {
+      if (!parseFloat(argv[2], focusDistance) || !(focusDistance > 0.0f)) {
+        std::fprintf(stderr, "gsp_render: bad focus distance '%s' (expected a distance > 0)\n", argv[2]);
+        return 2;
+      }
+      used = 2;
+    } else if (flag == "--focus-pixel" && argc > 2) {
+      const std::string v = argv[2];
+      const size_t comma = v.find(',');
+      if (comma == std::string::npos || !parseFloat(v.substr(0, comma).c_str(), focusX) || !parseFloat(v.c_str() + comma + 1, focusY)) {
+        std::fprintf(stderr, "gsp_render: bad focus pixel '%s' (expected X,Y)\n", argv[2]);
+        return 2;
+      }
+      focusPixel = true;
+      used = 2;
+    } else if (flag == "--blades" && argc > 2) {
+      const std::string v = argv[2];
+      const size_t colon = v.find(':');
+      char* e = nullptr;
+      const std::string nstr = v.substr(0, colon);
+      const long n = std::strtol(nstr.c_str(), &e, 10);
+      float deg = 0.0f;
+      if (e == nstr.c_str() || *e != 0 || !(n == 0 || (n >= 3 && n <= 16)) || (colon != std::string::npos && !parseFloat(v.c_str() + colon + 1, deg))) {
+        std::fprintf(stderr, "gsp_render: bad blades '%s' (expected 0 or 3..16, optionally :rotation in degrees)\n", argv[2]);
+        return 2;
+      }
+      blades = (int)n;
+      bladeRotation = deg * 3.14159265358979323846f / 180.0f;
+      used = 2;
+    }
     else if (flag == "--filter" && argc > 2) {
       const std::string v = argv[2];
       const size_t colon = v.find(':');
@@ -72,8 +122,12 @@ int main(int argc, char** argv) {
     argc -= used;
     argv += used;
   }
+  if (aperture > 0.0f && !(focusDistance > 0.0f) && !focusPixel && !options.readLens) {
+    std::fprintf(stderr, "gsp_render: --aperture needs --focus-distance D, --focus-pixel X,Y or --scene-lens\n");
+    return 2;
+  }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -109,6 +163,19 @@ int main(int argc, char** argv) {
   try {
     Scene scene = loadScene(argv[1], "", options);
     for (auto& w : scene.warnings) std::fprintf(stderr, "WARN: %s\n", w.c_str());
+    // thin lens: the scene's (--scene-lens), overridden flag by flag
+    if (aperture >= 0.0f || focusDistance > 0.0f || blades >= 0 || focusPixel) {
+      float fd = focusDistance > 0.0f ? focusDistance : scene.camera.getFocusDistance();
+      if (focusPixel) {  // autofocus on one GPU, before the renderer proper is set up
+        PathTracer af(width, height, devices[0], {}, &ctxOptions);
+        fd = af.focusDistance(scene, focusX, focusY);
+        if (!(fd > 0.0f)) throw std::runtime_error("--focus-pixel: the ray through that pixel hits nothing");
+        std::printf("focus distance %g (pixel %g,%g)\n", fd, focusX, focusY);
+      }
+      scene.camera.setLens(aperture >= 0.0f ? aperture : scene.camera.getApertureRadius(), fd,
+                           blades >= 0 ? (uint32_t)blades : scene.camera.getApertureBlades(),
+                           blades >= 0 ? bladeRotation : scene.camera.getApertureRotation());
+    }
     std::vector<float> img;
     gsp_stats st;
     double s;

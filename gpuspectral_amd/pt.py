@@ -27,6 +27,8 @@ EXPORTS = (
     "gsp_update_camera",
     "gsp_update_instances",
     "gsp_update_tables",
+    "gsp_set_lens",
+    "gsp_focus_distance",
     "gsp_frame_begin",
     "gsp_render",
     "gsp_download_pixel_stats",
@@ -49,6 +51,7 @@ EXPORTS = (
     "gsp_multi_num_shares",
     "gsp_multi_upload_scene",
     "gsp_multi_update_camera",
+    "gsp_multi_set_lens",
     "gsp_multi_update_instances",
     "gsp_multi_update_tables",
     "gsp_multi_frame_begin",
@@ -95,6 +98,9 @@ def load():
     L.gsp_default_ctx_options.restype = None
     L.gsp_ctx_create_ex.argtypes = [C.c_int, C.POINTER(abi.CtxOptions), C.POINTER(vp)]
     L.gsp_update_camera.argtypes = [vp, C.POINTER(abi.Camera)]
+    L.gsp_set_lens.argtypes = [vp, C.POINTER(abi.Lens)]
+    L.gsp_focus_distance.argtypes = [vp, u32, u32, C.c_float, C.c_float, C.POINTER(C.c_float)]
+    L.gsp_multi_set_lens.argtypes = [vp, C.POINTER(abi.Lens)]
     L.gsp_update_instances.argtypes = [vp, vp, u32]
     L.gsp_update_tables.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_ctx_destroy.argtypes = [vp]
@@ -239,6 +245,19 @@ class Context:
             cam.to_world[i] = float(v)
         cam.fov = float(fov)
         self._check(self._L.gsp_update_camera(self._h, C.byref(cam)), "gsp_update_camera")
+
+    def set_lens(self, radius=0.0, focus_distance=0.0, blades=0, rotation=0.0, lens=None):
+        """gsp_set_lens: thin-lens depth of field (gpuspectral_pt.h "Thin lens").  Context state: holds until changed; radius 0
+        (or no argument) = the pinhole.  lens: an abi.Lens to pass as it is (None with no other argument = NULL)."""
+        if lens is None:
+            lens = abi.lens(radius, focus_distance, blades, rotation)
+        self._check(self._L.gsp_set_lens(self._h, C.byref(lens)), "gsp_set_lens")
+
+    def focus_distance(self, width, height, fx, fy):
+        """gsp_focus_distance: camera-space depth of what the pinhole ray through fragCoord (fx, fy) hits, 0.0 on a miss."""
+        out = C.c_float(0.0)
+        self._check(self._L.gsp_focus_distance(self._h, width, height, fx, fy, C.byref(out)), "gsp_focus_distance")
+        return np.float32(out.value)
 
     def update_instances(self, instances):
         """gsp_update_instances: abi.INSTANCE_DT records (same count and vertex ranges as the uploaded scene)."""
@@ -398,6 +417,12 @@ class MultiContext:
             cam.to_world[i] = float(v)
         cam.fov = float(fov)
         self._check(self._L.gsp_multi_update_camera(self._h, C.byref(cam)), "gsp_multi_update_camera")
+
+    def set_lens(self, radius=0.0, focus_distance=0.0, blades=0, rotation=0.0, lens=None):
+        """gsp_multi_set_lens: Context.set_lens on every share."""
+        if lens is None:
+            lens = abi.lens(radius, focus_distance, blades, rotation)
+        self._check(self._L.gsp_multi_set_lens(self._h, C.byref(lens)), "gsp_multi_set_lens")
 
     def update_instances(self, instances):
         inst = np.ascontiguousarray(instances, abi.INSTANCE_DT)

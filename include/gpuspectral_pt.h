@@ -64,7 +64,9 @@ extern "C" {
                              7: gsp_render_params.nee -> disable_nee (a zeroed struct is the reference as shipped),
                                 gsp_stats.shadow_stat_no_triangle;
                              9: adaptive sampling: gsp_render_params.adaptive_threshold / _min_spp / _step,
-                                gsp_download_pixel_stats, gsp_stats.adaptive_rounds / adaptive_active_pixels */
+                                gsp_download_pixel_stats, gsp_stats.adaptive_rounds / adaptive_active_pixels;
+                                additions within version 9 (new exports only, no struct changed): gsp_set_lens,
+                                gsp_multi_set_lens, gsp_focus_distance (see "Thin lens") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -514,6 +516,52 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* params);
  * order), num_pixels entries each; either pointer may be NULL.  GSP_ERR_INVALID on a frame that is not adaptive. */
 int gsp_download_pixel_stats(gsp_context* ctx, float* second_moment, uint32_t* spp);
 
+/*
+ * Thin lens: opt-in depth of field.
+ *
+ * The reference's camera is a pinhole (raygen.rgen has no lens code) and its loader ignores a `thinlens` sensor's parameters.
+ * The lens is CONTEXT STATE, like the camera: it holds until changed, survives gsp_update_camera, gsp_frame_begin and
+ * gsp_upload_scene, needs no drain (paths in flight have left the camera behind) and may change between the gsp_render calls of
+ * one frame; a change takes effect with the next gsp_render.  gsp_set_lens(ctx, NULL) and radius == 0 are the pinhole: the
+ * reference, bit for bit, whatever the other fields hold.  struct_size follows the rule of gsp_render_params: fields beyond it are
+ * taken as 0.  GSP_ERR_INVALID (text at gsp_last_error) for: a non-finite or negative radius; radius > 0 with a focus distance
+ * that is not finite and positive; blades outside {0, 3..16}; a non-finite rotation.
+ *
+ * Camera ray.  The pinhole ray of fragCoord (fx, fy) is v = (-(fx - W/2), fy - H/2, zplane), dir = flipY(M * normalize(v)),
+ * origin = eye (M = the upper 3x3 of to_world, flipY negates y).  With a lens point l = (lx, ly, 0) in camera space and
+ * s = focus_distance / zplane (formed once on the host, like zplane):
+ *     pf     = (v.x * s, v.y * s, focus_distance)       the pinhole ray's point on the plane of focus
+ *     dir    = flipY(M * normalize(pf - l))
+ *     origin = eye + flipY(M * l)
+ * Offset and direction go through the same linear map, so all lens rays of one fragCoord meet on the plane of focus where the
+ * pinhole ray crosses it.  All arithmetic is float32 in the order written.
+ *
+ * Draws.  u3 = randUniform(), then u4 = randUniform(), from rngState directly after the pixel filter's two draws (directly after
+ * pcgHash(tea(..)) when the filter is NONE); prd.seed is the state AFTER them.  Radius 0 draws nothing.
+ *   blades == 0  circle: Shirley's concentric map of (u3, u4) (the one of rayhit.rchit:89-111), times radius.
+ *   blades == n  regular polygon inscribed in the circle, vertices v_j = radius * (cos, sin)(rotation + (2 pi j) / n), j = 0..n-1,
+ *                v_n = v_0:  t = u3 * n, k = min((uint)t, n - 1), a = sqrt(t - k), b = u4,
+ *                l = a * ((1 - b) * v_k + b * v_{k+1}).
+ * Both are uniform over the aperture.  sin and cos are the library's deterministic functions, sqrt is correctly rounded.
+ *
+ * A call with radius > 0 traces every camera ray, exactly as a filtered call does: the primary-hit memo is neither read nor
+ * touched, gsp_stats.memoised_rays does not grow, and a later pinhole call of the same frame reuses the memo.  The lens composes
+ * with pixel filters, adaptive sampling, pixel_ids shares and gsp_multi_render (gsp_multi_set_lens sets it on every share).
+ */
+typedef struct gsp_lens {
+  uint32_t struct_size;   /* sizeof(gsp_lens) of the host's header; same rule as gsp_render_params */
+  float radius;           /* aperture radius in camera-space units; 0 = pinhole = the reference, bit for bit */
+  float focus_distance;   /* distance of the plane of focus along the camera's local z; > 0 when radius > 0 */
+  uint32_t blades;        /* 0 = circular aperture; 3..16 = regular polygon inscribed in the circle */
+  float rotation;         /* radians, angle of polygon vertex 0 */
+} gsp_lens;
+int gsp_set_lens(gsp_context* ctx, const gsp_lens* lens); /* NULL = pinhole */
+/* Autofocus: traces the pinhole ray through fragCoord (fx, fy) of a width x height frame against the uploaded scene (the
+ * closest-hit path of gsp_trace) and writes the hit's camera-space depth t * normalize(v).z -- the value to put into
+ * gsp_lens.focus_distance -- or 0 on a miss.  Not affected by the current lens or pixel filter; needs no gsp_frame_begin.
+ * Completes the samples already queued first, like gsp_sync. */
+int gsp_focus_distance(gsp_context* ctx, uint32_t width, uint32_t height, float fx, float fy, float* out);
+
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
 
@@ -584,6 +632,7 @@ int gsp_multi_num_shares(const gsp_multi* m);
 int gsp_multi_upload_scene(gsp_multi* m, const gsp_scene_desc* scene);
 /* (ABI 5) gsp_update_camera / _instances / _tables on every share */
 int gsp_multi_update_camera(gsp_multi* m, const gsp_camera* camera);
+int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens); /* gsp_set_lens on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);
 int gsp_multi_update_tables(gsp_multi* m, const gsp_scene_desc* scene);
 int gsp_multi_frame_begin(gsp_multi* m, uint32_t width, uint32_t height);
