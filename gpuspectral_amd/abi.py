@@ -166,6 +166,39 @@ def lens(radius=0.0, focus_distance=0.0, blades=0, rotation=0.0):
     return Lens(C.sizeof(Lens), radius, focus_distance, blades, rotation)
 
 
+# LDR film (include/gpuspectral_pt.h "LDR film")
+TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
+TONEMAP_NAMES = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}
+
+
+class Display(C.Structure):
+    """gsp_display: how gsp_download_display / gsp_peek_display turn the accumulate buffer into RGBA8; all zero = clamp + sRGB."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("tonemap", C.c_uint32),  # TONEMAP_*
+        ("exposure", C.c_float),  # f-stops
+        ("gamma", C.c_float),  # > 0: v^(1/gamma); 0 = the sRGB curve
+        ("key", C.c_float),  # Reinhard; 0 = 0.18
+        ("burn", C.c_float),
+        ("log_avg_luminance", C.c_float),  # Reinhard: > 0 = use this value, 0 = measure the frame
+        ("max_luminance", C.c_float),
+    ]
+
+
+def display(tonemap=TONEMAP_CLAMP, exposure=0.0, gamma=0.0, key=0.0, burn=0.0, log_avg_luminance=0.0, max_luminance=0.0):
+    return Display(C.sizeof(Display), tonemap, exposure, gamma, key, burn, log_avg_luminance, max_luminance)
+
+
+class Luminance(C.Structure):
+    """gsp_luminance: the frame statistics of the Reinhard operator (gsp_frame_luminance)."""
+
+    _fields_ = [("log_sum_q20", C.c_int64), ("pixels", C.c_uint64), ("log_avg", C.c_float), ("max", C.c_float)]
+
+    def as_dict(self):
+        return dict(log_sum_q20=int(self.log_sum_q20), pixels=int(self.pixels), log_avg=float(self.log_avg), max=float(self.max))
+
+
 # gsp_render_params.pixel_filter (GSP_FILTER_*, include/gpuspectral_pt.h "Pixel filter")
 FILTER_NONE, FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN = 0, 1, 2, 3
 FILTER_NAMES = {"none": FILTER_NONE, "box": FILTER_BOX, "tent": FILTER_TENT, "gaussian": FILTER_GAUSSIAN}

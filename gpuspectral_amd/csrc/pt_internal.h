@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/gpuspectral_pt.h"
+#include "pt_display.h"
 #include "pt_stages.h"
 
 namespace gsp {
@@ -67,6 +68,13 @@ struct BuildInput {
 __attribute__((visibility("hidden"))) int gsp_internal_accum(gsp_context* ctx, void** accum, uint64_t* num_pixels, hipStream_t* stream);
 // The options a context was created with, defaults filled in (pt_multi.hip divides memory_share among the shares of a device).
 __attribute__((visibility("hidden"))) void gsp_internal_resolve_options(const gsp_ctx_options* in, gsp_ctx_options* out);
+
+// ---- LDR film (pt_display.h) on `n` RGBA32F records at `src`, device memory of the current device; both queue on `stream` ----
+// display_measure: the frame statistics through the 24-byte device record `d_rec` and its pinned host mirror `h_rec`;
+// synchronises the stream.  display_map: `n` RGBA8 words into `dst` (device, 16-byte aligned); does not synchronise.
+__attribute__((visibility("hidden"))) hipError_t display_measure(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, DisplayStatsRec* d_rec,
+                                                                 DisplayStatsRec* h_rec, gsp_luminance* out);
+__attribute__((visibility("hidden"))) hipError_t display_map(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, const DisplayConsts& k, uint32_t* dst);
 
 // Bakes the instances' triangles to world space and builds the wide BVH (PLOC + reinsertion + collapse) on `stream`.
 // Returns GSP_OK or an error code with `err` set.

@@ -106,6 +106,10 @@ struct gsp_multi {
   q4* frame = nullptr;       // width * height
   uint32_t* d_ids = nullptr; // all shares' pixel ids back to back
   size_t frame_pixels = 0;
+  // LDR film on the gathered frame (gsp_multi_download_display): RGBA8 frame, statistics record + pinned mirror, made on first use
+  uint32_t* d_display = nullptr;
+  DisplayStatsRec* d_display_rec = nullptr;
+  DisplayStatsRec* h_display_rec = nullptr;
   std::string err;
   // RCCL: one communicator rank per share (device lists without repeats), ranks = share indices
   std::vector<ncclComm_t> comms;
@@ -167,6 +171,11 @@ void free_frame(gsp_multi* m) {
   if (m->staging) (void)hipFree(m->staging);
   if (m->frame) (void)hipFree(m->frame);
   if (m->d_ids) (void)hipFree(m->d_ids);
+  if (m->d_display) (void)hipFree(m->d_display);
+  if (m->d_display_rec) (void)hipFree(m->d_display_rec);
+  if (m->h_display_rec) (void)hipHostFree(m->h_display_rec);
+  m->d_display = nullptr;
+  m->d_display_rec = m->h_display_rec = nullptr;
   m->staging = m->frame = nullptr;
   m->d_ids = nullptr;
   m->have_frame = false;
@@ -527,6 +536,41 @@ int gsp_multi_download(gsp_multi* m, float* out_rgba) {
   if (rc != GSP_OK) return rc;
   MULTI_TRY(m, hipSetDevice(m->devices[0]));
   MULTI_TRY(m, hipMemcpyAsync(out_rgba, m->frame, m->frame_pixels * sizeof(q4), hipMemcpyDeviceToHost, m->stream));
+  MULTI_TRY(m, hipStreamSynchronize(m->stream));
+  return GSP_OK;
+}
+
+int gsp_multi_download_display(gsp_multi* m, const gsp_display* display, uint32_t* out_rgba8) {
+  if (!m) return GSP_ERR_INVALID;
+  if (!out_rgba8 || !m->have_frame) {
+    m->err = !out_rgba8 ? "gsp_multi_download_display: null output buffer" : "gsp_multi_download_display needs gsp_multi_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  if (m->ctx.size() == 1 && !m->use_rccl) {
+    int rc = gsp_download_display(m->ctx[0], display, out_rgba8);
+    if (rc != GSP_OK) m->err = gsp_last_error(m->ctx[0]);
+    return rc;
+  }
+  gsp_display d;
+  if (const char* why = resolve_display(display, d)) {
+    m->err = why;
+    return GSP_ERR_INVALID;
+  }
+  int rc = gsp_multi_gather(m, nullptr);
+  if (rc != GSP_OK) return rc;
+  MULTI_TRY(m, hipSetDevice(m->devices[0]));
+  int cus = 256;
+  MULTI_TRY(m, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->devices[0]));
+  // every pixel of the gathered frame belongs to one share: the statistics cover the whole frame
+  gsp_luminance lum{};
+  if (display_needs_stats(d)) {
+    if (!m->d_display_rec) MULTI_TRY(m, hipMalloc((void**)&m->d_display_rec, sizeof(DisplayStatsRec)));
+    if (!m->h_display_rec) MULTI_TRY(m, hipHostMalloc((void**)&m->h_display_rec, sizeof(DisplayStatsRec), hipHostMallocDefault));
+    MULTI_TRY(m, display_measure(m->stream, (uint32_t)cus, m->frame, m->frame_pixels, m->d_display_rec, m->h_display_rec, &lum));
+  }
+  if (!m->d_display) MULTI_TRY(m, hipMalloc((void**)&m->d_display, (m->frame_pixels + 3) / 4 * 4 * sizeof(uint32_t)));
+  MULTI_TRY(m, display_map(m->stream, (uint32_t)cus, m->frame, m->frame_pixels, display_consts(d, lum), m->d_display));
+  MULTI_TRY(m, hipMemcpyAsync(out_rgba8, m->d_display, m->frame_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   MULTI_TRY(m, hipStreamSynchronize(m->stream));
   return GSP_OK;
 }

@@ -138,6 +138,10 @@ struct gsp_context {
   uint8_t* h_stage[2] = {nullptr, nullptr};
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   bool stage_warm = false;  // the staging buffers have been through one copy + one host read (gsp_frame_begin)
+  // LDR film (gsp_*_display, gsp_frame_luminance): the RGBA8 frame on the device, the statistics record and its pinned mirror
+  DevBuf<uint32_t> display_out;
+  DevBuf<DisplayStatsRec> display_rec;
+  DisplayStatsRec* h_display_rec = nullptr;
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;
@@ -493,6 +497,7 @@ void gsp_ctx_destroy(gsp_context* ctx) {
     if (ctx->h_stage[k]) (void)hipHostFree(ctx->h_stage[k]);
     if (ctx->stage_ev[k]) (void)hipEventDestroy(ctx->stage_ev[k]);
   }
+  if (ctx->h_display_rec) (void)hipHostFree(ctx->h_display_rec);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

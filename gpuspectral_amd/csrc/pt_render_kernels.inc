@@ -987,6 +987,62 @@ __global__ __launch_bounds__(kBlock) void k_retire_triangles(uint32_t num_tris, 
   }
 }
 
+// ---- LDR film (pt_display.h; include/gpuspectral_pt.h "LDR film") ------------------------------------------------
+// Frame statistics: grid-stride over the compact RGBA32F buffer, one 16-byte load per lane; (sum of q, count, max Y) are reduced
+// over the wave and reach the 24-byte record with two 64-bit atomic adds and one 32-bit atomic max per wave.  The sum is an
+// integer and the max is taken on non-negative float bit patterns, so the record does not depend on the launch shape.
+__global__ __launch_bounds__(kBlock) void k_display_stats(const v4f* __restrict__ src, uint64_t n, DisplayStatsRec* __restrict__ rec) {
+  long long s = 0;
+  uint32_t c = 0, m = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const v4f v = src[i];
+    long long q;
+    float Y;
+    if (display_stat(v.x, v.y, v.z, q, Y)) {
+      s += q;
+      c += 1u;
+      m = max(m, fb(Y));  // Y >= 0 and finite: its bit pattern orders like its value
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o);
+    c += __shfl_xor(c, o);
+    m = max(m, (uint32_t)__shfl_xor((int)m, o));
+  }
+  if ((threadIdx.x & 63u) == 0u && c != 0u) {
+    atomicAdd(&rec->sum, (unsigned long long)s);
+    atomicAdd(&rec->count, (unsigned long long)c);
+    atomicMax(&rec->max_bits, m);
+  }
+}
+
+// Tone map + encode: each lane converts four consecutive pixels (four 16-byte loads, one 16-byte store); the last group of a
+// buffer whose length is not a multiple of four stores its words one by one.  The curve and the encode are template parameters:
+// the CLAMP + gamma instantiation carries no Reinhard registers.
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+template <uint32_t TONEMAP, bool SRGB>
+__global__ __launch_bounds__(kBlock) void k_display_map(const v4f* __restrict__ src, uint64_t n, DisplayConsts k, uint32_t* __restrict__ dst) {
+  const uint64_t groups = (n + 3) / 4;
+  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < groups; g += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t base = 4 * g;
+    if (base + 4 <= n) {
+      const v4f a = src[base], b = src[base + 1], c = src[base + 2], d = src[base + 3];
+      v4u o;
+      o.x = display_pixel_t<TONEMAP, SRGB>(a.x, a.y, a.z, k);
+      o.y = display_pixel_t<TONEMAP, SRGB>(b.x, b.y, b.z, k);
+      o.z = display_pixel_t<TONEMAP, SRGB>(c.x, c.y, c.z, k);
+      o.w = display_pixel_t<TONEMAP, SRGB>(d.x, d.y, d.z, k);
+      *(v4u*)(dst + base) = o;
+    } else {
+      for (uint64_t i = base; i < n; ++i) {
+        const v4f a = src[i];
+        dst[i] = display_pixel_t<TONEMAP, SRGB>(a.x, a.y, a.z, k);
+      }
+    }
+  }
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

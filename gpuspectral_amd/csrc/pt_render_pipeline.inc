@@ -808,10 +808,12 @@ static int ensure_read_back_stage(gsp_context* ctx) {
   return GSP_OK;
 }
 // the accumulate buffer -> caller's host memory, through the two pinned staging buffers (gsp_context::h_stage)
-static int read_back_frame(gsp_context* ctx, float* out) {
-  const size_t total = ctx->num_pixels * sizeof(q4);
+static int read_back_bytes(gsp_context* ctx, const void* device_src, size_t total, void* out);
+static int read_back_frame(gsp_context* ctx, float* out) { return read_back_bytes(ctx, ctx->accum.p, ctx->num_pixels * sizeof(q4), out); }
+// (the same for any device buffer of the context: the RGBA8 frame of the LDR film goes through the same two staging buffers)
+static int read_back_bytes(gsp_context* ctx, const void* device_src, size_t total, void* out) {
   if (total <= gsp_context::kStageBytes / 4) {  // small frames: one plain copy
-    CTX_TRY(ctx, hipMemcpyAsync(out, ctx->accum.p, total, hipMemcpyDeviceToHost, ctx->stream));
+    CTX_TRY(ctx, hipMemcpyAsync(out, device_src, total, hipMemcpyDeviceToHost, ctx->stream));
     CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GSP_OK;
   }
@@ -820,7 +822,7 @@ static int read_back_frame(gsp_context* ctx, float* out) {
     if (rc_ != GSP_OK) return rc_;
   }
   const size_t chunks = (total + gsp_context::kStageBytes - 1) / gsp_context::kStageBytes;
-  const uint8_t* src = (const uint8_t*)ctx->accum.p;
+  const uint8_t* src = (const uint8_t*)device_src;
   auto bytes_of = [&](size_t c) { return std::min(gsp_context::kStageBytes, total - c * gsp_context::kStageBytes); };
   CTX_TRY(ctx, hipMemcpyAsync(ctx->h_stage[0], src, bytes_of(0), hipMemcpyDeviceToHost, ctx->stream));
   CTX_TRY(ctx, hipEventRecord(ctx->stage_ev[0], ctx->stream));
@@ -1045,6 +1047,137 @@ int gsp_focus_distance(gsp_context* ctx, uint32_t width, uint32_t height, float 
   int rc_ = gsp_trace(ctx, ray, 1, 0, &hit);
   if (rc_ != GSP_OK) return rc_;
   *out = hit.prim < 0 ? 0.0f : hit.t * cosz;
+  return GSP_OK;
+}
+
+
+}  // extern "C"
+
+// ---- LDR film (include/gpuspectral_pt.h, "LDR film"; per-pixel code: pt_display.h) ----
+hipError_t gsp::display_measure(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, DisplayStatsRec* d_rec, DisplayStatsRec* h_rec,
+                                gsp_luminance* out) {
+  hipError_t e = hipMemsetAsync(d_rec, 0, sizeof(DisplayStatsRec), stream);
+  if (e != hipSuccess) return e;
+  if (n) {
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 4));
+    hipLaunchKernelGGL(k_display_stats, dim3(grid), dim3(kBlock), 0, stream, (const v4f*)src, n, d_rec);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if ((e = hipMemcpyAsync(h_rec, d_rec, sizeof(DisplayStatsRec), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+  *out = display_luminance(*h_rec);
+  return hipSuccess;
+}
+
+hipError_t gsp::display_map(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, const DisplayConsts& k, uint32_t* dst) {
+  if (n == 0) return hipSuccess;
+  const uint64_t groups = (n + 3) / 4;
+  const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((groups + kBlock - 1) / kBlock, (uint64_t)num_cus * 8))), block(kBlock);
+  const v4f* s = (const v4f*)src;
+#define GSP_DISPLAY_LAUNCH(T, S) hipLaunchKernelGGL((k_display_map<T, S>), grid, block, 0, stream, s, n, k, dst)
+  if (k.srgb) {
+    if (k.tonemap == GSP_TONEMAP_ACES) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_ACES, true);
+    else if (k.tonemap == GSP_TONEMAP_REINHARD) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_REINHARD, true);
+    else GSP_DISPLAY_LAUNCH(GSP_TONEMAP_CLAMP, true);
+  } else {
+    if (k.tonemap == GSP_TONEMAP_ACES) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_ACES, false);
+    else if (k.tonemap == GSP_TONEMAP_REINHARD) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_REINHARD, false);
+    else GSP_DISPLAY_LAUNCH(GSP_TONEMAP_CLAMP, false);
+  }
+#undef GSP_DISPLAY_LAUNCH
+  return hipGetLastError();
+}
+
+// gsp_peek's ordering: the folds queued so far finish, the paths in flight keep their state
+static int display_peek_sync(gsp_context* ctx, uint32_t* samples_folded) {
+  uint32_t folded = 0xffffffffu;
+  for (uint32_t l = 0; l < ctx->num_lanes; ++l) {
+    gsp_context::Lane& L = ctx->lanes[l];
+    if (L.num_pixels == 0) continue;
+    CTX_TRY(ctx, hipStreamSynchronize(L.stream));
+    folded = std::min(folded, ctx->pipe_active && L.pipe.active ? L.pipe.folded_end : ctx->folded_idle);
+  }
+  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : folded;
+  return GSP_OK;
+}
+
+static int display_measure_ctx(gsp_context* ctx, gsp_luminance* out) {
+  CTX_TRY(ctx, ctx->display_rec.ensure(1, &ctx->bytes));
+  if (!ctx->h_display_rec) CTX_TRY(ctx, hipHostMalloc((void**)&ctx->h_display_rec, sizeof(DisplayStatsRec), hipHostMallocDefault));
+  CTX_TRY(ctx, display_measure(ctx->stream, (uint32_t)ctx->num_cus, ctx->accum.p, ctx->num_pixels, ctx->display_rec.p, ctx->h_display_rec, out));
+  return GSP_OK;
+}
+
+// validates `display_host`, measures the frame where the display asks for it and queues the map of the compact accumulate
+// buffer into `dst` (device, 16-byte aligned; nullptr = the context's own RGBA8 buffer) on ctx->stream
+static int display_run(gsp_context* ctx, const gsp_display* display_host, uint32_t* dst) {
+  gsp_display d;
+  if (const char* why = resolve_display(display_host, d)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  gsp_luminance lum{};
+  if (display_needs_stats(d)) {
+    int rc = display_measure_ctx(ctx, &lum);
+    if (rc != GSP_OK) return rc;
+  }
+  if (!dst) {
+    CTX_TRY(ctx, ctx->display_out.ensure((ctx->num_pixels + 3) / 4 * 4, &ctx->bytes));
+    dst = ctx->display_out.p;
+  }
+  CTX_TRY(ctx, display_map(ctx->stream, (uint32_t)ctx->num_cus, ctx->accum.p, ctx->num_pixels, display_consts(d, lum), dst));
+  return GSP_OK;
+}
+
+extern "C" {
+
+int gsp_frame_luminance(gsp_context* ctx, int drain, gsp_luminance* out) {
+  if (!ctx || !out || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain ? pipeline_drain(ctx) : display_peek_sync(ctx, nullptr);
+  if (rc != GSP_OK) return rc;
+  return display_measure_ctx(ctx, out);
+}
+
+int gsp_peek_display(gsp_context* ctx, const gsp_display* display, uint32_t* out, uint32_t* samples_folded) {
+  if (!ctx || !out || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = display_peek_sync(ctx, samples_folded);
+  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
+}
+
+int gsp_peek_display_to_device(gsp_context* ctx, const gsp_display* display, void* dst, uint64_t bytes, uint32_t* samples_folded) {
+  if (!ctx || !dst || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  if (bytes < ctx->num_pixels * sizeof(uint32_t)) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  int rc = display_peek_sync(ctx, samples_folded);
+  if (rc != GSP_OK) return rc;
+  // the kernel stores 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
+  const bool direct = ((uintptr_t)dst & 15u) == 0;
+  rc = display_run(ctx, display, direct ? (uint32_t*)dst : nullptr);
+  if (rc != GSP_OK) return rc;
+  if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+int gsp_download_display(gsp_context* ctx, const gsp_display* display, uint32_t* out) {
+  if (!ctx || !out || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = pipeline_drain(ctx);
+  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr);
+  if (rc != GSP_OK) return rc;
+  if (!ctx->subset) return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
+  std::vector<uint32_t> tmp(ctx->num_pixels);
+  rc = read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), tmp.data());
+  if (rc != GSP_OK) return rc;
+  std::memset(out, 0, sizeof(uint32_t) * (size_t)ctx->width * ctx->height);
+  for (uint64_t i = 0; i < ctx->num_pixels; ++i) out[ctx->pixel_ids_host[i]] = tmp[i];
   return GSP_OK;
 }
 

@@ -79,6 +79,12 @@ def load():
     L.gsph_write_pfm.argtypes = [C.c_char_p, vp, u32, u32]
     L.gsph_write_ppm.argtypes = [C.c_char_p, vp, u32, u32, C.c_int]
     L.gsph_tone_map.argtypes = [vp, u32, u32, C.c_int, vp]
+    L.gsph_scene_film.argtypes = [vp, C.POINTER(abi.Display)]
+    L.gsph_write_png.argtypes = [C.c_char_p, vp, u32, u32, C.c_int]
+    L.gsph_encode_png.argtypes = [vp, u32, u32, C.c_int, vp, C.POINTER(u64)]
+    L.gsph_decode_png.argtypes = [vp, u64, C.POINTER(u32), C.POINTER(u32), vp]
+    L.gsph_pathtracer_set_display.argtypes = [vp, C.POINTER(abi.Display)]
+    L.gsph_pathtracer_download_display.argtypes = [vp, vp, u64]
     _LIB = L
     return L
 
@@ -98,17 +104,19 @@ class Scene:
     """A C++ GPUSpectral::Scene produced by loadScene (S/engine/Loader.cpp:253-349)."""
 
     def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False,
-                 read_lens=False):
+                 read_lens=False, read_film=False):
         """dormant_features: LoadOptions::dormantFeatures (textures / environment map, SURVEY 8(f).3); builtin_shapes:
         LoadOptions::builtinShapes (`disk` and `sphere` shapes are built instead of skipped, SURVEY 8(f).1); the defaults are
         the reference's behaviour.  read_filter: LoadOptions::readFilter (the film's <rfilter> becomes `pixel_filter`, which
         PathTracer.render applies unless its params name a filter of their own).  read_lens: LoadOptions::readLens (a `thinlens`
-        sensor's aperture_radius / focus_distance become the camera's lens, which PathTracer hands to the device)."""
+        sensor's aperture_radius / focus_distance become the camera's lens, which PathTracer hands to the device).  read_film:
+        LoadOptions::readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn become `film`)."""
         self._L = load()
         ad = asset_dir.encode() if asset_dir else None
-        if builtin_shapes or read_filter or read_lens:
+        if builtin_shapes or read_filter or read_lens or read_film:
             self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) |
-                                                   (4 if builtin_shapes else 0) | (8 if read_filter else 0) | (16 if read_lens else 0))
+                                                   (4 if builtin_shapes else 0) | (8 if read_filter else 0) | (16 if read_lens else 0) |
+                                                   (32 if read_film else 0))
         elif dormant_features:
             self._h = self._L.gsph_load_scene_ex(path.encode(), ad, 1, 1 if srgb_textures else 0)
         else:
@@ -144,6 +152,13 @@ class Scene:
         out = (C.c_float * 4)()
         self._L.gsph_scene_lens(self._h, C.byref(out))
         return float(out[0]), float(out[1]), int(out[2]), float(out[3])
+
+    @property
+    def film(self):
+        """(an ldrfilm was read, abi.Display of Scene::film); (False, clamp + sRGB) without read_film."""
+        d = abi.Display()
+        ldr = self._L.gsph_scene_film(self._h, C.byref(d))
+        return bool(ldr), d
 
     def set_lens(self, radius, focus_distance, blades=0, rotation=0.0):
         """Camera::setLens: the tracer sends it with the next pass (gsp_set_lens) when its value changed."""
@@ -294,6 +309,14 @@ class PathTracer:
         self._check(self._L.gsph_pathtracer_download(self._h, out.ctypes.data, out.size), "download")
         return out
 
+    def download_display(self, display=None):
+        """PathTracer::downloadDisplay with PathTracer::display = `display` (abi.Display; None keeps the current one)."""
+        if display is not None:
+            self._check(self._L.gsph_pathtracer_set_display(self._h, C.byref(display)), "set_display")
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsph_pathtracer_download_display(self._h, out.ctypes.data, out.size), "downloadDisplay")
+        return out
+
     def stats(self):
         s = abi.Stats()
         self._check(self._L.gsph_pathtracer_stats(self._h, C.byref(s)), "stats")
@@ -324,3 +347,36 @@ def write_ppm(path, rgba, aces=False):
     L = load()
     if L.gsph_write_ppm(path.encode(), rgba.ctypes.data, rgba.shape[1], rgba.shape[0], 1 if aces else 0) != 0:
         raise GspError("write_ppm: %s" % _err(L))
+
+
+def encode_png(rgba8, alpha=False):
+    """Image.h encodePng: the PNG file (bytes) of an (H, W) uint32 RGBA8 image, row 0 = top."""
+    rgba8 = np.ascontiguousarray(rgba8, np.uint32)
+    L = load()
+    size = C.c_uint64(0)
+    if L.gsph_encode_png(rgba8.ctypes.data, rgba8.shape[1], rgba8.shape[0], 1 if alpha else 0, None, C.byref(size)) != 0:
+        raise GspError("encode_png: %s" % _err(L))
+    out = np.zeros(size.value, np.uint8)
+    if L.gsph_encode_png(rgba8.ctypes.data, rgba8.shape[1], rgba8.shape[0], 1 if alpha else 0, out.ctypes.data, C.byref(size)) != 0:
+        raise GspError("encode_png: %s" % _err(L))
+    return out.tobytes()
+
+
+def write_png(path, rgba8, alpha=False):
+    rgba8 = np.ascontiguousarray(rgba8, np.uint32)
+    L = load()
+    if L.gsph_write_png(path.encode(), rgba8.ctypes.data, rgba8.shape[1], rgba8.shape[0], 1 if alpha else 0) != 0:
+        raise GspError("write_png: %s" % _err(L))
+
+
+def decode_png(data):
+    """Image.h decodePng: (H, W) uint32 RGBA8 (A = 255), row 0 = BOTTOM image row."""
+    buf = np.frombuffer(data, np.uint8)
+    L = load()
+    w, h = C.c_uint32(), C.c_uint32()
+    if L.gsph_decode_png(buf.ctypes.data, len(buf), C.byref(w), C.byref(h), None) != 0:
+        raise GspError("decode_png: %s" % _err(L))
+    out = np.zeros((h.value, w.value), np.uint32)
+    if L.gsph_decode_png(buf.ctypes.data, len(buf), C.byref(w), C.byref(h), out.ctypes.data) != 0:
+        raise GspError("decode_png: %s" % _err(L))
+    return out

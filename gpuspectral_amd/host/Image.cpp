@@ -289,6 +289,202 @@ Image8 decodePng(const uint8_t* data, size_t size) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// PNG writer: 8-bit RGB / RGBA, non-interlaced, over an own deflate (one block of fixed Huffman codes, RFC 1951 3.2.6, fed by a
+// hash-chain LZ77) inside a zlib stream (RFC 1950) with its Adler-32; CRC-32 per chunk (PNG 5.5)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct LsbWriter {
+  std::vector<uint8_t>& out;
+  uint64_t acc = 0;
+  int n = 0;
+  void put(uint32_t v, int bits) {  // `bits` <= 16, least significant bit first
+    acc |= (uint64_t)v << n;
+    n += bits;
+    while (n >= 8) {
+      out.push_back((uint8_t)(acc & 0xffu));
+      acc >>= 8;
+      n -= 8;
+    }
+  }
+  void code(uint32_t c, int bits) {  // a Huffman code: most significant bit first
+    uint32_t r = 0;
+    for (int i = 0; i < bits; ++i) r |= ((c >> i) & 1u) << (bits - 1 - i);
+    put(r, bits);
+  }
+  void flush() {
+    if (n) out.push_back((uint8_t)(acc & 0xffu));
+    acc = 0;
+    n = 0;
+  }
+};
+
+void fixedSymbol(LsbWriter& w, uint32_t sym) {  // literal / length alphabet of the fixed code
+  if (sym < 144) w.code(0x30 + sym, 8);
+  else if (sym < 256) w.code(0x190 + (sym - 144), 9);
+  else if (sym < 280) w.code(sym - 256, 7);
+  else w.code(0xc0 + (sym - 280), 8);
+}
+
+// (kLenBase / kLenExtra / kDistBase / kDistExtra: the inflate tables above)
+void fixedMatch(LsbWriter& w, uint32_t len, uint32_t dist) {
+  int l = 28;
+  while (kLenBase[l] > len) --l;
+  fixedSymbol(w, 257 + l);
+  if (kLenExtra[l]) w.put(len - kLenBase[l], kLenExtra[l]);
+  int d = 29;
+  while (kDistBase[d] > dist) --d;
+  w.code((uint32_t)d, 5);
+  if (kDistExtra[d]) w.put(dist - kDistBase[d], kDistExtra[d]);
+}
+
+// raw deflate stream of `n` bytes: greedy longest match within a 32-KiB window, chains of at most 64 candidates
+void deflateFixed(const uint8_t* data, size_t n, std::vector<uint8_t>& out) {
+  constexpr size_t kWindow = 32768, kHashSize = 1u << 15, kMaxLen = 258, kMaxChain = 64;
+  LsbWriter w{out};
+  w.put(1, 1);  // BFINAL
+  w.put(1, 2);  // BTYPE = 01: fixed Huffman codes
+  std::vector<int64_t> head(kHashSize, -1), prev(kWindow, -1);
+  auto hash = [&](size_t i) { return ((uint32_t)data[i] * 2654435761u ^ (uint32_t)data[i + 1] * 40503u * 65599u ^ (uint32_t)data[i + 2] * 0x9e3779b1u) >> 17; };
+  auto insert = [&](size_t i) {
+    if (i + 3 > n) return;
+    const uint32_t h = hash(i);
+    prev[i % kWindow] = head[h];
+    head[h] = (int64_t)i;
+  };
+  size_t i = 0;
+  while (i < n) {
+    size_t best = 0, bestDist = 0;
+    if (i + 3 <= n) {
+      int64_t cand = head[hash(i)];
+      const size_t limit = std::min(kMaxLen, n - i);
+      for (size_t chain = 0; cand >= 0 && i - (size_t)cand <= kWindow && chain < kMaxChain; ++chain) {
+        const uint8_t* a = data + cand;
+        const uint8_t* b = data + i;
+        size_t len = 0;
+        while (len < limit && a[len] == b[len]) ++len;
+        if (len > best) {
+          best = len;
+          bestDist = i - (size_t)cand;
+          if (len == limit) break;
+        }
+        const int64_t next = prev[(size_t)cand % kWindow];
+        if (next >= cand) break;  // (the slot has been reused by a newer position: the chain ends here)
+        cand = next;
+      }
+    }
+    if (best >= 3) {
+      fixedMatch(w, (uint32_t)best, (uint32_t)bestDist);
+      for (size_t k = 0; k < best; ++k) insert(i + k);
+      i += best;
+    } else {
+      fixedSymbol(w, data[i]);
+      insert(i);
+      ++i;
+    }
+  }
+  fixedSymbol(w, 256);
+  w.flush();
+}
+
+uint32_t crc32Of(const uint8_t* p, size_t n) {
+  static uint32_t table[256];
+  static bool made = false;
+  if (!made) {
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
+      table[i] = c;
+    }
+    made = true;
+  }
+  uint32_t c = 0xffffffffu;
+  for (size_t i = 0; i < n; ++i) c = table[(c ^ p[i]) & 0xffu] ^ (c >> 8);
+  return c ^ 0xffffffffu;
+}
+
+uint32_t adler32Of(const uint8_t* p, size_t n) {
+  uint32_t a = 1, b = 0;
+  for (size_t i = 0; i < n;) {
+    const size_t end = std::min(n, i + 5552);  // (the largest run for which the sums stay below 2^32)
+    for (; i < end; ++i) {
+      a += p[i];
+      b += a;
+    }
+    a %= 65521u;
+    b %= 65521u;
+  }
+  return (b << 16) | a;
+}
+
+void putBe32(std::vector<uint8_t>& v, uint32_t x) {
+  for (int s = 24; s >= 0; s -= 8) v.push_back((uint8_t)(x >> s));
+}
+
+void pngChunk(std::vector<uint8_t>& file, const char type[4], const std::vector<uint8_t>& body) {
+  putBe32(file, (uint32_t)body.size());
+  const size_t start = file.size();
+  file.insert(file.end(), type, type + 4);
+  file.insert(file.end(), body.begin(), body.end());
+  putBe32(file, crc32Of(file.data() + start, file.size() - start));
+}
+
+}  // namespace
+
+std::vector<uint8_t> encodePng(const uint32_t* rgba8, uint32_t width, uint32_t height, bool alpha) {
+  if (!rgba8 || width == 0 || height == 0 || width > (1u << 15) || height > (1u << 15)) fail("png: size 0 or above 32768");
+  const size_t bpp = alpha ? 4 : 3, stride = (size_t)width * bpp;
+  // scanlines, each behind its filter byte: None, Sub or Up, whichever leaves the smallest sum of absolute residuals (PNG 12.8)
+  std::vector<uint8_t> raw((stride + 1) * height), row(stride), upRow(stride, 0), cand[3];
+  for (auto& c : cand) c.resize(stride);
+  for (uint32_t y = 0; y < height; ++y) {
+    for (uint32_t x = 0; x < width; ++x) {
+      const uint32_t t = rgba8[(size_t)y * width + x];
+      for (size_t c = 0; c < bpp; ++c) row[x * bpp + c] = (uint8_t)(t >> (8 * c));
+    }
+    uint64_t cost[3] = {0, 0, 0};
+    for (size_t x = 0; x < stride; ++x) {
+      cand[0][x] = row[x];
+      cand[1][x] = (uint8_t)(row[x] - (x >= bpp ? row[x - bpp] : 0));
+      cand[2][x] = (uint8_t)(row[x] - upRow[x]);
+      for (int f = 0; f < 3; ++f) cost[f] += (uint64_t)std::abs((int)(int8_t)cand[f][x]);
+    }
+    int f = 0;
+    if (cost[1] < cost[f]) f = 1;
+    if (cost[2] < cost[f]) f = 2;
+    uint8_t* dst = raw.data() + (stride + 1) * y;
+    dst[0] = (uint8_t)f;
+    std::memcpy(dst + 1, cand[f].data(), stride);
+    upRow = row;
+  }
+  std::vector<uint8_t> z;
+  z.push_back(0x78);  // deflate, 32-KiB window
+  z.push_back(0x01);  // (0x7801 is a multiple of 31; no preset dictionary)
+  deflateFixed(raw.data(), raw.size(), z);
+  putBe32(z, adler32Of(raw.data(), raw.size()));
+  std::vector<uint8_t> file = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a}, ihdr;
+  putBe32(ihdr, width);
+  putBe32(ihdr, height);
+  ihdr.push_back(8);                         // bit depth
+  ihdr.push_back((uint8_t)(alpha ? 6 : 2));  // colour type: RGBA / RGB
+  ihdr.push_back(0);
+  ihdr.push_back(0);
+  ihdr.push_back(0);  // compression, filter method, no interlace
+  pngChunk(file, "IHDR", ihdr);
+  pngChunk(file, "IDAT", z);
+  pngChunk(file, "IEND", {});
+  return file;
+}
+
+void writePng(const std::string& path, const uint32_t* rgba8, uint32_t width, uint32_t height, bool alpha) {
+  const std::vector<uint8_t> file = encodePng(rgba8, width, height, alpha);
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) fail("cannot write " + path);
+  const size_t put = std::fwrite(file.data(), 1, file.size(), f);
+  if (std::fclose(f) != 0 || put != file.size()) fail("cannot write " + path);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // JPEG: sequential Huffman (SOF0 / SOF1), 8-bit samples
 // ---------------------------------------------------------------------------------------------------------------
 namespace {

@@ -35,6 +35,12 @@ ImageF decodeRgbe(const uint8_t* data, size_t size);
 // zlib stream (RFC 1950 wrapper around RFC 1951 deflate) -> bytes; `expected` = output size hint
 std::vector<uint8_t> inflateZlib(const uint8_t* data, size_t size, size_t expected);
 
+// PNG writer (the ldrfilm's fileFormat): 8-bit RGB (alpha = false: the A byte is dropped) or RGBA, non-interlaced, per-row filter
+// None / Sub / Up, own deflate.  `rgba8`: width * height words, R in bits 0-7, row 0 = TOP image row (the frame's order --
+// decodePng hands the same rows back bottom-up).  Throw std::runtime_error like the readers.
+std::vector<uint8_t> encodePng(const uint32_t* rgba8, uint32_t width, uint32_t height, bool alpha);
+void writePng(const std::string& path, const uint32_t* rgba8, uint32_t width, uint32_t height, bool alpha);
+
 // The reference's dormant checkerboard (Loader.cpp:127-139): a (2*uSize*100) x (2*vSize*100) RGBA8 image of
 // 2*uSize x 2*vSize cells alternating color0 / color1, cell (0, 0) at the bottom left = color0.
 Image8 makeCheckerboard(uint32_t uSize, uint32_t vSize, const float color0[3], const float color1[3]);

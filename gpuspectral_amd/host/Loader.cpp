@@ -761,13 +761,39 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
           throw std::runtime_error("thinlens sensor: focus_distance must be finite and positive when aperture_radius > 0");
         outScene.camera.setLens(radius, focus);
       }
+      auto each = [](const Object& o, const std::string& kind, const std::function<void(const Object&)>& f) {
+        for (auto& c : o.children)
+          if (c && c->kind == kind) f(*c);
+        for (auto& nc : o.named)
+          if (nc.second && nc.second->kind == kind) f(*nc.second);
+      };
+      if (options.readFilm) {  // <sensor><film type="ldrfilm"> ... </film></sensor>
+        each(*obj, "film", [&](const Object& film) {
+          if (film.plugin != "ldrfilm") {
+            outScene.warnings.push_back("film type '" + film.plugin + "' is not an ldrfilm: display settings left at their defaults");
+            return;
+          }
+          Scene::Film f;
+          f.ldr = true;
+          if (film.has("gamma")) f.gamma = film.number("gamma");
+          if (f.gamma == -1.0f) f.gamma = 0.0f;  // Mitsuba: -1 = sRGB
+          if (film.has("exposure")) f.exposure = film.number("exposure");
+          if (film.has("key")) f.key = film.number("key");
+          if (film.has("burn")) f.burn = film.number("burn");
+          if (film.has("tonemap_method")) {
+            const std::string m = film.string("tonemap_method");
+            if (m == "gamma") f.tonemap = GSP_TONEMAP_CLAMP;
+            else if (m == "reinhard") f.tonemap = GSP_TONEMAP_REINHARD;
+            else throw std::runtime_error("ldrfilm: tonemapMethod '" + m + "' is not supported: gamma or reinhard");
+          }
+          if (!(f.gamma >= 0.0f) || std::isinf(f.gamma)) throw std::runtime_error("ldrfilm: gamma must be -1 (sRGB) or finite and positive");
+          if (!std::isfinite(f.exposure) || f.exposure < -64.0f || f.exposure > 64.0f) throw std::runtime_error("ldrfilm: exposure must be finite, within -64 .. 64");
+          if (!(f.key >= 0.0f) || !(f.key <= 1.0f)) throw std::runtime_error("ldrfilm: key must be within 0 .. 1");
+          if (!(f.burn >= 0.0f) || !(f.burn <= 1.0f)) throw std::runtime_error("ldrfilm: burn must be within 0 .. 1");
+          outScene.film = f;
+        });
+      }
       if (options.readFilter) {  // <sensor><film><rfilter type=... /></film></sensor>
-        auto each = [](const Object& o, const std::string& kind, const std::function<void(const Object&)>& f) {
-          for (auto& c : o.children)
-            if (c && c->kind == kind) f(*c);
-          for (auto& nc : o.named)
-            if (nc.second && nc.second->kind == kind) f(*nc.second);
-        };
         each(*obj, "film", [&](const Object& film) {
           each(film, "rfilter", [&](const Object& rf) {
             const bool hasParam = rf.plugin == "tent" ? rf.has("radius") : rf.has("stddev");

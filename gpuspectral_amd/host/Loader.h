@@ -38,6 +38,12 @@ struct LoadOptions {
   // radius > 0 without a finite positive focus distance, is a load error.  Other sensor types are not affected.
   // false (default): the sensor plugin is ignored and the camera is a pinhole, as in the reference.
   bool readLens = false;
+  // Every scene the reference ships declares `<film type="ldrfilm">` (fileFormat png, gamma 2.2), and its loader never looks at
+  // it.  readFilm = true reads an ldrfilm's float `gamma` (-1, Mitsuba's default, becomes 0 = the sRGB curve), float `exposure`,
+  // string `tonemapMethod` (`gamma` | `reinhard`), float `key` and `burn` into Scene::film (include/gpuspectral_pt.h "LDR film");
+  // a value gsp_display would refuse is a load error.  Any other film type leaves the record at its defaults, with a warning.
+  // false (default): the film is ignored, as in the reference.
+  bool readFilm = false;
 };
 
 // assetDir: where rect.obj / box.obj / disk.obj live (Engine::assetPath); "" = the

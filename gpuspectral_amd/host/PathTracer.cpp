@@ -220,6 +220,28 @@ void PathTracer::peekToDevice(void* deviceDst, uint64_t bytes, uint32_t* samples
   check(gsp_peek_to_device(ctx, deviceDst, bytes, samplesFolded), "gsp_peek_to_device");
 }
 
+std::vector<uint32_t> PathTracer::downloadDisplay() {
+  std::vector<uint32_t> out((size_t)width * height);
+  check(gsp_download_display(ctx, &display, out.data()), "gsp_download_display");
+  return out;
+}
+
+std::vector<uint32_t> PathTracer::peekDisplay(uint32_t* samplesFolded) {
+  std::vector<uint32_t> out(pixelIds.empty() ? (size_t)width * height : pixelIds.size());
+  check(gsp_peek_display(ctx, &display, out.data(), samplesFolded), "gsp_peek_display");
+  return out;
+}
+
+void PathTracer::peekDisplayToDevice(void* deviceDst, uint64_t bytes, uint32_t* samplesFolded) {
+  check(gsp_peek_display_to_device(ctx, &display, deviceDst, bytes, samplesFolded), "gsp_peek_display_to_device");
+}
+
+gsp_luminance PathTracer::frameLuminance(bool drain) {
+  gsp_luminance l;
+  check(gsp_frame_luminance(ctx, drain ? 1 : 0, &l), "gsp_frame_luminance");
+  return l;
+}
+
 gsp_stats PathTracer::stats() {
   gsp_stats s;
   check(gsp_get_stats(ctx, &s), "gsp_get_stats");
@@ -293,6 +315,12 @@ void MultiGpuPathTracer::createRenderPass(const Scene& scene) { render(scene, 1)
 std::vector<float> MultiGpuPathTracer::download() {
   std::vector<float> out((size_t)width * height * 4);
   check(gsp_multi_download(multi, out.data()), "gsp_multi_download");
+  return out;
+}
+
+std::vector<uint32_t> MultiGpuPathTracer::downloadDisplay() {
+  std::vector<uint32_t> out((size_t)width * height);
+  check(gsp_multi_download_display(multi, &display, out.data()), "gsp_multi_download_display");
   return out;
 }
 

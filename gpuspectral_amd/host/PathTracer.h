@@ -86,12 +86,21 @@ class PathTracer : public RenderPassCreator {
   std::vector<float> peek(uint32_t* samplesFolded = nullptr);
   // ... into caller-owned DEVICE memory (>= owned pixels * 16 bytes): the blit's source without a trip through the host
   void peekToDevice(void* deviceDst, uint64_t bytes, uint32_t* samplesFolded = nullptr);
+  // LDR film (gpuspectral_pt.h "LDR film"): the frame tone-mapped and encoded on the GPU with `display`, RGBA8 words (R in bits
+  // 0-7).  downloadDisplay: the full frame after every queued sample; peekDisplay: compact, as it stands -- what a viewer
+  // presents each frame instead of peek() + a host tone map (4 bytes per pixel over PCIe instead of 16)
+  std::vector<uint32_t> downloadDisplay();
+  std::vector<uint32_t> peekDisplay(uint32_t* samplesFolded = nullptr);
+  void peekDisplayToDevice(void* deviceDst, uint64_t bytes, uint32_t* samplesFolded = nullptr);
+  // the frame statistics Reinhard measures (drain = false: the buffer as it stands)
+  gsp_luminance frameLuminance(bool drain = true);
   void reset();  // timestamp = 0, accumulate buffer cleared
   int getTimestamp() const { return timestamp; }
   gsp_stats stats();
   // reference literals by default (MAX_DEPTH 50, RR > 10, clamp 20).  params.pixel_filter != GSP_FILTER_NONE overrides the
   // filter a scene carries (Scene::pixelFilter, LoadOptions::readFilter); NONE leaves the choice to the scene
   gsp_render_params params;
+  gsp_display display{};  // the LDR film of downloadDisplay / peekDisplay; zeroed = clamp + sRGB
 
  private:
   void check(int rc, const char* what);
@@ -121,11 +130,13 @@ class MultiGpuPathTracer : public RenderPassCreator {
   void prepareScene(const Scene& scene);  // as PathTracer::prepareScene, on every share
   void invalidateScene() { tracker.forget(); }
   std::vector<float> download();  // RGBA32F, row-major, width*height*4 floats
+  std::vector<uint32_t> downloadDisplay();  // as PathTracer::downloadDisplay, on the gathered frame
   void reset();
   int getTimestamp() const { return timestamp; }
   int numShares() const { return (int)devices.size(); }
   gsp_stats stats(std::vector<gsp_stats>* perShare = nullptr);  // totals over the shares
   gsp_render_params params;
+  gsp_display display{};
 
  private:
   void check(int rc, const char* what);

@@ -203,6 +203,23 @@ struct Scene {
   // 0 = none: the renderer's own params decide.  PathTracer::render uses these when its params.pixel_filter is GSP_FILTER_NONE
   uint32_t pixelFilter = 0;
   float pixelFilterParam = 0.0f;
+  // the sensor's <film type="ldrfilm">, read only with LoadOptions::readFilm (include/gpuspectral_pt.h "LDR film"); the defaults
+  // are Mitsuba's: tonemapMethod gamma, gamma -1 (= 0 here: the sRGB curve), exposure 0, key 0.18 (= 0 here), burn 0
+  struct Film {
+    bool ldr = false;  // an ldrfilm was read
+    uint32_t tonemap = GSP_TONEMAP_CLAMP;
+    float gamma = 0.0f, exposure = 0.0f, key = 0.0f, burn = 0.0f;
+    gsp_display display() const {
+      gsp_display d{};
+      d.struct_size = (uint32_t)sizeof(d);
+      d.tonemap = tonemap;
+      d.gamma = gamma;
+      d.exposure = exposure;
+      d.key = key;
+      d.burn = burn;
+      return d;
+    }
+  } film;
 
   // dormant features: filled only by loadScene(..., LoadOptions{.dormantFeatures = true}); a BSDF record's hasTexture is
   // 1 + the index into `textures`

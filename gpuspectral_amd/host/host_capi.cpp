@@ -64,7 +64,8 @@ void* gsph_load_scene_ex(const char* path, const char* asset_dir, int dormant, i
   return b;
 }
 // flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere),
-// 8 = readFilter (the film's <rfilter>), 16 = readLens (a thinlens sensor's aperture_radius / focus_distance)
+// 8 = readFilter (the film's <rfilter>), 16 = readLens (a thinlens sensor's aperture_radius / focus_distance),
+// 32 = readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn)
 void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned flags) {
   SceneBox* b = nullptr;
   int rc = guard([&] {
@@ -75,6 +76,7 @@ void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned fla
     opt.builtinShapes = (flags & 4u) != 0;
     opt.readFilter = (flags & 8u) != 0;
     opt.readLens = (flags & 16u) != 0;
+    opt.readFilm = (flags & 32u) != 0;
     b->scene = loadScene(path, asset_dir ? asset_dir : "", opt);
     flattenScene(b->scene, b->flat);
   });
@@ -122,6 +124,12 @@ void gsph_scene_lens(void* s, float* out4) {
 }
 void gsph_scene_set_lens(void* s, float radius, float focus, uint32_t blades, float rotation) {
   ((SceneBox*)s)->scene.camera.setLens(radius, focus, blades, rotation);
+}
+// the scene's film (LoadOptions::readFilm) as the gsp_display PathTracer::display takes; returns 1 when an ldrfilm was read
+int gsph_scene_film(void* s, gsp_display* out) {
+  const Scene::Film& f = ((SceneBox*)s)->scene.film;
+  if (out) *out = f.display();
+  return f.ldr ? 1 : 0;
 }
 uint32_t gsph_scene_num_materials(void* s) { return (uint32_t)((SceneBox*)s)->scene.materials.size(); }
 
@@ -251,6 +259,36 @@ int gsph_write_pfm(const char* path, const float* rgba, uint32_t width, uint32_t
 
 int gsph_write_ppm(const char* path, const float* rgba, uint32_t width, uint32_t height, int tone_map) {
   return guard([&] { writePpm(path, rgba, width, height, tone_map != 0); });
+}
+// Image.h PNG writer.  gsph_encode_png: two calls, out == NULL returns the size
+int gsph_write_png(const char* path, const uint32_t* rgba8, uint32_t width, uint32_t height, int alpha) {
+  return guard([&] { writePng(path, rgba8, width, height, alpha != 0); });
+}
+int gsph_encode_png(const uint32_t* rgba8, uint32_t width, uint32_t height, int alpha, uint8_t* out, uint64_t* size) {
+  return guard([&] {
+    const std::vector<uint8_t> f = encodePng(rgba8, width, height, alpha != 0);
+    if (out && *size >= f.size()) std::memcpy(out, f.data(), f.size());
+    *size = f.size();
+  });
+}
+// decodePng of a buffer: texels == NULL returns the size; rows bottom-up
+int gsph_decode_png(const uint8_t* data, uint64_t size, uint32_t* width, uint32_t* height, uint32_t* texels) {
+  return guard([&] {
+    Image8 img = decodePng(data, size);
+    *width = img.width;
+    *height = img.height;
+    if (texels) std::memcpy(texels, img.texels.data(), img.texels.size() * sizeof(uint32_t));
+  });
+}
+int gsph_pathtracer_set_display(void* pt, const gsp_display* d) {
+  return guard([&] { ((PathTracer*)pt)->display = *d; });
+}
+int gsph_pathtracer_download_display(void* pt, uint32_t* out, uint64_t count) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadDisplay();
+    if (count < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(uint32_t));
+  });
 }
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {

@@ -43,6 +43,12 @@ class PathTracerHip : public RenderPassCreator {
   void download(float* rgba) { check(gsp_download(ctx, rgba)); }  // what the DrawTexture blit sampled, once every path has ended
   // ... and as it stands this frame, into the device memory the blit reads (PathTracer.cpp:41-55): no wait, no trip through the host
   void blitSource(void* deviceRgba, uint64_t bytes, uint32_t* samples = nullptr) { check(gsp_peek_to_device(ctx, deviceRgba, bytes, samples)); }
+  // ... or already tone-mapped and encoded (gpuspectral_pt.h "LDR film"): RGBA8, 4 bytes per pixel, ready for a swapchain image.
+  // `display` holds until changed; zeroed = clamp + sRGB, GSP_TONEMAP_ACES = the reference's ACESFilm (common.glsl:74-82)
+  gsp_display display{};
+  void blitSourceDisplay(void* deviceRgba8, uint64_t bytes, uint32_t* samples = nullptr) {
+    check(gsp_peek_display_to_device(ctx, &display, deviceRgba8, bytes, samples));
+  }
   // anti-aliasing, opt-in (gpuspectral_pt.h "Pixel filter"): e.g. GSP_FILTER_TENT, 0 = the <rfilter type="tent"/> of the shipped
   // scenes; call restart() after a change, or the running mean mixes filtered and unfiltered samples
   uint32_t pixelFilter = GSP_FILTER_NONE;

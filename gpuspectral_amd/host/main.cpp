@@ -13,6 +13,9 @@
 //   --aperture R --focus-distance D | --focus-pixel X,Y [--blades N[:rot_deg]]: thin lens (gsp_set_lens; depth of field).
 //   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
 //   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
+//   --ldr out.png: also write the LDR film (gpuspectral_pt.h "LDR film": tone-mapped and encoded on the GPU) as an 8-bit RGB PNG;
+//   --tonemap clamp|aces|reinhard[:key[:burn]], --exposure E (f-stops), --gamma G|srgb: its gsp_display; --scene-film:
+//   LoadOptions::readFilm (the sensor's ldrfilm; the flags override the scene's values one by one).  Without --ldr: no PNG
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -22,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "Image.h"
 #include "Loader.h"
 #include "PathTracer.h"
 
@@ -39,6 +43,10 @@ int main(int argc, char** argv) {
   float aperture = -1.0f, focusDistance = -1.0f, focusX = 0.0f, focusY = 0.0f, bladeRotation = 0.0f;  // (-1 = not given)
   bool focusPixel = false;
   int blades = -1;
+  std::string ldrPath;
+  int tonemap = -1;  // (-1 = not given)
+  float tmKey = -1.0f, tmBurn = -1.0f, exposure = 0.0f, gamma = -1.0f;
+  bool haveExposure = false;
   auto parseFloat = [](const char* s, float& out) {
     char* e = nullptr;
     out = std::strtof(s, &e);
@@ -57,6 +65,41 @@ int main(int argc, char** argv) {
     else if (flag == "--adaptive-step" && argc > 2) adaptiveStep = (uint32_t)std::strtoul(argv[2], nullptr, 10), used = 2;
     else if (flag == "--scene-filter") options.readFilter = true;
     else if (flag == "--scene-lens") options.readLens = true;
+    else if (flag == "--scene-film") options.readFilm = true;
+    else if (flag == "--ldr" && argc > 2) ldrPath = argv[2], used = 2;
+    else if (flag == "--tonemap" && argc > 2) {
+      const std::string v = argv[2];
+      const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+      const std::string name = v.substr(0, c1);
+      bool ok = true;
+      if (name == "clamp") tonemap = (int)GSP_TONEMAP_CLAMP;
+      else if (name == "aces") tonemap = (int)GSP_TONEMAP_ACES;
+      else if (name == "reinhard") tonemap = (int)GSP_TONEMAP_REINHARD;
+      else ok = false;
+      if (ok && c1 != std::string::npos) {
+        ok = name == "reinhard" && parseFloat(v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1).c_str(), tmKey) && tmKey > 0.0f && tmKey <= 1.0f;
+        if (ok && c2 != std::string::npos) ok = parseFloat(v.c_str() + c2 + 1, tmBurn) && tmBurn >= 0.0f && tmBurn <= 1.0f;
+      }
+      if (!ok) {
+        std::fprintf(stderr, "gsp_render: bad tonemap '%s' (expected clamp, aces or reinhard[:key[:burn]], key in (0,1], burn in [0,1])\n", argv[2]);
+        return 2;
+      }
+      used = 2;
+    } else if (flag == "--exposure" && argc > 2) {
+      if (!parseFloat(argv[2], exposure) || exposure < -64.0f || exposure > 64.0f) {
+        std::fprintf(stderr, "gsp_render: bad exposure '%s' (expected f-stops within -64 .. 64)\n", argv[2]);
+        return 2;
+      }
+      haveExposure = true;
+      used = 2;
+    } else if (flag == "--gamma" && argc > 2) {
+      if (std::string(argv[2]) == "srgb") gamma = 0.0f;
+      else if (!parseFloat(argv[2], gamma) || !(gamma > 0.0f)) {
+        std::fprintf(stderr, "gsp_render: bad gamma '%s' (expected a value > 0, or srgb)\n", argv[2]);
+        return 2;
+      }
+      used = 2;
+    }
     else if (flag == "--aperture" && argc > 2) {
       if (!parseFloat(argv[2], aperture) || aperture < 0.0f) {
         std::fprintf(stderr, "gsp_render: bad aperture '%s' (expected a radius >= 0)\n", argv[2]);
@@ -126,8 +169,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --aperture needs --focus-distance D, --focus-pixel X,Y or --scene-lens\n");
     return 2;
   }
+  if (ldrPath.empty() && (tonemap >= 0 || haveExposure || gamma >= 0.0f || options.readFilm)) {
+    std::fprintf(stderr, "gsp_render: --tonemap, --exposure, --gamma and --scene-film need --ldr out.png\n");
+    return 2;
+  }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -176,6 +223,14 @@ int main(int argc, char** argv) {
                            blades >= 0 ? (uint32_t)blades : scene.camera.getApertureBlades(),
                            blades >= 0 ? bladeRotation : scene.camera.getApertureRotation());
     }
+    // LDR film: the scene's (--scene-film), overridden flag by flag
+    gsp_display display = scene.film.display();
+    if (tonemap >= 0) display.tonemap = (uint32_t)tonemap;
+    if (tmKey > 0.0f) display.key = tmKey;
+    if (tmBurn >= 0.0f) display.burn = tmBurn;
+    if (haveExposure) display.exposure = exposure;
+    if (gamma >= 0.0f) display.gamma = gamma;
+    std::vector<uint32_t> ldr;
     std::vector<float> img;
     gsp_stats st;
     double s;
@@ -192,6 +247,10 @@ int main(int argc, char** argv) {
       img = pt.download();
       s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       st = pt.stats();
+      if (!ldrPath.empty()) {
+        pt.display = display;
+        ldr = pt.downloadDisplay();
+      }
     } else {
       MultiGpuPathTracer pt(width, height, devices, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
@@ -203,10 +262,15 @@ int main(int argc, char** argv) {
       img = pt.download();
       s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       st = pt.stats();
+      if (!ldrPath.empty()) {
+        pt.display = display;
+        ldr = pt.downloadDisplay();
+      }
       std::printf("%zu shares (32x32 tiles), gathered on device %d\n", devices.size(), devices[0]);
     }
     writePfm(argv[2], img.data(), width, height);
     writePpm(std::string(argv[2]) + ".ppm", img.data(), width, height, false);  // LDR preview, gamma 2.2
+    if (!ldrPath.empty()) writePng(ldrPath, ldr.data(), width, height, false);
     std::printf("%llu triangles, %ux%u x %u spp in %.3f s: %.1f Mrays/s, %.2f Msamples/s (BVH build %.1f ms)\n",
                 (unsigned long long)st.num_triangles, width, height, spp, s,
                 (st.extension_rays + st.shadow_rays) / s / 1e6, st.samples / s / 1e6, st.bvh_build_ms);

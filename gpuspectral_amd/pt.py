@@ -39,6 +39,10 @@ EXPORTS = (
     "gsp_copy_accum_to_device",
     "gsp_peek_to_device",
     "gsp_upload_accum",
+    "gsp_frame_luminance",
+    "gsp_download_display",
+    "gsp_peek_display",
+    "gsp_peek_display_to_device",
     "gsp_get_stats",
     "gsp_reset_stats",
     "gsp_trace",
@@ -60,6 +64,7 @@ EXPORTS = (
     "gsp_multi_gather",
     "gsp_multi_gather_route",
     "gsp_multi_download",
+    "gsp_multi_download_display",
     "gsp_multi_get_stats",
     "gsp_multi_reset_stats",
     "gsp_multi_last_error",
@@ -116,6 +121,11 @@ def load():
     L.gsp_copy_accum_to_device.argtypes = [vp, vp, u64]
     L.gsp_peek_to_device.argtypes = [vp, vp, u64, C.POINTER(C.c_uint32)]
     L.gsp_upload_accum.argtypes = [vp, vp, u64]
+    L.gsp_frame_luminance.argtypes = [vp, C.c_int, C.POINTER(abi.Luminance)]
+    L.gsp_download_display.argtypes = [vp, C.POINTER(abi.Display), vp]
+    L.gsp_peek_display.argtypes = [vp, C.POINTER(abi.Display), vp, C.POINTER(C.c_uint32)]
+    L.gsp_peek_display_to_device.argtypes = [vp, C.POINTER(abi.Display), vp, u64, C.POINTER(C.c_uint32)]
+    L.gsp_multi_download_display.argtypes = [vp, C.POINTER(abi.Display), vp]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -166,7 +176,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -321,6 +331,34 @@ class Context:
         self._check(self._L.gsp_peek_to_device(self._h, device_ptr, nbytes, C.byref(folded)), "gsp_peek_to_device")
         return int(folded.value)
 
+    # ---- LDR film (gpuspectral_pt.h "LDR film"); display: an abi.Display (abi.display(...)), None = NULL = clamp + sRGB ----
+    def download_display(self, display=None):
+        """gsp_download_display: the frame tone-mapped and encoded on the GPU, (height, width) uint32 RGBA8 words (R in bits 0-7)."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsp_download_display(self._h, C.byref(display) if display is not None else None, out.ctypes.data), "gsp_download_display")
+        return out
+
+    def peek_display(self, display=None):
+        """gsp_peek_display: (compact RGBA8 words of the frame as it stands, timestamps folded), no drain."""
+        out = np.zeros(self.num_pixels, np.uint32)
+        folded = C.c_uint32(0)
+        self._check(self._L.gsp_peek_display(self._h, C.byref(display) if display is not None else None, out.ctypes.data, C.byref(folded)),
+                    "gsp_peek_display")
+        return out, int(folded.value)
+
+    def peek_display_to_device(self, device_ptr, nbytes, display=None):
+        """gsp_peek_display into device memory (e.g. a torch tensor's data_ptr()); returns the timestamps folded."""
+        folded = C.c_uint32(0)
+        self._check(self._L.gsp_peek_display_to_device(self._h, C.byref(display) if display is not None else None, device_ptr, nbytes,
+                                                       C.byref(folded)), "gsp_peek_display_to_device")
+        return int(folded.value)
+
+    def frame_luminance(self, drain=True):
+        """gsp_frame_luminance: {log_sum_q20, pixels, log_avg, max} over the owned finite pixels."""
+        out = abi.Luminance()
+        self._check(self._L.gsp_frame_luminance(self._h, 1 if drain else 0, C.byref(out)), "gsp_frame_luminance")
+        return out.as_dict()
+
     def pixel_stats(self):
         """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of
         Y^2 over each pixel's samples and the samples folded into it (gsp_download_pixel_stats)."""
@@ -457,6 +495,13 @@ class MultiContext:
     def download(self):
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._check(self._L.gsp_multi_download(self._h, out.ctypes.data), "gsp_multi_download")
+        return out
+
+    def download_display(self, display=None):
+        """gsp_multi_download_display: Context.download_display of the gathered frame."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsp_multi_download_display(self._h, C.byref(display) if display is not None else None, out.ctypes.data),
+                    "gsp_multi_download_display")
         return out
 
     def stats(self, per_share=False):

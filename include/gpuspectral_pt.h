@@ -66,7 +66,8 @@ extern "C" {
                              9: adaptive sampling: gsp_render_params.adaptive_threshold / _min_spp / _step,
                                 gsp_download_pixel_stats, gsp_stats.adaptive_rounds / adaptive_active_pixels;
                                 additions within version 9 (new exports only, no struct changed): gsp_set_lens,
-                                gsp_multi_set_lens, gsp_focus_distance (see "Thin lens") */
+                                gsp_multi_set_lens, gsp_focus_distance (see "Thin lens"); gsp_frame_luminance, gsp_download_display,
+                                gsp_peek_display, gsp_peek_display_to_device, gsp_multi_download_display (see "LDR film") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -589,6 +590,69 @@ int gsp_peek_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes, uint3
  * buffer + next timestamp are the whole integrator state). */
 int gsp_upload_accum(gsp_context* ctx, const float* rgba, uint64_t num_pixels);
 
+/*
+ * LDR film: tone mapping on the GPU and an 8-bit read-back.
+ *
+ * The reference's scenes declare <film type="ldrfilm"> (PNG, gamma 2.2) and its presentation pass tone-maps in a shader
+ * (ACESFilm, common.glsl:74-82); no running reference code defines an 8-bit frame, so this header does.  The calls below read
+ * the accumulate buffer and write RGBA8 (R in bits 0-7, the convention of gsp_texture); they change no state of the frame.  A
+ * display needs 4 bytes per pixel over PCIe instead of 16.
+ *
+ * Per pixel.  Arithmetic is float32 in the order written; log and exp are the library's deterministic functions.  The constants
+ * derived from the struct are formed once on the host in double and rounded to float: 2^exposure, 1/gamma, scale, invWp2.
+ *   1. rgb from the accumulate buffer; a NaN channel becomes 0 and a negative channel (-Inf included) becomes 0.
+ *   2. c *= 2^exposure.
+ *   3. the tone curve:
+ *        CLAMP     nothing.
+ *        ACES      per channel (x * (2.51 x + 0.03)) / (x * (2.43 x + 0.59) + 0.14).
+ *        REINHARD  Y = (0.2126 r + 0.7152 g) + 0.0722 b  (the weights of the adaptive rule), Lp = Y * scale,
+ *                  Y' = (Lp * (1 + Lp * invWp2)) / (1 + Lp), c *= Y' / Y; Y == 0: the pixel is black.
+ *                  scale = key / Lavg (key 0 = 0.18), invWp2 = 1 / ((Lmax * scale)^2 * b^4), b = clamp(1 - burn, 1e-8, 1).
+ *   4. clamp to [0, 1].  A NaN at this point can only be an overflowed curve (Inf / Inf: a saturated pixel) and becomes 1.
+ *   5. encode: gamma > 0: v == 0 ? 0 : exp(log(v) * (1 / gamma));
+ *              gamma == 0 (sRGB): v <= 0.0031308 ? 12.92 v : 1.055 * exp(log(v) * (1 / 2.4f)) - 0.055.
+ *   6. byte = (uint32)(v * 255 + 0.5); A = 255.
+ *
+ * Frame statistics (REINHARD with log_avg_luminance or max_luminance left 0, and gsp_frame_luminance).  Over the owned pixels
+ * whose three channels are finite and whose Y is, on the buffer as it is (exposure does not enter), channels after step 1:
+ *     q = (int64) rintf(log(Y + 1e-3f) * 1048576.0f),  S = sum of q,  n = their number,  Lmax = max Y,
+ *     Lavg = (float) exp((double) S / (1048576.0 * n)).
+ * S is an INTEGER sum and Lmax a max over non-negative float bit patterns: neither depends on the order of summation, so any
+ * launch shape, any partition of the frame over shares or GPUs and a plain host loop give the same bits.  A frame with n == 0,
+ * Lavg <= 0 or Lmax <= 0 tone-maps with scale = 1 and invWp2 = 0.
+ *
+ * struct_size follows the rule of gsp_render_params (fields beyond it are 0); a NULL gsp_display and struct_size 0 are the zeroed
+ * struct = CLAMP + sRGB.  GSP_ERR_INVALID (text at gsp_last_error) for: an unknown tonemap id; an exposure that is not finite or
+ * lies outside -64 .. 64; a negative or non-finite gamma; key or burn outside 0 .. 1; negative or non-finite supplied luminances.
+ */
+#define GSP_TONEMAP_CLAMP 0u    /* ldrfilm tonemapMethod "gamma": scale, clamp, encode */
+#define GSP_TONEMAP_REINHARD 1u /* ldrfilm tonemapMethod "reinhard" (global photographic operator) */
+#define GSP_TONEMAP_ACES 2u     /* the reference's ACESFilm, common.glsl:74-82 */
+typedef struct gsp_display {
+  uint32_t struct_size;    /* sizeof(gsp_display) of the host's header; same rule as gsp_render_params / gsp_lens */
+  uint32_t tonemap;        /* GSP_TONEMAP_* */
+  float exposure;          /* f-stops; colour is multiplied by 2^exposure first */
+  float gamma;             /* > 0: v^(1/gamma); 0 = the sRGB curve */
+  float key, burn;         /* Reinhard: key 0 = 0.18; burn in [0, 1] */
+  float log_avg_luminance; /* Reinhard: > 0 = use this value; 0 = measure the frame */
+  float max_luminance;     /* same */
+} gsp_display;             /* all zero = clamp + sRGB */
+typedef struct gsp_luminance {
+  int64_t log_sum_q20; /* S */
+  uint64_t pixels;     /* n */
+  float log_avg, max;  /* Lavg (0 when n == 0), Lmax */
+} gsp_luminance;
+/* The frame statistics above.  drain != 0 completes the queued samples first (like gsp_download); 0 measures the buffer as it
+ * stands (like gsp_peek). */
+int gsp_frame_luminance(gsp_context* ctx, int drain, gsp_luminance* out);
+/* gsp_download's 8-bit counterpart: completes the queued samples; full frame, width*height words, unowned pixels = 0. */
+int gsp_download_display(gsp_context* ctx, const gsp_display* display, uint32_t* out_rgba8);
+/* gsp_peek's: compact (num_pixels words), no wait for the paths in flight, same meaning of samples_folded. */
+int gsp_peek_display(gsp_context* ctx, const gsp_display* display, uint32_t* out_rgba8, uint32_t* samples_folded);
+/* gsp_peek_to_device's: `bytes` >= num_pixels * 4; complete when the call returns.  The kernel writes a 16-byte aligned
+ * destination directly; any other one receives a device-to-device copy of the context's own RGBA8 buffer. */
+int gsp_peek_display_to_device(gsp_context* ctx, const gsp_display* display, void* device_dst, uint64_t bytes, uint32_t* samples_folded);
+
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
 
@@ -653,6 +717,9 @@ int gsp_multi_gather(gsp_multi* m, void** device_frame);
 int gsp_multi_gather_route(const gsp_multi* m, uint64_t* rccl_gathers, uint64_t* copy_gathers);
 /* gsp_multi_gather + one copy to the host: width*height*4 floats, identical to a single-GPU gsp_download. */
 int gsp_multi_download(gsp_multi* m, float* out_rgba);
+/* gsp_multi_gather + the LDR film on the gathered frame (statistics over the whole frame) + one copy to the host: width*height
+ * words, identical to a single-GPU gsp_download_display. */
+int gsp_multi_download_display(gsp_multi* m, const gsp_display* display, uint32_t* out_rgba8);
 /* total (optional): counters summed over the shares, times of the slowest share (they run concurrently);
  * per_share (optional): gsp_multi_num_shares() records. */
 int gsp_multi_get_stats(gsp_multi* m, gsp_stats* total, gsp_stats* per_share);
