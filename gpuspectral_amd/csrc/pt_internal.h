@@ -66,6 +66,8 @@ struct BuildInput {
 // Completes everything queued and returns the context's compact RGBA32F accumulate buffer (device memory on the
 // context's device, num_pixels records) and the stream its copies are ordered on.
 __attribute__((visibility("hidden"))) int gsp_internal_accum(gsp_context* ctx, void** accum, uint64_t* num_pixels, hipStream_t* stream);
+// ... and its three compact feature planes (gsp_render_features), 16 bytes per owned pixel each
+__attribute__((visibility("hidden"))) int gsp_internal_features(gsp_context* ctx, void** albedo, void** geom, void** ids, uint64_t* num_pixels);
 // The options a context was created with, defaults filled in (pt_multi.hip divides memory_share among the shares of a device).
 __attribute__((visibility("hidden"))) void gsp_internal_resolve_options(const gsp_ctx_options* in, gsp_ctx_options* out);
 

@@ -575,6 +575,62 @@ int gsp_multi_download_display(gsp_multi* m, const gsp_display* display, uint32_
   return GSP_OK;
 }
 
+// ---- feature buffers over the shares (include/gpuspectral_pt.h, "Feature buffers") ----
+int gsp_multi_render_features(gsp_multi* m, const gsp_render_params* params) {
+  if (!m) return GSP_ERR_INVALID;
+  if (!params) {
+    m->err = "gsp_multi_render_features: null parameters";
+    return GSP_ERR_INVALID;
+  }
+  return for_each_share(m, [&](size_t r) { return gsp_render_features(m->ctx[r], params); });
+}
+
+// Every share's compact planes travel into the staging buffer on devices[0] by the copy route (also where the beauty gather goes
+// through RCCL), k_scatter_tiles places them in the frame buffer, one copy per plane brings them to the host.  The staging and
+// frame buffers are the beauty gather's: the three planes and the image are 16 bytes per pixel alike.
+int gsp_multi_download_features(gsp_multi* m, float* albedo, float* geom, uint32_t* ids) {
+  if (!m) return GSP_ERR_INVALID;
+  if (!m->have_frame) {
+    m->err = "gsp_multi_download_features needs gsp_multi_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  const uint32_t world = (uint32_t)m->ctx.size();
+  if (world == 1 && !m->use_rccl) {
+    int rc = gsp_download_features(m->ctx[0], albedo, geom, ids);
+    if (rc != GSP_OK) m->err = gsp_last_error(m->ctx[0]);
+    return rc;
+  }
+  std::vector<void*> src[3];
+  for (auto& v : src) v.assign(world, nullptr);
+  std::vector<uint64_t> cnt(world, 0);
+  int rc = for_each_share(m, [&](size_t r) { return gsp_internal_features(m->ctx[r], &src[0][r], &src[1][r], &src[2][r], &cnt[r]); });
+  if (rc != GSP_OK) return rc;
+  for (uint32_t r = 0; r < world; ++r)
+    if (cnt[r] != m->ids[r].size()) {
+      m->err = "internal error: a share's pixel count differs from its tile list";
+      return GSP_ERR_DEVICE;
+    }
+  void* const out[3] = {albedo, geom, ids};
+  MULTI_TRY(m, hipSetDevice(m->devices[0]));
+  const uint64_t total = m->frame_pixels;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256 * 8);
+  for (int k = 0; k < 3; ++k) {
+    if (!out[k]) continue;
+    for (uint32_t r = 0; r < world; ++r) {
+      if (cnt[r] == 0) continue;
+      if (m->devices[r] == m->devices[0])
+        MULTI_TRY(m, hipMemcpyAsync(m->staging + m->offset[r], src[k][r], cnt[r] * sizeof(q4), hipMemcpyDeviceToDevice, m->stream));
+      else
+        MULTI_TRY(m, hipMemcpyPeerAsync(m->staging + m->offset[r], m->devices[0], src[k][r], m->devices[r], cnt[r] * sizeof(q4), m->stream));
+    }
+    hipLaunchKernelGGL(k_scatter_tiles, dim3(grid), dim3(256), 0, m->stream, m->staging, m->d_ids, total, m->frame);
+    MULTI_TRY(m, hipGetLastError());
+    MULTI_TRY(m, hipMemcpyAsync(out[k], m->frame, total * sizeof(q4), hipMemcpyDeviceToHost, m->stream));
+    MULTI_TRY(m, hipStreamSynchronize(m->stream));
+  }
+  return GSP_OK;
+}
+
 // total (optional): counters summed over the shares, times = the slowest share's (they run concurrently);
 // per_share (optional): gsp_multi_num_shares() records.
 int gsp_multi_get_stats(gsp_multi* m, gsp_stats* total, gsp_stats* per_share) {

@@ -48,6 +48,7 @@
 #include "pt_internal.h"
 #include "pt_versions.h"
 #include "pt_wavetrace.h"
+#include "pt_features.h"
 
 #include "pt_render_kernels.inc"  // namespace gsp { kernels, queue layouts, ray sources, DevBuf }
 
@@ -142,6 +143,11 @@ struct gsp_context {
   DevBuf<uint32_t> display_out;
   DevBuf<DisplayStatsRec> display_rec;
   DisplayStatsRec* h_display_rec = nullptr;
+  // feature buffers (gsp_render_features): three compact planes of 16 bytes per owned pixel -- {albedo.rgb, coverage}, {normal.xyz,
+  // depth}, {triangle, bsdf, instance, samples folded} -- made by the first call that asks for them; gsp_frame_begin only marks
+  // them stale (features_ready = false) and the next feature call of the frame sizes and zeroes them
+  DevBuf<q4> feat_albedo, feat_geom, feat_ids;
+  bool features_ready = false;
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;
@@ -258,12 +264,13 @@ struct gsp_context {
     return true;
   }
   // versioned == false: the tables and the geometry of the current version (all samples in flight belong to it); true: slot 0
-  // of the rings + the strides, for the <VER> instantiations
-  SceneView view(bool versioned = false) const {
+  // of the rings + the strides, for the <VER> instantiations.  newest_tables: the tables of the newest version whatever is in
+  // flight (gsp_render_features reads one version, the newest, next to samples that still carry older ones)
+  SceneView view(bool versioned = false, bool newest_tables = false) const {
     SceneView v;
     if (split) versioned = true;  // (a split scene has no array a plain kernel could walk)
     const bool ring = versioned && geo.stride != 0;
-    const bool tab_versions = versioned && oldest_live_version() != tab.ver;  // (else: one version of the tables, wherever it sits)
+    const bool tab_versions = versioned && !newest_tables && oldest_live_version() != tab.ver;  // (else: one version of the tables, wherever it sits)
     v.nodes = ring ? ring_nodes.p : bvh.nodes;
     v.tri_isect = ring ? ring_isect.p : bvh.tri_isect;
     v.tri_shade = ring ? ring_shade.p : bvh.tri_shade;

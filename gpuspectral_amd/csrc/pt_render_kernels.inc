@@ -1043,6 +1043,104 @@ __global__ __launch_bounds__(kBlock) void k_display_map(const v4f* __restrict__ 
   }
 }
 
+// ---- first-hit feature buffers (pt_features.h; include/gpuspectral_pt.h "Feature buffers") -------------------------------
+// One lane owns one owned pixel for the whole call: it loads the pixel's three planes once (16 bytes each), loops over the call's
+// timestamps -- the camera ray of the beauty sample (generate_path_t / generate_path_lens), k_finish's per-lane traversal with
+// its stack and step table in LDS, the hit's features, the running mean in registers -- and stores the planes once.  No atomics:
+// nothing is shared between lanes.  CAMERA as generate_body's MODE: 0 pinhole, 1 pixel filter, 2 thin lens.
+// Split scene (G.dyn_nodes != nullptr): the ray walks the static tree and the newest version of the edited instances' tree and
+// keeps min (t, tie-break key), as k_finish does.
+struct FeatureGeo {
+  const q4* dyn_nodes;   // split scene: the edited instances' tree, newest version (else nullptr)
+  const q4* dyn_isect;
+  const q4* dyn_shade;
+  uint32_t static_slots;                // ... whose slots are counted behind these in slot_to_global
+  uint32_t num_tris;                    // 0: an empty scene, every ray misses
+  const uint32_t* slot_to_global;       // slot -> scene-wide triangle index, as gsp_trace reports it
+  const uint32_t* tri_first;            // per instance: its first scene triangle (num_instances + 1 entries)
+  uint32_t num_instances;
+};
+template <int CAMERA>
+struct FeatureConsts {
+  typedef RenderConstsBase type;
+};
+template <>
+struct FeatureConsts<1> {
+  typedef RenderConsts type;
+};
+template <>
+struct FeatureConsts<2> {
+  typedef RenderConstsLens type;
+};
+typedef uint32_t v4w __attribute__((ext_vector_type(4)));
+template <bool TEX, int CAMERA>
+__global__ __launch_bounds__(kBlock) void k_features(SceneView S, typename FeatureConsts<CAMERA>::type rc, FeatureGeo G, uint32_t num_pixels,
+                                                      uint32_t K, uint32_t first_timestamp, const uint32_t* __restrict__ pixel_ids,
+                                                      q4* __restrict__ albedo, q4* __restrict__ geom, v4w* __restrict__ ids) {
+  __shared__ uint32_t s_stack[kFinishLevels * kStackWords * kBlock];
+  __shared__ uint32_t s_table[kStepTableBytes / 4];
+  stage_step_table(s_table, threadIdx.x, kBlock);
+  __syncthreads();
+  const LdsStepTable tab{(const __attribute__((address_space(3))) char*)s_table};
+  FinishStack stk{(lds_u32*)s_stack + threadIdx.x, 0u};
+  const uint32_t lp = blockIdx.x * kBlock + threadIdx.x;
+  if (lp >= num_pixels) return;  // (no barrier below)
+  const uint32_t gid = pixel_ids ? pixel_ids[lp] : lp;
+  FeaturePixel px;
+  px.albedo = qld(&albedo[lp]);
+  px.geom = qld(&geom[lp]);
+  {
+    const v4w w = __builtin_nontemporal_load(&ids[lp]);
+    px.tri = w.x;
+    px.bsdf = w.y;
+    px.inst = w.z;
+    px.n = w.w;
+  }
+  for (uint32_t k = 0; k < K; ++k) {
+    PathState p;
+    if constexpr (CAMERA == 2) generate_path_lens(rc, gid, first_timestamp + k, 0u, p);
+    else generate_path_t<CAMERA != 0>(rc, gid, first_timestamp + k, 0u, p);
+    HitRec h;
+    uint32_t aux, key = 0xffffffffu;
+    stk.top = 0;
+    bool hit = trace_ray<false>(S.nodes, S.tri_isect, p.o, p.d, 0.0f, 1e10f, h, aux, stk, tab, &key);
+    const q4* shade = S.tri_shade;
+    uint32_t slot_base = 0;
+    if (G.dyn_nodes != nullptr) {
+      HitRec h2;
+      uint32_t aux2, key2 = 0xffffffffu;
+      stk.top = 0;
+      if (trace_ray<false>(G.dyn_nodes, G.dyn_isect, p.o, p.d, 0.0f, 1e10f, h2, aux2, stk, tab, &key2) &&
+          (!hit || h2.t < h.t || (h2.t == h.t && key2 < key))) {
+        h = h2;
+        hit = true;
+        shade = G.dyn_shade;
+        slot_base = G.static_slots;
+      }
+    }
+    if (hit && G.num_tris != 0u) {
+      // (tri_uv is indexed by the slot within the tree that was hit: a textured scene never splits -- scene_may_still_split wants
+      // num_textures == 0 -- so a hit that takes uv is a hit in the one tree and slot_base is 0)
+      const q4* uv = (TEX && S.tex.tri_uv != nullptr) ? (const q4*)S.tex.tri_uv + 2ll * h.slot : nullptr;
+      const FeatureSample f = feature_vertex<TEX>(S.bsdf, S.tex, shade + 4ll * h.slot, uv, p.d, h);
+      uint32_t tri = 0u, inst = 0u;
+      if (px.n == 0u) {  // (only the first sample of the frame names the pixel's ids)
+        tri = G.slot_to_global[slot_base + (uint32_t)h.slot];
+        inst = feature_instance(G.tri_first, G.num_instances, tri);
+      }
+      feature_fold(px, f, tri, inst);
+    } else {
+      feature_fold(px, feature_miss(), 0xffffffffu, 0xffffffffu);
+    }
+  }
+  qst(&albedo[lp], px.albedo);
+  qst(&geom[lp], px.geom);
+  {
+    const v4w w = {px.tri, px.bsdf, px.inst, px.n};
+    __builtin_nontemporal_store(w, &ids[lp]);
+  }
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

@@ -32,8 +32,7 @@ static int ensure_pool(gsp_context* ctx, gsp_context::Lane& L, uint64_t cap, uin
   return GSP_OK;
 }
 
-static RenderConstsLens render_consts(const gsp_context* ctx) {
-  const gsp_render_params* rp = &ctx->pipe_params;
+static RenderConstsLens render_consts(const gsp_context* ctx, const gsp_render_params* rp) {
   RenderConstsLens rcst;
   rcst.width = ctx->width;
   rcst.height = ctx->height;
@@ -55,6 +54,7 @@ static RenderConstsLens render_consts(const gsp_context* ctx) {
   set_lens_consts(rcst, ctx->lens);  // thin lens (gsp_set_lens)
   return rcst;
 }
+static RenderConstsLens render_consts(const gsp_context* ctx) { return render_consts(ctx, &ctx->pipe_params); }  // the running pipeline's
 
 #ifndef GSP_PIPE_DEPTH
 #define GSP_PIPE_DEPTH 2  // iterations queued ahead of the host's view of the counters (1 = wait for every read-back)
@@ -914,7 +914,175 @@ int gsp_copy_accum_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
   return GSP_OK;
 }
 
+// ---- first-hit feature buffers (include/gpuspectral_pt.h, "Feature buffers"; per-hit code: pt_features.h) ----
+// the three planes of the current frame: made by the first call that asks for them, zeroed once per frame
+static int ensure_features(gsp_context* ctx) {
+  if (ctx->features_ready) return GSP_OK;
+  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
+  for (DevBuf<q4>* b : {&ctx->feat_albedo, &ctx->feat_geom, &ctx->feat_ids}) {
+    CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
+    CTX_TRY(ctx, hipMemsetAsync(b->p, 0, n * sizeof(q4), ctx->stream));
+  }
+  ctx->features_ready = true;
+  return GSP_OK;
+}
+
 }  // extern "C"
+
+template <bool TEX, int CAMERA>
+static void launch_features(gsp_context* ctx, const SceneView& view, const RenderConstsLens& rc, const FeatureGeo& geo, const gsp_render_params* rp) {
+  const uint32_t n = (uint32_t)ctx->num_pixels;
+  hipLaunchKernelGGL((k_features<TEX, CAMERA>), dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, view,
+                     static_cast<const typename FeatureConsts<CAMERA>::type&>(rc), geo, n, rp->spp, rp->first_timestamp,
+                     ctx->subset ? (const uint32_t*)ctx->pixel_ids.p : (const uint32_t*)nullptr, ctx->feat_albedo.p, ctx->feat_geom.p,
+                     (v4w*)ctx->feat_ids.p);
+}
+
+extern "C" {
+
+int gsp_render_features(gsp_context* ctx, const gsp_render_params* rp_host) {
+  if (!ctx || !rp_host) return GSP_ERR_INVALID;
+  gsp_render_params rp_copy;  // struct_size: the rule of gsp_render (fields beyond the host's struct are 0)
+  std::memset(&rp_copy, 0, sizeof(rp_copy));
+  {
+    const size_t abi8 = offsetof(gsp_render_params, disable_nee) + sizeof(uint32_t);
+    const size_t n = rp_host->struct_size ? std::min<size_t>(rp_host->struct_size, sizeof(rp_copy)) : abi8;
+    if (n < abi8) {
+      ctx->err = "gsp_render_params.struct_size " + std::to_string(rp_host->struct_size) + " is smaller than the ABI-8 struct (" + std::to_string(abi8) +
+                 " bytes): set it with gsp_default_render_params or sizeof(gsp_render_params)";
+      return GSP_ERR_INVALID;
+    }
+    std::memcpy(&rp_copy, rp_host, n);
+  }
+  const gsp_render_params* const rp = &rp_copy;
+  if (!ctx->have_scene || !ctx->have_frame) {
+    ctx->err = "gsp_render_features needs gsp_upload_scene and gsp_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  if (rp->spp == 0) {
+    ctx->err = "gsp_render_features: spp must be at least 1";
+    return GSP_ERR_INVALID;
+  }
+  if (rp->pixel_filter > GSP_FILTER_GAUSSIAN) {
+    ctx->err = "pixel_filter " + std::to_string(rp->pixel_filter) + " is not a GSP_FILTER_* value";
+    return GSP_ERR_INVALID;
+  }
+  if (!(rp->pixel_filter_param >= 0.0f) || std::isinf(rp->pixel_filter_param)) {
+    ctx->err = "pixel_filter_param must be 0 (the filter's default) or a finite positive value";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  // NO DRAIN: the samples gsp_render has left in flight stay where they are (between two calls nothing of them runs: every lane's
+  // stream is idle) and finish with the next gsp_render / gsp_download, exactly as without this call -- the pipeline, the accumulate
+  // buffer, the memo, the pixel statistics and every counter of gsp_stats are not touched.  The pass reads ONE version of the
+  // scene, the newest: the context's own tree pointers and the newest slot of the table ring, as gsp_trace does.
+  if (std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 > kFinishLevels) {
+    ctx->err = "gsp_render_features: the scene's BVH has " + std::to_string(std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u)) +
+               " levels, the per-lane traversal stack holds " + std::to_string(kFinishLevels - 2);
+    return GSP_ERR_INVALID;
+  }
+  {
+    int rc_ = ensure_features(ctx);
+    if (rc_ != GSP_OK) return rc_;
+  }
+  if (ctx->num_pixels == 0) return GSP_OK;
+  if (ctx->split && !ctx->s2g_all_valid) {
+    int rc_ = make_split_s2g(ctx);
+    if (rc_ != GSP_OK) return rc_;
+  }
+  // the newest version of everything: the tables from wherever their ring holds it, the tree(s) from the context's own pointers
+  // (a split scene: `bvh` is the static tree at the front of the ring, `dyn` the newest slot of the edited instances' tree)
+  SceneView view = ctx->view(true, true);
+  view.nodes = ctx->bvh.nodes;
+  view.tri_isect = ctx->bvh.tri_isect;
+  view.tri_shade = ctx->bvh.tri_shade;
+  FeatureGeo geo{};
+  if (ctx->split) {
+    geo.dyn_nodes = ctx->dyn.nodes;
+    geo.dyn_isect = ctx->dyn.tri_isect;
+    geo.dyn_shade = ctx->dyn.tri_shade;
+    geo.static_slots = ctx->static_slots;
+  }
+  geo.num_tris = (uint32_t)ctx->total_tris;
+  geo.slot_to_global = ctx->split ? ctx->s2g_all.p : ctx->bvh.slot_to_global;
+  geo.tri_first = ctx->d_first.p;
+  geo.num_instances = (uint32_t)ctx->h_inst.size();
+  const RenderConstsLens rc = render_consts(ctx, rp);
+  const int camera = rc.lens_radius > 0.0f ? 2 : (rc.pixel_filter != GSP_FILTER_NONE ? 1 : 0);
+  if (ctx->textured) {
+    if (camera == 2) launch_features<true, 2>(ctx, view, rc, geo, rp);
+    else if (camera == 1) launch_features<true, 1>(ctx, view, rc, geo, rp);
+    else launch_features<true, 0>(ctx, view, rc, geo, rp);
+  } else {
+    if (camera == 2) launch_features<false, 2>(ctx, view, rc, geo, rp);
+    else if (camera == 1) launch_features<false, 1>(ctx, view, rc, geo, rp);
+    else launch_features<false, 0>(ctx, view, rc, geo, rp);
+  }
+  CTX_TRY(ctx, hipGetLastError());
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the pass is complete when the call returns: a scene edit may follow at once)
+  return GSP_OK;
+}
+
+// one compact plane -> `out` in the full-frame layout (unowned pixels 0), through read_back_bytes
+static int download_feature_plane(gsp_context* ctx, const q4* plane, void* out) {
+  if (!out) return GSP_OK;
+  if (!ctx->subset) return read_back_bytes(ctx, plane, ctx->num_pixels * sizeof(q4), out);
+  std::vector<q4> tmp(ctx->num_pixels);
+  int rc = read_back_bytes(ctx, plane, ctx->num_pixels * sizeof(q4), tmp.data());
+  if (rc != GSP_OK) return rc;
+  std::memset(out, 0, sizeof(q4) * (size_t)ctx->width * ctx->height);
+  for (uint64_t i = 0; i < ctx->num_pixels; ++i) std::memcpy((uint8_t*)out + sizeof(q4) * ctx->pixel_ids_host[i], &tmp[i], sizeof(q4));
+  return GSP_OK;
+}
+
+int gsp_download_features(gsp_context* ctx, float* albedo, float* geom, uint32_t* ids) {
+  if (!ctx || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_features(ctx);
+  if (rc == GSP_OK && ctx->num_pixels == 0) {
+    const size_t bytes = sizeof(q4) * (size_t)ctx->width * ctx->height;
+    for (void* o : {(void*)albedo, (void*)geom, (void*)ids})
+      if (o) std::memset(o, 0, bytes);
+    return GSP_OK;
+  }
+  if (rc == GSP_OK) rc = download_feature_plane(ctx, ctx->feat_albedo.p, albedo);
+  if (rc == GSP_OK) rc = download_feature_plane(ctx, ctx->feat_geom.p, geom);
+  if (rc == GSP_OK) rc = download_feature_plane(ctx, ctx->feat_ids.p, ids);
+  return rc;
+}
+
+int gsp_copy_features_to_device(gsp_context* ctx, void* albedo, void* geom, void* ids, uint64_t bytes_each) {
+  if (!ctx || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  if (bytes_each < ctx->num_pixels * sizeof(q4)) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  int rc = ensure_features(ctx);
+  if (rc != GSP_OK) return rc;
+  const size_t n = ctx->num_pixels * sizeof(q4);
+  if (albedo && n) CTX_TRY(ctx, hipMemcpyAsync(albedo, ctx->feat_albedo.p, n, hipMemcpyDeviceToDevice, ctx->stream));
+  if (geom && n) CTX_TRY(ctx, hipMemcpyAsync(geom, ctx->feat_geom.p, n, hipMemcpyDeviceToDevice, ctx->stream));
+  if (ids && n) CTX_TRY(ctx, hipMemcpyAsync(ids, ctx->feat_ids.p, n, hipMemcpyDeviceToDevice, ctx->stream));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+}  // extern "C"
+
+// gsp_multi_*: the three compact feature planes of a share (device pointers; complete: gsp_render_features returns synchronised)
+int gsp::gsp_internal_features(gsp_context* ctx, void** albedo, void** geom, void** ids, uint64_t* num_pixels) {
+  if (!ctx || !ctx->have_frame) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_features(ctx);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *albedo = ctx->feat_albedo.p;
+  *geom = ctx->feat_geom.p;
+  *ids = ctx->feat_ids.p;
+  *num_pixels = ctx->num_pixels;
+  return GSP_OK;
+}
 
 int gsp::gsp_internal_accum(gsp_context* ctx, void** accum, uint64_t* num_pixels, hipStream_t* stream) {
   if (!ctx || !ctx->have_frame) return GSP_ERR_INVALID;

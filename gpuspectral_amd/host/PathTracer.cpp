@@ -133,6 +133,7 @@ void PathTracer::setup() {
 
 void PathTracer::reset() {
   timestamp = 0;
+  featureTimestamp = 0;
   check(gsp_frame_begin(ctx, width, height, pixelIds.empty() ? nullptr : pixelIds.data(), pixelIds.size()),
         "gsp_frame_begin");
 }
@@ -242,6 +243,38 @@ gsp_luminance PathTracer::frameLuminance(bool drain) {
   return l;
 }
 
+// the render call's parameters for a feature pass: the same filter choice, the feature frame's own timestamps
+static gsp_render_params featureParams(const gsp_render_params& params, const Scene& scene, uint32_t spp, int first) {
+  gsp_render_params p = params;
+  p.spp = spp;
+  p.first_timestamp = (uint32_t)first;
+  if (p.pixel_filter == GSP_FILTER_NONE && scene.pixelFilter != GSP_FILTER_NONE) {
+    p.pixel_filter = scene.pixelFilter;
+    p.pixel_filter_param = scene.pixelFilterParam;
+  }
+  return p;
+}
+
+void PathTracer::renderFeatures(const Scene& scene, uint32_t spp) {
+  prepareScene(scene);
+  const gsp_render_params p = featureParams(params, scene, spp, featureTimestamp);
+  check(gsp_render_features(ctx, &p), "gsp_render_features");
+  featureTimestamp += (int)spp;
+}
+
+void PathTracer::downloadFeatures(std::vector<float>* albedo, std::vector<float>* geom, std::vector<uint32_t>* ids) {
+  const size_t n = (size_t)width * height * 4;
+  if (albedo) albedo->assign(n, 0.0f);
+  if (geom) geom->assign(n, 0.0f);
+  if (ids) ids->assign(n, 0u);
+  check(gsp_download_features(ctx, albedo ? albedo->data() : nullptr, geom ? geom->data() : nullptr, ids ? ids->data() : nullptr),
+        "gsp_download_features");
+}
+
+void PathTracer::copyFeaturesToDevice(void* albedo, void* geom, void* ids, uint64_t bytesEach) {
+  check(gsp_copy_features_to_device(ctx, albedo, geom, ids, bytesEach), "gsp_copy_features_to_device");
+}
+
 gsp_stats PathTracer::stats() {
   gsp_stats s;
   check(gsp_get_stats(ctx, &s), "gsp_get_stats");
@@ -265,6 +298,7 @@ void MultiGpuPathTracer::check(int rc, const char* what) {
 
 void MultiGpuPathTracer::reset() {
   timestamp = 0;
+  featureTimestamp = 0;
   check(gsp_multi_frame_begin(multi, width, height), "gsp_multi_frame_begin");
 }
 
@@ -322,6 +356,22 @@ std::vector<uint32_t> MultiGpuPathTracer::downloadDisplay() {
   std::vector<uint32_t> out((size_t)width * height);
   check(gsp_multi_download_display(multi, &display, out.data()), "gsp_multi_download_display");
   return out;
+}
+
+void MultiGpuPathTracer::renderFeatures(const Scene& scene, uint32_t spp) {
+  prepareScene(scene);
+  const gsp_render_params p = featureParams(params, scene, spp, featureTimestamp);
+  check(gsp_multi_render_features(multi, &p), "gsp_multi_render_features");
+  featureTimestamp += (int)spp;
+}
+
+void MultiGpuPathTracer::downloadFeatures(std::vector<float>* albedo, std::vector<float>* geom, std::vector<uint32_t>* ids) {
+  const size_t n = (size_t)width * height * 4;
+  if (albedo) albedo->assign(n, 0.0f);
+  if (geom) geom->assign(n, 0.0f);
+  if (ids) ids->assign(n, 0u);
+  check(gsp_multi_download_features(multi, albedo ? albedo->data() : nullptr, geom ? geom->data() : nullptr, ids ? ids->data() : nullptr),
+        "gsp_multi_download_features");
 }
 
 gsp_stats MultiGpuPathTracer::stats(std::vector<gsp_stats>* perShare) {

@@ -94,7 +94,14 @@ class PathTracer : public RenderPassCreator {
   void peekDisplayToDevice(void* deviceDst, uint64_t bytes, uint32_t* samplesFolded = nullptr);
   // the frame statistics Reinhard measures (drain = false: the buffer as it stands)
   gsp_luminance frameLuminance(bool drain = true);
-  void reset();  // timestamp = 0, accumulate buffer cleared
+  // Feature buffers (gpuspectral_pt.h "Feature buffers"): `spp` feature samples per owned pixel -- the first hit of the beauty
+  // samples' camera rays under this tracer's filter and the scene's lens -- from timestamp 0 on the first call of a frame and
+  // continuing from there; independent of render() and of getTimestamp().  downloadFeatures: full-frame planes, width*height*4
+  // values each ({r, g, b, coverage}, {nx, ny, nz, t}, {triangle, bsdf, instance, samples}); any pointer may be null.
+  void renderFeatures(const Scene& scene, uint32_t spp);
+  void downloadFeatures(std::vector<float>* albedo, std::vector<float>* geom, std::vector<uint32_t>* ids);
+  void copyFeaturesToDevice(void* albedo, void* geom, void* ids, uint64_t bytesEach);  // compact planes, device memory
+  void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }
   gsp_stats stats();
   // reference literals by default (MAX_DEPTH 50, RR > 10, clamp 20).  params.pixel_filter != GSP_FILTER_NONE overrides the
@@ -111,6 +118,7 @@ class PathTracer : public RenderPassCreator {
   gsp_ctx_options options{};
   SceneTracker tracker;
   int timestamp{0};
+  int featureTimestamp{0};  // feature samples folded since the last reset()
 };
 
 // The same pass over several GPUs of one node: the frame is cut into interleaved 32x32 tiles (one share per entry of
@@ -131,6 +139,8 @@ class MultiGpuPathTracer : public RenderPassCreator {
   void invalidateScene() { tracker.forget(); }
   std::vector<float> download();  // RGBA32F, row-major, width*height*4 floats
   std::vector<uint32_t> downloadDisplay();  // as PathTracer::downloadDisplay, on the gathered frame
+  void renderFeatures(const Scene& scene, uint32_t spp);  // as PathTracer::renderFeatures, on every share
+  void downloadFeatures(std::vector<float>* albedo, std::vector<float>* geom, std::vector<uint32_t>* ids);  // the gathered planes
   void reset();
   int getTimestamp() const { return timestamp; }
   int numShares() const { return (int)devices.size(); }
@@ -145,6 +155,7 @@ class MultiGpuPathTracer : public RenderPassCreator {
   std::vector<int> devices;
   SceneTracker tracker;
   int timestamp{0};
+  int featureTimestamp{0};
 };
 
 // Headless output step: little-endian PFM ("PF", bottom-to-top rows) of the RGB channels.

@@ -13,6 +13,9 @@
 //   --aperture R --focus-distance D | --focus-pixel X,Y [--blades N[:rot_deg]]: thin lens (gsp_set_lens; depth of field).
 //   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
 //   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
+//   --features PREFIX [--feature-spp N]: also render the feature buffers (gpuspectral_pt.h "Feature buffers"; N samples per pixel,
+//   default the frame's spp, under the frame's filter and lens) and write PREFIX.albedo.pfm / .normal.pfm / .depth.pfm and
+//   PREFIX.albedo.png / .normal.png (the normal mapped as 0.5 + 0.5 n).  Without --features nothing more is written or printed.
 //   --ldr out.png: also write the LDR film (gpuspectral_pt.h "LDR film": tone-mapped and encoded on the GPU) as an 8-bit RGB PNG;
 //   --tonemap clamp|aces|reinhard[:key[:burn]], --exposure E (f-stops), --gamma G|srgb: its gsp_display; --scene-film:
 //   LoadOptions::readFilm (the sensor's ldrfilm; the flags override the scene's values one by one).  Without --ldr: no PNG
@@ -44,6 +47,8 @@ int main(int argc, char** argv) {
   bool focusPixel = false;
   int blades = -1;
   std::string ldrPath;
+  std::string featuresPrefix;
+  int featureSpp = -1;  // (-1 = not given: the frame's spp)
   int tonemap = -1;  // (-1 = not given)
   float tmKey = -1.0f, tmBurn = -1.0f, exposure = 0.0f, gamma = -1.0f;
   bool haveExposure = false;
@@ -67,6 +72,16 @@ int main(int argc, char** argv) {
     else if (flag == "--scene-lens") options.readLens = true;
     else if (flag == "--scene-film") options.readFilm = true;
     else if (flag == "--ldr" && argc > 2) ldrPath = argv[2], used = 2;
+    else if (flag == "--features" && argc > 2) featuresPrefix = argv[2], used = 2;
+    else if (flag == "--feature-spp" && argc > 2) {
+      char* e = nullptr;
+      const long v = std::strtol(argv[2], &e, 10);
+      if (e == argv[2] || *e != 0 || v < 1 || v > 1000000) {
+        std::fprintf(stderr, "gsp_render: --feature-spp N: a sample count of at least 1\n");
+        return 2;
+      }
+      featureSpp = (int)v, used = 2;
+    }
     else if (flag == "--tonemap" && argc > 2) {
       const std::string v = argv[2];
       const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
@@ -173,8 +188,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --tonemap, --exposure, --gamma and --scene-film need --ldr out.png\n");
     return 2;
   }
+  if (featuresPrefix.empty() && featureSpp >= 0) {
+    std::fprintf(stderr, "gsp_render: --feature-spp needs --features PREFIX\n");
+    return 2;
+  }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -231,7 +250,8 @@ int main(int argc, char** argv) {
     if (haveExposure) display.exposure = exposure;
     if (gamma >= 0.0f) display.gamma = gamma;
     std::vector<uint32_t> ldr;
-    std::vector<float> img;
+    std::vector<float> img, featAlbedo, featGeom;
+    const uint32_t fspp = featureSpp > 0 ? (uint32_t)featureSpp : spp;
     gsp_stats st;
     double s;
     if (devices.size() == 1) {
@@ -251,6 +271,10 @@ int main(int argc, char** argv) {
         pt.display = display;
         ldr = pt.downloadDisplay();
       }
+      if (!featuresPrefix.empty()) {  // after the timed frame: the feature planes (gpuspectral_pt.h "Feature buffers")
+        pt.renderFeatures(scene, fspp);
+        pt.downloadFeatures(&featAlbedo, &featGeom, nullptr);
+      }
     } else {
       MultiGpuPathTracer pt(width, height, devices, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
@@ -266,11 +290,34 @@ int main(int argc, char** argv) {
         pt.display = display;
         ldr = pt.downloadDisplay();
       }
+      if (!featuresPrefix.empty()) {  // after the timed frame: the feature planes (gpuspectral_pt.h "Feature buffers")
+        pt.renderFeatures(scene, fspp);
+        pt.downloadFeatures(&featAlbedo, &featGeom, nullptr);
+      }
       std::printf("%zu shares (32x32 tiles), gathered on device %d\n", devices.size(), devices[0]);
     }
     writePfm(argv[2], img.data(), width, height);
     writePpm(std::string(argv[2]) + ".ppm", img.data(), width, height, false);  // LDR preview, gamma 2.2
     if (!ldrPath.empty()) writePng(ldrPath, ldr.data(), width, height, false);
+    if (!featuresPrefix.empty()) {
+      // albedo and normal as RGB PFM + an 8-bit PNG (the normal mapped as 0.5 + 0.5 n), the depth as a PFM with t in every channel
+      const size_t n = (size_t)width * height;
+      std::vector<float> depth(4 * n);
+      std::vector<uint32_t> a8(n), n8(n);
+      auto byte = [](float v) { return (uint32_t)(std::min(std::max(v, 0.0f), 1.0f) * 255.0f + 0.5f); };
+      for (size_t i = 0; i < n; ++i) {
+        depth[4 * i] = depth[4 * i + 1] = depth[4 * i + 2] = featGeom[4 * i + 3];
+        depth[4 * i + 3] = 1.0f;
+        a8[i] = byte(featAlbedo[4 * i]) | (byte(featAlbedo[4 * i + 1]) << 8) | (byte(featAlbedo[4 * i + 2]) << 16) | 0xff000000u;
+        n8[i] = byte(0.5f + 0.5f * featGeom[4 * i]) | (byte(0.5f + 0.5f * featGeom[4 * i + 1]) << 8) | (byte(0.5f + 0.5f * featGeom[4 * i + 2]) << 16) | 0xff000000u;
+      }
+      writePfm(featuresPrefix + ".albedo.pfm", featAlbedo.data(), width, height);
+      writePfm(featuresPrefix + ".normal.pfm", featGeom.data(), width, height);
+      writePfm(featuresPrefix + ".depth.pfm", depth.data(), width, height);
+      writePng(featuresPrefix + ".albedo.png", a8.data(), width, height, false);
+      writePng(featuresPrefix + ".normal.png", n8.data(), width, height, false);
+      std::printf("features: %u samples per pixel -> %s.{albedo,normal,depth}.pfm, %s.{albedo,normal}.png\n", fspp, featuresPrefix.c_str(), featuresPrefix.c_str());
+    }
     std::printf("%llu triangles, %ux%u x %u spp in %.3f s: %.1f Mrays/s, %.2f Msamples/s (BVH build %.1f ms)\n",
                 (unsigned long long)st.num_triangles, width, height, spp, s,
                 (st.extension_rays + st.shadow_rays) / s / 1e6, st.samples / s / 1e6, st.bvh_build_ms);

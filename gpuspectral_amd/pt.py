@@ -43,6 +43,9 @@ EXPORTS = (
     "gsp_download_display",
     "gsp_peek_display",
     "gsp_peek_display_to_device",
+    "gsp_render_features",
+    "gsp_download_features",
+    "gsp_copy_features_to_device",
     "gsp_get_stats",
     "gsp_reset_stats",
     "gsp_trace",
@@ -65,6 +68,8 @@ EXPORTS = (
     "gsp_multi_gather_route",
     "gsp_multi_download",
     "gsp_multi_download_display",
+    "gsp_multi_render_features",
+    "gsp_multi_download_features",
     "gsp_multi_get_stats",
     "gsp_multi_reset_stats",
     "gsp_multi_last_error",
@@ -126,6 +131,11 @@ def load():
     L.gsp_peek_display.argtypes = [vp, C.POINTER(abi.Display), vp, C.POINTER(C.c_uint32)]
     L.gsp_peek_display_to_device.argtypes = [vp, C.POINTER(abi.Display), vp, u64, C.POINTER(C.c_uint32)]
     L.gsp_multi_download_display.argtypes = [vp, C.POINTER(abi.Display), vp]
+    L.gsp_render_features.argtypes = [vp, C.POINTER(abi.RenderParams)]
+    L.gsp_download_features.argtypes = [vp, vp, vp, vp]
+    L.gsp_copy_features_to_device.argtypes = [vp, vp, vp, vp, u64]
+    L.gsp_multi_render_features.argtypes = [vp, C.POINTER(abi.RenderParams)]
+    L.gsp_multi_download_features.argtypes = [vp, vp, vp, vp]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -176,7 +186,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -359,6 +369,29 @@ class Context:
         self._check(self._L.gsp_frame_luminance(self._h, 1 if drain else 0, C.byref(out)), "gsp_frame_luminance")
         return out.as_dict()
 
+    # ---- feature buffers (gpuspectral_pt.h "Feature buffers") ----
+    def render_features(self, spp=1, first_timestamp=0, params=None, **overrides):
+        """gsp_render_features: spp feature samples (first hit of the beauty sample's camera ray) for every owned pixel; of the
+        keyword fields only pixel_filter / pixel_filter_param are read."""
+        p = params or abi.default_render_params()
+        p.spp, p.first_timestamp = spp, first_timestamp
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        self._check(self._L.gsp_render_features(self._h, C.byref(p)), "gsp_render_features")
+
+    def download_features(self, albedo=True, geom=True, ids=True):
+        """gsp_download_features: (albedo[h,w,4] float32 {r,g,b,coverage}, geom[h,w,4] float32 {nx,ny,nz,depth}, ids[h,w,4] uint32
+        {triangle, bsdf, instance, samples folded}); a plane switched off is None (its pointer is NULL)."""
+        a = np.zeros((self.height, self.width, 4), np.float32) if albedo else None
+        g = np.zeros((self.height, self.width, 4), np.float32) if geom else None
+        i = np.zeros((self.height, self.width, 4), np.uint32) if ids else None
+        self._check(self._L.gsp_download_features(self._h, *(x.ctypes.data if x is not None else None for x in (a, g, i))), "gsp_download_features")
+        return a, g, i
+
+    def copy_features_to_device(self, albedo_ptr, geom_ptr, ids_ptr, nbytes_each):
+        """gsp_copy_features_to_device: the compact planes into device memory (e.g. torch tensors' data_ptr()); a pointer may be None."""
+        self._check(self._L.gsp_copy_features_to_device(self._h, albedo_ptr, geom_ptr, ids_ptr, nbytes_each), "gsp_copy_features_to_device")
+
     def pixel_stats(self):
         """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of
         Y^2 over each pixel's samples and the samples folded into it (gsp_download_pixel_stats)."""
@@ -503,6 +536,22 @@ class MultiContext:
         self._check(self._L.gsp_multi_download_display(self._h, C.byref(display) if display is not None else None, out.ctypes.data),
                     "gsp_multi_download_display")
         return out
+
+    def render_features(self, spp=1, first_timestamp=0, params=None, **overrides):
+        """gsp_multi_render_features: Context.render_features on every share."""
+        p = params or abi.default_render_params()
+        p.spp, p.first_timestamp = spp, first_timestamp
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        self._check(self._L.gsp_multi_render_features(self._h, C.byref(p)), "gsp_multi_render_features")
+
+    def download_features(self):
+        """gsp_multi_download_features: Context.download_features of the gathered planes."""
+        a = np.zeros((self.height, self.width, 4), np.float32)
+        g = np.zeros((self.height, self.width, 4), np.float32)
+        i = np.zeros((self.height, self.width, 4), np.uint32)
+        self._check(self._L.gsp_multi_download_features(self._h, a.ctypes.data, g.ctypes.data, i.ctypes.data), "gsp_multi_download_features")
+        return a, g, i
 
     def stats(self, per_share=False):
         tot = abi.Stats()

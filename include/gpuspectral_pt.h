@@ -67,7 +67,9 @@ extern "C" {
                                 gsp_download_pixel_stats, gsp_stats.adaptive_rounds / adaptive_active_pixels;
                                 additions within version 9 (new exports only, no struct changed): gsp_set_lens,
                                 gsp_multi_set_lens, gsp_focus_distance (see "Thin lens"); gsp_frame_luminance, gsp_download_display,
-                                gsp_peek_display, gsp_peek_display_to_device, gsp_multi_download_display (see "LDR film") */
+                                gsp_peek_display, gsp_peek_display_to_device, gsp_multi_download_display (see "LDR film");
+                                gsp_render_features, gsp_download_features, gsp_copy_features_to_device,
+                                gsp_multi_render_features, gsp_multi_download_features (see "Feature buffers") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -653,6 +655,58 @@ int gsp_peek_display(gsp_context* ctx, const gsp_display* display, uint32_t* out
  * destination directly; any other one receives a device-to-device copy of the context's own RGBA8 buffer. */
 int gsp_peek_display_to_device(gsp_context* ctx, const gsp_display* display, void* device_dst, uint64_t bytes, uint32_t* samples_folded);
 
+/*
+ * Feature buffers: first-hit albedo, shading normal, depth and object identity per pixel.
+ *
+ * What a denoiser, a compositor or a debugger needs beside the beauty image.  No reference code defines them, so this header does.
+ *
+ * A FEATURE SAMPLE of (pixel, timestamp) is the primary ray generate_path yields for that pixel and timestamp under the context's
+ * lens (gsp_set_lens) and the pixel_filter / pixel_filter_param of the call: the camera ray of the beauty sample with the same
+ * timestamp, bit for bit.  With no filter and no lens every feature sample of a pixel is the same ray and the mean equals one
+ * sample, bit for bit; with a filter or a lens the planes are anti-aliased / defocused exactly as the beauty image is.
+ *
+ * The closest hit follows the library's rule (min t, then min triangle id).  At the hit, with shade_vertex's expressions:
+ *   normal    SN as shade_vertex forms it: the interpolated transformInvT * n, normalised, after the two-faced flip
+ *             (rayhit.rchit:690-707); world space.
+ *   depth     the hit's t: the distance along the ray -- not camera z (with a lens there is no single camera axis).
+ *   albedo    DIFFUSE: reflectance.  SMOOTH_PLASTIC, ROUGH_PLASTIC, SMOOTH_FLOOR, ROUGH_FLOOR: diffuse.  ROUGH_CONDUCTOR:
+ *             reflectance.  SMOOTH_CONDUCTOR, SMOOTH_DIELECTRIC: (1, 1, 1).  A record whose has_texture resolves in a textured
+ *             scene: the texture value shade_vertex takes as kD.  A hit on a triangle with non-zero emission: min(emission, 1)
+ *             per channel instead.  The resident diffuse record holds reflectance / pi (float32, formed at upload): the albedo of
+ *             DIFFUSE is DEFINED as that float32 value times float32 pi, which may differ from the uploaded reflectance in the
+ *             last bit.
+ *   coverage  1 on a hit.  A miss contributes 0 to every channel of both float planes, with or without an environment map.
+ *   ids       uint32 x 4, not averaged: {scene-wide triangle index as gsp_trace reports it, BSDF handle, instance index, feature
+ *             samples folded}.  The first three are those of the FIRST feature sample folded into the pixel in this frame, and
+ *             0xffffffff when that sample missed.
+ *
+ * Three planes per owned pixel, 16 bytes each: albedo = {r, g, b, coverage} and geom = {nx, ny, nz, depth} (RGBA32F running means)
+ * and ids.  The mean: with n = the pixel's folded count and a = 1.0f / (float)(n + 1), every channel becomes
+ *     mean + (sample - mean) * a            (float32, in this order: mix(mean, sample, a))
+ * -- the form that returns the sample exactly for n == 0 and the mean exactly when sample == mean.  Samples are folded in
+ * increasing timestamp order, so one call of 5 samples and calls of 2 + 3 give the same bits.  The mean normal is not
+ * re-normalised.  gsp_frame_begin clears the planes; they are allocated by the first call of a context that asks for them
+ * (48 bytes per owned pixel), a context that never does holds nothing.
+ *
+ * gsp_render_features reads struct_size, spp, first_timestamp, pixel_filter and pixel_filter_param of `params` and ignores the
+ * rest, the adaptive fields included: EVERY owned pixel gets spp feature samples.  It does not touch the accumulate buffer, the
+ * primary-hit memo, the pixel statistics or the beauty timestamps, and adds nothing to gsp_stats.  It does NOT wait for the
+ * samples gsp_render has left in flight: they stay queued and finish with the next gsp_render / gsp_download exactly as they would
+ * have without this call, so a frame's image and counters do not depend on feature calls between its render calls.  The pass sees
+ * the newest version of the scene (tables and geometry, whatever versions the samples in flight still carry); on a scene that
+ * gsp_update_instances has split into two trees it walks BOTH trees per ray and keeps the closer hit, as the tail of a drain does
+ * -- the scene is not rebuilt.
+ * The pass is complete when the call returns.  GSP_ERR_INVALID (text at gsp_last_error): no scene or no frame, spp == 0, an
+ * unknown filter id, a negative or non-finite filter parameter, or a BVH deeper than the 34 levels a lane's stack holds.
+ */
+int gsp_render_features(gsp_context* ctx, const gsp_render_params* params);
+/* Full-frame layout like gsp_download: width*height records of 4 floats / 4 floats / 4 words, unowned pixels 0.  Any pointer may
+ * be NULL.  Staged through the pinned buffers of the frame read-back. */
+int gsp_download_features(gsp_context* ctx, float* albedo, float* geom, uint32_t* ids);
+/* The same planes, COMPACT (num_pixels records each, pixel_ids order, as gsp_copy_accum_to_device), into caller-owned device
+ * memory of bytes_each >= num_pixels * 16 bytes per destination; any pointer may be NULL.  Complete when the call returns. */
+int gsp_copy_features_to_device(gsp_context* ctx, void* albedo, void* geom, void* ids, uint64_t bytes_each);
+
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
 
@@ -720,6 +774,11 @@ int gsp_multi_download(gsp_multi* m, float* out_rgba);
 /* gsp_multi_gather + the LDR film on the gathered frame (statistics over the whole frame) + one copy to the host: width*height
  * words, identical to a single-GPU gsp_download_display. */
 int gsp_multi_download_display(gsp_multi* m, const gsp_display* display, uint32_t* out_rgba8);
+/* Feature buffers over the shares: gsp_render_features on every share (its gsp_tile_partition pixels); the download gathers the
+ * three planes into devices[0] with peer copies (also where the beauty gather goes through RCCL), assembles them there and
+ * copies them to the host: identical to a single-GPU gsp_download_features.  Any pointer may be NULL. */
+int gsp_multi_render_features(gsp_multi* m, const gsp_render_params* params);
+int gsp_multi_download_features(gsp_multi* m, float* albedo, float* geom, uint32_t* ids);
 /* total (optional): counters summed over the shares, times of the slowest share (they run concurrently);
  * per_share (optional): gsp_multi_num_shares() records. */
 int gsp_multi_get_stats(gsp_multi* m, gsp_stats* total, gsp_stats* per_share);
