@@ -190,6 +190,23 @@ def display(tonemap=TONEMAP_CLAMP, exposure=0.0, gamma=0.0, key=0.0, burn=0.0, l
     return Display(C.sizeof(Display), tonemap, exposure, gamma, key, burn, log_avg_luminance, max_luminance)
 
 
+class Denoise(C.Structure):
+    """gsp_denoise: the edge-avoiding a-trous denoiser's parameters (gsp_download_denoised); all zero = every default."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("iterations", C.c_uint32),  # 0 = 5; otherwise 1..8
+        ("sigma_color", C.c_float),  # 0 = default, +inf = the term is off
+        ("sigma_normal", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("sigma_albedo", C.c_float),
+    ]
+
+
+def denoise(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, sigma_albedo=0.0):
+    return Denoise(C.sizeof(Denoise), iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
+
+
 class Luminance(C.Structure):
     """gsp_luminance: the frame statistics of the Reinhard operator (gsp_frame_luminance)."""
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/gpuspectral_pt.h"
+#include "pt_denoise.h"
 #include "pt_display.h"
 #include "pt_stages.h"
 
@@ -68,6 +69,8 @@ struct BuildInput {
 __attribute__((visibility("hidden"))) int gsp_internal_accum(gsp_context* ctx, void** accum, uint64_t* num_pixels, hipStream_t* stream);
 // ... and its three compact feature planes (gsp_render_features), 16 bytes per owned pixel each
 __attribute__((visibility("hidden"))) int gsp_internal_features(gsp_context* ctx, void** albedo, void** geom, void** ids, uint64_t* num_pixels);
+// ... and whether gsp_render_features has run on it since its gsp_frame_begin (1 / 0; the denoiser refuses planes nobody rendered)
+__attribute__((visibility("hidden"))) int gsp_internal_features_rendered(const gsp_context* ctx);
 // The options a context was created with, defaults filled in (pt_multi.hip divides memory_share among the shares of a device).
 __attribute__((visibility("hidden"))) void gsp_internal_resolve_options(const gsp_ctx_options* in, gsp_ctx_options* out);
 
@@ -77,6 +80,12 @@ __attribute__((visibility("hidden"))) void gsp_internal_resolve_options(const gs
 __attribute__((visibility("hidden"))) hipError_t display_measure(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, DisplayStatsRec* d_rec,
                                                                  DisplayStatsRec* h_rec, gsp_luminance* out);
 __attribute__((visibility("hidden"))) hipError_t display_map(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, const DisplayConsts& k, uint32_t* dst);
+
+// ---- denoiser (pt_denoise.h) on a full frame of width x height: `accum`, `albedo`, `geom` are its RGBA32F planes, `e0`, `e1`, `a`
+// scratch planes and `out` the result, all 16 bytes per pixel, 16-byte aligned device memory of the current device.  Queues
+// k_denoise_prepare and k.iterations launches of k_denoise_atrous on `stream`; does not synchronise.
+__attribute__((visibility("hidden"))) hipError_t denoise_run(hipStream_t stream, uint32_t num_cus, const void* accum, const void* albedo, const void* geom,
+                                                             uint32_t width, uint32_t height, const DenoiseConsts& k, void* e0, void* e1, void* a, void* out);
 
 // Bakes the instances' triangles to world space and builds the wide BVH (PLOC + reinsertion + collapse) on `stream`.
 // Returns GSP_OK or an error code with `err` set.

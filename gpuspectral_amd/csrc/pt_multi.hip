@@ -110,6 +110,9 @@ struct gsp_multi {
   uint32_t* d_display = nullptr;
   DisplayStatsRec* d_display_rec = nullptr;
   DisplayStatsRec* h_display_rec = nullptr;
+  // denoiser on the gathered frame (gsp_multi_download_denoised): the gathered albedo and geom planes (m->frame holds the beauty
+  // image meanwhile), the filter's three scratch planes and its result; width * height records each, made on first use
+  q4* dn[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   std::string err;
   // RCCL: one communicator rank per share (device lists without repeats), ranks = share indices
   std::vector<ncclComm_t> comms;
@@ -174,6 +177,10 @@ void free_frame(gsp_multi* m) {
   if (m->d_display) (void)hipFree(m->d_display);
   if (m->d_display_rec) (void)hipFree(m->d_display_rec);
   if (m->h_display_rec) (void)hipHostFree(m->h_display_rec);
+  for (q4*& b : m->dn) {
+    if (b) (void)hipFree(b);
+    b = nullptr;
+  }
   m->d_display = nullptr;
   m->d_display_rec = m->h_display_rec = nullptr;
   m->staging = m->frame = nullptr;
@@ -628,6 +635,66 @@ int gsp_multi_download_features(gsp_multi* m, float* albedo, float* geom, uint32
     MULTI_TRY(m, hipMemcpyAsync(out[k], m->frame, total * sizeof(q4), hipMemcpyDeviceToHost, m->stream));
     MULTI_TRY(m, hipStreamSynchronize(m->stream));
   }
+  return GSP_OK;
+}
+
+// The beauty gather fills m->frame; the albedo and geom planes of every share follow by the copy route through the staging buffer
+// into two frame buffers of the denoiser's own; denoise_run's kernels then see what a single context sees.
+int gsp_multi_download_denoised(gsp_multi* m, const gsp_denoise* denoise, float* out_rgba) {
+  if (!m) return GSP_ERR_INVALID;
+  if (!out_rgba || !m->have_frame) {
+    m->err = !out_rgba ? "gsp_multi_download_denoised: null output pointer" : "gsp_multi_download_denoised needs gsp_multi_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  const uint32_t world = (uint32_t)m->ctx.size();
+  if (world == 1 && !m->use_rccl) {
+    int rc = gsp_download_denoised(m->ctx[0], denoise, out_rgba);
+    if (rc != GSP_OK) m->err = gsp_last_error(m->ctx[0]);
+    return rc;
+  }
+  DenoiseConsts k;
+  if (const char* why = resolve_denoise(denoise, k)) {
+    m->err = why;
+    return GSP_ERR_INVALID;
+  }
+  for (uint32_t r = 0; r < world; ++r)
+    if (!gsp_internal_features_rendered(m->ctx[r])) {
+      m->err = "gsp_multi_download_denoised needs a gsp_multi_render_features call since gsp_multi_frame_begin";
+      return GSP_ERR_INVALID;
+    }
+  int rc = gsp_multi_gather(m, nullptr);
+  if (rc != GSP_OK) return rc;
+  std::vector<void*> src[3];
+  for (auto& v : src) v.assign(world, nullptr);
+  std::vector<uint64_t> cnt(world, 0);
+  rc = for_each_share(m, [&](size_t r) { return gsp_internal_features(m->ctx[r], &src[0][r], &src[1][r], &src[2][r], &cnt[r]); });
+  if (rc != GSP_OK) return rc;
+  for (uint32_t r = 0; r < world; ++r)
+    if (cnt[r] != m->ids[r].size()) {
+      m->err = "internal error: a share's pixel count differs from its tile list";
+      return GSP_ERR_DEVICE;
+    }
+  MULTI_TRY(m, hipSetDevice(m->devices[0]));
+  const uint64_t total = m->frame_pixels;
+  for (q4*& b : m->dn)
+    if (!b) MULTI_TRY(m, hipMalloc((void**)&b, std::max<uint64_t>(total, 1) * sizeof(q4)));
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((total + 255) / 256, 256 * 8);
+  for (int p = 0; p < 2; ++p) {  // albedo, geom
+    for (uint32_t r = 0; r < world; ++r) {
+      if (cnt[r] == 0) continue;
+      if (m->devices[r] == m->devices[0])
+        MULTI_TRY(m, hipMemcpyAsync(m->staging + m->offset[r], src[p][r], cnt[r] * sizeof(q4), hipMemcpyDeviceToDevice, m->stream));
+      else
+        MULTI_TRY(m, hipMemcpyPeerAsync(m->staging + m->offset[r], m->devices[0], src[p][r], m->devices[r], cnt[r] * sizeof(q4), m->stream));
+    }
+    hipLaunchKernelGGL(k_scatter_tiles, dim3(grid), dim3(256), 0, m->stream, m->staging, m->d_ids, total, m->dn[p]);
+    MULTI_TRY(m, hipGetLastError());
+  }
+  int cus = 256;
+  MULTI_TRY(m, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->devices[0]));
+  MULTI_TRY(m, denoise_run(m->stream, (uint32_t)cus, m->frame, m->dn[0], m->dn[1], m->width, m->height, k, m->dn[2], m->dn[3], m->dn[4], m->dn[5]));
+  MULTI_TRY(m, hipMemcpyAsync(out_rgba, m->dn[5], total * sizeof(q4), hipMemcpyDeviceToHost, m->stream));
+  MULTI_TRY(m, hipStreamSynchronize(m->stream));
   return GSP_OK;
 }
 

@@ -148,6 +148,10 @@ struct gsp_context {
   // them stale (features_ready = false) and the next feature call of the frame sizes and zeroes them
   DevBuf<q4> feat_albedo, feat_geom, feat_ids;
   bool features_ready = false;
+  bool features_rendered = false;  // gsp_render_features has run since gsp_frame_begin (the denoiser asks)
+  // denoiser (gsp_*_denoised*): two ping-pong planes of the demodulated colour, the albedo' / validity plane and the result, 16
+  // bytes per pixel each, made by the first denoise call of the context
+  DevBuf<q4> dn_e0, dn_e1, dn_a, dn_out;
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;

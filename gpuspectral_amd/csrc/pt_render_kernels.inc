@@ -1141,6 +1141,90 @@ __global__ __launch_bounds__(kBlock) void k_features(SceneView S, typename Featu
   }
 }
 
+// ---- denoiser (pt_denoise.h; include/gpuspectral_pt.h "Denoiser") ---------------------------------------------------------
+// Three planes of 16 bytes per pixel go through a level: E = {e.rgb, L}, A = {a'.rgb, valid}, G = {n.xyz, z}.
+__device__ __forceinline__ dn4 dn_load(const v4f* p) {
+  const v4f v = *p;
+  return dn4{v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ void dn_store(v4f* p, const dn4& d) {
+  v4f v;
+  v.x = d.x;
+  v.y = d.y;
+  v.z = d.z;
+  v.w = d.w;
+  *p = v;
+}
+
+// Prepare: streaming, one pixel per lane and trip -- two 16-byte loads, two 16-byte stores, every access of a wave one 1-KiB run.
+// (Records are 16 bytes on both sides, so several pixels per lane would widen nothing, unlike k_display_map's 4-byte words.)
+__global__ __launch_bounds__(kBlock) void k_denoise_prepare(const v4f* __restrict__ accum, const v4f* __restrict__ albedo, uint64_t n,
+                                                            v4f* __restrict__ E, v4f* __restrict__ A) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    dn4 e, a;
+    denoise_prepare(dn_load(accum + i), dn_load(albedo + i), e, a);
+    dn_store(E + i, e);
+    dn_store(A + i, a);
+  }
+}
+
+// One level.  A block of 256 lanes owns a tile of 32 x 8 pixels: a wave covers two rows of 32 pixels, i.e. 512-byte runs that
+// start on a 16-byte boundary (every record does).
+//   S = 1, 2 (levels 0 and 1): the three planes of tile + halo of 2 S pixels are staged in LDS -- (32 + 4 S) x (8 + 4 S) records
+//     per plane, 20 736 bytes (S = 1) and 30 720 bytes (S = 2) per block -- by row-major 16-byte loads, and the 25 taps are
+//     ds_read_b128 from there.  Out-of-frame records are zero and never read (denoise_pixel_level skips the tap first).
+//   S = 0 (levels >= 2): the halo would be wider than the tile; the taps are 16-byte loads from global memory (L2).
+// The per-pixel text is denoise_pixel_level either way, with the same taps in the same order: the fetch path cannot change a bit.
+// LAST: the level's output goes through denoise_finish (remodulation; an invalid pixel = its accumulate record) into `out`.
+constexpr int kDnTileW = 32, kDnTileH = 8;
+static_assert(kDnTileW * kDnTileH == kBlock, "a lane per pixel of the tile");
+template <int S, bool LAST>
+__global__ __launch_bounds__(kBlock) void k_denoise_atrous(const v4f* __restrict__ Ein, const v4f* __restrict__ A, const v4f* __restrict__ G,
+                                                           const v4f* __restrict__ accum, v4f* __restrict__ out, DenoiseConsts k, uint32_t level,
+                                                           int width, int height) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  dn4 r;
+  if constexpr (S != 0) {
+    constexpr int PW = kDnTileW + 4 * S, PH = kDnTileH + 4 * S;
+    __shared__ v4f sE[PW * PH], sA[PW * PH], sG[PW * PH];
+    const int x0 = (int)blockIdx.x * kDnTileW - 2 * S, y0 = (int)blockIdx.y * kDnTileH - 2 * S;
+    for (int i = (int)threadIdx.x; i < PW * PH; i += kBlock) {
+      const int ly = i / PW, lx = i - ly * PW;
+      const int gx = x0 + lx, gy = y0 + ly;
+      v4f e = {0.0f, 0.0f, 0.0f, 0.0f}, a = e, g = e;
+      if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+        const size_t idx = (size_t)gy * (size_t)width + (size_t)gx;
+        e = Ein[idx];
+        a = A[idx];
+        g = G[idx];
+      }
+      sE[i] = e;
+      sA[i] = a;
+      sG[i] = g;
+    }
+    __syncthreads();
+    if (px >= width || py >= height) return;  // (no barrier below)
+    r = denoise_pixel_level(k, level, width, height, px, py, [&](int x, int y, dn4& E_, dn4& A_, dn4& G_) {
+      const int i = (y - y0) * PW + (x - x0);  // |x - px| <= 2 S and |y - py| <= 2 S: inside the staged rectangle
+      E_ = dn_load(&sE[i]);
+      A_ = dn_load(&sA[i]);
+      G_ = dn_load(&sG[i]);
+    });
+  } else {
+    if (px >= width || py >= height) return;
+    r = denoise_pixel_level(k, level, width, height, px, py, [&](int x, int y, dn4& E_, dn4& A_, dn4& G_) {
+      const size_t idx = (size_t)y * (size_t)width + (size_t)x;  // denoise_pixel_level asks for pixels of the frame only
+      E_ = dn_load(Ein + idx);
+      A_ = dn_load(A + idx);
+      G_ = dn_load(G + idx);
+    });
+  }
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  if constexpr (LAST) r = denoise_finish(r, dn_load(A + p), dn_load(accum + p));
+  dn_store(out + p, r);
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

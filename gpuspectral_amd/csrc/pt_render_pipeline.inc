@@ -985,7 +985,10 @@ int gsp_render_features(gsp_context* ctx, const gsp_render_params* rp_host) {
     int rc_ = ensure_features(ctx);
     if (rc_ != GSP_OK) return rc_;
   }
-  if (ctx->num_pixels == 0) return GSP_OK;
+  if (ctx->num_pixels == 0) {
+    ctx->features_rendered = true;
+    return GSP_OK;
+  }
   if (ctx->split && !ctx->s2g_all_valid) {
     int rc_ = make_split_s2g(ctx);
     if (rc_ != GSP_OK) return rc_;
@@ -1020,6 +1023,7 @@ int gsp_render_features(gsp_context* ctx, const gsp_render_params* rp_host) {
   }
   CTX_TRY(ctx, hipGetLastError());
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the pass is complete when the call returns: a scene edit may follow at once)
+  ctx->features_rendered = true;
   return GSP_OK;
 }
 
@@ -1083,6 +1087,8 @@ int gsp::gsp_internal_features(gsp_context* ctx, void** albedo, void** geom, voi
   *num_pixels = ctx->num_pixels;
   return GSP_OK;
 }
+
+int gsp::gsp_internal_features_rendered(const gsp_context* ctx) { return ctx && ctx->have_frame && ctx->features_rendered ? 1 : 0; }
 
 int gsp::gsp_internal_accum(gsp_context* ctx, void** accum, uint64_t* num_pixels, hipStream_t* stream) {
   if (!ctx || !ctx->have_frame) return GSP_ERR_INVALID;
@@ -1269,16 +1275,17 @@ static int display_peek_sync(gsp_context* ctx, uint32_t* samples_folded) {
   return GSP_OK;
 }
 
-static int display_measure_ctx(gsp_context* ctx, gsp_luminance* out) {
+static int display_measure_ctx(gsp_context* ctx, gsp_luminance* out, const void* src = nullptr) {
   CTX_TRY(ctx, ctx->display_rec.ensure(1, &ctx->bytes));
   if (!ctx->h_display_rec) CTX_TRY(ctx, hipHostMalloc((void**)&ctx->h_display_rec, sizeof(DisplayStatsRec), hipHostMallocDefault));
-  CTX_TRY(ctx, display_measure(ctx->stream, (uint32_t)ctx->num_cus, ctx->accum.p, ctx->num_pixels, ctx->display_rec.p, ctx->h_display_rec, out));
+  CTX_TRY(ctx, display_measure(ctx->stream, (uint32_t)ctx->num_cus, src ? src : ctx->accum.p, ctx->num_pixels, ctx->display_rec.p, ctx->h_display_rec, out));
   return GSP_OK;
 }
 
 // validates `display_host`, measures the frame where the display asks for it and queues the map of the compact accumulate
-// buffer into `dst` (device, 16-byte aligned; nullptr = the context's own RGBA8 buffer) on ctx->stream
-static int display_run(gsp_context* ctx, const gsp_display* display_host, uint32_t* dst) {
+// buffer (or of `src`: the denoised frame) into `dst` (device, 16-byte aligned; nullptr = the context's own RGBA8 buffer) on
+// ctx->stream
+static int display_run(gsp_context* ctx, const gsp_display* display_host, uint32_t* dst, const void* src = nullptr) {
   gsp_display d;
   if (const char* why = resolve_display(display_host, d)) {
     ctx->err = why;
@@ -1286,16 +1293,127 @@ static int display_run(gsp_context* ctx, const gsp_display* display_host, uint32
   }
   gsp_luminance lum{};
   if (display_needs_stats(d)) {
-    int rc = display_measure_ctx(ctx, &lum);
+    int rc = display_measure_ctx(ctx, &lum, src);
     if (rc != GSP_OK) return rc;
   }
   if (!dst) {
     CTX_TRY(ctx, ctx->display_out.ensure((ctx->num_pixels + 3) / 4 * 4, &ctx->bytes));
     dst = ctx->display_out.p;
   }
-  CTX_TRY(ctx, display_map(ctx->stream, (uint32_t)ctx->num_cus, ctx->accum.p, ctx->num_pixels, display_consts(d, lum), dst));
+  CTX_TRY(ctx, display_map(ctx->stream, (uint32_t)ctx->num_cus, src ? src : ctx->accum.p, ctx->num_pixels, display_consts(d, lum), dst));
   return GSP_OK;
 }
+
+// ---- denoiser (include/gpuspectral_pt.h, "Denoiser"; per-pixel code: pt_denoise.h) ----
+hipError_t gsp::denoise_run(hipStream_t stream, uint32_t num_cus, const void* accum, const void* albedo, const void* geom, uint32_t width, uint32_t height,
+                            const DenoiseConsts& k, void* e0, void* e1, void* a, void* out) {
+  const uint64_t n = (uint64_t)width * height;
+  if (n == 0) return hipSuccess;
+  const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 8));
+  hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)accum, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH), block(kBlock);
+  v4f* E[2] = {(v4f*)e0, (v4f*)e1};
+  for (uint32_t i = 0; i < k.iterations; ++i) {
+    const bool last = i + 1 == k.iterations;
+    const v4f* in = E[i & 1u];
+    v4f* dst = last ? (v4f*)out : E[(i + 1u) & 1u];
+#define GSP_DENOISE_LAUNCH(S, LAST) \
+  hipLaunchKernelGGL((k_denoise_atrous<S, LAST>), grid, block, 0, stream, in, (const v4f*)a, (const v4f*)geom, (const v4f*)accum, dst, k, i, (int)width, (int)height)
+    // levels 0 and 1 (steps 1 and 2) stage tile + halo in LDS, the wider steps read their taps from global memory
+    if (i == 0) {
+      if (last) GSP_DENOISE_LAUNCH(1, true);
+      else GSP_DENOISE_LAUNCH(1, false);
+    } else if (i == 1) {
+      if (last) GSP_DENOISE_LAUNCH(2, true);
+      else GSP_DENOISE_LAUNCH(2, false);
+    } else {
+      if (last) GSP_DENOISE_LAUNCH(0, true);
+      else GSP_DENOISE_LAUNCH(0, false);
+    }
+#undef GSP_DENOISE_LAUNCH
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// Validates, completes the queued samples and queues the filter of the frame into `dst` (device, 16-byte aligned; nullptr = the
+// context's own buffer) on ctx->stream.  `out_ptr` is the caller's output pointer (checked for NULL only).
+static int denoise_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const char* who, const void* out_ptr, void* dst) {
+  if (!out_ptr) {
+    ctx->err = std::string(who) + ": null output pointer";
+    return GSP_ERR_INVALID;
+  }
+  if (!ctx->have_frame) {
+    ctx->err = std::string(who) + " needs gsp_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->subset) {
+    ctx->err = std::string(who) + ": the frame was begun with pixel_ids; a share has no neighbours (use gsp_multi_download_denoised)";
+    return GSP_ERR_INVALID;
+  }
+  if (!ctx->features_rendered) {
+    ctx->err = std::string(who) + " needs a gsp_render_features call since gsp_frame_begin";
+    return GSP_ERR_INVALID;
+  }
+  DenoiseConsts k;
+  if (const char* why = resolve_denoise(denoise_host, k)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  {
+    int rc_ = pipeline_drain(ctx);
+    if (rc_ != GSP_OK) return rc_;
+  }
+  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
+  for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
+  CTX_TRY(ctx, denoise_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->width, ctx->height, k,
+                           ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, dst ? dst : (void*)ctx->dn_out.p));
+  return GSP_OK;
+}
+
+extern "C" {
+
+int gsp_download_denoised(gsp_context* ctx, const gsp_denoise* denoise, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = denoise_ctx(ctx, denoise, "gsp_download_denoised", out, nullptr);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
+}
+
+int gsp_denoise_to_device(gsp_context* ctx, const gsp_denoise* denoise, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (dst && ctx->have_frame && bytes < ctx->num_pixels * sizeof(q4)) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  // the kernels store 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
+  const bool direct = ((uintptr_t)dst & 15u) == 0;
+  int rc = denoise_ctx(ctx, denoise, "gsp_denoise_to_device", dst, direct ? dst : nullptr);
+  if (rc != GSP_OK) return rc;
+  if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), hipMemcpyDeviceToDevice, ctx->stream));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+int gsp_download_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  {  // (an invalid display is refused before anything is queued)
+    gsp_display d;
+    if (const char* why = resolve_display(display, d)) {
+      ctx->err = why;
+      return GSP_ERR_INVALID;
+    }
+  }
+  int rc = denoise_ctx(ctx, denoise, "gsp_download_denoised_display", out, nullptr);
+  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
+}
+
+}  // extern "C"
 
 extern "C" {
 

@@ -896,6 +896,7 @@ int gsp_frame_begin(gsp_context* ctx, uint32_t width, uint32_t height, const uin
   }
   ctx->frame_mode = gsp_context::kFrameUndecided;
   ctx->adaptive_n = 0;
+  ctx->features_rendered = false;
   ctx->features_ready = false;  // (the feature planes, where a frame has asked for them, start from zero again)
   ctx->subset = pixel_ids != nullptr;
   if (pixel_ids) {

@@ -85,6 +85,10 @@ def load():
     L.gsph_decode_png.argtypes = [vp, u64, C.POINTER(u32), C.POINTER(u32), vp]
     L.gsph_pathtracer_set_display.argtypes = [vp, C.POINTER(abi.Display)]
     L.gsph_pathtracer_download_display.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_render_features.argtypes = [vp, vp, C.c_uint32]
+    L.gsph_pathtracer_download_features.argtypes = [vp, vp, vp, u64]
+    L.gsph_pathtracer_download_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
+    L.gsph_pathtracer_download_denoised_display.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
     _LIB = L
     return L
 
@@ -315,6 +319,33 @@ class PathTracer:
             self._check(self._L.gsph_pathtracer_set_display(self._h, C.byref(display)), "set_display")
         out = np.zeros((self.height, self.width), np.uint32)
         self._check(self._L.gsph_pathtracer_download_display(self._h, out.ctypes.data, out.size), "downloadDisplay")
+        return out
+
+    def render_features(self, scene, spp):
+        """PathTracer::renderFeatures: spp feature samples per pixel under this tracer's filter and the scene's lens."""
+        self._check(self._L.gsph_pathtracer_render_features(self._h, scene._h, spp), "renderFeatures")
+
+    def download_features(self):
+        """PathTracer::downloadFeatures: (albedo[h,w,4], geom[h,w,4]) float32."""
+        a = np.zeros((self.height, self.width, 4), np.float32)
+        g = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_features(self._h, a.ctypes.data, g.ctypes.data, a.size), "downloadFeatures")
+        return a, g
+
+    def download_denoised(self, denoise=None):
+        """PathTracer::downloadDenoised (abi.Denoise; None = every default): (h, w, 4) float32."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_denoised(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data, out.size),
+                    "downloadDenoised")
+        return out
+
+    def download_denoised_display(self, denoise=None, display=None):
+        """PathTracer::downloadDenoisedDisplay with PathTracer::display = `display` (None keeps the current one): (h, w) uint32."""
+        if display is not None:
+            self._check(self._L.gsph_pathtracer_set_display(self._h, C.byref(display)), "set_display")
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsph_pathtracer_download_denoised_display(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data,
+                                                                      out.size), "downloadDenoisedDisplay")
         return out
 
     def stats(self):

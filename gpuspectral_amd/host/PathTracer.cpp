@@ -275,6 +275,18 @@ void PathTracer::copyFeaturesToDevice(void* albedo, void* geom, void* ids, uint6
   check(gsp_copy_features_to_device(ctx, albedo, geom, ids, bytesEach), "gsp_copy_features_to_device");
 }
 
+std::vector<float> PathTracer::downloadDenoised(const gsp_denoise* denoise) {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_denoised(ctx, denoise, out.data()), "gsp_download_denoised");
+  return out;
+}
+
+std::vector<uint32_t> PathTracer::downloadDenoisedDisplay(const gsp_denoise* denoise) {
+  std::vector<uint32_t> out((size_t)width * height);
+  check(gsp_download_denoised_display(ctx, denoise, &display, out.data()), "gsp_download_denoised_display");
+  return out;
+}
+
 gsp_stats PathTracer::stats() {
   gsp_stats s;
   check(gsp_get_stats(ctx, &s), "gsp_get_stats");
@@ -372,6 +384,12 @@ void MultiGpuPathTracer::downloadFeatures(std::vector<float>* albedo, std::vecto
   if (ids) ids->assign(n, 0u);
   check(gsp_multi_download_features(multi, albedo ? albedo->data() : nullptr, geom ? geom->data() : nullptr, ids ? ids->data() : nullptr),
         "gsp_multi_download_features");
+}
+
+std::vector<float> MultiGpuPathTracer::downloadDenoised(const gsp_denoise* denoise) {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_multi_download_denoised(multi, denoise, out.data()), "gsp_multi_download_denoised");
+  return out;
 }
 
 gsp_stats MultiGpuPathTracer::stats(std::vector<gsp_stats>* perShare) {

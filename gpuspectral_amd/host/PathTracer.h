@@ -101,6 +101,11 @@ class PathTracer : public RenderPassCreator {
   void renderFeatures(const Scene& scene, uint32_t spp);
   void downloadFeatures(std::vector<float>* albedo, std::vector<float>* geom, std::vector<uint32_t>* ids);
   void copyFeaturesToDevice(void* albedo, void* geom, void* ids, uint64_t bytesEach);  // compact planes, device memory
+  // Denoiser (gpuspectral_pt.h "Denoiser"): the frame through the edge-avoiding a-trous filter, guided by the planes of a
+  // renderFeatures call of this frame; RGBA32F, width*height*4 floats.  nullptr = every default.  downloadDenoisedDisplay: the LDR
+  // film (`display`) of the denoised frame, RGBA8 words.  The frame itself is not changed.
+  std::vector<float> downloadDenoised(const gsp_denoise* denoise = nullptr);
+  std::vector<uint32_t> downloadDenoisedDisplay(const gsp_denoise* denoise = nullptr);
   void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }
   gsp_stats stats();
@@ -141,6 +146,7 @@ class MultiGpuPathTracer : public RenderPassCreator {
   std::vector<uint32_t> downloadDisplay();  // as PathTracer::downloadDisplay, on the gathered frame
   void renderFeatures(const Scene& scene, uint32_t spp);  // as PathTracer::renderFeatures, on every share
   void downloadFeatures(std::vector<float>* albedo, std::vector<float>* geom, std::vector<uint32_t>* ids);  // the gathered planes
+  std::vector<float> downloadDenoised(const gsp_denoise* denoise = nullptr);  // as PathTracer::downloadDenoised, on the gathered frame
   void reset();
   int getTimestamp() const { return timestamp; }
   int numShares() const { return (int)devices.size(); }

@@ -290,6 +290,33 @@ int gsph_pathtracer_download_display(void* pt, uint32_t* out, uint64_t count) {
     std::memcpy(out, img.data(), img.size() * sizeof(uint32_t));
   });
 }
+// feature pass + denoiser of a PathTracer (gpuspectral_pt.h "Feature buffers", "Denoiser"); denoise may be NULL
+int gsph_pathtracer_render_features(void* pt, void* scene, uint32_t spp) {
+  return guard([&] { ((PathTracer*)pt)->renderFeatures(*(Scene*)scene, spp); });
+}
+int gsph_pathtracer_download_features(void* pt, float* albedo, float* geom, uint64_t floats_each) {
+  return guard([&] {
+    std::vector<float> a, g;
+    ((PathTracer*)pt)->downloadFeatures(&a, &g, nullptr);
+    if (floats_each < a.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(albedo, a.data(), a.size() * sizeof(float));
+    std::memcpy(geom, g.data(), g.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_download_denoised(void* pt, const gsp_denoise* denoise, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadDenoised(denoise);
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_download_denoised_display(void* pt, const gsp_denoise* denoise, uint32_t* out, uint64_t count) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadDenoisedDisplay(denoise);
+    if (count < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(uint32_t));
+  });
+}
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {
     std::vector<uint8_t> v;

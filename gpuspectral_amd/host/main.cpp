@@ -19,6 +19,10 @@
 //   --ldr out.png: also write the LDR film (gpuspectral_pt.h "LDR film": tone-mapped and encoded on the GPU) as an 8-bit RGB PNG;
 //   --tonemap clamp|aces|reinhard[:key[:burn]], --exposure E (f-stops), --gamma G|srgb: its gsp_display; --scene-film:
 //   LoadOptions::readFilm (the sensor's ldrfilm; the flags override the scene's values one by one).  Without --ldr: no PNG
+//   --denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]: also write the denoised frame (gpuspectral_pt.h
+//   "Denoiser"; N = 1..8 levels, the four sigmas of colour, normal, depth and albedo: 0 = the default, inf = that term off).  It
+//   uses the feature planes of --features, or runs a feature pass of its own at the frame's spp, filter and lens.  With --ldr
+//   (one device) the LDR film of the denoised frame goes to out.png beside it.  Without --denoise nothing more is written or printed.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -49,6 +53,10 @@ int main(int argc, char** argv) {
   std::string ldrPath;
   std::string featuresPrefix;
   int featureSpp = -1;  // (-1 = not given: the frame's spp)
+  std::string denoisePath;
+  gsp_denoise denoise{};
+  denoise.struct_size = (uint32_t)sizeof(gsp_denoise);
+  bool denoiseOptions = false;
   int tonemap = -1;  // (-1 = not given)
   float tmKey = -1.0f, tmBurn = -1.0f, exposure = 0.0f, gamma = -1.0f;
   bool haveExposure = false;
@@ -81,6 +89,33 @@ int main(int argc, char** argv) {
         return 2;
       }
       featureSpp = (int)v, used = 2;
+    }
+    else if (flag == "--denoise" && argc > 2) denoisePath = argv[2], used = 2;
+    else if (flag == "--denoise-iterations" && argc > 2) {
+      char* e = nullptr;
+      const long v = std::strtol(argv[2], &e, 10);
+      if (e == argv[2] || *e != 0 || v < 1 || v > 8) {
+        std::fprintf(stderr, "gsp_render: bad denoise iterations '%s' (expected 1..8)\n", argv[2]);
+        return 2;
+      }
+      denoise.iterations = (uint32_t)v, denoiseOptions = true, used = 2;
+    } else if (flag == "--denoise-sigma" && argc > 2) {
+      float* const dst[4] = {&denoise.sigma_color, &denoise.sigma_normal, &denoise.sigma_depth, &denoise.sigma_albedo};
+      std::string v = argv[2];
+      bool ok = true;
+      for (int k = 0; k < 4 && ok; ++k) {
+        const size_t comma = v.find(',');
+        ok = (comma == std::string::npos) == (k == 3);
+        const std::string part = v.substr(0, comma);
+        if (ok && part == "inf") *dst[k] = INFINITY;
+        else ok = ok && parseFloat(part.c_str(), *dst[k]) && *dst[k] >= 0.0f;
+        v = comma == std::string::npos ? "" : v.substr(comma + 1);
+      }
+      if (!ok) {
+        std::fprintf(stderr, "gsp_render: bad denoise sigma '%s' (expected c,n,z,a: four values >= 0, 0 = the default, inf = off)\n", argv[2]);
+        return 2;
+      }
+      denoiseOptions = true, used = 2;
     }
     else if (flag == "--tonemap" && argc > 2) {
       const std::string v = argv[2];
@@ -192,8 +227,12 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --feature-spp needs --features PREFIX\n");
     return 2;
   }
+  if (denoisePath.empty() && denoiseOptions) {
+    std::fprintf(stderr, "gsp_render: --denoise-iterations and --denoise-sigma need --denoise out.pfm\n");
+    return 2;
+  }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -249,8 +288,10 @@ int main(int argc, char** argv) {
     if (tmBurn >= 0.0f) display.burn = tmBurn;
     if (haveExposure) display.exposure = exposure;
     if (gamma >= 0.0f) display.gamma = gamma;
-    std::vector<uint32_t> ldr;
-    std::vector<float> img, featAlbedo, featGeom;
+    if (!denoisePath.empty() && !ldrPath.empty() && devices.size() > 1)
+      throw std::runtime_error("--denoise with --ldr needs a single device (the LDR film of the denoised frame is a single-context call)");
+    std::vector<uint32_t> ldr, denoisedLdr;
+    std::vector<float> img, featAlbedo, featGeom, denoised;
     const uint32_t fspp = featureSpp > 0 ? (uint32_t)featureSpp : spp;
     gsp_stats st;
     double s;
@@ -275,6 +316,11 @@ int main(int argc, char** argv) {
         pt.renderFeatures(scene, fspp);
         pt.downloadFeatures(&featAlbedo, &featGeom, nullptr);
       }
+      if (!denoisePath.empty()) {  // the denoiser (gpuspectral_pt.h "Denoiser"), on the planes above or on a pass of its own
+        if (featuresPrefix.empty()) pt.renderFeatures(scene, spp);
+        denoised = pt.downloadDenoised(&denoise);
+        if (!ldrPath.empty()) denoisedLdr = pt.downloadDenoisedDisplay(&denoise);
+      }
     } else {
       MultiGpuPathTracer pt(width, height, devices, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
@@ -293,6 +339,10 @@ int main(int argc, char** argv) {
       if (!featuresPrefix.empty()) {  // after the timed frame: the feature planes (gpuspectral_pt.h "Feature buffers")
         pt.renderFeatures(scene, fspp);
         pt.downloadFeatures(&featAlbedo, &featGeom, nullptr);
+      }
+      if (!denoisePath.empty()) {
+        if (featuresPrefix.empty()) pt.renderFeatures(scene, spp);
+        denoised = pt.downloadDenoised(&denoise);
       }
       std::printf("%zu shares (32x32 tiles), gathered on device %d\n", devices.size(), devices[0]);
     }
@@ -317,6 +367,16 @@ int main(int argc, char** argv) {
       writePng(featuresPrefix + ".albedo.png", a8.data(), width, height, false);
       writePng(featuresPrefix + ".normal.png", n8.data(), width, height, false);
       std::printf("features: %u samples per pixel -> %s.{albedo,normal,depth}.pfm, %s.{albedo,normal}.png\n", fspp, featuresPrefix.c_str(), featuresPrefix.c_str());
+    }
+    if (!denoisePath.empty()) {
+      writePfm(denoisePath, denoised.data(), width, height);
+      std::string png;
+      if (!denoisedLdr.empty()) {
+        const size_t dot = denoisePath.rfind('.');
+        png = (dot != std::string::npos && denoisePath.find('/', dot) == std::string::npos ? denoisePath.substr(0, dot) : denoisePath) + ".png";
+        writePng(png, denoisedLdr.data(), width, height, false);
+      }
+      std::printf("denoised: %u levels -> %s%s%s\n", denoise.iterations ? denoise.iterations : 5u, denoisePath.c_str(), png.empty() ? "" : ", ", png.c_str());
     }
     std::printf("%llu triangles, %ux%u x %u spp in %.3f s: %.1f Mrays/s, %.2f Msamples/s (BVH build %.1f ms)\n",
                 (unsigned long long)st.num_triangles, width, height, spp, s,

@@ -46,6 +46,9 @@ EXPORTS = (
     "gsp_render_features",
     "gsp_download_features",
     "gsp_copy_features_to_device",
+    "gsp_download_denoised",
+    "gsp_denoise_to_device",
+    "gsp_download_denoised_display",
     "gsp_get_stats",
     "gsp_reset_stats",
     "gsp_trace",
@@ -70,6 +73,7 @@ EXPORTS = (
     "gsp_multi_download_display",
     "gsp_multi_render_features",
     "gsp_multi_download_features",
+    "gsp_multi_download_denoised",
     "gsp_multi_get_stats",
     "gsp_multi_reset_stats",
     "gsp_multi_last_error",
@@ -136,6 +140,10 @@ def load():
     L.gsp_copy_features_to_device.argtypes = [vp, vp, vp, vp, u64]
     L.gsp_multi_render_features.argtypes = [vp, C.POINTER(abi.RenderParams)]
     L.gsp_multi_download_features.argtypes = [vp, vp, vp, vp]
+    L.gsp_download_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp]
+    L.gsp_denoise_to_device.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
+    L.gsp_download_denoised_display.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Display), vp]
+    L.gsp_multi_download_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -186,7 +194,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -392,6 +400,26 @@ class Context:
         """gsp_copy_features_to_device: the compact planes into device memory (e.g. torch tensors' data_ptr()); a pointer may be None."""
         self._check(self._L.gsp_copy_features_to_device(self._h, albedo_ptr, geom_ptr, ids_ptr, nbytes_each), "gsp_copy_features_to_device")
 
+    # ---- denoiser (gpuspectral_pt.h "Denoiser"); denoise: an abi.Denoise (abi.denoise(...)), None = NULL = every default ----
+    def download_denoised(self, denoise=None):
+        """gsp_download_denoised: the frame through the edge-avoiding a-trous filter, guided by the feature planes of a
+        render_features call of this frame; (height, width, 4) float32.  The frame itself is not changed."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_denoised(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data), "gsp_download_denoised")
+        return out
+
+    def denoise_to_device(self, device_ptr, nbytes, denoise=None):
+        """gsp_denoise_to_device: the denoised frame into device memory (e.g. a torch tensor's data_ptr()), width*height*16 bytes."""
+        self._check(self._L.gsp_denoise_to_device(self._h, C.byref(denoise) if denoise is not None else None, device_ptr, nbytes), "gsp_denoise_to_device")
+
+    def download_denoised_display(self, denoise=None, display=None):
+        """gsp_download_denoised_display: the LDR film of the denoised frame, (height, width) uint32 RGBA8 words."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsp_download_denoised_display(self._h, C.byref(denoise) if denoise is not None else None,
+                                                          C.byref(display) if display is not None else None, out.ctypes.data),
+                    "gsp_download_denoised_display")
+        return out
+
     def pixel_stats(self):
         """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of
         Y^2 over each pixel's samples and the samples folded into it (gsp_download_pixel_stats)."""
@@ -552,6 +580,13 @@ class MultiContext:
         i = np.zeros((self.height, self.width, 4), np.uint32)
         self._check(self._L.gsp_multi_download_features(self._h, a.ctypes.data, g.ctypes.data, i.ctypes.data), "gsp_multi_download_features")
         return a, g, i
+
+    def download_denoised(self, denoise=None):
+        """gsp_multi_download_denoised: Context.download_denoised of the gathered frame and planes."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_multi_download_denoised(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data),
+                    "gsp_multi_download_denoised")
+        return out
 
     def stats(self, per_share=False):
         tot = abi.Stats()

@@ -69,7 +69,9 @@ extern "C" {
                                 gsp_multi_set_lens, gsp_focus_distance (see "Thin lens"); gsp_frame_luminance, gsp_download_display,
                                 gsp_peek_display, gsp_peek_display_to_device, gsp_multi_download_display (see "LDR film");
                                 gsp_render_features, gsp_download_features, gsp_copy_features_to_device,
-                                gsp_multi_render_features, gsp_multi_download_features (see "Feature buffers") */
+                                gsp_multi_render_features, gsp_multi_download_features (see "Feature buffers");
+                                gsp_download_denoised, gsp_denoise_to_device, gsp_download_denoised_display,
+                                gsp_multi_download_denoised (see "Denoiser") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -707,6 +709,59 @@ int gsp_download_features(gsp_context* ctx, float* albedo, float* geom, uint32_t
  * memory of bytes_each >= num_pixels * 16 bytes per destination; any pointer may be NULL.  Complete when the call returns. */
 int gsp_copy_features_to_device(gsp_context* ctx, void* albedo, void* geom, void* ids, uint64_t bytes_each);
 
+/*
+ * Denoiser: an edge-avoiding a-trous wavelet filter of the frame, guided by the feature buffers.
+ *
+ * For a frame stopped at a few samples per pixel.  No reference code defines one, so this header does, down to the order of the
+ * float32 operations.  The calls complete the queued samples first (as gsp_download does), read the accumulate buffer c (RGBA) and
+ * the feature planes albedo = {a.rgb, cov} and geom = {n.xyz, z}, and change no state of the frame: the image, the feature planes,
+ * the pixel statistics, the memo and gsp_stats stay as they were.  Scratch buffers of 16 bytes per pixel each (four of them) are
+ * allocated by the first denoise call of a context; a context that never denoises holds none.
+ *
+ * Arithmetic is float32 in the order written (no contraction); exp is the library's deterministic exp (0 below -87.34).
+ *
+ * Prepare, per pixel p:
+ *     valid = every one of c.r, c.g, c.b is finite
+ *     a'_k  = a_k + (1 - cov)                 (a miss counts as albedo 1: the background passes through)
+ *     A_k   = a'_k < 0.01f ? 0.01f : a'_k
+ *     e_k   = c_k / A_k
+ *     L     = (0.2126 e.r + 0.7152 e.g) + 0.0722 e.b
+ * Level i = 0 .. iterations-1, step s = 2^i.  For a valid centre p the taps are q = p + s * (dx, dy), dy = -2..2 in the outer loop,
+ * dx = -2..2 in the inner loop: this is the order of summation.  A tap outside the frame is skipped, a tap whose pixel is not
+ * valid is skipped.  For every other tap, with k = {0.0625, 0.25, 0.375, 0.25, 0.0625}:
+ *     h   = k[dx+2] * k[dy+2]
+ *     dn  = ((n_p-n_q).x^2 + (n_p-n_q).y^2) + (n_p-n_q).z^2
+ *     rz  = z_p == z_q ? 0 : (z_p - z_q) / (z_p + z_q)
+ *     da  = ((a'_p-a'_q).r^2 + (a'_p-a'_q).g^2) + (a'_p-a'_q).b^2
+ *     rl  = (L_p - L_q) / ((L_p + L_q) + 1e-3f)                  (L of THIS level's input)
+ *     x   = ((dn * inv_sn2 + rz*rz * inv_sz2) + da * inv_sa2) + (rl*rl) * (inv_sc2 * 4^i)
+ *     w   = h * exp(-x);   sum_w += w;   sum_k += w * e_q.k
+ * then e'_p.k = sum_k / sum_w and L' is recomputed from e'.  The centre tap has x = 0 exactly, so sum_w >= 9/64.  inv_* are
+ * 1 / sigma^2, formed once on the host in double and rounded to float (at most FLT_MAX); a sigma of +Inf gives 0: that term is
+ * off.  4^i is an exact float.  A pixel that is not valid keeps its e, is never a neighbour, and leaves the filter as c, unchanged
+ * bit for bit.
+ * Output: out.k = e_final.k * A_k for a valid pixel, out.w = c.w.
+ *
+ * Defaults (a field left 0): iterations 5, sigma_color 0.5, sigma_normal 0.3, sigma_depth 0.05, sigma_albedo 0.1.
+ *
+ * struct_size follows the rule of gsp_render_params (fields beyond it are 0); a NULL gsp_denoise and struct_size 0 are the zeroed
+ * struct = every default.  GSP_ERR_INVALID (text at gsp_last_error) for: no frame; a frame begun with pixel_ids (a share has no
+ * neighbours: use gsp_multi_*); no gsp_render_features call since gsp_frame_begin; iterations > 8; a negative or NaN sigma; a NULL
+ * output pointer; `bytes` too small.
+ */
+typedef struct gsp_denoise {
+  uint32_t struct_size; /* sizeof(gsp_denoise) of the host's header; same rule as gsp_render_params / gsp_display */
+  uint32_t iterations;  /* a-trous levels, step 2^i for level i; 0 = 5; otherwise 1..8 */
+  float sigma_color, sigma_normal, sigma_depth, sigma_albedo; /* 0 = default; +Inf = that term off */
+} gsp_denoise;
+/* Full frame like gsp_download: width*height*4 floats, through the staged read-back. */
+int gsp_download_denoised(gsp_context* ctx, const gsp_denoise* denoise, float* out_rgba);
+/* The same frame into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
+int gsp_denoise_to_device(gsp_context* ctx, const gsp_denoise* denoise, void* device_dst, uint64_t bytes);
+/* The LDR film (see "LDR film") of the DENOISED frame: the tone map, the encode and -- where the display asks for them -- the frame
+ * statistics are those of the denoised buffer, not of the accumulate buffer.  width*height RGBA8 words. */
+int gsp_download_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out_rgba8);
+
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
 
@@ -779,6 +834,10 @@ int gsp_multi_download_display(gsp_multi* m, const gsp_display* display, uint32_
  * copies them to the host: identical to a single-GPU gsp_download_features.  Any pointer may be NULL. */
 int gsp_multi_render_features(gsp_multi* m, const gsp_render_params* params);
 int gsp_multi_download_features(gsp_multi* m, float* albedo, float* geom, uint32_t* ids);
+/* The denoiser on the gathered frame: gsp_multi_gather, the albedo and geom planes of every share brought to devices[0] (into two
+ * frame buffers of the denoiser's own, made on first use), the same kernels there, one copy to the host: identical to a single-GPU
+ * gsp_download_denoised.  Every share must have had gsp_multi_render_features since gsp_multi_frame_begin. */
+int gsp_multi_download_denoised(gsp_multi* m, const gsp_denoise* denoise, float* out_rgba);
 /* total (optional): counters summed over the shares, times of the slowest share (they run concurrently);
  * per_share (optional): gsp_multi_num_shares() records. */
 int gsp_multi_get_stats(gsp_multi* m, gsp_stats* total, gsp_stats* per_share);
