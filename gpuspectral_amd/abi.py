@@ -207,6 +207,22 @@ def denoise(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, si
     return Denoise(C.sizeof(Denoise), iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo)
 
 
+class Temporal(C.Structure):
+    """gsp_temporal: the parameters of temporal accumulation (gsp_temporal_accumulate); all zero = every default."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("max_history", C.c_uint32),  # 0 = 32; otherwise 1..65536
+        ("alpha", C.c_float),  # 0 = 0.2; otherwise (0, 1]; FLT_MIN = the pure running mean
+        ("depth_tolerance", C.c_float),  # 0 = 0.02
+        ("normal_min", C.c_float),  # 0 = 0.9; otherwise [-1, 1]
+    ]
+
+
+def temporal(max_history=0, alpha=0.0, depth_tolerance=0.0, normal_min=0.0):
+    return Temporal(C.sizeof(Temporal), max_history, alpha, depth_tolerance, normal_min)
+
+
 class Luminance(C.Structure):
     """gsp_luminance: the frame statistics of the Reinhard operator (gsp_frame_luminance)."""
 

@@ -10,6 +10,7 @@
 #include "pt_denoise.h"
 #include "pt_display.h"
 #include "pt_stages.h"
+#include "pt_temporal.h"
 
 namespace gsp {
 
@@ -86,6 +87,13 @@ __attribute__((visibility("hidden"))) hipError_t display_map(hipStream_t stream,
 // k_denoise_prepare and k.iterations launches of k_denoise_atrous on `stream`; does not synchronise.
 __attribute__((visibility("hidden"))) hipError_t denoise_run(hipStream_t stream, uint32_t num_cus, const void* accum, const void* albedo, const void* geom,
                                                              uint32_t width, uint32_t height, const DenoiseConsts& k, void* e0, void* e1, void* a, void* out);
+
+// ---- temporal accumulation (pt_temporal.h) on a full frame of k.cur.width x k.cur.height: `accum`, `albedo`, `geom`, `ids` are the
+// frame's 16-byte planes, {h, g, i}_prev the history set read (not read when k.history_valid == 0) and {h, g, i}_out the set
+// written (16, 16 and 4 bytes per pixel).  Queues one launch of k_temporal_reproject on `stream`; does not synchronise.
+__attribute__((visibility("hidden"))) hipError_t temporal_run(hipStream_t stream, const void* accum, const void* albedo, const void* geom, const void* ids,
+                                                              const void* h_prev, const void* g_prev, const void* i_prev, void* h_out, void* g_out,
+                                                              void* i_out, const TemporalConsts& k);
 
 // Bakes the instances' triangles to world space and builds the wide BVH (PLOC + reinsertion + collapse) on `stream`.
 // Returns GSP_OK or an error code with `err` set.

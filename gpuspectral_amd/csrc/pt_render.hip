@@ -152,6 +152,15 @@ struct gsp_context {
   // denoiser (gsp_*_denoised*): two ping-pong planes of the demodulated colour, the albedo' / validity plane and the result, 16
   // bytes per pixel each, made by the first denoise call of the context
   DevBuf<q4> dn_e0, dn_e1, dn_a, dn_out;
+  // temporal accumulation (gsp_temporal_*): two ping-pong history sets {H, G, I} over the full frame (72 bytes per pixel in all),
+  // made by the first gsp_temporal_accumulate of the context; tp_cur = the newest set.  The history belongs to tp_camera and
+  // tp_width x tp_height while tp_valid; tp_done = an accumulate has run in this frame (gsp_frame_begin clears it)
+  DevBuf<q4> tp_h[2], tp_g[2];
+  DevBuf<uint32_t> tp_i[2];
+  int tp_cur = 0;
+  bool tp_valid = false, tp_done = false;
+  uint32_t tp_width = 0, tp_height = 0;
+  gsp_camera tp_camera{};
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;
@@ -230,6 +239,7 @@ struct gsp_context {
   Lane lanes[kMaxLanes];
   uint32_t num_lanes = 1;  // gsp_ctx_options.lanes = 2: +11 % with 8 M-path pools, +-0 with the 32 M-path pool and k_finish
   gsp_render_params pipe_params{};  // integrator constants the lanes are running with
+  uint32_t sample_base = 0;         // gsp_frame_sample_base: timestamp of the frame's first sample (seeds keep it, the fold subtracts it)
   uint32_t folded_idle = 0;         // timestamps folded when no pipeline is running (gsp_peek)
   uint32_t finish_paths = 0;        // k_finish takes over below this many live paths (gsp_ctx_options.finish_paths; 0 = never)
   bool primary_memo = true;         // gsp_ctx_options.primary_memo = 2: every sample traces its camera ray

@@ -1225,6 +1225,34 @@ __global__ __launch_bounds__(kBlock) void k_denoise_atrous(const v4f* __restrict
   dn_store(out + p, r);
 }
 
+// ---- temporal accumulation (pt_temporal.h; include/gpuspectral_pt.h "Temporal accumulation") --------------------------------
+// One launch per frame.  A block of 256 lanes owns a tile of 32 x 8 pixels like k_denoise_atrous: a wave's own loads (c, albedo,
+// geom, ids: 16 bytes each) and stores (H', G': 16 bytes, I': 4 bytes) are 512-byte runs (128-byte for I'), and the four taps of
+// neighbouring lanes fall into the same few rows of the previous planes.  A latency-bound gather: temporal_pixel fetches every
+// in-frame tap (H, G 16 bytes, I 4 bytes) before it tests the first, so up to twelve independent loads per lane are in flight;
+// no LDS, no atomics.  The new history is read again at once (next frame, the denoiser): plain stores.
+__global__ __launch_bounds__(kBlock) void k_temporal_reproject(const v4f* __restrict__ accum, const v4f* __restrict__ albedo,
+                                                               const v4f* __restrict__ geom, const v4u* __restrict__ ids,
+                                                               const v4f* __restrict__ Hprev, const v4f* __restrict__ Gprev,
+                                                               const uint32_t* __restrict__ Iprev, v4f* __restrict__ Hout,
+                                                               v4f* __restrict__ Gout, uint32_t* __restrict__ Iout, TemporalConsts k) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  const int width = (int)k.cur.width;
+  if (px >= width || py >= (int)k.cur.height) return;
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  const TemporalOut o = temporal_pixel(k, px, py, dn_load(accum + p), dn_load(albedo + p), dn_load(geom + p), ids[p].z,
+                                       [&](int x, int y, dn4& H_, dn4& G_, uint32_t& I_) {
+                                         const size_t q = (size_t)y * (size_t)width + (size_t)x;  // temporal_pixel asks for pixels of the frame only
+                                         H_ = dn_load(Hprev + q);
+                                         G_ = dn_load(Gprev + q);
+                                         I_ = Iprev[q];
+                                       });
+  dn_store(Hout + p, o.H);
+  dn_store(Gout + p, o.G);
+  Iout[p] = o.I;
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

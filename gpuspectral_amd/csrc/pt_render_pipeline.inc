@@ -393,7 +393,8 @@ static int lane_collect(gsp_context* ctx, gsp_context::Lane& L) {
                          (const uint32_t*)L.active[L.act].p, L.result.p + (uint64_t)b.slot * P.batch_paths, ctx->accum.p,
                          ctx->pix_m2.p, ctx->pix_spp.p, L.index, ctx->num_lanes);
     else
-    hipLaunchKernelGGL(k_resolve, dim3(ctx->grid_for(L.num_pixels)), dim3(kBlock), 0, st, (uint32_t)L.num_pixels, b.kb, b.t0,
+    // (the fold counts the frame's samples from its sample base -- 0 unless gsp_frame_sample_base moved it; the seeds do not)
+    hipLaunchKernelGGL(k_resolve, dim3(ctx->grid_for(L.num_pixels)), dim3(kBlock), 0, st, (uint32_t)L.num_pixels, b.kb, b.t0 - ctx->sample_base,
                        L.result.p + (uint64_t)b.slot * P.batch_paths, ctx->accum.p, L.index, ctx->num_lanes);
     CTX_TRY(ctx, hipGetLastError());
     P.slot_used[b.slot] = 0;
@@ -521,6 +522,16 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
     ctx->err = adaptive ? "adaptive_threshold > 0 in a frame that began uniform: call gsp_frame_begin first"
                         : "adaptive_threshold == 0 in an adaptive frame: call gsp_frame_begin first";
     return GSP_ERR_INVALID;
+  }
+  if (ctx->sample_base != 0) {  // gsp_frame_sample_base
+    if (adaptive) {
+      ctx->err = "adaptive_threshold > 0 in a frame with a sample base (gsp_frame_sample_base): adaptive frames count from timestamp 0";
+      return GSP_ERR_INVALID;
+    }
+    if (rp->first_timestamp < ctx->sample_base) {
+      ctx->err = "first_timestamp " + std::to_string(rp->first_timestamp) + " lies before the frame's sample base " + std::to_string(ctx->sample_base);
+      return GSP_ERR_INVALID;
+    }
   }
   if (adaptive) return render_adaptive(ctx, rp);
   ctx->frame_mode = gsp_context::kFrameUniform;
@@ -862,7 +873,7 @@ int gsp_peek(gsp_context* ctx, float* out, uint32_t* samples_folded) {
     int rc_ = read_back_frame(ctx, out);
     if (rc_ != GSP_OK) return rc_;
   }
-  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : folded;
+  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : (folded >= ctx->sample_base ? folded - ctx->sample_base : folded);
   return GSP_OK;
 }
 
@@ -882,7 +893,7 @@ int gsp_peek_to_device(gsp_context* ctx, void* dst, uint64_t bytes, uint32_t* sa
   }
   CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->accum.p, ctx->num_pixels * sizeof(q4), hipMemcpyDeviceToDevice, ctx->stream));
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : folded;
+  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : (folded >= ctx->sample_base ? folded - ctx->sample_base : folded);
   return GSP_OK;
 }
 
@@ -1271,7 +1282,7 @@ static int display_peek_sync(gsp_context* ctx, uint32_t* samples_folded) {
     CTX_TRY(ctx, hipStreamSynchronize(L.stream));
     folded = std::min(folded, ctx->pipe_active && L.pipe.active ? L.pipe.folded_end : ctx->folded_idle);
   }
-  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : folded;
+  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : (folded >= ctx->sample_base ? folded - ctx->sample_base : folded);
   return GSP_OK;
 }
 
@@ -1408,6 +1419,170 @@ int gsp_download_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, 
     }
   }
   int rc = denoise_ctx(ctx, denoise, "gsp_download_denoised_display", out, nullptr);
+  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
+}
+
+}  // extern "C"
+
+// ---- temporal accumulation (include/gpuspectral_pt.h, "Temporal accumulation"; per-pixel code: pt_temporal.h) ----
+hipError_t gsp::temporal_run(hipStream_t stream, const void* accum, const void* albedo, const void* geom, const void* ids, const void* h_prev,
+                             const void* g_prev, const void* i_prev, void* h_out, void* g_out, void* i_out, const TemporalConsts& k) {
+  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
+  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
+  hipLaunchKernelGGL(k_temporal_reproject, grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids,
+                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (v4f*)h_out, (v4f*)g_out, (uint32_t*)i_out, k);
+  return hipGetLastError();
+}
+
+// what every temporal read-out asks first
+static int temporal_have_history(gsp_context* ctx, const char* who, const void* out_ptr) {
+  if (!out_ptr) {
+    ctx->err = std::string(who) + ": null output pointer";
+    return GSP_ERR_INVALID;
+  }
+  if (!ctx->tp_valid) {
+    ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since the history was last invalidated";
+    return GSP_ERR_INVALID;
+  }
+  return GSP_OK;
+}
+
+// Validates and queues the denoiser with the newest history as its colour source into `dst` (nullptr = the context's own buffer)
+static int temporal_denoise_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const char* who, const void* out_ptr) {
+  int rc = temporal_have_history(ctx, who, out_ptr);
+  if (rc != GSP_OK) return rc;
+  // (tp_valid: the history has the size of the frame -- gsp_frame_begin invalidates any other -- and the frame is a full one)
+  if (!ctx->have_frame || ctx->subset || !ctx->features_rendered) {
+    ctx->err = std::string(who) + " needs a full frame (no pixel_ids) and a gsp_render_features call since gsp_frame_begin";
+    return GSP_ERR_INVALID;
+  }
+  DenoiseConsts k;
+  if (const char* why = resolve_denoise(denoise_host, k)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
+  for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
+  CTX_TRY(ctx, denoise_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->tp_h[ctx->tp_cur].p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->width, ctx->height, k,
+                           ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, ctx->dn_out.p));
+  return GSP_OK;
+}
+
+extern "C" {
+
+int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
+  if (!ctx) return GSP_ERR_INVALID;
+  const char* who = "gsp_temporal_accumulate";
+  if (!ctx->have_frame) {
+    ctx->err = std::string(who) + " needs gsp_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->subset) {
+    ctx->err = std::string(who) + ": the frame was begun with pixel_ids; a share has no neighbours and there is no multi-GPU variant";
+    return GSP_ERR_INVALID;
+  }
+  if (!ctx->features_rendered) {
+    ctx->err = std::string(who) + " needs a gsp_render_features call since gsp_frame_begin";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->tp_done) {
+    ctx->err = std::string(who) + ": the frame has been accumulated already (one call per gsp_frame_begin)";
+    return GSP_ERR_INVALID;
+  }
+  TemporalParams tp;
+  if (const char* why = resolve_temporal(temporal, tp)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  // (gsp_frame_begin has invalidated a history of another size)
+  TemporalConsts k;
+  if (const char* why = temporal_consts(ctx->camera, &ctx->tp_camera, ctx->tp_valid, ctx->width, ctx->height, tp, k)) {
+    ctx->err = std::string(who) + ": " + why;
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  {
+    int rc_ = pipeline_drain(ctx);
+    if (rc_ != GSP_OK) return rc_;
+  }
+  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
+  for (int s = 0; s < 2; ++s) {
+    CTX_TRY(ctx, ctx->tp_h[s].ensure(n, &ctx->bytes));
+    CTX_TRY(ctx, ctx->tp_g[s].ensure(n, &ctx->bytes));
+    CTX_TRY(ctx, ctx->tp_i[s].ensure(n, &ctx->bytes));
+  }
+  const int from = ctx->tp_cur, to = from ^ 1;
+  CTX_TRY(ctx, temporal_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p, ctx->tp_g[from].p,
+                            ctx->tp_i[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p, k));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (complete when the call returns: a camera or scene edit may follow at once)
+  ctx->tp_cur = to;
+  ctx->tp_camera = ctx->camera;
+  ctx->tp_width = ctx->width;
+  ctx->tp_height = ctx->height;
+  ctx->tp_valid = true;
+  ctx->tp_done = true;
+  return GSP_OK;
+}
+
+int gsp_frame_sample_base(gsp_context* ctx, uint32_t base) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (!ctx->have_frame || ctx->frame_mode != gsp_context::kFrameUndecided) {
+    ctx->err = "gsp_frame_sample_base belongs between gsp_frame_begin and the frame's first gsp_render";
+    return GSP_ERR_INVALID;
+  }
+  ctx->sample_base = base;
+  return GSP_OK;
+}
+
+int gsp_temporal_reset(gsp_context* ctx) {
+  if (!ctx) return GSP_ERR_INVALID;
+  ctx->tp_valid = false;
+  return GSP_OK;
+}
+
+int gsp_download_temporal(gsp_context* ctx, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_history(ctx, "gsp_download_temporal", out);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  return read_back_bytes(ctx, ctx->tp_h[ctx->tp_cur].p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
+}
+
+int gsp_temporal_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_history(ctx, "gsp_temporal_to_device", dst);
+  if (rc != GSP_OK) return rc;
+  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
+  if (bytes < need) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->tp_h[ctx->tp_cur].p, need, hipMemcpyDeviceToDevice, ctx->stream));  // (a copy: any alignment)
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+int gsp_download_temporal_denoised(gsp_context* ctx, const gsp_denoise* denoise, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_denoise_ctx(ctx, denoise, "gsp_download_temporal_denoised", out);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
+}
+
+int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  {  // (an invalid display is refused before anything is queued)
+    gsp_display d;
+    if (const char* why = resolve_display(display, d)) {
+      ctx->err = why;
+      return GSP_ERR_INVALID;
+    }
+  }
+  int rc = temporal_denoise_ctx(ctx, denoise, "gsp_download_temporal_denoised_display", out);
   if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
   if (rc != GSP_OK) return rc;
   return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);

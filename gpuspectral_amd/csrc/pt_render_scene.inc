@@ -536,6 +536,7 @@ int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
     if (rc_ != GSP_OK) return rc_;
   }
   ctx->have_scene = false;
+  ctx->tp_valid = false;  // (temporal accumulation: a new scene has no history)
   for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
   ctx->geo_ring_failed = false;
   ctx->inst_dynamic.clear();
@@ -897,6 +898,8 @@ int gsp_frame_begin(gsp_context* ctx, uint32_t width, uint32_t height, const uin
   ctx->frame_mode = gsp_context::kFrameUndecided;
   ctx->adaptive_n = 0;
   ctx->features_rendered = false;
+  ctx->tp_done = false;
+  if (width != ctx->tp_width || height != ctx->tp_height) ctx->tp_valid = false;  // (the history is of another size)
   ctx->features_ready = false;  // (the feature planes, where a frame has asked for them, start from zero again)
   ctx->subset = pixel_ids != nullptr;
   if (pixel_ids) {
@@ -937,6 +940,7 @@ int gsp_frame_begin(gsp_context* ctx, uint32_t width, uint32_t height, const uin
     ctx->stage_warm = true;
   }
   ctx->folded_idle = 0;
+  ctx->sample_base = 0;
   ctx->have_frame = true;
   return GSP_OK;
 }

@@ -89,6 +89,11 @@ def load():
     L.gsph_pathtracer_download_features.argtypes = [vp, vp, vp, u64]
     L.gsph_pathtracer_download_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
     L.gsph_pathtracer_download_denoised_display.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
+    L.gsph_pathtracer_next_frame.argtypes = [vp]
+    L.gsph_pathtracer_temporal_accumulate.argtypes = [vp, C.POINTER(abi.Temporal)]
+    L.gsph_pathtracer_temporal_reset.argtypes = [vp]
+    L.gsph_pathtracer_download_temporal.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_download_temporal_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
     _LIB = L
     return L
 
@@ -346,6 +351,30 @@ class PathTracer:
         out = np.zeros((self.height, self.width), np.uint32)
         self._check(self._L.gsph_pathtracer_download_denoised_display(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data,
                                                                       out.size), "downloadDenoisedDisplay")
+        return out
+
+    def next_frame(self):
+        """PathTracer::nextFrame: a new frame whose samples continue the timestamp sequence."""
+        self._check(self._L.gsph_pathtracer_next_frame(self._h), "nextFrame")
+
+    def temporal_accumulate(self, temporal=None):
+        """PathTracer::temporalAccumulate (abi.Temporal; None = every default)."""
+        self._check(self._L.gsph_pathtracer_temporal_accumulate(self._h, C.byref(temporal) if temporal is not None else None), "temporalAccumulate")
+
+    def temporal_reset(self):
+        self._check(self._L.gsph_pathtracer_temporal_reset(self._h), "temporalReset")
+
+    def download_temporal(self):
+        """PathTracer::downloadTemporal: (h, w, 4) float32, .w = the history length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_temporal(self._h, out.ctypes.data, out.size), "downloadTemporal")
+        return out
+
+    def download_temporal_denoised(self, denoise=None):
+        """PathTracer::downloadTemporalDenoised (abi.Denoise; None = every default): (h, w, 4) float32."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_temporal_denoised(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data,
+                                                                       out.size), "downloadTemporalDenoised")
         return out
 
     def stats(self):

@@ -287,6 +287,28 @@ std::vector<uint32_t> PathTracer::downloadDenoisedDisplay(const gsp_denoise* den
   return out;
 }
 
+void PathTracer::temporalAccumulate(const gsp_temporal* temporal) { check(gsp_temporal_accumulate(ctx, temporal), "gsp_temporal_accumulate"); }
+
+void PathTracer::temporalReset() { check(gsp_temporal_reset(ctx), "gsp_temporal_reset"); }
+
+std::vector<float> PathTracer::downloadTemporal() {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_temporal(ctx, out.data()), "gsp_download_temporal");
+  return out;
+}
+
+std::vector<float> PathTracer::downloadTemporalDenoised(const gsp_denoise* denoise) {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_temporal_denoised(ctx, denoise, out.data()), "gsp_download_temporal_denoised");
+  return out;
+}
+
+void PathTracer::nextFrame() {
+  featureTimestamp = timestamp;  // (the feature samples of the new frame are those of its beauty samples)
+  check(gsp_frame_begin(ctx, width, height, pixelIds.empty() ? nullptr : pixelIds.data(), pixelIds.size()), "gsp_frame_begin");
+  check(gsp_frame_sample_base(ctx, (uint32_t)timestamp), "gsp_frame_sample_base");  // (the frame holds the plain mean of its own samples)
+}
+
 gsp_stats PathTracer::stats() {
   gsp_stats s;
   check(gsp_get_stats(ctx, &s), "gsp_get_stats");

@@ -106,6 +106,15 @@ class PathTracer : public RenderPassCreator {
   // film (`display`) of the denoised frame, RGBA8 words.  The frame itself is not changed.
   std::vector<float> downloadDenoised(const gsp_denoise* denoise = nullptr);
   std::vector<uint32_t> downloadDenoisedDisplay(const gsp_denoise* denoise = nullptr);
+  // Temporal accumulation (gpuspectral_pt.h "Temporal accumulation"): the viewer loop is nextFrame() -> render -> renderFeatures ->
+  // temporalAccumulate -> downloadTemporal / downloadTemporalDenoised.  temporalAccumulate reprojects the history of earlier
+  // frames into the scene's current camera and blends this frame in (once per frame; nullptr = every default); downloadTemporal
+  // is that history (RGBA32F, .w = the history length), downloadTemporalDenoised its a-trous filter guided by this frame's planes.
+  void temporalAccumulate(const gsp_temporal* temporal = nullptr);
+  void temporalReset();
+  std::vector<float> downloadTemporal();
+  std::vector<float> downloadTemporalDenoised(const gsp_denoise* denoise = nullptr);
+  void nextFrame();  // a new frame (accumulate buffer and feature planes cleared) whose samples continue the timestamp sequence
   void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }
   gsp_stats stats();

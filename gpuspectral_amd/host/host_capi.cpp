@@ -317,6 +317,30 @@ int gsph_pathtracer_download_denoised_display(void* pt, const gsp_denoise* denoi
     std::memcpy(out, img.data(), img.size() * sizeof(uint32_t));
   });
 }
+// temporal accumulation of a PathTracer (gpuspectral_pt.h "Temporal accumulation"); temporal / denoise may be NULL
+int gsph_pathtracer_next_frame(void* pt) {
+  return guard([&] { ((PathTracer*)pt)->nextFrame(); });
+}
+int gsph_pathtracer_temporal_accumulate(void* pt, const gsp_temporal* temporal) {
+  return guard([&] { ((PathTracer*)pt)->temporalAccumulate(temporal); });
+}
+int gsph_pathtracer_temporal_reset(void* pt) {
+  return guard([&] { ((PathTracer*)pt)->temporalReset(); });
+}
+int gsph_pathtracer_download_temporal(void* pt, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTemporal();
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_download_temporal_denoised(void* pt, const gsp_denoise* denoise, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTemporalDenoised(denoise);
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {
     std::vector<uint8_t> v;

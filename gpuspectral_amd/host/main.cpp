@@ -23,6 +23,10 @@
 //   "Denoiser"; N = 1..8 levels, the four sigmas of colour, normal, depth and albedo: 0 = the default, inf = that term off).  It
 //   uses the feature planes of --features, or runs a feature pass of its own at the frame's spp, filter and lens.  With --ldr
 //   (one device) the LDR film of the denoised frame goes to out.png beside it.  Without --denoise nothing more is written or printed.
+//   --temporal out.pfm --temporal-frames N [--temporal-orbit DEG]: render N frames of spp samples each (gpuspectral_pt.h "Temporal
+//   accumulation"), the scene's camera turned by DEG degrees about the world y axis through the origin between frames (the
+//   loader keeps no look-at point), every frame accumulated into the history; out.pfm receives the history after the last frame
+//   and, with --denoise, out.dn.pfm its filtered form.  The files of the other flags are those of the LAST frame.  One device.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -54,6 +58,10 @@ int main(int argc, char** argv) {
   std::string featuresPrefix;
   int featureSpp = -1;  // (-1 = not given: the frame's spp)
   std::string denoisePath;
+  std::string temporalPath;
+  int temporalFrames = 0;  // (0 = not given)
+  float temporalOrbit = 0.0f;
+  bool temporalOptions = false;
   gsp_denoise denoise{};
   denoise.struct_size = (uint32_t)sizeof(gsp_denoise);
   bool denoiseOptions = false;
@@ -91,6 +99,22 @@ int main(int argc, char** argv) {
       featureSpp = (int)v, used = 2;
     }
     else if (flag == "--denoise" && argc > 2) denoisePath = argv[2], used = 2;
+    else if (flag == "--temporal" && argc > 2) temporalPath = argv[2], used = 2;
+    else if (flag == "--temporal-frames" && argc > 2) {
+      char* e = nullptr;
+      const long v = std::strtol(argv[2], &e, 10);
+      if (e == argv[2] || *e != 0 || v < 1 || v > 100000) {
+        std::fprintf(stderr, "gsp_render: bad temporal frames '%s' (expected 1..100000)\n", argv[2]);
+        return 2;
+      }
+      temporalFrames = (int)v, temporalOptions = true, used = 2;
+    } else if (flag == "--temporal-orbit" && argc > 2) {
+      if (!parseFloat(argv[2], temporalOrbit) || temporalOrbit < -360.0f || temporalOrbit > 360.0f) {
+        std::fprintf(stderr, "gsp_render: bad temporal orbit '%s' (expected degrees per frame within -360 .. 360)\n", argv[2]);
+        return 2;
+      }
+      temporalOptions = true, used = 2;
+    }
     else if (flag == "--denoise-iterations" && argc > 2) {
       char* e = nullptr;
       const long v = std::strtol(argv[2], &e, 10);
@@ -231,8 +255,16 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --denoise-iterations and --denoise-sigma need --denoise out.pfm\n");
     return 2;
   }
+  if (temporalPath.empty() && temporalOptions) {
+    std::fprintf(stderr, "gsp_render: --temporal-frames and --temporal-orbit need --temporal out.pfm\n");
+    return 2;
+  }
+  if (!temporalPath.empty() && temporalFrames == 0) {
+    std::fprintf(stderr, "gsp_render: --temporal needs --temporal-frames N\n");
+    return 2;
+  }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -265,6 +297,10 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (!temporalPath.empty() && devices.size() > 1) {
+    std::fprintf(stderr, "gsp_render: --temporal needs a single device (temporal accumulation has no multi-GPU variant)\n");
+    return 2;
+  }
   try {
     Scene scene = loadScene(argv[1], "", options);
     for (auto& w : scene.warnings) std::fprintf(stderr, "WARN: %s\n", w.c_str());
@@ -291,7 +327,8 @@ int main(int argc, char** argv) {
     if (!denoisePath.empty() && !ldrPath.empty() && devices.size() > 1)
       throw std::runtime_error("--denoise with --ldr needs a single device (the LDR film of the denoised frame is a single-context call)");
     std::vector<uint32_t> ldr, denoisedLdr;
-    std::vector<float> img, featAlbedo, featGeom, denoised;
+    std::vector<float> img, featAlbedo, featGeom, denoised, temporal, temporalDenoised;
+    double temporalLength = 0.0;
     const uint32_t fspp = featureSpp > 0 ? (uint32_t)featureSpp : spp;
     gsp_stats st;
     double s;
@@ -303,6 +340,22 @@ int main(int argc, char** argv) {
       pt.params.adaptive_step = adaptiveStep;
       pt.params.pixel_filter = filter;
       pt.params.pixel_filter_param = filterParam;
+      // temporal accumulation: the frames before the last one, each rendered, given a feature pass and accumulated, then the
+      // camera turned about the world y axis; the last frame is the ordinary frame below
+      for (int f = 0; f + 1 < temporalFrames; ++f) {
+        pt.render(scene, spp);
+        pt.renderFeatures(scene, spp);
+        pt.temporalAccumulate();
+        const float a = temporalOrbit * 3.14159265358979323846f / 180.0f, cs = std::cos(a), sn = std::sin(a);
+        const mat4 m = scene.camera.getToWorld();
+        mat4 r = m;
+        for (int c = 0; c < 4; ++c) {  // R_y(a) * m, column by column
+          r[c][0] = cs * m[c][0] + sn * m[c][2];
+          r[c][2] = -sn * m[c][0] + cs * m[c][2];
+        }
+        scene.camera.setToWorld(r);
+        pt.nextFrame();
+      }
       auto t0 = std::chrono::steady_clock::now();
       pt.render(scene, spp);
       img = pt.download();
@@ -320,6 +373,14 @@ int main(int argc, char** argv) {
         if (featuresPrefix.empty()) pt.renderFeatures(scene, spp);
         denoised = pt.downloadDenoised(&denoise);
         if (!ldrPath.empty()) denoisedLdr = pt.downloadDenoisedDisplay(&denoise);
+      }
+      if (!temporalPath.empty()) {  // the last frame into the history, on the planes above or on a pass of its own
+        if (featuresPrefix.empty() && denoisePath.empty()) pt.renderFeatures(scene, spp);
+        pt.temporalAccumulate();
+        temporal = pt.downloadTemporal();
+        if (!denoisePath.empty()) temporalDenoised = pt.downloadTemporalDenoised(&denoise);
+        for (size_t i = 3; i < temporal.size(); i += 4) temporalLength += temporal[i];
+        temporalLength /= (double)width * height;
       }
     } else {
       MultiGpuPathTracer pt(width, height, devices, &ctxOptions);
@@ -377,6 +438,17 @@ int main(int argc, char** argv) {
         writePng(png, denoisedLdr.data(), width, height, false);
       }
       std::printf("denoised: %u levels -> %s%s%s\n", denoise.iterations ? denoise.iterations : 5u, denoisePath.c_str(), png.empty() ? "" : ", ", png.c_str());
+    }
+    if (!temporalPath.empty()) {
+      writePfm(temporalPath, temporal.data(), width, height);
+      std::string dn;
+      if (!temporalDenoised.empty()) {
+        const size_t dot = temporalPath.rfind('.');
+        dn = (dot != std::string::npos && temporalPath.find('/', dot) == std::string::npos ? temporalPath.substr(0, dot) : temporalPath) + ".dn.pfm";
+        writePfm(dn, temporalDenoised.data(), width, height);
+      }
+      std::printf("temporal: %d frame%s of %u spp, %g degrees per frame, mean history length %.2f -> %s%s%s\n", temporalFrames, temporalFrames == 1 ? "" : "s",
+                  spp, (double)temporalOrbit, temporalLength, temporalPath.c_str(), dn.empty() ? "" : ", ", dn.c_str());
     }
     std::printf("%llu triangles, %ux%u x %u spp in %.3f s: %.1f Mrays/s, %.2f Msamples/s (BVH build %.1f ms)\n",
                 (unsigned long long)st.num_triangles, width, height, spp, s,

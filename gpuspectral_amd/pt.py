@@ -49,6 +49,13 @@ EXPORTS = (
     "gsp_download_denoised",
     "gsp_denoise_to_device",
     "gsp_download_denoised_display",
+    "gsp_temporal_accumulate",
+    "gsp_temporal_reset",
+    "gsp_download_temporal",
+    "gsp_temporal_to_device",
+    "gsp_download_temporal_denoised",
+    "gsp_download_temporal_denoised_display",
+    "gsp_frame_sample_base",
     "gsp_get_stats",
     "gsp_reset_stats",
     "gsp_trace",
@@ -144,6 +151,13 @@ def load():
     L.gsp_denoise_to_device.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
     L.gsp_download_denoised_display.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Display), vp]
     L.gsp_multi_download_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp]
+    L.gsp_temporal_accumulate.argtypes = [vp, C.POINTER(abi.Temporal)]
+    L.gsp_temporal_reset.argtypes = [vp]
+    L.gsp_frame_sample_base.argtypes = [vp, C.c_uint32]
+    L.gsp_download_temporal.argtypes = [vp, vp]
+    L.gsp_temporal_to_device.argtypes = [vp, vp, u64]
+    L.gsp_download_temporal_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp]
+    L.gsp_download_temporal_denoised_display.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Display), vp]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -194,7 +208,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -418,6 +432,46 @@ class Context:
         self._check(self._L.gsp_download_denoised_display(self._h, C.byref(denoise) if denoise is not None else None,
                                                           C.byref(display) if display is not None else None, out.ctypes.data),
                     "gsp_download_denoised_display")
+        return out
+
+    # ---- temporal accumulation (gpuspectral_pt.h "Temporal accumulation"); temporal: an abi.Temporal, None = every default ----
+    def temporal_accumulate(self, temporal=None):
+        """gsp_temporal_accumulate: reprojects the history of earlier frames into this frame's camera and blends this frame in.
+        Once per frame_begin, after render and render_features.  The frame itself is not changed."""
+        self._check(self._L.gsp_temporal_accumulate(self._h, C.byref(temporal) if temporal is not None else None), "gsp_temporal_accumulate")
+
+    def frame_sample_base(self, base):
+        """gsp_frame_sample_base: between frame_begin and the frame's first render -- the frame's samples keep timestamps base,
+        base + 1, ... for their seeds and are folded as samples 0, 1, ... of the fresh frame (its plain mean)."""
+        self._check(self._L.gsp_frame_sample_base(self._h, base), "gsp_frame_sample_base")
+
+    def temporal_reset(self):
+        """gsp_temporal_reset: forgets the history."""
+        self._check(self._L.gsp_temporal_reset(self._h), "gsp_temporal_reset")
+
+    def download_temporal(self):
+        """gsp_download_temporal: the newest history, (height, width, 4) float32; .w = the history length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_temporal(self._h, out.ctypes.data), "gsp_download_temporal")
+        return out
+
+    def temporal_to_device(self, device_ptr, nbytes):
+        """gsp_temporal_to_device: the newest history into device memory (e.g. a torch tensor's data_ptr()), width*height*16 bytes."""
+        self._check(self._L.gsp_temporal_to_device(self._h, device_ptr, nbytes), "gsp_temporal_to_device")
+
+    def download_temporal_denoised(self, denoise=None):
+        """gsp_download_temporal_denoised: the a-trous filter of the history, guided by this frame's feature planes."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_temporal_denoised(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data),
+                    "gsp_download_temporal_denoised")
+        return out
+
+    def download_temporal_denoised_display(self, denoise=None, display=None):
+        """gsp_download_temporal_denoised_display: the LDR film of the filtered history, (height, width) uint32 RGBA8 words."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsp_download_temporal_denoised_display(self._h, C.byref(denoise) if denoise is not None else None,
+                                                                   C.byref(display) if display is not None else None, out.ctypes.data),
+                    "gsp_download_temporal_denoised_display")
         return out
 
     def pixel_stats(self):

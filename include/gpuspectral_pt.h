@@ -71,7 +71,9 @@ extern "C" {
                                 gsp_render_features, gsp_download_features, gsp_copy_features_to_device,
                                 gsp_multi_render_features, gsp_multi_download_features (see "Feature buffers");
                                 gsp_download_denoised, gsp_denoise_to_device, gsp_download_denoised_display,
-                                gsp_multi_download_denoised (see "Denoiser") */
+                                gsp_multi_download_denoised (see "Denoiser"); gsp_temporal_accumulate, gsp_temporal_reset,
+                                gsp_download_temporal, gsp_temporal_to_device, gsp_download_temporal_denoised,
+                                gsp_download_temporal_denoised_display, gsp_frame_sample_base (see "Temporal accumulation") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -761,6 +763,107 @@ int gsp_denoise_to_device(gsp_context* ctx, const gsp_denoise* denoise, void* de
 /* The LDR film (see "LDR film") of the DENOISED frame: the tone map, the encode and -- where the display asks for them -- the frame
  * statistics are those of the denoised buffer, not of the accumulate buffer.  width*height RGBA8 words. */
 int gsp_download_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out_rgba8);
+
+/*
+ * Temporal accumulation: the history of earlier frames reprojected into the new camera and blended with the new frame.
+ *
+ * For a viewer that renders a sample or a few per frame under a moving camera: gsp_frame_begin clears the accumulate buffer, this
+ * keeps what earlier frames collected.  It is the temporal half of SVGF; the "Denoiser" above is the spatial half and runs on the
+ * result (gsp_download_temporal_denoised).  No reference code defines it, so this header does, down to the order of the float32
+ * operations.  Arithmetic is float32 in the order written (no contraction).
+ *
+ * State, allocated by the first temporal call of a context (a context that never makes one holds none): two ping-pong sets of
+ * history planes over the full frame, H = {r, g, b, len} (16 bytes; len = the history length as a float), G = {n.x, n.y, n.z, z}
+ * (16 bytes) and I = the instance index (4 bytes, 0xffffffff = background) -- 72 bytes per pixel in all --, the camera and the
+ * frame size the history belongs to, and a flag history_valid.  history_valid is cleared by gsp_temporal_reset, by
+ * gsp_upload_scene and by a gsp_frame_begin whose width or height differs from the history's.
+ *
+ * The pixel's own data come from the feature planes of THIS frame (gsp_render_features): cov = albedo.w, inst = ids.z, geom.
+ *     surface pixel      inst != 0xffffffff && cov >= 0.5f:   n = geom.xyz / cov (three divisions), z = geom.w / cov, I = inst
+ *                        (exact for the unfiltered pinhole, where cov == 1)
+ *     background pixel   otherwise:  n = 0, z = 0, I = 0xffffffff
+ *     c = the pixel's accumulate record; c is finite when c.r, c.g and c.b are.
+ *
+ * Reprojection of pixel (px, py), W x H the frame, M / eye / zplane the CURRENT camera's (see "Thin lens": Camera ray):
+ *  1. d = flipY(M * normalize((-((float)px - W/2), (float)py - H/2, zplane))) -- the PINHOLE ray through the integer pixel
+ *     coordinate, whatever lens or pixel filter the frame was rendered with.
+ *  2. surface:     P.k = eye.k + d.k * z;   v.k = P.k - eye_prev.k;   ze = sqrt((v.x*v.x + v.y*v.y) + v.z*v.z)
+ *     background:  v = d  (a point at infinity: the camera's translation does not move it)
+ *  3. l = Minv_prev * (v.x, -v.y, v.z), each component summed as (m_r0 * a + m_r1 * b) + m_r2 * c.  Minv_prev is the inverse of
+ *     the upper-left 3x3 of the previous to_world, formed once on the host in double (adjugate / determinant) and rounded to
+ *     float.  A determinant that is 0 or not finite, or an entry that is not finite as a float: GSP_ERR_INVALID at the call.
+ *  4. not (l.z > 0): no history.
+ *  5. t = zplane_prev / l.z;   fx = W/2 - l.x * t;   fy = H/2 + l.y * t.   zplane_prev = (max(W, H) / 2) / tanf(fov_prev / 2),
+ *     formed on the host in float as gsp_focus_distance forms zplane; W/2 is (float)W / 2.0f.
+ *  6. Snap: r = rint(fx); if |fx - r| < 1e-3f then fx = r; the same for fy.  An unmoved camera then reads exactly its own pixel
+ *     with weight 1.  The constant, a thousandth of a pixel, is part of the definition.
+ *  7. not (fx > -1 && fx < W && fy > -1 && fy < H): no tap can lie inside the frame: no history.  Otherwise x0 = floor(fx),
+ *     wx = fx - x0, y0 = floor(fy), wy = fy - y0; the taps are (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1) in this order with
+ *     weights (1-wx)*(1-wy), wx*(1-wy), (1-wx)*wy, wx*wy.
+ * A tap q is skipped when its weight is 0; when it lies outside the frame; when not (H_q.len > 0) or one of H_q.r, .g, .b is not
+ * finite; when I_q != I (for a background pixel: I_q != 0xffffffff); and, for a surface pixel, when
+ * |ze - z_q| > depth_tolerance * ze, or when (n.x*n_q.x + n.y*n_q.y) + n.z*n_q.z < normal_min.  ze is the distance of P from the
+ * previous eye: the sense in which the feature depth of the previous frame is a depth.  Over the kept taps, in tap order:
+ *     sw += w;   s.k += w * H_q.k;   sl += w * H_q.len
+ * Blend.  There is history when history_valid and sw >= 0.01f.
+ *     with history:     prev.k = s.k / sw;   len = sl / sw
+ *         c finite:     N = min(len + 1, max_history);  a = max(alpha, 1 / N);  H'.k = prev.k + (c.k - prev.k) * a;  H'.len = N
+ *         c not finite: H'.k = prev.k;  H'.len = min(len, max_history)
+ *     without history:  H' = {c.r, c.g, c.b, 1} when c is finite, {c.r, c.g, c.b, 0} when not: the pixel is nobody's history
+ * G' = {n, z} and I' = I of this frame in both cases.
+ *
+ * Defaults (a field left 0): max_history 32, alpha 0.2, depth_tolerance 0.02, normal_min 0.9 (the last three formed in double
+ * and rounded to float).  Because 0 means the default, alpha is any value in (0, 1]; the pure running mean is alpha = FLT_MIN
+ * (a = 1 / N until max_history caps N).  Likewise a tolerance or normal_min of exactly 0 is written as a tiny value.
+ *
+ * Frames of a viewer.  Each frame is gsp_frame_begin, gsp_frame_sample_base(first timestamp of the frame), gsp_render,
+ * gsp_render_features, gsp_temporal_accumulate: with the base the frame's record c is the plain mean of its own samples and every
+ * frame draws new random numbers (see gsp_frame_sample_base below); without it a frame rendered at first_timestamp T > 0 on the
+ * cleared buffer is darker by n / (T + n), and frames that all start at timestamp 0 repeat one noise pattern.
+ *
+ * Out of scope.  The world is taken as static between two frames: an instance that moved is handled only by rejection (the
+ * instance-index, depth and normal tests); per-instance motion vectors are a later change.  There are no gsp_multi_* variants: a
+ * share has no neighbours, and gathering the ids plane is a change of its own -- a frame begun with pixel_ids is refused.  The
+ * filtered output is not fed back into the history.
+ */
+typedef struct gsp_temporal {
+  uint32_t struct_size; /* sizeof(gsp_temporal) of the host's header; same rule as gsp_denoise (fields beyond it are 0; NULL and
+                           struct_size 0 = the zeroed struct = every default) */
+  uint32_t max_history; /* cap of the history length; 0 = 32; otherwise 1..65536 */
+  float alpha;           /* floor of the blend weight of the new frame; 0 = 0.2; otherwise (0, 1] */
+  float depth_tolerance; /* relative; 0 = 0.02; otherwise > 0 */
+  float normal_min;      /* smallest dot product of the two normals; 0 = 0.9; otherwise [-1, 1] */
+} gsp_temporal;
+/* The frame's samples are numbered from `base`.  gsp_frame_begin clears the accumulate buffer, and the fold of sample `timestamp`
+ * weighs it 1 / (timestamp + 1) (raygen.rgen:84-108): a fresh frame rendered at first_timestamp T > 0 holds its mean times
+ * n / (T + n), not its mean.  A viewer that wants a NEW random sequence in every frame (the seed is tea(pixel, timestamp)) and the
+ * plain mean of the frame's own samples calls this between gsp_frame_begin and the frame's first gsp_render: the samples keep
+ * their timestamps for the seeds, bit for bit, and sample base + k is folded as the frame's k-th sample, so the frame equals,
+ * bit for bit, what a frame would hold whose timestamps 0 .. n-1 drew the random numbers of base .. base + n-1.  The frame's
+ * gsp_render calls then take first_timestamp >= base; gsp_peek's *samples_folded counts from base.  gsp_frame_begin sets the
+ * base back to 0.  GSP_ERR_INVALID: no frame; after the frame's first gsp_render; with base != 0 an adaptive gsp_render or a
+ * first_timestamp below base (at that gsp_render).  gsp_render_features is not concerned: its planes fold by their own count. */
+int gsp_frame_sample_base(gsp_context* ctx, uint32_t base);
+/* Completes the queued samples (as gsp_download does), runs the reprojection from the old history set into the other one and
+ * swaps them, records the current camera and size and sets history_valid.  Changes nothing of the frame: the accumulate buffer,
+ * the feature planes, the pixel statistics, the memo and gsp_stats stay as they were.  GSP_ERR_INVALID (text at gsp_last_error):
+ * no frame; a frame begun with pixel_ids; no gsp_render_features call since gsp_frame_begin; a second accumulate in the same
+ * frame; max_history > 65536; alpha outside [0, 1] or NaN; a negative or NaN depth_tolerance; normal_min outside [-1, 1] or NaN;
+ * a singular previous camera (step 3). */
+int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal);
+/* Forgets the history: the next gsp_temporal_accumulate starts from its frame alone.  Frees nothing. */
+int gsp_temporal_reset(gsp_context* ctx);
+/* The four read-outs below return GSP_ERR_INVALID when no gsp_temporal_accumulate has succeeded since the history was last
+ * invalidated (or since the context was made). */
+/* H of the newest set: width*height*4 floats, .w = the history length.  Through the staged read-back. */
+int gsp_download_temporal(gsp_context* ctx, float* out_rgba);
+/* The same into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
+int gsp_temporal_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
+/* The "Denoiser" with H as its colour source c instead of the accumulate buffer, guided by THIS frame's feature planes (so it
+ * needs a frame and its gsp_render_features, like gsp_download_denoised); out.w = the history length. */
+int gsp_download_temporal_denoised(gsp_context* ctx, const gsp_denoise* denoise, float* out_rgba);
+/* ... and the LDR film of that (as gsp_download_denoised_display): width*height RGBA8 words. */
+int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out_rgba8);
 
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
