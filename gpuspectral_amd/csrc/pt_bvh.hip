@@ -148,13 +148,18 @@ __global__ __launch_bounds__(kBlock) void k_bake(BuildInput in, q4* __restrict__
     const f3 e3 = p2 - p1;
     const float l2 = fmaxf(fmaxf(dot(e1, e1), dot(e2, e2)), dot(e3, e3));
     const f3 cr = cross(e1, e2);
-    // (a triangle thinner than 1e-6 of its length is a line at the precision of its own coordinates: nothing to protect,
-    // and 5 % of the reference's staircase2 scene is such triangles -- padding them cost it 9 % of its speed)
-    const float aspect = l2 / fmaxf(gsqrt(dot(cr, cr)), 1e-30f);
-    const float sliver = aspect < 1.0e6f ? fminf(fmaxf(aspect * (1.0f / 32.0f), 1.0f), 1024.0f) : 1.0f;
+    // Beyond aspect 32768 the error keeps growing while the factor stays at 1024, but the reported point cannot leave the
+    // triangle's span along the ray, so a pad of the triangle's own extent is enough whatever the aspect (`span`).  Triangles
+    // beyond aspect 1e6 used to get the plain pad ("a line at the precision of its own coordinates"); a 6 x 3e-6 triangle at
+    // coordinate 1 is 25 float32 spacings wide, was hit with tmax = 1e10 and missed with tmax just above the reported t
+    // (tests/trace_reference.py, range consistency).  Triangles of zero area are never hit and keep the plain pad.
+    const float area2 = gsqrt(dot(cr, cr));
+    const float aspect = l2 / fmaxf(area2, 1e-30f);
+    const float sliver = area2 > 0.0f ? fminf(fmaxf(aspect * (1.0f / 32.0f), 1.0f), 1024.0f) : 1.0f;
+    const float span = area2 > 0.0f ? diag * fminf(aspect * (1e-5f / 32.0f), 1.0f) : 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const float pad = 1e-5f * fmaxf(fmaxf(fabsf(l[k]), fabsf(h[k])), fmaxf(diag, 1e-3f)) * sliver;
+      const float pad = fmaxf(1e-5f * fmaxf(fmaxf(fabsf(l[k]), fabsf(h[k])), fmaxf(diag, 1e-3f)) * sliver, span);
       lo[k] = l[k] - pad;
       hi[k] = h[k] + pad;
     }

@@ -134,11 +134,16 @@ static void buildAccel(const gsp_scene_desc& sc, Accel& A) {
     // that aspect ratio (the product pads the same way, gpuspectral_amd/csrc/pt_bvh.hip k_bake)
     const vec3 e1 = b - a, e2 = c - a, e3 = c - b, cr = cross(e1, e2);
     const float l2 = std::max(std::max(dot(e1, e1), dot(e2, e2)), dot(e3, e3));
-    // (a triangle thinner than 1e-6 of its length is a line at the precision of its own coordinates: no extra pad)
-    const float aspect = l2 / std::max(std::sqrt(dot(cr, cr)), 1e-30f);
-    const float sliver = aspect < 1.0e6f ? std::min(std::max(aspect * (1.0f / 32.0f), 1.0f), 1024.0f) : 1.0f;
+    // Beyond aspect 32768 the t error keeps growing while that factor stays at 1024, but the reported point cannot leave the
+    // triangle's span along the ray, so a pad of the triangle's own extent is enough whatever the aspect: the second term.
+    // (Until tests/trace_reference.py's range-consistency property, triangles beyond aspect 1e6 got the plain pad: a 6 x 3e-6
+    // triangle was hit with tmax = 1e10 and missed with tmax just above the reported t.)  Zero area: never hit, plain pad.
+    const float area2 = std::sqrt(dot(cr, cr));
+    const float aspect = l2 / std::max(area2, 1e-30f);
+    const float sliver = area2 > 0.0f ? std::min(std::max(aspect * (1.0f / 32.0f), 1.0f), 1024.0f) : 1.0f;
+    const float span = area2 > 0.0f ? diag * std::min(aspect * (1e-5f / 32.0f), 1.0f) : 0.0f;
     for (int k = 0; k < 3; ++k) {
-      float pad = 1e-5f * std::max(std::max(std::fabs(lo[k]), std::fabs(hi[k])), std::max(diag, 1e-3f)) * sliver;
+      float pad = std::max(1e-5f * std::max(std::max(std::fabs(lo[k]), std::fabs(hi[k])), std::max(diag, 1e-3f)) * sliver, span);
       cmin[3ull * i + k] = lo[k] - pad;
       cmax[3ull * i + k] = hi[k] + pad;
       cen[3ull * i + k] = 0.5f * (lo[k] + hi[k]);
