@@ -223,6 +223,20 @@ def temporal(max_history=0, alpha=0.0, depth_tolerance=0.0, normal_min=0.0):
     return Temporal(C.sizeof(Temporal), max_history, alpha, depth_tolerance, normal_min)
 
 
+class Svgf(C.Structure):
+    """gsp_svgf: the parameters of the variance-guided filter (gsp_download_temporal_svgf); all zero = every default."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("min_history", C.c_uint32),  # 0 = 4; otherwise 2..65536
+        ("sigma_variance", C.c_float),  # 0 = 4.0; +inf = the term is off
+    ]
+
+
+def svgf(min_history=0, sigma_variance=0.0):
+    return Svgf(C.sizeof(Svgf), min_history, sigma_variance)
+
+
 class Luminance(C.Structure):
     """gsp_luminance: the frame statistics of the Reinhard operator (gsp_frame_luminance)."""
 

@@ -57,16 +57,25 @@ GSP_HD void denoise_prepare(const dn4& c, const dn4& alb, dn4& E, dn4& A) {
   E.w = display_luma(E.x, E.y, E.z);
 }
 
+// The guide differences of a tap: dn and da are squared distances, rz the relative depth difference
+GSP_HD float denoise_dn(const dn4& Gp, const dn4& Gq) {
+  const float nx = Gp.x - Gq.x, ny = Gp.y - Gq.y, nz = Gp.z - Gq.z;
+  return (nx * nx + ny * ny) + nz * nz;
+}
+GSP_HD float denoise_rz(const dn4& Gp, const dn4& Gq) { return Gp.w == Gq.w ? 0.0f : (Gp.w - Gq.w) / (Gp.w + Gq.w); }
+GSP_HD float denoise_da(const dn4& Ap, const dn4& Aq) {
+  const float ar = Ap.x - Aq.x, ag = Ap.y - Aq.y, ab = Ap.z - Aq.z;
+  return (ar * ar + ag * ag) + ab * ab;
+}
+
 // One tap q of centre p (both inside the frame; the centre is valid).  h = k[dx+2] * k[dy+2]; inv_sc2_level = inv_sc2 * 4^level.
 // An invalid q adds nothing.
 GSP_HD void denoise_tap(const DenoiseConsts& k, float inv_sc2_level, float h, const dn4& Ep, const dn4& Ap, const dn4& Gp, const dn4& Eq,
                         const dn4& Aq, const dn4& Gq, DenoiseAcc& acc) {
   if (Aq.w == 0.0f) return;
-  const float nx = Gp.x - Gq.x, ny = Gp.y - Gq.y, nz = Gp.z - Gq.z;
-  const float dn = (nx * nx + ny * ny) + nz * nz;
-  const float rz = Gp.w == Gq.w ? 0.0f : (Gp.w - Gq.w) / (Gp.w + Gq.w);
-  const float ar = Ap.x - Aq.x, ag = Ap.y - Aq.y, ab = Ap.z - Aq.z;
-  const float da = (ar * ar + ag * ag) + ab * ab;
+  const float dn = denoise_dn(Gp, Gq);
+  const float rz = denoise_rz(Gp, Gq);
+  const float da = denoise_da(Ap, Aq);
   const float rl = (Ep.w - Eq.w) / ((Ep.w + Eq.w) + 1e-3f);
   const float x = ((dn * k.inv_sn2 + rz * rz * k.inv_sz2) + da * k.inv_sa2) + (rl * rl) * inv_sc2_level;
   const float w = h * det_expf(-x);

@@ -161,6 +161,12 @@ struct gsp_context {
   bool tp_valid = false, tp_done = false;
   uint32_t tp_width = 0, tp_height = 0;
   gsp_camera tp_camera{};
+  // variance-guided filter (gsp_temporal_track_moments, gsp_*_temporal_svgf*): while tp_moments, every history set has a moments
+  // plane M beside it (made by the first accumulate with tracking on); sv_v = the two ping-pong variance planes of the filter, 4
+  // bytes per pixel each, made by its first call
+  bool tp_moments = false;
+  DevBuf<q4> tp_m[2];
+  DevBuf<float> sv_v[2];
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;

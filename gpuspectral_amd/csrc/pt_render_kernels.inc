@@ -1253,6 +1253,134 @@ __global__ __launch_bounds__(kBlock) void k_temporal_reproject(const v4f* __rest
   Iout[p] = o.I;
 }
 
+// ---- variance-guided filter (pt_svgf.h; include/gpuspectral_pt.h "Variance-guided filter") ----------------------------------
+// k_temporal_reproject with the moments plane M beside H: a kernel of its own, so that a context which does not track moments
+// runs the instruction stream it ran before.  Four more 16-byte loads per lane in flight and one more 16-byte store.
+__global__ __launch_bounds__(kBlock) void k_temporal_reproject_moments(const v4f* __restrict__ accum, const v4f* __restrict__ albedo,
+                                                                       const v4f* __restrict__ geom, const v4u* __restrict__ ids,
+                                                                       const v4f* __restrict__ Hprev, const v4f* __restrict__ Gprev,
+                                                                       const uint32_t* __restrict__ Iprev, const v4f* __restrict__ Mprev,
+                                                                       v4f* __restrict__ Hout, v4f* __restrict__ Gout, uint32_t* __restrict__ Iout,
+                                                                       v4f* __restrict__ Mout, TemporalConsts k) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  const int width = (int)k.cur.width;
+  if (px >= width || py >= (int)k.cur.height) return;
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  const TemporalMomentsOut o = temporal_pixel_moments(k, px, py, dn_load(accum + p), dn_load(albedo + p), dn_load(geom + p), ids[p].z,
+                                                      [&](int x, int y, dn4& H_, dn4& G_, uint32_t& I_, dn4& M_) {
+                                                        const size_t q = (size_t)y * (size_t)width + (size_t)x;  // a pixel of the frame
+                                                        H_ = dn_load(Hprev + q);
+                                                        G_ = dn_load(Gprev + q);
+                                                        I_ = Iprev[q];
+                                                        M_ = dn_load(Mprev + q);
+                                                      });
+  dn_store(Hout + p, o.t.H);
+  dn_store(Gout + p, o.t.G);
+  Iout[p] = o.t.I;
+  dn_store(Mout + p, o.M);
+}
+
+// The initial variance.  A block owns a tile of 32 x 8 pixels and stages tile + halo of 3 -- 38 x 14 records -- in LDS by
+// row-major 16-byte loads of E, A and G: G as it is and of E and A the two floats the pass reads, {L, valid}; 12 768 bytes per
+// block.  H.len and M are read at the centre only.  Only a pixel whose history is too short walks the 49 taps.  Out-of-frame
+// records are zero and never read (svgf_variance_pixel skips the tap first).
+__global__ __launch_bounds__(kBlock) void k_svgf_variance(const v4f* __restrict__ E, const v4f* __restrict__ A, const v4f* __restrict__ G,
+                                                          const v4f* __restrict__ H, const v4f* __restrict__ M, float* __restrict__ V, SvgfConsts k,
+                                                          int width, int height) {
+  constexpr int R = kSvgfVarianceRadius, PW = kDnTileW + 2 * R, PH = kDnTileH + 2 * R;
+  __shared__ v4f sG[PW * PH];
+  __shared__ float2 sLV[PW * PH];
+  const int x0 = (int)blockIdx.x * kDnTileW - R, y0 = (int)blockIdx.y * kDnTileH - R;
+  for (int i = (int)threadIdx.x; i < PW * PH; i += kBlock) {
+    const int ly = i / PW, lx = i - ly * PW;
+    const int gx = x0 + lx, gy = y0 + ly;
+    v4f g = {0.0f, 0.0f, 0.0f, 0.0f};
+    float2 lv = {0.0f, 0.0f};
+    if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+      const size_t idx = (size_t)gy * (size_t)width + (size_t)gx;
+      g = G[idx];
+      lv.x = E[idx].w;
+      lv.y = A[idx].w;
+    }
+    sG[i] = g;
+    sLV[i] = lv;
+  }
+  __syncthreads();
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  if (px >= width || py >= height) return;  // (no barrier below)
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  V[p] = svgf_variance_pixel(k, width, height, px, py, H[p].w, dn_load(M + p), [&](int x, int y, float& L_, float& valid_, dn4& G_) {
+    const int i = (y - y0) * PW + (x - x0);  // |x - px| <= 3 and |y - py| <= 3: inside the staged rectangle
+    const float2 lv = sLV[i];
+    L_ = lv.x;
+    valid_ = lv.y;
+    G_ = dn_load(&sG[i]);
+  });
+}
+
+// One level, shaped like k_denoise_atrous: S = 1, 2 (levels 0 and 1) stage E, A, G and V -- 52 bytes per record -- of tile + halo
+// of 2 S pixels in LDS, 22 464 bytes (S = 1) and 33 280 bytes (S = 2) per block; the 3 x 3 variance prefilter (step 1) lies
+// inside the halo.  S = 0 (levels >= 2) reads its taps from global memory.  The per-pixel text is svgf_pixel_level either way.
+// LAST: the colour goes through denoise_finish into `out` and V' is not stored.
+template <int S, bool LAST>
+__global__ __launch_bounds__(kBlock) void k_svgf_atrous(const v4f* __restrict__ Ein, const v4f* __restrict__ A, const v4f* __restrict__ G,
+                                                        const float* __restrict__ Vin, const v4f* __restrict__ hist, v4f* __restrict__ out,
+                                                        float* __restrict__ Vout, SvgfConsts k, uint32_t level, int width, int height) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  SvgfLevelOut r;
+  if constexpr (S != 0) {
+    constexpr int PW = kDnTileW + 4 * S, PH = kDnTileH + 4 * S;
+    __shared__ v4f sE[PW * PH], sA[PW * PH], sG[PW * PH];
+    __shared__ float sV[PW * PH];
+    const int x0 = (int)blockIdx.x * kDnTileW - 2 * S, y0 = (int)blockIdx.y * kDnTileH - 2 * S;
+    for (int i = (int)threadIdx.x; i < PW * PH; i += kBlock) {
+      const int ly = i / PW, lx = i - ly * PW;
+      const int gx = x0 + lx, gy = y0 + ly;
+      v4f e = {0.0f, 0.0f, 0.0f, 0.0f}, a = e, g = e;
+      float v = 0.0f;
+      if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+        const size_t idx = (size_t)gy * (size_t)width + (size_t)gx;
+        e = Ein[idx];
+        a = A[idx];
+        g = G[idx];
+        v = Vin[idx];
+      }
+      sE[i] = e;
+      sA[i] = a;
+      sG[i] = g;
+      sV[i] = v;
+    }
+    __syncthreads();
+    if (px >= width || py >= height) return;  // (no barrier below)
+    r = svgf_pixel_level(k, level, width, height, px, py, [&](int x, int y, dn4& E_, dn4& A_, dn4& G_, float& V_) {
+      const int i = (y - y0) * PW + (x - x0);  // |x - px| <= 2 S and |y - py| <= 2 S: inside the staged rectangle
+      E_ = dn_load(&sE[i]);
+      A_ = dn_load(&sA[i]);
+      G_ = dn_load(&sG[i]);
+      V_ = sV[i];
+    });
+  } else {
+    if (px >= width || py >= height) return;
+    r = svgf_pixel_level(k, level, width, height, px, py, [&](int x, int y, dn4& E_, dn4& A_, dn4& G_, float& V_) {
+      const size_t idx = (size_t)y * (size_t)width + (size_t)x;  // svgf_pixel_level asks for pixels of the frame only
+      E_ = dn_load(Ein + idx);
+      A_ = dn_load(A + idx);
+      G_ = dn_load(G + idx);
+      V_ = Vin[idx];
+    });
+  }
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  if constexpr (LAST) {
+    dn_store(out + p, denoise_finish(r.E, dn_load(A + p), dn_load(hist + p)));
+  } else {
+    dn_store(out + p, r.E);
+    Vout[p] = r.V;
+  }
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

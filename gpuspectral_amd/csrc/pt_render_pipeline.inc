@@ -1436,6 +1436,18 @@ hipError_t gsp::temporal_run(hipStream_t stream, const void* accum, const void* 
   return hipGetLastError();
 }
 
+// ... with the moments plane beside the history (k_temporal_reproject_moments; pt_svgf.h)
+static hipError_t temporal_moments_run(hipStream_t stream, const void* accum, const void* albedo, const void* geom, const void* ids, const void* h_prev,
+                                       const void* g_prev, const void* i_prev, const void* m_prev, void* h_out, void* g_out, void* i_out, void* m_out,
+                                       const TemporalConsts& k) {
+  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
+  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
+  hipLaunchKernelGGL(k_temporal_reproject_moments, grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids,
+                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (const v4f*)m_prev, (v4f*)h_out, (v4f*)g_out, (uint32_t*)i_out,
+                     (v4f*)m_out, k);
+  return hipGetLastError();
+}
+
 // what every temporal read-out asks first
 static int temporal_have_history(gsp_context* ctx, const char* who, const void* out_ptr) {
   if (!out_ptr) {
@@ -1513,10 +1525,16 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
     CTX_TRY(ctx, ctx->tp_h[s].ensure(n, &ctx->bytes));
     CTX_TRY(ctx, ctx->tp_g[s].ensure(n, &ctx->bytes));
     CTX_TRY(ctx, ctx->tp_i[s].ensure(n, &ctx->bytes));
+    if (ctx->tp_moments) CTX_TRY(ctx, ctx->tp_m[s].ensure(n, &ctx->bytes));
   }
   const int from = ctx->tp_cur, to = from ^ 1;
-  CTX_TRY(ctx, temporal_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p, ctx->tp_g[from].p,
-                            ctx->tp_i[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p, k));
+  if (ctx->tp_moments)
+    CTX_TRY(ctx, temporal_moments_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
+                                      ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p,
+                                      ctx->tp_m[to].p, k));
+  else
+    CTX_TRY(ctx, temporal_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p, ctx->tp_g[from].p,
+                              ctx->tp_i[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p, k));
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (complete when the call returns: a camera or scene edit may follow at once)
   ctx->tp_cur = to;
   ctx->tp_camera = ctx->camera;
@@ -1583,6 +1601,135 @@ int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* 
     }
   }
   int rc = temporal_denoise_ctx(ctx, denoise, "gsp_download_temporal_denoised_display", out);
+  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
+}
+
+}  // extern "C"
+
+// ---- variance-guided filter (include/gpuspectral_pt.h, "Variance-guided filter"; per-pixel code: pt_svgf.h) ----
+// The filter of the history `hist` with moments `moments` on a full frame: k_denoise_prepare, k_svgf_variance and k.iterations
+// launches of k_svgf_atrous on `stream`; does not synchronise.  e0, e1, a, out: 16 bytes per pixel; v0, v1: 4 bytes per pixel.
+static hipError_t svgf_run(hipStream_t stream, uint32_t num_cus, const void* hist, const void* moments, const void* albedo, const void* geom, uint32_t width,
+                           uint32_t height, const SvgfConsts& k, void* e0, void* e1, void* a, void* v0, void* v1, void* out) {
+  const uint64_t n = (uint64_t)width * height;
+  if (n == 0) return hipSuccess;
+  const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 8));
+  hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)hist, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH), block(kBlock);
+  hipLaunchKernelGGL(k_svgf_variance, grid, block, 0, stream, (const v4f*)e0, (const v4f*)a, (const v4f*)geom, (const v4f*)hist, (const v4f*)moments,
+                     (float*)v0, k, (int)width, (int)height);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  v4f* E[2] = {(v4f*)e0, (v4f*)e1};
+  float* V[2] = {(float*)v0, (float*)v1};
+  for (uint32_t i = 0; i < k.iterations; ++i) {
+    const bool last = i + 1 == k.iterations;
+    v4f* dst = last ? (v4f*)out : E[(i + 1u) & 1u];
+#define GSP_SVGF_LAUNCH(S, LAST)                                                                                                                    \
+  hipLaunchKernelGGL((k_svgf_atrous<S, LAST>), grid, block, 0, stream, (const v4f*)E[i & 1u], (const v4f*)a, (const v4f*)geom, (const float*)V[i & 1u], \
+                     (const v4f*)hist, dst, V[(i + 1u) & 1u], k, i, (int)width, (int)height)
+    // as denoise_run: levels 0 and 1 stage tile + halo in LDS, the wider steps read their taps from global memory
+    if (i == 0) {
+      if (last) GSP_SVGF_LAUNCH(1, true);
+      else GSP_SVGF_LAUNCH(1, false);
+    } else if (i == 1) {
+      if (last) GSP_SVGF_LAUNCH(2, true);
+      else GSP_SVGF_LAUNCH(2, false);
+    } else {
+      if (last) GSP_SVGF_LAUNCH(0, true);
+      else GSP_SVGF_LAUNCH(0, false);
+    }
+#undef GSP_SVGF_LAUNCH
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// Validates and queues the filter into `dst` (device, 16-byte aligned; nullptr = the context's own buffer) on ctx->stream
+static int svgf_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const gsp_svgf* svgf_host, const char* who, const void* out_ptr, void* dst) {
+  int rc = temporal_have_history(ctx, who, out_ptr);
+  if (rc != GSP_OK) return rc;
+  if (!ctx->tp_moments) {
+    ctx->err = std::string(who) + " needs gsp_temporal_track_moments(ctx, 1) before the history was accumulated";
+    return GSP_ERR_INVALID;
+  }
+  if (!ctx->have_frame || ctx->subset || !ctx->features_rendered) {
+    ctx->err = std::string(who) + " needs a full frame (no pixel_ids) and a gsp_render_features call since gsp_frame_begin";
+    return GSP_ERR_INVALID;
+  }
+  SvgfConsts k;
+  if (const char* why = resolve_svgf(denoise_host, svgf_host, k)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
+  for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
+  for (DevBuf<float>& b : ctx->sv_v) CTX_TRY(ctx, b.ensure(n, &ctx->bytes));
+  CTX_TRY(ctx, svgf_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->tp_h[ctx->tp_cur].p, ctx->tp_m[ctx->tp_cur].p, ctx->feat_albedo.p, ctx->feat_geom.p,
+                        ctx->width, ctx->height, k, ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, ctx->sv_v[0].p, ctx->sv_v[1].p,
+                        dst ? dst : (void*)ctx->dn_out.p));
+  return GSP_OK;
+}
+
+extern "C" {
+
+int gsp_temporal_track_moments(gsp_context* ctx, int on) {
+  if (!ctx) return GSP_ERR_INVALID;
+  const bool want = on != 0;
+  if (want == ctx->tp_moments) return GSP_OK;
+  ctx->tp_moments = want;
+  ctx->tp_valid = false;  // (moments and history have the same age)
+  return GSP_OK;
+}
+
+int gsp_download_temporal_moments(gsp_context* ctx, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_history(ctx, "gsp_download_temporal_moments", out);
+  if (rc != GSP_OK) return rc;
+  if (!ctx->tp_moments) {
+    ctx->err = "gsp_download_temporal_moments needs gsp_temporal_track_moments(ctx, 1) before the history was accumulated";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  return read_back_bytes(ctx, ctx->tp_m[ctx->tp_cur].p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
+}
+
+int gsp_download_temporal_svgf(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_download_temporal_svgf", out, nullptr);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
+}
+
+int gsp_temporal_svgf_to_device(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (dst && ctx->have_frame && bytes < ctx->num_pixels * sizeof(q4)) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  // the kernels store 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
+  const bool direct = ((uintptr_t)dst & 15u) == 0;
+  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_temporal_svgf_to_device", dst, direct ? dst : nullptr);
+  if (rc != GSP_OK) return rc;
+  if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), hipMemcpyDeviceToDevice, ctx->stream));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+int gsp_download_temporal_svgf_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, const gsp_display* display, uint32_t* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  {  // (an invalid display is refused before anything is queued)
+    gsp_display d;
+    if (const char* why = resolve_display(display, d)) {
+      ctx->err = why;
+      return GSP_ERR_INVALID;
+    }
+  }
+  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_download_temporal_svgf_display", out, nullptr);
   if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
   if (rc != GSP_OK) return rc;
   return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);

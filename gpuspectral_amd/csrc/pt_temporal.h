@@ -125,20 +125,32 @@ GSP_HD TemporalProj temporal_project(const TemporalConsts& k, const TemporalPixe
   return o;
 }
 
+// The test of one tap q inside the previous frame: is it this pixel's history?
+GSP_HD bool temporal_tap_kept(const TemporalParams& k, const TemporalPixel& p, float ze, const dn4& Hq, const dn4& Gq, uint32_t Iq) {
+  if (!(Hq.w > 0.0f) || !temporal_finite3(Hq)) return false;
+  if (Iq != p.inst) return false;  // (a background pixel has inst = 0xffffffff)
+  if (p.surface) {
+    if (gabs(ze - Gq.w) > k.depth_tol * ze) return false;
+    if (dot(p.n, mk3(Gq.x, Gq.y, Gq.z)) < k.normal_min) return false;
+  }
+  return true;
+}
+
 // One tap q inside the previous frame with weight w != 0: tested and, when kept, summed
 GSP_HD void temporal_tap(const TemporalParams& k, const TemporalPixel& p, float ze, float w, const dn4& Hq, const dn4& Gq, uint32_t Iq,
                          TemporalAcc& acc) {
-  if (!(Hq.w > 0.0f) || !temporal_finite3(Hq)) return;
-  if (Iq != p.inst) return;  // (a background pixel has inst = 0xffffffff)
-  if (p.surface) {
-    if (gabs(ze - Gq.w) > k.depth_tol * ze) return;
-    if (dot(p.n, mk3(Gq.x, Gq.y, Gq.z)) < k.normal_min) return;
-  }
+  if (!temporal_tap_kept(k, p, ze, Hq, Gq, Iq)) return;
   acc.sw += w;
   acc.r += w * Hq.x;
   acc.g += w * Hq.y;
   acc.b += w * Hq.z;
   acc.sl += w * Hq.w;
+}
+
+// The blend weight of a finite new frame on a history of length len: N = min(len + 1, max_history), a = max(alpha, 1 / N)
+GSP_HD float temporal_blend_weight(const TemporalParams& k, float len, float& N) {
+  N = gmin(len + 1.0f, k.max_history);
+  return gmax(k.alpha, 1.0f / N);
 }
 
 // history = history_valid and sw >= 0.01f
@@ -161,8 +173,8 @@ GSP_HD dn4 temporal_blend(const TemporalParams& k, bool history, const TemporalA
     o.w = gmin(len, k.max_history);
     return o;
   }
-  const float N = gmin(len + 1.0f, k.max_history);
-  const float a = gmax(k.alpha, 1.0f / N);
+  float N;
+  const float a = temporal_blend_weight(k, len, N);
   o.x = pr + (c.x - pr) * a;
   o.y = pg + (c.y - pg) * a;
   o.z = pb + (c.z - pb) * a;

@@ -94,6 +94,9 @@ def load():
     L.gsph_pathtracer_temporal_reset.argtypes = [vp]
     L.gsph_pathtracer_download_temporal.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_download_temporal_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp, u64]
+    L.gsph_pathtracer_temporal_track_moments.argtypes = [vp, C.c_int]
+    L.gsph_pathtracer_download_temporal_moments.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_download_temporal_svgf.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp, u64]
     _LIB = L
     return L
 
@@ -375,6 +378,24 @@ class PathTracer:
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._check(self._L.gsph_pathtracer_download_temporal_denoised(self._h, C.byref(denoise) if denoise is not None else None, out.ctypes.data,
                                                                        out.size), "downloadTemporalDenoised")
+        return out
+
+    def temporal_track_moments(self, on=True):
+        """PathTracer::temporalTrackMoments: the history keeps its luminance moments (a change drops the history)."""
+        self._check(self._L.gsph_pathtracer_temporal_track_moments(self._h, 1 if on else 0), "temporalTrackMoments")
+
+    def download_temporal_moments(self):
+        """PathTracer::downloadTemporalMoments: (h, w, 4) float32 {m1, m2, r, 0}."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_temporal_moments(self._h, out.ctypes.data, out.size), "downloadTemporalMoments")
+        return out
+
+    def download_temporal_svgf(self, denoise=None, svgf=None):
+        """PathTracer::downloadTemporalSvgf (abi.Denoise, abi.Svgf; None = every default): (h, w, 4) float32."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_temporal_svgf(self._h, C.byref(denoise) if denoise is not None else None,
+                                                                   C.byref(svgf) if svgf is not None else None, out.ctypes.data, out.size),
+                    "downloadTemporalSvgf")
         return out
 
     def stats(self):

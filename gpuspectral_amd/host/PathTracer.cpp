@@ -303,6 +303,20 @@ std::vector<float> PathTracer::downloadTemporalDenoised(const gsp_denoise* denoi
   return out;
 }
 
+void PathTracer::temporalTrackMoments(bool on) { check(gsp_temporal_track_moments(ctx, on ? 1 : 0), "gsp_temporal_track_moments"); }
+
+std::vector<float> PathTracer::downloadTemporalMoments() {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_temporal_moments(ctx, out.data()), "gsp_download_temporal_moments");
+  return out;
+}
+
+std::vector<float> PathTracer::downloadTemporalSvgf(const gsp_denoise* denoise, const gsp_svgf* svgf) {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_temporal_svgf(ctx, denoise, svgf, out.data()), "gsp_download_temporal_svgf");
+  return out;
+}
+
 void PathTracer::nextFrame() {
   featureTimestamp = timestamp;  // (the feature samples of the new frame are those of its beauty samples)
   check(gsp_frame_begin(ctx, width, height, pixelIds.empty() ? nullptr : pixelIds.data(), pixelIds.size()), "gsp_frame_begin");

@@ -114,6 +114,13 @@ class PathTracer : public RenderPassCreator {
   void temporalReset();
   std::vector<float> downloadTemporal();
   std::vector<float> downloadTemporalDenoised(const gsp_denoise* denoise = nullptr);
+  // Variance-guided filter (gpuspectral_pt.h "Variance-guided filter"): temporalTrackMoments(true) before the first
+  // temporalAccumulate makes the history keep its luminance moments (a change of the value drops the history);
+  // downloadTemporalMoments is that plane {m1, m2, r, 0}, downloadTemporalSvgf the a-trous filter of the history whose luminance
+  // edge-stop follows the per-pixel variance (RGBA32F, .w = the history length; nullptr = every default).
+  void temporalTrackMoments(bool on);
+  std::vector<float> downloadTemporalMoments();
+  std::vector<float> downloadTemporalSvgf(const gsp_denoise* denoise = nullptr, const gsp_svgf* svgf = nullptr);
   void nextFrame();  // a new frame (accumulate buffer and feature planes cleared) whose samples continue the timestamp sequence
   void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }

@@ -341,6 +341,24 @@ int gsph_pathtracer_download_temporal_denoised(void* pt, const gsp_denoise* deno
     std::memcpy(out, img.data(), img.size() * sizeof(float));
   });
 }
+// variance-guided filter of a PathTracer (gpuspectral_pt.h "Variance-guided filter"); denoise / svgf may be NULL
+int gsph_pathtracer_temporal_track_moments(void* pt, int on) {
+  return guard([&] { ((PathTracer*)pt)->temporalTrackMoments(on != 0); });
+}
+int gsph_pathtracer_download_temporal_moments(void* pt, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTemporalMoments();
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_download_temporal_svgf(void* pt, const gsp_denoise* denoise, const gsp_svgf* svgf, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTemporalSvgf(denoise, svgf);
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {
     std::vector<uint8_t> v;

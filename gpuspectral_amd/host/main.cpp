@@ -27,6 +27,9 @@
 //   accumulation"), the scene's camera turned by DEG degrees about the world y axis through the origin between frames (the
 //   loader keeps no look-at point), every frame accumulated into the history; out.pfm receives the history after the last frame
 //   and, with --denoise, out.dn.pfm its filtered form.  The files of the other flags are those of the LAST frame.  One device.
+//   --svgf out.pfm [--svgf-sigma S] [--svgf-min-history N] (with --temporal): the history keeps its luminance moments and out.pfm
+//   receives its variance-guided filter (gpuspectral_pt.h "Variance-guided filter"; S = sigma_variance, inf = the term off; N =
+//   2..65536), with the levels and guide sigmas of --denoise-iterations / --denoise-sigma where --denoise is given.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -62,6 +65,10 @@ int main(int argc, char** argv) {
   int temporalFrames = 0;  // (0 = not given)
   float temporalOrbit = 0.0f;
   bool temporalOptions = false;
+  std::string svgfPath;
+  gsp_svgf svgf{};
+  svgf.struct_size = (uint32_t)sizeof(gsp_svgf);
+  bool svgfOptions = false;
   gsp_denoise denoise{};
   denoise.struct_size = (uint32_t)sizeof(gsp_denoise);
   bool denoiseOptions = false;
@@ -114,6 +121,23 @@ int main(int argc, char** argv) {
         return 2;
       }
       temporalOptions = true, used = 2;
+    }
+    else if (flag == "--svgf" && argc > 2) svgfPath = argv[2], used = 2;
+    else if (flag == "--svgf-sigma" && argc > 2) {
+      if (std::string(argv[2]) == "inf") svgf.sigma_variance = INFINITY;
+      else if (!parseFloat(argv[2], svgf.sigma_variance) || !(svgf.sigma_variance > 0.0f)) {
+        std::fprintf(stderr, "gsp_render: bad svgf sigma '%s' (expected a value > 0, or inf = the variance term off)\n", argv[2]);
+        return 2;
+      }
+      svgfOptions = true, used = 2;
+    } else if (flag == "--svgf-min-history" && argc > 2) {
+      char* e = nullptr;
+      const long v = std::strtol(argv[2], &e, 10);
+      if (e == argv[2] || *e != 0 || v < 2 || v > 65536) {
+        std::fprintf(stderr, "gsp_render: bad svgf min history '%s' (expected 2..65536)\n", argv[2]);
+        return 2;
+      }
+      svgf.min_history = (uint32_t)v, svgfOptions = true, used = 2;
     }
     else if (flag == "--denoise-iterations" && argc > 2) {
       char* e = nullptr;
@@ -263,8 +287,16 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --temporal needs --temporal-frames N\n");
     return 2;
   }
+  if (svgfPath.empty() && svgfOptions) {
+    std::fprintf(stderr, "gsp_render: --svgf-sigma and --svgf-min-history need --svgf out.pfm\n");
+    return 2;
+  }
+  if (!svgfPath.empty() && temporalPath.empty()) {
+    std::fprintf(stderr, "gsp_render: --svgf needs --temporal out.pfm (it filters the history)\n");
+    return 2;
+  }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -327,7 +359,7 @@ int main(int argc, char** argv) {
     if (!denoisePath.empty() && !ldrPath.empty() && devices.size() > 1)
       throw std::runtime_error("--denoise with --ldr needs a single device (the LDR film of the denoised frame is a single-context call)");
     std::vector<uint32_t> ldr, denoisedLdr;
-    std::vector<float> img, featAlbedo, featGeom, denoised, temporal, temporalDenoised;
+    std::vector<float> img, featAlbedo, featGeom, denoised, temporal, temporalDenoised, temporalSvgf;
     double temporalLength = 0.0;
     const uint32_t fspp = featureSpp > 0 ? (uint32_t)featureSpp : spp;
     gsp_stats st;
@@ -340,6 +372,7 @@ int main(int argc, char** argv) {
       pt.params.adaptive_step = adaptiveStep;
       pt.params.pixel_filter = filter;
       pt.params.pixel_filter_param = filterParam;
+      if (!svgfPath.empty()) pt.temporalTrackMoments(true);  // (before the first accumulate: moments and history of one age)
       // temporal accumulation: the frames before the last one, each rendered, given a feature pass and accumulated, then the
       // camera turned about the world y axis; the last frame is the ordinary frame below
       for (int f = 0; f + 1 < temporalFrames; ++f) {
@@ -379,6 +412,7 @@ int main(int argc, char** argv) {
         pt.temporalAccumulate();
         temporal = pt.downloadTemporal();
         if (!denoisePath.empty()) temporalDenoised = pt.downloadTemporalDenoised(&denoise);
+        if (!svgfPath.empty()) temporalSvgf = pt.downloadTemporalSvgf(&denoise, &svgf);
         for (size_t i = 3; i < temporal.size(); i += 4) temporalLength += temporal[i];
         temporalLength /= (double)width * height;
       }
@@ -449,6 +483,13 @@ int main(int argc, char** argv) {
       }
       std::printf("temporal: %d frame%s of %u spp, %g degrees per frame, mean history length %.2f -> %s%s%s\n", temporalFrames, temporalFrames == 1 ? "" : "s",
                   spp, (double)temporalOrbit, temporalLength, temporalPath.c_str(), dn.empty() ? "" : ", ", dn.c_str());
+      if (!svgfPath.empty()) {
+        writePfm(svgfPath, temporalSvgf.data(), width, height);
+        if (std::isinf(svgf.sigma_variance)) std::printf("svgf: %u levels, the variance term off -> %s\n", denoise.iterations ? denoise.iterations : 5u, svgfPath.c_str());
+        else
+          std::printf("svgf: %u levels, sigma_variance %g, min history %u -> %s\n", denoise.iterations ? denoise.iterations : 5u,
+                      svgf.sigma_variance != 0.0f ? (double)svgf.sigma_variance : 4.0, svgf.min_history ? svgf.min_history : 4u, svgfPath.c_str());
+      }
     }
     std::printf("%llu triangles, %ux%u x %u spp in %.3f s: %.1f Mrays/s, %.2f Msamples/s (BVH build %.1f ms)\n",
                 (unsigned long long)st.num_triangles, width, height, spp, s,

@@ -55,6 +55,11 @@ EXPORTS = (
     "gsp_temporal_to_device",
     "gsp_download_temporal_denoised",
     "gsp_download_temporal_denoised_display",
+    "gsp_temporal_track_moments",
+    "gsp_download_temporal_moments",
+    "gsp_download_temporal_svgf",
+    "gsp_temporal_svgf_to_device",
+    "gsp_download_temporal_svgf_display",
     "gsp_frame_sample_base",
     "gsp_get_stats",
     "gsp_reset_stats",
@@ -158,6 +163,11 @@ def load():
     L.gsp_temporal_to_device.argtypes = [vp, vp, u64]
     L.gsp_download_temporal_denoised.argtypes = [vp, C.POINTER(abi.Denoise), vp]
     L.gsp_download_temporal_denoised_display.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Display), vp]
+    L.gsp_temporal_track_moments.argtypes = [vp, C.c_int]
+    L.gsp_download_temporal_moments.argtypes = [vp, vp]
+    L.gsp_download_temporal_svgf.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp]
+    L.gsp_temporal_svgf_to_device.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp, u64]
+    L.gsp_download_temporal_svgf_display.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.POINTER(abi.Display), vp]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -208,7 +218,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -472,6 +482,38 @@ class Context:
         self._check(self._L.gsp_download_temporal_denoised_display(self._h, C.byref(denoise) if denoise is not None else None,
                                                                    C.byref(display) if display is not None else None, out.ctypes.data),
                     "gsp_download_temporal_denoised_display")
+        return out
+
+    # ---- variance-guided filter (gpuspectral_pt.h "Variance-guided filter"); svgf: an abi.Svgf, None = every default ----
+    def temporal_track_moments(self, on=True):
+        """gsp_temporal_track_moments: temporal_accumulate also keeps the luminance moments; a change drops the history."""
+        self._check(self._L.gsp_temporal_track_moments(self._h, 1 if on else 0), "gsp_temporal_track_moments")
+
+    def download_temporal_moments(self):
+        """gsp_download_temporal_moments: the newest M = {m1, m2, r, 0}, (height, width, 4) float32."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_temporal_moments(self._h, out.ctypes.data), "gsp_download_temporal_moments")
+        return out
+
+    def download_temporal_svgf(self, denoise=None, svgf=None):
+        """gsp_download_temporal_svgf: the variance-guided a-trous filter of the history; .w = the history length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_temporal_svgf(self._h, C.byref(denoise) if denoise is not None else None,
+                                                       C.byref(svgf) if svgf is not None else None, out.ctypes.data), "gsp_download_temporal_svgf")
+        return out
+
+    def temporal_svgf_to_device(self, device_ptr, nbytes, denoise=None, svgf=None):
+        """gsp_temporal_svgf_to_device: the same frame into device memory (e.g. a torch tensor's data_ptr()), width*height*16 bytes."""
+        self._check(self._L.gsp_temporal_svgf_to_device(self._h, C.byref(denoise) if denoise is not None else None,
+                                                        C.byref(svgf) if svgf is not None else None, device_ptr, nbytes), "gsp_temporal_svgf_to_device")
+
+    def download_temporal_svgf_display(self, denoise=None, svgf=None, display=None):
+        """gsp_download_temporal_svgf_display: the LDR film of the variance-guided filter, (height, width) uint32 RGBA8 words."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsp_download_temporal_svgf_display(self._h, C.byref(denoise) if denoise is not None else None,
+                                                               C.byref(svgf) if svgf is not None else None,
+                                                               C.byref(display) if display is not None else None, out.ctypes.data),
+                    "gsp_download_temporal_svgf_display")
         return out
 
     def pixel_stats(self):

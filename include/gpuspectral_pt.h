@@ -73,7 +73,9 @@ extern "C" {
                                 gsp_download_denoised, gsp_denoise_to_device, gsp_download_denoised_display,
                                 gsp_multi_download_denoised (see "Denoiser"); gsp_temporal_accumulate, gsp_temporal_reset,
                                 gsp_download_temporal, gsp_temporal_to_device, gsp_download_temporal_denoised,
-                                gsp_download_temporal_denoised_display, gsp_frame_sample_base (see "Temporal accumulation") */
+                                gsp_download_temporal_denoised_display, gsp_frame_sample_base (see "Temporal accumulation");
+                                gsp_temporal_track_moments, gsp_download_temporal_moments, gsp_download_temporal_svgf,
+                                gsp_temporal_svgf_to_device, gsp_download_temporal_svgf_display (see "Variance-guided filter") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -864,6 +866,75 @@ int gsp_temporal_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
 int gsp_download_temporal_denoised(gsp_context* ctx, const gsp_denoise* denoise, float* out_rgba);
 /* ... and the LDR film of that (as gsp_download_denoised_display): width*height RGBA8 words. */
 int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out_rgba8);
+
+/*
+ * Variance-guided filter: luminance moments beside the history, and the a-trous filter with SVGF's variance-scaled edge-stop.
+ *
+ * The "Denoiser" tolerates a fixed relative luminance difference, whatever the pixel's noise.  This section adds the part that
+ * gives SVGF its name: the temporal pass keeps the first and second luminance moments of the history, they become a per-pixel
+ * variance (a spatial estimate where the history is too short), and the luminance edge-stop of every level is scaled by the local
+ * standard deviation, with the variance carried through the levels.  No reference code defines it, so this header does, down to
+ * the order of the float32 operations.  Arithmetic is float32 in the order written (no contraction); exp is the library's
+ * deterministic exp (0 below -87.34); sqrt and / are correctly rounded; max(x, 0) is x > 0 ? x : 0, so a NaN gives 0.
+ *
+ * 1. Moments.  gsp_temporal_track_moments(ctx, on) is context state, off by default.  A CHANGE of the value clears history_valid,
+ * so moments and history always have the same age; a call with the current value does nothing.  While it is on,
+ * gsp_temporal_accumulate also keeps two ping-pong planes M = {m1, m2, r, 0} (16 bytes per pixel each, allocated by the first
+ * accumulate with tracking on: 104 bytes per pixel of temporal state in all), and H, G and I are, bit for bit, what the call
+ * produces with tracking off.  Per pixel, with l = L of "Denoiser: Prepare" applied to this frame's c and albedo record:
+ *     over the kept taps of H, in tap order, with the same weights w:   sm.k += w * M_q.k   (k = m1, m2, r)
+ *     with history:      prev.k = sm.k / sw
+ *         c finite:      a = the blend weight of H;   m1' = prev.m1 + (l - prev.m1) * a;   m2' = prev.m2 + (l*l - prev.m2) * a;
+ *                        r' = ((1 - a) * (1 - a)) * prev.r + a * a
+ *         c not finite:  M' = prev
+ *     without history:   M' = {l, l*l, 1, 0} when c is finite, {0, 0, 1, 0} when not
+ * r is the sum of the squared frame weights inside the history: 1 / N for a running mean of N frames.  It is exact for an unmoved
+ * camera; under reprojection it is mixed bilinearly like everything else, which makes it an approximation (the frames of four
+ * neighbours are not the same frames).  Luminances whose square overflows float32 are outside the filter's domain.
+ *
+ * 2. The filter of the history.  gsp_denoise supplies iterations, sigma_normal, sigma_depth and sigma_albedo; sigma_color is
+ * validated as always and not used: the variance term replaces it.
+ * Prepare: "Denoiser: Prepare" with H as c.  It yields e, L, a', valid; n and z are this frame's geom plane.
+ * Initial variance V of a valid pixel p (an invalid pixel has V = 0 and is nobody's neighbour):
+ *     H.len >= min_history && M.r < 1:    V = max(M.m2 - M.m1 * M.m1, 0) * (M.r / (1 - M.r))
+ *         (the unbiased variance of the blended history; s^2 / (N - 1) for a running mean)
+ *     otherwise, over q = p + (dx, dy), dy = -3..3 in the outer loop, dx = -3..3 in the inner loop, taps outside the frame or not
+ *     valid skipped, with dn and rz as in the "Denoiser":
+ *         g = exp(-(dn * inv_sn2 + rz*rz * inv_sz2));   sg += g;   s1 += g * L_q;   s2 += g * (L_q * L_q)
+ *         m = s1 / sg;   V = max(s2 / sg - m * m, 0)
+ * Level i = 0 .. iterations-1, step s = 2^i, for a valid centre p (a pixel that is not valid keeps its e and its V):
+ *     Vg: over q = p + (dx, dy), dy = -1..1 outer, dx = -1..1 inner (step 1 at every level), in-frame valid taps only, with
+ *         t = {0.25, 0.5, 0.25}[dx+1] * {0.25, 0.5, 0.25}[dy+1]:   st += t;   sv += t * V_q;   Vg = sv / st
+ *     inv_l = 1 / (sigma_variance * sqrt(Vg) + 1e-4f), once per centre; 0 (and Vg not formed) when sigma_variance is +Inf
+ *     per tap q = p + s * (dx, dy) in the "Denoiser"'s order, with its h, dn, rz, da and its skips:
+ *         x = ((dn * inv_sn2 + rz*rz * inv_sz2) + da * inv_sa2) + |L_p - L_q| * inv_l
+ *         w = h * exp(-x);   sum_w += w;   sum_k += w * e_q.k;   sum_v += (w * w) * V_q
+ *     e'.k = sum_k / sum_w, L' recomputed from e';   V' = sum_v / (sum_w * sum_w).  There is no 4^i factor.
+ * Output: as the "Denoiser"'s (out.k = e_final.k * A_k; an invalid pixel leaves as H's record, bit for bit); out.w = H.len.
+ *
+ * Defaults (a field left 0): min_history 4, sigma_variance 4.  Scratch: the denoiser's four planes and two V planes of 4 bytes
+ * per pixel, allocated by the first call.  The calls change no state of the frame or of the history.  GSP_ERR_INVALID: what
+ * gsp_download_temporal_denoised refuses; tracking off; min_history 1 or above 65536; a negative or NaN sigma_variance.
+ *
+ * Out of scope.  The filtered frame is not fed back into the history; moved instances have no motion vectors (see "Temporal
+ * accumulation"); there are no gsp_multi_* variants.
+ */
+typedef struct gsp_svgf {
+  uint32_t struct_size; /* sizeof(gsp_svgf) of the host's header; same rule as gsp_denoise (NULL and struct_size 0 = every default) */
+  uint32_t min_history; /* shortest history whose moments are trusted; 0 = 4; otherwise 2..65536 */
+  float sigma_variance; /* luminance tolerance in standard deviations; 0 = 4.0; +Inf = the term off */
+} gsp_svgf;
+/* on != 0: gsp_temporal_accumulate keeps M.  Never fails on a context; frees nothing. */
+int gsp_temporal_track_moments(gsp_context* ctx, int on);
+/* M of the newest set: width*height*4 floats.  GSP_ERR_INVALID when tracking is off or there is no valid history. */
+int gsp_download_temporal_moments(gsp_context* ctx, float* out_rgba);
+/* The variance-guided filter of H: full frame like gsp_download_temporal_denoised. */
+int gsp_download_temporal_svgf(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, float* out_rgba);
+/* The same frame into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
+int gsp_temporal_svgf_to_device(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, void* device_dst, uint64_t bytes);
+/* ... and the LDR film of it (as gsp_download_denoised_display): width*height RGBA8 words. */
+int gsp_download_temporal_svgf_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, const gsp_display* display,
+                                       uint32_t* out_rgba8);
 
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
