@@ -10,6 +10,7 @@
 #include "pt_denoise.h"
 #include "pt_display.h"
 #include "pt_stages.h"
+#include "pt_motion.h"
 #include "pt_svgf.h"
 #include "pt_temporal.h"
 

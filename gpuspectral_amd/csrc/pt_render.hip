@@ -167,6 +167,17 @@ struct gsp_context {
   bool tp_moments = false;
   DevBuf<q4> tp_m[2];
   DevBuf<float> sv_v[2];
+  // moved instances (gsp_temporal_follow_instances): while tp_follow, an accumulate records the instances' transforms beside the
+  // camera (tp_xforms: 16 floats each; empty = none recorded), forms the per-instance records of pt_motion.h in the pinned h_motion
+  // (h_motion_cap records), copies them to tp_table and writes the motion plane tp_v.  All made by the first followed accumulate.
+  // inst_edits counts the gsp_update_instances calls that changed something; feat_inst_edits = its value at the frame's first
+  // gsp_render_features
+  bool tp_follow = false;
+  std::vector<float> tp_xforms;
+  uint64_t inst_edits = 0, feat_inst_edits = 0;
+  DevBuf<q4> tp_table, tp_v;
+  MotionRecord* h_motion = nullptr;
+  size_t h_motion_cap = 0;
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;
@@ -525,6 +536,7 @@ void gsp_ctx_destroy(gsp_context* ctx) {
     if (ctx->stage_ev[k]) (void)hipEventDestroy(ctx->stage_ev[k]);
   }
   if (ctx->h_display_rec) (void)hipHostFree(ctx->h_display_rec);
+  if (ctx->h_motion) (void)hipHostFree(ctx->h_motion);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

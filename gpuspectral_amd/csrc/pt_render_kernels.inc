@@ -1281,6 +1281,54 @@ __global__ __launch_bounds__(kBlock) void k_temporal_reproject_moments(const v4f
   dn_store(Mout + p, o.M);
 }
 
+// ---- moved instances (pt_motion.h; include/gpuspectral_pt.h "Temporal accumulation: moved instances") -------------------------
+// k_temporal_reproject / k_temporal_reproject_moments with the per-instance records: kernels of their own, so that a context which
+// does not follow instances runs the instruction streams it ran before.  The same 32 x 8 tile.  The chain ids -> record ->
+// projection -> taps is three dependent loads deep, so the ids word is asked for first and the six record quads (96 bytes, the
+// same few cache lines for every lane of an instance) go out before c, albedo and geom are waited for; the taps are in flight
+// together as in the kernels above.  The table is read from global memory: a tile sees a handful of instances, their records stay
+// in the vector cache, and a copy to LDS would put a block-wide barrier in front of the first tap (not measured).  A wave none
+// of whose lanes is of class 1 skips the record arithmetic (one ballot).  One more 16-byte store per lane: V.
+template <bool MOMENTS>
+__global__ __launch_bounds__(kBlock) void k_temporal_reproject_follow(const v4f* __restrict__ accum, const v4f* __restrict__ albedo,
+                                                                      const v4f* __restrict__ geom, const v4u* __restrict__ ids,
+                                                                      const v4f* __restrict__ Hprev, const v4f* __restrict__ Gprev,
+                                                                      const uint32_t* __restrict__ Iprev, const v4f* __restrict__ Mprev,
+                                                                      const v4f* __restrict__ table, uint32_t num_records, v4f* __restrict__ Hout,
+                                                                      v4f* __restrict__ Gout, uint32_t* __restrict__ Iout, v4f* __restrict__ Mout,
+                                                                      v4f* __restrict__ Vout, TemporalConsts k) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  const int width = (int)k.cur.width;
+  if (px >= width || py >= (int)k.cur.height) return;
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  const uint32_t inst = ids[p].z;
+  const dn4 c = dn_load(accum + p), alb = dn_load(albedo + p), g = dn_load(geom + p);  // (in flight behind ids; consumed after the record)
+  MotionRecord rec = motion_record_of_class(kMotionNoHistory);  // an index the table does not have (the background's among them)
+  if (inst < num_records) {
+    const v4f* r = table + (size_t)inst * kMotionRecordQuads;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      rec.b[i] = dn_load(r + i);
+      rec.n[i] = dn_load(r + 3 + i);
+    }
+  }
+  const bool wave_moved = __ballot(motion_class(rec) == kMotionMoved) != 0;
+  const MotionOut o = temporal_pixel_follow<MOMENTS>(k, px, py, c, alb, g, inst, rec, wave_moved,
+                                                     [&](int x, int y, dn4& H_, dn4& G_, uint32_t& I_, dn4& M_) {
+                                                       const size_t q = (size_t)y * (size_t)width + (size_t)x;  // a pixel of the frame
+                                                       H_ = dn_load(Hprev + q);
+                                                       G_ = dn_load(Gprev + q);
+                                                       I_ = Iprev[q];
+                                                       if constexpr (MOMENTS) M_ = dn_load(Mprev + q);
+                                                     });
+  dn_store(Hout + p, o.t.H);
+  dn_store(Gout + p, o.t.G);
+  Iout[p] = o.t.I;
+  if constexpr (MOMENTS) dn_store(Mout + p, o.M);
+  dn_store(Vout + p, o.V);
+}
+
 // The initial variance.  A block owns a tile of 32 x 8 pixels and stages tile + halo of 3 -- 38 x 14 records -- in LDS by
 // row-major 16-byte loads of E, A and G: G as it is and of E and A the two floats the pass reads, {L, valid}; 12 768 bytes per
 // block.  H.len and M are read at the centre only.  Only a pixel whose history is too short walks the 49 taps.  Out-of-frame

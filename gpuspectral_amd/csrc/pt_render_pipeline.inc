@@ -996,6 +996,7 @@ int gsp_render_features(gsp_context* ctx, const gsp_render_params* rp_host) {
     int rc_ = ensure_features(ctx);
     if (rc_ != GSP_OK) return rc_;
   }
+  if (!ctx->features_rendered) ctx->feat_inst_edits = ctx->inst_edits;  // (the frame's first call: whose transforms its planes show)
   if (ctx->num_pixels == 0) {
     ctx->features_rendered = true;
     return GSP_OK;
@@ -1448,6 +1449,22 @@ static hipError_t temporal_moments_run(hipStream_t stream, const void* accum, co
   return hipGetLastError();
 }
 
+// ... with the moved instances followed (k_temporal_reproject_follow; pt_motion.h): m_prev / m_out may be nullptr when !moments
+static hipError_t temporal_follow_run(hipStream_t stream, bool moments, const void* accum, const void* albedo, const void* geom, const void* ids,
+                                      const void* h_prev, const void* g_prev, const void* i_prev, const void* m_prev, const void* table, uint32_t num_records,
+                                      void* h_out, void* g_out, void* i_out, void* m_out, void* v_out, const TemporalConsts& k) {
+  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
+  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
+#define GSP_FOLLOW_LAUNCH(M)                                                                                                                       \
+  hipLaunchKernelGGL((k_temporal_reproject_follow<M>), grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids, \
+                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (const v4f*)m_prev, (const v4f*)table, num_records, (v4f*)h_out,     \
+                     (v4f*)g_out, (uint32_t*)i_out, (v4f*)m_out, (v4f*)v_out, k)
+  if (moments) GSP_FOLLOW_LAUNCH(true);
+  else GSP_FOLLOW_LAUNCH(false);
+#undef GSP_FOLLOW_LAUNCH
+  return hipGetLastError();
+}
+
 // what every temporal read-out asks first
 static int temporal_have_history(gsp_context* ctx, const char* who, const void* out_ptr) {
   if (!out_ptr) {
@@ -1504,6 +1521,11 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
     ctx->err = std::string(who) + ": the frame has been accumulated already (one call per gsp_frame_begin)";
     return GSP_ERR_INVALID;
   }
+  if (ctx->tp_follow && ctx->inst_edits != ctx->feat_inst_edits) {
+    ctx->err = std::string(who) + ": gsp_update_instances has changed the instances since the frame's gsp_render_features; with "
+               "gsp_temporal_follow_instances on, an edit belongs before the frame's gsp_render_features";
+    return GSP_ERR_INVALID;
+  }
   TemporalParams tp;
   if (const char* why = resolve_temporal(temporal, tp)) {
     ctx->err = why;
@@ -1528,7 +1550,34 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
     if (ctx->tp_moments) CTX_TRY(ctx, ctx->tp_m[s].ensure(n, &ctx->bytes));
   }
   const int from = ctx->tp_cur, to = from ^ 1;
-  if (ctx->tp_moments)
+  std::vector<float> cur;  // (following: the instances' transforms of this frame)
+  if (ctx->tp_follow) {
+    // the records of the instances between the history's frame and this one: formed in the pinned buffer, copied on the stream
+    // in front of the launch.  Without a history (or without a snapshot of its transforms) the table is not read.
+    const uint32_t ni = (uint32_t)ctx->h_inst.size();
+    const bool have_prev = ctx->tp_valid && ctx->tp_xforms.size() == 16ull * ni;
+    if (!have_prev) k.history_valid = 0;
+    cur.resize(16ull * ni);
+    for (uint32_t i = 0; i < ni; ++i) std::memcpy(&cur[16ull * i], ctx->h_inst[i].transform, 16 * sizeof(float));
+    CTX_TRY(ctx, ctx->tp_v.ensure(n, &ctx->bytes));
+    CTX_TRY(ctx, ctx->tp_table.ensure((size_t)std::max<uint32_t>(ni, 1) * kMotionRecordQuads, &ctx->bytes));
+    if (ctx->h_motion_cap < std::max<uint32_t>(ni, 1)) {
+      if (ctx->h_motion) (void)hipHostFree(ctx->h_motion);
+      ctx->h_motion = nullptr;
+      ctx->h_motion_cap = 0;
+      CTX_TRY(ctx, hipHostMalloc((void**)&ctx->h_motion, (size_t)std::max<uint32_t>(ni, 1) * sizeof(MotionRecord), hipHostMallocDefault));
+      ctx->h_motion_cap = std::max<uint32_t>(ni, 1);
+    }
+    uint32_t records = 0;
+    if (k.history_valid && ni) {
+      motion_table(ctx->tp_xforms.data(), cur.data(), ni, ctx->h_motion);
+      CTX_TRY(ctx, hipMemcpyAsync(ctx->tp_table.p, ctx->h_motion, (size_t)ni * sizeof(MotionRecord), hipMemcpyHostToDevice, ctx->stream));
+      records = ni;
+    }
+    CTX_TRY(ctx, temporal_follow_run(ctx->stream, ctx->tp_moments, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
+                                     ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_table.p, records, ctx->tp_h[to].p, ctx->tp_g[to].p,
+                                     ctx->tp_i[to].p, ctx->tp_m[to].p, ctx->tp_v.p, k));
+  } else if (ctx->tp_moments)
     CTX_TRY(ctx, temporal_moments_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
                                       ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p,
                                       ctx->tp_m[to].p, k));
@@ -1538,6 +1587,7 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (complete when the call returns: a camera or scene edit may follow at once)
   ctx->tp_cur = to;
   ctx->tp_camera = ctx->camera;
+  if (ctx->tp_follow) ctx->tp_xforms.swap(cur);
   ctx->tp_width = ctx->width;
   ctx->tp_height = ctx->height;
   ctx->tp_valid = true;
@@ -1683,6 +1733,50 @@ int gsp_temporal_track_moments(gsp_context* ctx, int on) {
   if (want == ctx->tp_moments) return GSP_OK;
   ctx->tp_moments = want;
   ctx->tp_valid = false;  // (moments and history have the same age)
+  return GSP_OK;
+}
+
+int gsp_temporal_follow_instances(gsp_context* ctx, int on) {
+  if (!ctx) return GSP_ERR_INVALID;
+  const bool want = on != 0;
+  if (want == ctx->tp_follow) return GSP_OK;
+  ctx->tp_follow = want;
+  ctx->tp_valid = false;  // (the transforms the history belongs to are recorded only while following is on)
+  ctx->tp_xforms.clear();
+  return GSP_OK;
+}
+
+// what the two read-outs of the motion plane ask first
+static int temporal_have_motion(gsp_context* ctx, const char* who, const void* out_ptr) {
+  int rc = temporal_have_history(ctx, who, out_ptr);
+  if (rc != GSP_OK) return rc;
+  if (!ctx->tp_follow) {
+    ctx->err = std::string(who) + " needs gsp_temporal_follow_instances(ctx, 1) before the history was accumulated";
+    return GSP_ERR_INVALID;
+  }
+  return GSP_OK;
+}
+
+int gsp_download_temporal_motion(gsp_context* ctx, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_motion(ctx, "gsp_download_temporal_motion", out);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  return read_back_bytes(ctx, ctx->tp_v.p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
+}
+
+int gsp_temporal_motion_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_motion(ctx, "gsp_temporal_motion_to_device", dst);
+  if (rc != GSP_OK) return rc;
+  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
+  if (bytes < need) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->tp_v.p, need, hipMemcpyDeviceToDevice, ctx->stream));  // (a copy: any alignment)
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return GSP_OK;
 }
 

@@ -537,6 +537,7 @@ int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
   }
   ctx->have_scene = false;
   ctx->tp_valid = false;  // (temporal accumulation: a new scene has no history)
+  ctx->tp_xforms.clear();
   for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
   ctx->geo_ring_failed = false;
   ctx->inst_dynamic.clear();
@@ -674,6 +675,7 @@ int gsp_update_instances(gsp_context* ctx, const gsp_instance* instances, uint32
   rc = check_instances(ctx, instances, num_instances, ctx->num_bsdfs, ctx->num_vertices, nullptr);
   if (rc != GSP_OK) return rc;
   if (num_instances == 0 || std::memcmp(ctx->h_inst.data(), instances, num_instances * sizeof(gsp_instance)) == 0) return GSP_OK;
+  ++ctx->inst_edits;  // (gsp_temporal_follow_instances: the frame's features belong to the transforms before this edit)
   // r05, split scene.  The host that edits while samples are in flight (a viewer) usually moves a few objects of many: the first
   // such edit -- and every later one that touches an instance not edited before -- builds TWO trees, one over the instances that
   // have never changed and one over the edited ones (make_split: behind a drain, two builds); from then on an edit of those

@@ -97,6 +97,8 @@ def load():
     L.gsph_pathtracer_temporal_track_moments.argtypes = [vp, C.c_int]
     L.gsph_pathtracer_download_temporal_moments.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_download_temporal_svgf.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp, u64]
+    L.gsph_pathtracer_temporal_follow_instances.argtypes = [vp, C.c_int]
+    L.gsph_pathtracer_download_temporal_motion.argtypes = [vp, vp, u64]
     _LIB = L
     return L
 
@@ -396,6 +398,16 @@ class PathTracer:
         self._check(self._L.gsph_pathtracer_download_temporal_svgf(self._h, C.byref(denoise) if denoise is not None else None,
                                                                    C.byref(svgf) if svgf is not None else None, out.ctypes.data, out.size),
                     "downloadTemporalSvgf")
+        return out
+
+    def temporal_follow_instances(self, on=True):
+        """PathTracer::temporalFollowInstances: the history follows moved objects (a change drops the history)."""
+        self._check(self._L.gsph_pathtracer_temporal_follow_instances(self._h, 1 if on else 0), "temporalFollowInstances")
+
+    def download_temporal_motion(self):
+        """PathTracer::downloadTemporalMotion: (h, w, 4) float32 {dx, dy, kept weight, class}."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_temporal_motion(self._h, out.ctypes.data, out.size), "downloadTemporalMotion")
         return out
 
     def stats(self):

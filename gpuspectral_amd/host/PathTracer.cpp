@@ -317,6 +317,14 @@ std::vector<float> PathTracer::downloadTemporalSvgf(const gsp_denoise* denoise, 
   return out;
 }
 
+void PathTracer::temporalFollowInstances(bool on) { check(gsp_temporal_follow_instances(ctx, on ? 1 : 0), "gsp_temporal_follow_instances"); }
+
+std::vector<float> PathTracer::downloadTemporalMotion() {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_temporal_motion(ctx, out.data()), "gsp_download_temporal_motion");
+  return out;
+}
+
 void PathTracer::nextFrame() {
   featureTimestamp = timestamp;  // (the feature samples of the new frame are those of its beauty samples)
   check(gsp_frame_begin(ctx, width, height, pixelIds.empty() ? nullptr : pixelIds.data(), pixelIds.size()), "gsp_frame_begin");

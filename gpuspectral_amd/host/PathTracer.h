@@ -121,6 +121,12 @@ class PathTracer : public RenderPassCreator {
   void temporalTrackMoments(bool on);
   std::vector<float> downloadTemporalMoments();
   std::vector<float> downloadTemporalSvgf(const gsp_denoise* denoise = nullptr, const gsp_svgf* svgf = nullptr);
+  // Moved instances (gpuspectral_pt.h "Temporal accumulation: moved instances"): temporalFollowInstances(true) makes
+  // temporalAccumulate take a pixel of an object whose transform changed back through that motion (a change of the value drops the
+  // history).  render() uploads an edited transform, so it belongs before the frame's renderFeatures.  downloadTemporalMotion is
+  // the motion plane {dx, dy, kept weight, class} of the newest accumulate.
+  void temporalFollowInstances(bool on);
+  std::vector<float> downloadTemporalMotion();
   void nextFrame();  // a new frame (accumulate buffer and feature planes cleared) whose samples continue the timestamp sequence
   void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }

@@ -359,6 +359,17 @@ int gsph_pathtracer_download_temporal_svgf(void* pt, const gsp_denoise* denoise,
     std::memcpy(out, img.data(), img.size() * sizeof(float));
   });
 }
+// moved instances of a PathTracer (gpuspectral_pt.h "Temporal accumulation: moved instances")
+int gsph_pathtracer_temporal_follow_instances(void* pt, int on) {
+  return guard([&] { ((PathTracer*)pt)->temporalFollowInstances(on != 0); });
+}
+int gsph_pathtracer_download_temporal_motion(void* pt, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTemporalMotion();
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {
     std::vector<uint8_t> v;

@@ -27,6 +27,9 @@
 //   accumulation"), the scene's camera turned by DEG degrees about the world y axis through the origin between frames (the
 //   loader keeps no look-at point), every frame accumulated into the history; out.pfm receives the history after the last frame
 //   and, with --denoise, out.dn.pfm its filtered form.  The files of the other flags are those of the LAST frame.  One device.
+//   --temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm] (with --temporal): the history follows moved instances
+//   (gpuspectral_pt.h "Temporal accumulation: moved instances"); --temporal-move translates render object INST by (DX, DY, DZ)
+//   between frames, --motion writes the motion plane of the last frame as {dx, dy, class} (a PFM holds three channels).
 //   --svgf out.pfm [--svgf-sigma S] [--svgf-min-history N] (with --temporal): the history keeps its luminance moments and out.pfm
 //   receives its variance-guided filter (gpuspectral_pt.h "Variance-guided filter"; S = sigma_variance, inf = the term off; N =
 //   2..65536), with the levels and guide sigmas of --denoise-iterations / --denoise-sigma where --denoise is given.
@@ -65,6 +68,10 @@ int main(int argc, char** argv) {
   int temporalFrames = 0;  // (0 = not given)
   float temporalOrbit = 0.0f;
   bool temporalOptions = false;
+  bool temporalFollow = false, temporalMove = false;
+  long temporalMoveInst = 0;
+  float temporalMoveBy[3] = {0.0f, 0.0f, 0.0f};
+  std::string motionPath;
   std::string svgfPath;
   gsp_svgf svgf{};
   svgf.struct_size = (uint32_t)sizeof(gsp_svgf);
@@ -122,6 +129,24 @@ int main(int argc, char** argv) {
       }
       temporalOptions = true, used = 2;
     }
+    else if (flag == "--temporal-follow") temporalFollow = true, used = 1;
+    else if (flag == "--temporal-move" && argc > 2) {
+      char* end = nullptr;
+      temporalMoveInst = std::strtol(argv[2], &end, 10);
+      bool ok = end != argv[2] && temporalMoveInst >= 0;
+      for (int k = 0; k < 3 && ok; ++k) {
+        ok = *end == ',';
+        if (!ok) break;
+        const char* from = end + 1;
+        temporalMoveBy[k] = std::strtof(from, &end);
+        ok = end != from && std::isfinite(temporalMoveBy[k]);
+      }
+      if (!ok || *end != 0) {
+        std::fprintf(stderr, "gsp_render: bad temporal move '%s' (expected INST,DX,DY,DZ: an object index and a finite translation per frame)\n", argv[2]);
+        return 2;
+      }
+      temporalMove = true, used = 2;
+    } else if (flag == "--motion" && argc > 2) motionPath = argv[2], used = 2;
     else if (flag == "--svgf" && argc > 2) svgfPath = argv[2], used = 2;
     else if (flag == "--svgf-sigma" && argc > 2) {
       if (std::string(argv[2]) == "inf") svgf.sigma_variance = INFINITY;
@@ -287,6 +312,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --temporal needs --temporal-frames N\n");
     return 2;
   }
+  if (temporalPath.empty() && temporalFollow) {
+    std::fprintf(stderr, "gsp_render: --temporal-follow needs --temporal out.pfm\n");
+    return 2;
+  }
+  if (!temporalFollow && (temporalMove || !motionPath.empty())) {
+    std::fprintf(stderr, "gsp_render: --temporal-move and --motion need --temporal-follow\n");
+    return 2;
+  }
   if (svgfPath.empty() && svgfOptions) {
     std::fprintf(stderr, "gsp_render: --svgf-sigma and --svgf-min-history need --svgf out.pfm\n");
     return 2;
@@ -296,7 +329,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -359,7 +392,7 @@ int main(int argc, char** argv) {
     if (!denoisePath.empty() && !ldrPath.empty() && devices.size() > 1)
       throw std::runtime_error("--denoise with --ldr needs a single device (the LDR film of the denoised frame is a single-context call)");
     std::vector<uint32_t> ldr, denoisedLdr;
-    std::vector<float> img, featAlbedo, featGeom, denoised, temporal, temporalDenoised, temporalSvgf;
+    std::vector<float> img, featAlbedo, featGeom, denoised, temporal, temporalDenoised, temporalSvgf, motion;
     double temporalLength = 0.0;
     const uint32_t fspp = featureSpp > 0 ? (uint32_t)featureSpp : spp;
     gsp_stats st;
@@ -373,6 +406,10 @@ int main(int argc, char** argv) {
       pt.params.pixel_filter = filter;
       pt.params.pixel_filter_param = filterParam;
       if (!svgfPath.empty()) pt.temporalTrackMoments(true);  // (before the first accumulate: moments and history of one age)
+      if (temporalFollow) pt.temporalFollowInstances(true);
+      if (temporalMove && (size_t)temporalMoveInst >= scene.renderObjects.size())
+        throw std::runtime_error("--temporal-move: the scene has " + std::to_string(scene.renderObjects.size()) + " render objects, there is no object " +
+                                 std::to_string(temporalMoveInst));
       // temporal accumulation: the frames before the last one, each rendered, given a feature pass and accumulated, then the
       // camera turned about the world y axis; the last frame is the ordinary frame below
       for (int f = 0; f + 1 < temporalFrames; ++f) {
@@ -387,6 +424,8 @@ int main(int argc, char** argv) {
           r[c][2] = -sn * m[c][0] + cs * m[c][2];
         }
         scene.camera.setToWorld(r);
+        if (temporalMove)  // (the next frame's render uploads the edit: before its feature pass, as following asks)
+          for (int k = 0; k < 3; ++k) scene.renderObjects[(size_t)temporalMoveInst].transform[3][k] += temporalMoveBy[k];
         pt.nextFrame();
       }
       auto t0 = std::chrono::steady_clock::now();
@@ -413,6 +452,7 @@ int main(int argc, char** argv) {
         temporal = pt.downloadTemporal();
         if (!denoisePath.empty()) temporalDenoised = pt.downloadTemporalDenoised(&denoise);
         if (!svgfPath.empty()) temporalSvgf = pt.downloadTemporalSvgf(&denoise, &svgf);
+        if (!motionPath.empty()) motion = pt.downloadTemporalMotion();
         for (size_t i = 3; i < temporal.size(); i += 4) temporalLength += temporal[i];
         temporalLength /= (double)width * height;
       }
@@ -483,6 +523,15 @@ int main(int argc, char** argv) {
       }
       std::printf("temporal: %d frame%s of %u spp, %g degrees per frame, mean history length %.2f -> %s%s%s\n", temporalFrames, temporalFrames == 1 ? "" : "s",
                   spp, (double)temporalOrbit, temporalLength, temporalPath.c_str(), dn.empty() ? "" : ", ", dn.c_str());
+      if (!motionPath.empty()) {
+        size_t followed = 0;
+        for (size_t i = 3; i < motion.size(); i += 4) {
+          followed += motion[i] == 2.0f;
+          motion[i - 1] = motion[i];  // (a PFM holds three channels: dx, dy and the class)
+        }
+        writePfm(motionPath, motion.data(), width, height);
+        std::printf("motion: %zu followed pixels -> %s\n", followed, motionPath.c_str());
+      }
       if (!svgfPath.empty()) {
         writePfm(svgfPath, temporalSvgf.data(), width, height);
         if (std::isinf(svgf.sigma_variance)) std::printf("svgf: %u levels, the variance term off -> %s\n", denoise.iterations ? denoise.iterations : 5u, svgfPath.c_str());

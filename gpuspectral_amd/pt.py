@@ -60,6 +60,9 @@ EXPORTS = (
     "gsp_download_temporal_svgf",
     "gsp_temporal_svgf_to_device",
     "gsp_download_temporal_svgf_display",
+    "gsp_temporal_follow_instances",
+    "gsp_download_temporal_motion",
+    "gsp_temporal_motion_to_device",
     "gsp_frame_sample_base",
     "gsp_get_stats",
     "gsp_reset_stats",
@@ -168,6 +171,9 @@ def load():
     L.gsp_download_temporal_svgf.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp]
     L.gsp_temporal_svgf_to_device.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp, u64]
     L.gsp_download_temporal_svgf_display.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.POINTER(abi.Display), vp]
+    L.gsp_temporal_follow_instances.argtypes = [vp, C.c_int]
+    L.gsp_download_temporal_motion.argtypes = [vp, vp]
+    L.gsp_temporal_motion_to_device.argtypes = [vp, vp, u64]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -218,7 +224,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -515,6 +521,27 @@ class Context:
                                                                C.byref(display) if display is not None else None, out.ctypes.data),
                     "gsp_download_temporal_svgf_display")
         return out
+
+    # ---- moved instances (gpuspectral_pt.h "Temporal accumulation: moved instances") ----
+    def temporal_follow_instances(self, on=True):
+        """gsp_temporal_follow_instances: temporal_accumulate takes a pixel of a moved instance back through the instance's motion
+        and writes the motion plane; a change drops the history.  An update_instances belongs before the frame's render_features."""
+        self._check(self._L.gsp_temporal_follow_instances(self._h, 1 if on else 0), "gsp_temporal_follow_instances")
+
+    def download_temporal_motion(self):
+        """gsp_download_temporal_motion: V = {dx, dy, kept weight, class} of the newest accumulate, (height, width, 4) float32."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_temporal_motion(self._h, out.ctypes.data), "gsp_download_temporal_motion")
+        return out
+
+    def temporal_motion_to_device(self, dst, nbytes=None):
+        """gsp_temporal_motion_to_device: V into device memory, width*height*16 bytes.  dst: a torch tensor on the context's device
+        (its bytes from its storage offset on), or a device pointer with nbytes."""
+        if hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsp_temporal_motion_to_device(self._h, ptr, nbytes), "gsp_temporal_motion_to_device")
 
     def pixel_stats(self):
         """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of

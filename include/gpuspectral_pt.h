@@ -75,7 +75,9 @@ extern "C" {
                                 gsp_download_temporal, gsp_temporal_to_device, gsp_download_temporal_denoised,
                                 gsp_download_temporal_denoised_display, gsp_frame_sample_base (see "Temporal accumulation");
                                 gsp_temporal_track_moments, gsp_download_temporal_moments, gsp_download_temporal_svgf,
-                                gsp_temporal_svgf_to_device, gsp_download_temporal_svgf_display (see "Variance-guided filter") */
+                                gsp_temporal_svgf_to_device, gsp_download_temporal_svgf_display (see "Variance-guided filter");
+                                gsp_temporal_follow_instances, gsp_download_temporal_motion, gsp_temporal_motion_to_device
+                                (see "Temporal accumulation: moved instances") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -823,8 +825,8 @@ int gsp_download_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, 
  * frame draws new random numbers (see gsp_frame_sample_base below); without it a frame rendered at first_timestamp T > 0 on the
  * cleared buffer is darker by n / (T + n), and frames that all start at timestamp 0 repeat one noise pattern.
  *
- * Out of scope.  The world is taken as static between two frames: an instance that moved is handled only by rejection (the
- * instance-index, depth and normal tests); per-instance motion vectors are a later change.  There are no gsp_multi_* variants: a
+ * Out of scope.  By default the world is taken as static between two frames: an instance that moved is handled only by rejection
+ * (the instance-index, depth and normal tests); "Temporal accumulation: moved instances" below follows it.  There are no gsp_multi_* variants: a
  * share has no neighbours, and gathering the ids plane is a change of its own -- a frame begun with pixel_ids is refused.  The
  * filtered output is not fed back into the history.
  */
@@ -916,8 +918,7 @@ int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* 
  * per pixel, allocated by the first call.  The calls change no state of the frame or of the history.  GSP_ERR_INVALID: what
  * gsp_download_temporal_denoised refuses; tracking off; min_history 1 or above 65536; a negative or NaN sigma_variance.
  *
- * Out of scope.  The filtered frame is not fed back into the history; moved instances have no motion vectors (see "Temporal
- * accumulation"); there are no gsp_multi_* variants.
+ * Out of scope.  The filtered frame is not fed back into the history; there are no gsp_multi_* variants.
  */
 typedef struct gsp_svgf {
   uint32_t struct_size; /* sizeof(gsp_svgf) of the host's header; same rule as gsp_denoise (NULL and struct_size 0 = every default) */
@@ -935,6 +936,66 @@ int gsp_temporal_svgf_to_device(gsp_context* ctx, const gsp_denoise* denoise, co
 /* ... and the LDR film of it (as gsp_download_denoised_display): width*height RGBA8 words. */
 int gsp_download_temporal_svgf_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, const gsp_display* display,
                                        uint32_t* out_rgba8);
+
+/*
+ * Temporal accumulation: moved instances.  The history follows an instance whose transform gsp_update_instances changed, and the
+ * screen-space motion vector of every pixel is exported.
+ *
+ * "Temporal accumulation" reprojects a pixel as if only the camera had moved.  With gsp_temporal_follow_instances(ctx, 1) -- context
+ * state, off by default; a CHANGE of the value clears history_valid; a call with the current value does nothing -- a surface pixel
+ * of an instance that moved is taken back through the instance's motion first.  With following off every call runs the
+ * instructions and returns the bits it returns without this section, and nothing below is allocated, copied or launched.
+ * Arithmetic is float32 in the order written (no contraction); sqrt and / are correctly rounded.
+ *
+ * Snapshot.  While following is on, every successful gsp_temporal_accumulate records the 16 transform floats of every instance
+ * beside the camera it already records.  gsp_upload_scene drops the snapshot with the history.
+ *
+ * Which transforms a frame belongs to.  The context counts instance edits: a gsp_update_instances call that changes something
+ * (the call compares first; one that changes nothing does not count).  The frame's first gsp_render_features records the
+ * counter.  With following on, a gsp_temporal_accumulate whose counter differs from the recorded one returns GSP_ERR_INVALID: the
+ * feature planes would show other transforms than the ones the call would record.  An edit belongs BEFORE the frame's
+ * gsp_render_features.  With following off nothing is checked.
+ *
+ * Per-instance record, formed on the host in double at the accumulate and rounded to float once; T_prev = the snapshot's
+ * transform, T_cur = the current one, both taken as affine (3x3 A, translation t = column 3; the fourth row is not read).  6 quads
+ * = 96 bytes:
+ *     B = T_prev * T_cur^-1 as three rows of four floats: B3 = A_prev * A_cur^-1, b_r3 = t_prev.r - (B3 * t_cur).r.  A_cur^-1 is
+ *         adjugate / determinant, as step 3 of "Temporal accumulation" forms Minv_prev.
+ *     N = transpose(B3^-1) = transpose(A_cur * A_prev^-1) as three rows, computed from the two transforms (A_prev^-1 again
+ *         adjugate / determinant), not by inverting the rounded B.
+ *     a class word: 0 static, 1 moved, 2 no history.
+ *         static: the 16 floats of T_prev and T_cur are equal as bits (tested first).
+ *         no history: A_prev or A_cur has a determinant that is 0 or not finite, or an entry of B or N is not finite as a float.
+ *         This is not an error: a host may scale an object to nothing to hide it.
+ *     B and N of a record of class 0 or 2 are zero.  An instance index >= num_instances is of class 2.
+ *
+ * Pixel.  A background pixel and a surface pixel of a class-0 instance run steps 1-7 and the tap tests of "Temporal
+ * accumulation" as they stand: H', G', I' (and M') are bit for bit what they are with following off.  Class 2: no history.
+ * Class 1, after step 2's P:
+ *     P'.r = ((b_r0 * P.x + b_r1 * P.y) + b_r2 * P.z) + b_r3          (r = x, y, z)
+ *     v.k = P'.k - eye_prev.k;   ze = sqrt((v.x*v.x + v.y*v.y) + v.z*v.z)
+ *     m.r = (n_r0 * n.x + n_r1 * n.y) + n_r2 * n.z;   s = (m.x*m.x + m.y*m.y) + m.z*m.z
+ *     not (s > 0): no history;  otherwise q = sqrt(s), n' = (m.x / q, m.y / q, m.z / q)
+ * Steps 3-7 run on this v.  The tap test uses n' in its normal term; the instance test and the depth test (on this ze) are
+ * unchanged.  G' and I' hold this frame's own n, z and I, as always.
+ *
+ * Motion plane.  V, 16 bytes per pixel, one plane over the full frame (nothing reads it back), made by the first followed
+ * accumulate together with the table (96 bytes per instance) and counted in the context's bytes:
+ *     V = {fx - (float)px, fy - (float)py, sw, cls}     fx, fy after the snap of step 6; sw = the summed weight of the kept taps
+ *     cls = 0.0 where there is no reprojection (history_valid is 0, step 4 or 7 fails, class 2, s fails): the record is all zero
+ *     cls = 1.0 for the static path, 2.0 for a followed pixel
+ * V.xy is the screen-space motion vector an external TAA or denoiser asks for: this frame's pixel centre plus V.xy is where the
+ * surface point was in the previous frame.
+ *
+ * Limits.  The lighting of a moved object and the shadows it casts on others lag by the history: only alpha bounds that.
+ * Deforming meshes are not covered: a transform per instance is all gsp_update_instances knows.  There are no gsp_multi_* variants.
+ */
+/* on != 0: gsp_temporal_accumulate follows moved instances and writes V.  Never fails on a context; frees nothing. */
+int gsp_temporal_follow_instances(gsp_context* ctx, int on);
+/* V of the newest accumulate: width*height*4 floats.  GSP_ERR_INVALID when following is off or there is no valid history. */
+int gsp_download_temporal_motion(gsp_context* ctx, float* out_rgba);
+/* The same into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
+int gsp_temporal_motion_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
 
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
