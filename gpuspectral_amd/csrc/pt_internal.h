@@ -9,6 +9,7 @@
 #include "../../include/gpuspectral_pt.h"
 #include "pt_denoise.h"
 #include "pt_display.h"
+#include "pt_illum.h"
 #include "pt_stages.h"
 #include "pt_motion.h"
 #include "pt_svgf.h"
@@ -86,9 +87,11 @@ __attribute__((visibility("hidden"))) hipError_t display_map(hipStream_t stream,
 
 // ---- denoiser (pt_denoise.h) on a full frame of width x height: `accum`, `albedo`, `geom` are its RGBA32F planes, `e0`, `e1`, `a`
 // scratch planes and `out` the result, all 16 bytes per pixel, 16-byte aligned device memory of the current device.  Queues
-// k_denoise_prepare and k.iterations launches of k_denoise_atrous on `stream`; does not synchronise.
+// k_denoise_prepare and k.iterations launches of k_denoise_atrous on `stream`; does not synchronise.  illum: `accum` is a
+// demodulated history (pt_illum.h) and k_illum_prepare stands for k_denoise_prepare.
 __attribute__((visibility("hidden"))) hipError_t denoise_run(hipStream_t stream, uint32_t num_cus, const void* accum, const void* albedo, const void* geom,
-                                                             uint32_t width, uint32_t height, const DenoiseConsts& k, void* e0, void* e1, void* a, void* out);
+                                                             uint32_t width, uint32_t height, const DenoiseConsts& k, void* e0, void* e1, void* a, void* out,
+                                                             bool illum = false);
 
 // ---- temporal accumulation (pt_temporal.h) on a full frame of k.cur.width x k.cur.height: `accum`, `albedo`, `geom`, `ids` are the
 // frame's 16-byte planes, {h, g, i}_prev the history set read (not read when k.history_valid == 0) and {h, g, i}_out the set

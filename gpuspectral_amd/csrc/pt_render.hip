@@ -172,6 +172,9 @@ struct gsp_context {
   // (h_motion_cap records), copies them to tp_table and writes the motion plane tp_v.  All made by the first followed accumulate.
   // inst_edits counts the gsp_update_instances calls that changed something; feat_inst_edits = its value at the frame's first
   // gsp_render_features
+  // illumination history (gsp_temporal_demodulate): while tp_demod, tp_h holds c / albedo (pt_illum.h); tp_fed = the newest
+  // history has taken a gsp_temporal_svgf_feedback since its accumulate
+  bool tp_demod = false, tp_fed = false;
   bool tp_follow = false;
   std::vector<float> tp_xforms;
   uint64_t inst_edits = 0, feat_inst_edits = 0;

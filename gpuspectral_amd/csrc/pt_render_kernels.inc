@@ -1429,6 +1429,136 @@ __global__ __launch_bounds__(kBlock) void k_svgf_atrous(const v4f* __restrict__ 
   }
 }
 
+// ---- illumination history (pt_illum.h; include/gpuspectral_pt.h "Illumination history") ---------------------------------------
+// The accumulate with the frame demodulated: k_temporal_reproject (MOMENTS, FOLLOW = false, false), k_temporal_reproject_moments
+// (true, false) and k_temporal_reproject_follow<MOMENTS> (FOLLOW = true) with e = c / A blended in place of c.  Kernels of their
+// own, launched only by a context with gsp_temporal_demodulate on: every other context runs the instruction streams it ran
+// before.  Loads, stores and their order are those of the kernel each one stands for (!FOLLOW: no table read, no V store; the
+// record is the constant of class 0 and folds away); the three quotients per lane are added to a kernel that
+// waits for its taps.
+template <bool MOMENTS, bool FOLLOW>
+__global__ __launch_bounds__(kBlock) void k_temporal_reproject_illum(const v4f* __restrict__ accum, const v4f* __restrict__ albedo,
+                                                                     const v4f* __restrict__ geom, const v4u* __restrict__ ids,
+                                                                     const v4f* __restrict__ Hprev, const v4f* __restrict__ Gprev,
+                                                                     const uint32_t* __restrict__ Iprev, const v4f* __restrict__ Mprev,
+                                                                     const v4f* __restrict__ table, uint32_t num_records, v4f* __restrict__ Hout,
+                                                                     v4f* __restrict__ Gout, uint32_t* __restrict__ Iout, v4f* __restrict__ Mout,
+                                                                     v4f* __restrict__ Vout, TemporalConsts k) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  const int width = (int)k.cur.width;
+  if (px >= width || py >= (int)k.cur.height) return;
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  const uint32_t inst = ids[p].z;
+  const dn4 c = dn_load(accum + p), alb = dn_load(albedo + p), g = dn_load(geom + p);
+  MotionRecord rec = motion_record_of_class(FOLLOW ? kMotionNoHistory : kMotionStatic);
+  bool wave_moved = false;
+  if constexpr (FOLLOW) {
+    if (inst < num_records) {
+      const v4f* r = table + (size_t)inst * kMotionRecordQuads;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        rec.b[i] = dn_load(r + i);
+        rec.n[i] = dn_load(r + 3 + i);
+      }
+    }
+    wave_moved = __ballot(motion_class(rec) == kMotionMoved) != 0;
+  }
+  const MotionOut o = illum_pixel<MOMENTS>(k, px, py, c, alb, g, inst, rec, wave_moved, [&](int x, int y, dn4& H_, dn4& G_, uint32_t& I_, dn4& M_) {
+    const size_t q = (size_t)y * (size_t)width + (size_t)x;  // a pixel of the frame
+    H_ = dn_load(Hprev + q);
+    G_ = dn_load(Gprev + q);
+    I_ = Iprev[q];
+    if constexpr (MOMENTS) M_ = dn_load(Mprev + q);
+  });
+  dn_store(Hout + p, o.t.H);
+  dn_store(Gout + p, o.t.G);
+  Iout[p] = o.t.I;
+  if constexpr (MOMENTS) dn_store(Mout + p, o.M);
+  if constexpr (FOLLOW) dn_store(Vout + p, o.V);
+}
+
+// Prepare of a demodulated history, and the re-modulation of the image read-out: streaming like k_denoise_prepare, one pixel per
+// lane and trip, 16-byte loads and stores in 1-KiB runs per wave.
+__global__ __launch_bounds__(kBlock) void k_illum_prepare(const v4f* __restrict__ hist, const v4f* __restrict__ albedo, uint64_t n, v4f* __restrict__ E,
+                                                          v4f* __restrict__ A) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    dn4 e, a;
+    illum_prepare(dn_load(hist + i), dn_load(albedo + i), e, a);
+    dn_store(E + i, e);
+    dn_store(A + i, a);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_illum_image(const v4f* __restrict__ hist, const v4f* __restrict__ albedo, uint64_t n, v4f* __restrict__ out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+    dn_store(out + i, illum_image(dn_load(hist + i), dn_load(albedo + i)));
+}
+
+// k_svgf_atrous with the feedback store in its epilogue: the one level of a gsp_temporal_svgf_feedback whose output goes into the
+// history as well.  A kernel of its own, so that every other level -- and every call without feedback -- runs k_svgf_atrous as
+// it stands.  A lane loads its own record of `hist` (16 bytes; the LAST form has it already), replaces the colour by the level's
+// and stores it back: no level reads hist at another pixel, so there is no hazard, and the level needs no pass of its own.
+// DEMOD: hist holds illumination and takes e; otherwise it takes e * A.
+template <int S, bool LAST, bool DEMOD>
+__global__ __launch_bounds__(kBlock) void k_svgf_atrous_feedback(const v4f* __restrict__ Ein, const v4f* __restrict__ A, const v4f* __restrict__ G,
+                                                                 const float* __restrict__ Vin, v4f* __restrict__ hist, v4f* __restrict__ out,
+                                                                 float* __restrict__ Vout, SvgfConsts k, uint32_t level, int width, int height) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  SvgfLevelOut r;
+  if constexpr (S != 0) {
+    constexpr int PW = kDnTileW + 4 * S, PH = kDnTileH + 4 * S;
+    __shared__ v4f sE[PW * PH], sA[PW * PH], sG[PW * PH];
+    __shared__ float sV[PW * PH];
+    const int x0 = (int)blockIdx.x * kDnTileW - 2 * S, y0 = (int)blockIdx.y * kDnTileH - 2 * S;
+    for (int i = (int)threadIdx.x; i < PW * PH; i += kBlock) {
+      const int ly = i / PW, lx = i - ly * PW;
+      const int gx = x0 + lx, gy = y0 + ly;
+      v4f e = {0.0f, 0.0f, 0.0f, 0.0f}, a = e, g = e;
+      float v = 0.0f;
+      if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+        const size_t idx = (size_t)gy * (size_t)width + (size_t)gx;
+        e = Ein[idx];
+        a = A[idx];
+        g = G[idx];
+        v = Vin[idx];
+      }
+      sE[i] = e;
+      sA[i] = a;
+      sG[i] = g;
+      sV[i] = v;
+    }
+    __syncthreads();
+    if (px >= width || py >= height) return;  // (no barrier below)
+    r = svgf_pixel_level(k, level, width, height, px, py, [&](int x, int y, dn4& E_, dn4& A_, dn4& G_, float& V_) {
+      const int i = (y - y0) * PW + (x - x0);  // |x - px| <= 2 S and |y - py| <= 2 S: inside the staged rectangle
+      E_ = dn_load(&sE[i]);
+      A_ = dn_load(&sA[i]);
+      G_ = dn_load(&sG[i]);
+      V_ = sV[i];
+    });
+  } else {
+    if (px >= width || py >= height) return;
+    r = svgf_pixel_level(k, level, width, height, px, py, [&](int x, int y, dn4& E_, dn4& A_, dn4& G_, float& V_) {
+      const size_t idx = (size_t)y * (size_t)width + (size_t)x;  // svgf_pixel_level asks for pixels of the frame only
+      E_ = dn_load(Ein + idx);
+      A_ = dn_load(A + idx);
+      G_ = dn_load(G + idx);
+      V_ = Vin[idx];
+    });
+  }
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  const dn4 a = dn_load(A + p), h = dn_load(hist + p);
+  if constexpr (LAST) {
+    dn_store(out + p, denoise_finish(r.E, a, h));
+  } else {
+    dn_store(out + p, r.E);
+    Vout[p] = r.V;
+  }
+  dn_store(hist + p, illum_feedback<DEMOD>(r.E, a, h));
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

@@ -1318,11 +1318,12 @@ static int display_run(gsp_context* ctx, const gsp_display* display_host, uint32
 
 // ---- denoiser (include/gpuspectral_pt.h, "Denoiser"; per-pixel code: pt_denoise.h) ----
 hipError_t gsp::denoise_run(hipStream_t stream, uint32_t num_cus, const void* accum, const void* albedo, const void* geom, uint32_t width, uint32_t height,
-                            const DenoiseConsts& k, void* e0, void* e1, void* a, void* out) {
+                            const DenoiseConsts& k, void* e0, void* e1, void* a, void* out, bool illum) {
   const uint64_t n = (uint64_t)width * height;
   if (n == 0) return hipSuccess;
   const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 8));
-  hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)accum, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
+  if (illum) hipLaunchKernelGGL(k_illum_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)accum, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
+  else hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)accum, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH), block(kBlock);
@@ -1465,9 +1466,31 @@ static hipError_t temporal_follow_run(hipStream_t stream, bool moments, const vo
   return hipGetLastError();
 }
 
-// what every temporal read-out asks first
-static int temporal_have_history(gsp_context* ctx, const char* who, const void* out_ptr) {
-  if (!out_ptr) {
+// ... with the frame demodulated (k_temporal_reproject_illum; pt_illum.h): temporal_run, temporal_moments_run or
+// temporal_follow_run by `moments` and `follow`; the planes a form does not have may be nullptr
+static hipError_t temporal_illum_run(hipStream_t stream, bool moments, bool follow, const void* accum, const void* albedo, const void* geom, const void* ids,
+                                     const void* h_prev, const void* g_prev, const void* i_prev, const void* m_prev, const void* table, uint32_t num_records,
+                                     void* h_out, void* g_out, void* i_out, void* m_out, void* v_out, const TemporalConsts& k) {
+  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
+  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
+#define GSP_ILLUM_LAUNCH(M, F)                                                                                                                        \
+  hipLaunchKernelGGL((k_temporal_reproject_illum<M, F>), grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids, \
+                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (const v4f*)m_prev, (const v4f*)table, num_records, (v4f*)h_out,      \
+                     (v4f*)g_out, (uint32_t*)i_out, (v4f*)m_out, (v4f*)v_out, k)
+  if (follow) {
+    if (moments) GSP_ILLUM_LAUNCH(true, true);
+    else GSP_ILLUM_LAUNCH(false, true);
+  } else {
+    if (moments) GSP_ILLUM_LAUNCH(true, false);
+    else GSP_ILLUM_LAUNCH(false, false);
+  }
+#undef GSP_ILLUM_LAUNCH
+  return hipGetLastError();
+}
+
+// what every temporal read-out asks first (null_ok: the call may do without an output)
+static int temporal_have_history(gsp_context* ctx, const char* who, const void* out_ptr, bool null_ok = false) {
+  if (!out_ptr && !null_ok) {
     ctx->err = std::string(who) + ": null output pointer";
     return GSP_ERR_INVALID;
   }
@@ -1496,7 +1519,7 @@ static int temporal_denoise_ctx(gsp_context* ctx, const gsp_denoise* denoise_hos
   const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
   for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
   CTX_TRY(ctx, denoise_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->tp_h[ctx->tp_cur].p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->width, ctx->height, k,
-                           ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, ctx->dn_out.p));
+                           ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, ctx->dn_out.p, ctx->tp_demod));
   return GSP_OK;
 }
 
@@ -1574,10 +1597,19 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
       CTX_TRY(ctx, hipMemcpyAsync(ctx->tp_table.p, ctx->h_motion, (size_t)ni * sizeof(MotionRecord), hipMemcpyHostToDevice, ctx->stream));
       records = ni;
     }
-    CTX_TRY(ctx, temporal_follow_run(ctx->stream, ctx->tp_moments, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
+    if (ctx->tp_demod)
+      CTX_TRY(ctx, temporal_illum_run(ctx->stream, ctx->tp_moments, true, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p,
+                                      ctx->tp_h[from].p, ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_table.p, records, ctx->tp_h[to].p,
+                                      ctx->tp_g[to].p, ctx->tp_i[to].p, ctx->tp_m[to].p, ctx->tp_v.p, k));
+    else
+      CTX_TRY(ctx, temporal_follow_run(ctx->stream, ctx->tp_moments, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
                                      ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_table.p, records, ctx->tp_h[to].p, ctx->tp_g[to].p,
                                      ctx->tp_i[to].p, ctx->tp_m[to].p, ctx->tp_v.p, k));
-  } else if (ctx->tp_moments)
+  } else if (ctx->tp_demod)
+    CTX_TRY(ctx, temporal_illum_run(ctx->stream, ctx->tp_moments, false, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
+                                    ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, nullptr, 0u, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p,
+                                    ctx->tp_m[to].p, nullptr, k));
+  else if (ctx->tp_moments)
     CTX_TRY(ctx, temporal_moments_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
                                       ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p,
                                       ctx->tp_m[to].p, k));
@@ -1592,6 +1624,7 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
   ctx->tp_height = ctx->height;
   ctx->tp_valid = true;
   ctx->tp_done = true;
+  ctx->tp_fed = false;  // (gsp_temporal_svgf_feedback: at most one per accumulate)
   return GSP_OK;
 }
 
@@ -1661,12 +1694,16 @@ int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* 
 // ---- variance-guided filter (include/gpuspectral_pt.h, "Variance-guided filter"; per-pixel code: pt_svgf.h) ----
 // The filter of the history `hist` with moments `moments` on a full frame: k_denoise_prepare, k_svgf_variance and k.iterations
 // launches of k_svgf_atrous on `stream`; does not synchronise.  e0, e1, a, out: 16 bytes per pixel; v0, v1: 4 bytes per pixel.
-static hipError_t svgf_run(hipStream_t stream, uint32_t num_cus, const void* hist, const void* moments, const void* albedo, const void* geom, uint32_t width,
-                           uint32_t height, const SvgfConsts& k, void* e0, void* e1, void* a, void* v0, void* v1, void* out) {
+// illum: hist is a demodulated history (k_illum_prepare for k_denoise_prepare).  fb_levels > 0 (gsp_temporal_svgf_feedback): level
+// fb_levels - 1 is k_svgf_atrous_feedback and writes its colour into `hist`; with !want_out the levels after it are not run.
+static hipError_t svgf_run(hipStream_t stream, uint32_t num_cus, void* hist, const void* moments, const void* albedo, const void* geom, uint32_t width,
+                           uint32_t height, const SvgfConsts& k, void* e0, void* e1, void* a, void* v0, void* v1, void* out, bool illum = false,
+                           uint32_t fb_levels = 0, bool want_out = true) {
   const uint64_t n = (uint64_t)width * height;
   if (n == 0) return hipSuccess;
   const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 8));
-  hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)hist, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
+  if (illum) hipLaunchKernelGGL(k_illum_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)hist, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
+  else hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)hist, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH), block(kBlock);
@@ -1675,9 +1712,32 @@ static hipError_t svgf_run(hipStream_t stream, uint32_t num_cus, const void* his
   if ((e = hipGetLastError()) != hipSuccess) return e;
   v4f* E[2] = {(v4f*)e0, (v4f*)e1};
   float* V[2] = {(float*)v0, (float*)v1};
-  for (uint32_t i = 0; i < k.iterations; ++i) {
+  const uint32_t run_levels = fb_levels && !want_out ? fb_levels : k.iterations;
+  for (uint32_t i = 0; i < run_levels; ++i) {
     const bool last = i + 1 == k.iterations;
     v4f* dst = last ? (v4f*)out : E[(i + 1u) & 1u];
+    if (fb_levels && i + 1 == fb_levels) {
+#define GSP_SVGF_FB_LAUNCH(S, LAST, D)                                                                                                                    \
+  hipLaunchKernelGGL((k_svgf_atrous_feedback<S, LAST, D>), grid, block, 0, stream, (const v4f*)E[i & 1u], (const v4f*)a, (const v4f*)geom,                  \
+                     (const float*)V[i & 1u], (v4f*)hist, dst, V[(i + 1u) & 1u], k, i, (int)width, (int)height)
+#define GSP_SVGF_FB_STEP(S)                        \
+  do {                                             \
+    if (last) {                                    \
+      if (illum) GSP_SVGF_FB_LAUNCH(S, true, true);  \
+      else GSP_SVGF_FB_LAUNCH(S, true, false);       \
+    } else {                                       \
+      if (illum) GSP_SVGF_FB_LAUNCH(S, false, true); \
+      else GSP_SVGF_FB_LAUNCH(S, false, false);      \
+    }                                              \
+  } while (0)
+      if (i == 0) GSP_SVGF_FB_STEP(1);
+      else if (i == 1) GSP_SVGF_FB_STEP(2);
+      else GSP_SVGF_FB_STEP(0);
+#undef GSP_SVGF_FB_STEP
+#undef GSP_SVGF_FB_LAUNCH
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      continue;
+    }
 #define GSP_SVGF_LAUNCH(S, LAST)                                                                                                                    \
   hipLaunchKernelGGL((k_svgf_atrous<S, LAST>), grid, block, 0, stream, (const v4f*)E[i & 1u], (const v4f*)a, (const v4f*)geom, (const float*)V[i & 1u], \
                      (const v4f*)hist, dst, V[(i + 1u) & 1u], k, i, (int)width, (int)height)
@@ -1699,8 +1759,11 @@ static hipError_t svgf_run(hipStream_t stream, uint32_t num_cus, const void* his
 }
 
 // Validates and queues the filter into `dst` (device, 16-byte aligned; nullptr = the context's own buffer) on ctx->stream
-static int svgf_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const gsp_svgf* svgf_host, const char* who, const void* out_ptr, void* dst) {
-  int rc = temporal_have_history(ctx, who, out_ptr);
+// fb: the call is a gsp_temporal_svgf_feedback of `fb_levels` levels -- out_ptr may be NULL (then nothing is written to dst), the
+// frame must have been accumulated and not fed back yet, and the newest history takes the colour of level fb_levels - 1
+static int svgf_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const gsp_svgf* svgf_host, const char* who, const void* out_ptr, void* dst,
+                    bool fb = false, uint32_t fb_levels = 0) {
+  int rc = temporal_have_history(ctx, who, out_ptr, fb);
   if (rc != GSP_OK) return rc;
   if (!ctx->tp_moments) {
     ctx->err = std::string(who) + " needs gsp_temporal_track_moments(ctx, 1) before the history was accumulated";
@@ -1715,13 +1778,28 @@ static int svgf_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const gsp
     ctx->err = why;
     return GSP_ERR_INVALID;
   }
+  if (fb) {
+    if (fb_levels < 1 || fb_levels > k.iterations) {
+      ctx->err = std::string(who) + ": levels must be within 1 .. " + std::to_string(k.iterations) + " (the filter's iterations)";
+      return GSP_ERR_INVALID;
+    }
+    if (!ctx->tp_done) {
+      ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since gsp_frame_begin";
+      return GSP_ERR_INVALID;
+    }
+    if (ctx->tp_fed) {
+      ctx->err = std::string(who) + ": the history has been fed back already (one call per gsp_temporal_accumulate)";
+      return GSP_ERR_INVALID;
+    }
+  }
   CTX_TRY(ctx, hipSetDevice(ctx->device));
   const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
   for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
   for (DevBuf<float>& b : ctx->sv_v) CTX_TRY(ctx, b.ensure(n, &ctx->bytes));
   CTX_TRY(ctx, svgf_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->tp_h[ctx->tp_cur].p, ctx->tp_m[ctx->tp_cur].p, ctx->feat_albedo.p, ctx->feat_geom.p,
                         ctx->width, ctx->height, k, ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, ctx->sv_v[0].p, ctx->sv_v[1].p,
-                        dst ? dst : (void*)ctx->dn_out.p));
+                        dst ? dst : (void*)ctx->dn_out.p, ctx->tp_demod, fb ? fb_levels : 0u, !fb || out_ptr != nullptr));
+  if (fb) ctx->tp_fed = true;
   return GSP_OK;
 }
 
@@ -1827,6 +1905,103 @@ int gsp_download_temporal_svgf_display(gsp_context* ctx, const gsp_denoise* deno
   if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
   if (rc != GSP_OK) return rc;
   return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
+}
+
+}  // extern "C"
+
+// ---- illumination history (include/gpuspectral_pt.h, "Illumination history"; per-pixel code: pt_illum.h) ----
+// what the two image read-outs ask first
+static int temporal_have_image(gsp_context* ctx, const char* who, const void* out_ptr) {
+  int rc = temporal_have_history(ctx, who, out_ptr);
+  if (rc != GSP_OK) return rc;
+  if (!ctx->tp_done) {
+    ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since gsp_frame_begin";
+    return GSP_ERR_INVALID;
+  }
+  return GSP_OK;
+}
+
+// queues the re-modulated newest history into `dst` (device, 16-byte aligned) on ctx->stream
+static int temporal_image_run(gsp_context* ctx, void* dst) {
+  const uint64_t n = (uint64_t)ctx->tp_width * ctx->tp_height;
+  if (n == 0) return GSP_OK;
+  const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)ctx->num_cus * 8));
+  hipLaunchKernelGGL(k_illum_image, dim3(pgrid), dim3(kBlock), 0, ctx->stream, (const v4f*)ctx->tp_h[ctx->tp_cur].p, (const v4f*)ctx->feat_albedo.p, n,
+                     (v4f*)dst);
+  CTX_TRY(ctx, hipGetLastError());
+  return GSP_OK;
+}
+
+extern "C" {
+
+int gsp_temporal_demodulate(gsp_context* ctx, int on) {
+  if (!ctx) return GSP_ERR_INVALID;
+  const bool want = on != 0;
+  if (want == ctx->tp_demod) return GSP_OK;
+  ctx->tp_demod = want;
+  ctx->tp_valid = false;  // (a history of colour is no history of illumination)
+  return GSP_OK;
+}
+
+int gsp_download_temporal_image(gsp_context* ctx, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_image(ctx, "gsp_download_temporal_image", out);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
+  if (!ctx->tp_demod) return read_back_bytes(ctx, ctx->tp_h[ctx->tp_cur].p, bytes, out);
+  CTX_TRY(ctx, ctx->dn_out.ensure(std::max<uint64_t>(ctx->num_pixels, 1), &ctx->bytes));
+  rc = temporal_image_run(ctx, ctx->dn_out.p);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->dn_out.p, bytes, out);
+}
+
+int gsp_temporal_image_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_image(ctx, "gsp_temporal_image_to_device", dst);
+  if (rc != GSP_OK) return rc;
+  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
+  if (bytes < need) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->tp_demod) {
+    CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->tp_h[ctx->tp_cur].p, need, hipMemcpyDeviceToDevice, ctx->stream));  // (a copy: any alignment)
+  } else {
+    // the kernel stores 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
+    const bool direct = ((uintptr_t)dst & 15u) == 0;
+    if (!direct) CTX_TRY(ctx, ctx->dn_out.ensure(std::max<uint64_t>(ctx->num_pixels, 1), &ctx->bytes));
+    rc = temporal_image_run(ctx, direct ? dst : (void*)ctx->dn_out.p);
+    if (rc != GSP_OK) return rc;
+    if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, need, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+int gsp_temporal_svgf_feedback(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_temporal_svgf_feedback", out, nullptr, true, levels);
+  if (rc != GSP_OK) return rc;
+  if (out) return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+int gsp_temporal_svgf_feedback_to_device(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (dst && ctx->have_frame && bytes < ctx->num_pixels * sizeof(q4)) {
+    ctx->err = "destination too small";
+    return GSP_ERR_INVALID;
+  }
+  // the kernels store 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
+  const bool direct = dst && ((uintptr_t)dst & 15u) == 0;
+  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_temporal_svgf_feedback_to_device", dst, direct ? dst : nullptr, true, levels);
+  if (rc != GSP_OK) return rc;
+  if (dst && !direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), hipMemcpyDeviceToDevice, ctx->stream));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
 }
 
 }  // extern "C"

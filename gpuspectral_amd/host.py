@@ -99,6 +99,11 @@ def load():
     L.gsph_pathtracer_download_temporal_svgf.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp, u64]
     L.gsph_pathtracer_temporal_follow_instances.argtypes = [vp, C.c_int]
     L.gsph_pathtracer_download_temporal_motion.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_temporal_demodulate.argtypes = [vp, C.c_int]
+    L.gsph_pathtracer_download_temporal_image.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_temporal_image_to_device.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_temporal_svgf_feedback.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp, u64]
+    L.gsph_pathtracer_temporal_svgf_feedback_to_device.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp, u64]
     _LIB = L
     return L
 
@@ -409,6 +414,45 @@ class PathTracer:
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._check(self._L.gsph_pathtracer_download_temporal_motion(self._h, out.ctypes.data, out.size), "downloadTemporalMotion")
         return out
+
+    def temporal_demodulate(self, on=True):
+        """PathTracer::temporalDemodulate: the history accumulates colour / first-hit albedo (a change drops the history)."""
+        self._check(self._L.gsph_pathtracer_temporal_demodulate(self._h, 1 if on else 0), "temporalDemodulate")
+
+    def download_temporal_image(self):
+        """PathTracer::downloadTemporalImage: (h, w, 4) float32, the history as a viewer shows it; .w = the history length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_temporal_image(self._h, out.ctypes.data, out.size), "downloadTemporalImage")
+        return out
+
+    def temporal_image_to_device(self, dst, nbytes=None):
+        """PathTracer::temporalImageToDevice: dst = a torch tensor on the device, or a device pointer with nbytes."""
+        if hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsph_pathtracer_temporal_image_to_device(self._h, ptr, nbytes), "temporalImageToDevice")
+
+    def temporal_svgf_feedback(self, denoise=None, svgf=None, levels=1, out=True):
+        """PathTracer::temporalSvgfFeedback: download_temporal_svgf whose first `levels` levels go back into the history (once per
+        temporal_accumulate).  out=False: no output, returns None."""
+        res = np.zeros((self.height, self.width, 4), np.float32) if out else None
+        self._check(self._L.gsph_pathtracer_temporal_svgf_feedback(self._h, C.byref(denoise) if denoise is not None else None,
+                                                                   C.byref(svgf) if svgf is not None else None, levels,
+                                                                   res.ctypes.data if out else None, res.size if out else 0), "temporalSvgfFeedback")
+        return res
+
+    def temporal_svgf_feedback_to_device(self, dst, nbytes=None, denoise=None, svgf=None, levels=1):
+        """PathTracer::temporalSvgfFeedbackToDevice: dst = a torch tensor, a device pointer with nbytes, or None (no output)."""
+        if dst is None:
+            ptr, nbytes = None, 0
+        elif hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsph_pathtracer_temporal_svgf_feedback_to_device(self._h, C.byref(denoise) if denoise is not None else None,
+                                                                             C.byref(svgf) if svgf is not None else None, levels, ptr, nbytes),
+                    "temporalSvgfFeedbackToDevice")
 
     def stats(self):
         s = abi.Stats()

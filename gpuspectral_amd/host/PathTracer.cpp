@@ -325,6 +325,28 @@ std::vector<float> PathTracer::downloadTemporalMotion() {
   return out;
 }
 
+void PathTracer::temporalDemodulate(bool on) { check(gsp_temporal_demodulate(ctx, on ? 1 : 0), "gsp_temporal_demodulate"); }
+
+std::vector<float> PathTracer::downloadTemporalImage() {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_temporal_image(ctx, out.data()), "gsp_download_temporal_image");
+  return out;
+}
+
+void PathTracer::temporalImageToDevice(void* deviceDst, uint64_t bytes) {
+  check(gsp_temporal_image_to_device(ctx, deviceDst, bytes), "gsp_temporal_image_to_device");
+}
+
+std::vector<float> PathTracer::temporalSvgfFeedback(const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, bool wantOutput) {
+  std::vector<float> out(wantOutput ? (size_t)width * height * 4 : 0);
+  check(gsp_temporal_svgf_feedback(ctx, denoise, svgf, levels, wantOutput ? out.data() : nullptr), "gsp_temporal_svgf_feedback");
+  return out;
+}
+
+void PathTracer::temporalSvgfFeedbackToDevice(const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, void* deviceDst, uint64_t bytes) {
+  check(gsp_temporal_svgf_feedback_to_device(ctx, denoise, svgf, levels, deviceDst, bytes), "gsp_temporal_svgf_feedback_to_device");
+}
+
 void PathTracer::nextFrame() {
   featureTimestamp = timestamp;  // (the feature samples of the new frame are those of its beauty samples)
   check(gsp_frame_begin(ctx, width, height, pixelIds.empty() ? nullptr : pixelIds.data(), pixelIds.size()), "gsp_frame_begin");

@@ -127,6 +127,16 @@ class PathTracer : public RenderPassCreator {
   // the motion plane {dx, dy, kept weight, class} of the newest accumulate.
   void temporalFollowInstances(bool on);
   std::vector<float> downloadTemporalMotion();
+  // Illumination history (gpuspectral_pt.h "Illumination history"): temporalDemodulate(true) makes the history accumulate colour /
+  // first-hit albedo (a change of the value drops the history); downloadTemporalImage / temporalImageToDevice are what a viewer
+  // shows of it -- re-modulated by this frame's albedo, or the history itself with demodulation off -- and need this frame's
+  // temporalAccumulate.  temporalSvgfFeedback is downloadTemporalSvgf that also writes the output of its first `levels` levels
+  // into the history (once per temporalAccumulate; wantOutput = false: nothing is read back, the vector is empty).
+  void temporalDemodulate(bool on);
+  std::vector<float> downloadTemporalImage();
+  void temporalImageToDevice(void* deviceDst, uint64_t bytes);
+  std::vector<float> temporalSvgfFeedback(const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, bool wantOutput = true);
+  void temporalSvgfFeedbackToDevice(const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, void* deviceDst, uint64_t bytes);
   void nextFrame();  // a new frame (accumulate buffer and feature planes cleared) whose samples continue the timestamp sequence
   void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }

@@ -370,6 +370,32 @@ int gsph_pathtracer_download_temporal_motion(void* pt, float* out, uint64_t floa
     std::memcpy(out, img.data(), img.size() * sizeof(float));
   });
 }
+// illumination history of a PathTracer (gpuspectral_pt.h "Illumination history"); out may be NULL for the feedback (no output)
+int gsph_pathtracer_temporal_demodulate(void* pt, int on) {
+  return guard([&] { ((PathTracer*)pt)->temporalDemodulate(on != 0); });
+}
+int gsph_pathtracer_download_temporal_image(void* pt, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTemporalImage();
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_temporal_image_to_device(void* pt, void* device_dst, uint64_t bytes) {
+  return guard([&] { ((PathTracer*)pt)->temporalImageToDevice(device_dst, bytes); });
+}
+int gsph_pathtracer_temporal_svgf_feedback(void* pt, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->temporalSvgfFeedback(denoise, svgf, levels, out != nullptr);
+    if (!out) return;
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_temporal_svgf_feedback_to_device(void* pt, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, void* device_dst,
+                                                     uint64_t bytes) {
+  return guard([&] { ((PathTracer*)pt)->temporalSvgfFeedbackToDevice(denoise, svgf, levels, device_dst, bytes); });
+}
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {
     std::vector<uint8_t> v;

@@ -30,6 +30,10 @@
 //   --temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm] (with --temporal): the history follows moved instances
 //   (gpuspectral_pt.h "Temporal accumulation: moved instances"); --temporal-move translates render object INST by (DX, DY, DZ)
 //   between frames, --motion writes the motion plane of the last frame as {dx, dy, class} (a PFM holds three channels).
+//   --temporal-demodulate (with --temporal): the history accumulates colour / first-hit albedo (gpuspectral_pt.h "Illumination
+//   history") and out.pfm of --temporal receives the image read-out (the history re-modulated by the last frame's albedo).
+//   --svgf-feedback LEVELS (with --svgf): on every frame of --temporal-frames the output of the filter's first LEVELS levels is
+//   written back into the history (gsp_temporal_svgf_feedback); the files of --temporal and --denoise show the fed-back history.
 //   --svgf out.pfm [--svgf-sigma S] [--svgf-min-history N] (with --temporal): the history keeps its luminance moments and out.pfm
 //   receives its variance-guided filter (gpuspectral_pt.h "Variance-guided filter"; S = sigma_variance, inf = the term off; N =
 //   2..65536), with the levels and guide sigmas of --denoise-iterations / --denoise-sigma where --denoise is given.
@@ -72,6 +76,8 @@ int main(int argc, char** argv) {
   long temporalMoveInst = 0;
   float temporalMoveBy[3] = {0.0f, 0.0f, 0.0f};
   std::string motionPath;
+  bool temporalDemodulate = false;
+  long svgfFeedback = 0;  // (0 = not given)
   std::string svgfPath;
   gsp_svgf svgf{};
   svgf.struct_size = (uint32_t)sizeof(gsp_svgf);
@@ -147,7 +153,16 @@ int main(int argc, char** argv) {
       }
       temporalMove = true, used = 2;
     } else if (flag == "--motion" && argc > 2) motionPath = argv[2], used = 2;
-    else if (flag == "--svgf" && argc > 2) svgfPath = argv[2], used = 2;
+    else if (flag == "--temporal-demodulate") temporalDemodulate = true, used = 1;
+    else if (flag == "--svgf-feedback" && argc > 2) {
+      char* end = nullptr;
+      svgfFeedback = std::strtol(argv[2], &end, 10);
+      if (end == argv[2] || *end != 0 || svgfFeedback < 1 || svgfFeedback > 8) {
+        std::fprintf(stderr, "gsp_render: bad svgf feedback '%s' (expected the number of levels fed back, 1..8 and at most the filter's iterations)\n", argv[2]);
+        return 2;
+      }
+      used = 2;
+    } else if (flag == "--svgf" && argc > 2) svgfPath = argv[2], used = 2;
     else if (flag == "--svgf-sigma" && argc > 2) {
       if (std::string(argv[2]) == "inf") svgf.sigma_variance = INFINITY;
       else if (!parseFloat(argv[2], svgf.sigma_variance) || !(svgf.sigma_variance > 0.0f)) {
@@ -320,6 +335,10 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --temporal-move and --motion need --temporal-follow\n");
     return 2;
   }
+  if (temporalPath.empty() && temporalDemodulate) {
+    std::fprintf(stderr, "gsp_render: --temporal-demodulate needs --temporal out.pfm\n");
+    return 2;
+  }
   if (svgfPath.empty() && svgfOptions) {
     std::fprintf(stderr, "gsp_render: --svgf-sigma and --svgf-min-history need --svgf out.pfm\n");
     return 2;
@@ -329,7 +348,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -367,6 +386,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   try {
+    if (svgfFeedback && svgfPath.empty()) throw std::runtime_error("--svgf-feedback needs --svgf out.pfm (it feeds the filter's first levels back into the history)");
     Scene scene = loadScene(argv[1], "", options);
     for (auto& w : scene.warnings) std::fprintf(stderr, "WARN: %s\n", w.c_str());
     // thin lens: the scene's (--scene-lens), overridden flag by flag
@@ -407,6 +427,7 @@ int main(int argc, char** argv) {
       pt.params.pixel_filter_param = filterParam;
       if (!svgfPath.empty()) pt.temporalTrackMoments(true);  // (before the first accumulate: moments and history of one age)
       if (temporalFollow) pt.temporalFollowInstances(true);
+      if (temporalDemodulate) pt.temporalDemodulate(true);
       if (temporalMove && (size_t)temporalMoveInst >= scene.renderObjects.size())
         throw std::runtime_error("--temporal-move: the scene has " + std::to_string(scene.renderObjects.size()) + " render objects, there is no object " +
                                  std::to_string(temporalMoveInst));
@@ -416,6 +437,7 @@ int main(int argc, char** argv) {
         pt.render(scene, spp);
         pt.renderFeatures(scene, spp);
         pt.temporalAccumulate();
+        if (svgfFeedback) pt.temporalSvgfFeedback(&denoise, &svgf, (uint32_t)svgfFeedback, false);
         const float a = temporalOrbit * 3.14159265358979323846f / 180.0f, cs = std::cos(a), sn = std::sin(a);
         const mat4 m = scene.camera.getToWorld();
         mat4 r = m;
@@ -449,9 +471,10 @@ int main(int argc, char** argv) {
       if (!temporalPath.empty()) {  // the last frame into the history, on the planes above or on a pass of its own
         if (featuresPrefix.empty() && denoisePath.empty()) pt.renderFeatures(scene, spp);
         pt.temporalAccumulate();
-        temporal = pt.downloadTemporal();
+        if (svgfFeedback) temporalSvgf = pt.temporalSvgfFeedback(&denoise, &svgf, (uint32_t)svgfFeedback);  // (first: the files below show the fed-back history)
+        temporal = temporalDemodulate ? pt.downloadTemporalImage() : pt.downloadTemporal();
         if (!denoisePath.empty()) temporalDenoised = pt.downloadTemporalDenoised(&denoise);
-        if (!svgfPath.empty()) temporalSvgf = pt.downloadTemporalSvgf(&denoise, &svgf);
+        if (!svgfPath.empty() && !svgfFeedback) temporalSvgf = pt.downloadTemporalSvgf(&denoise, &svgf);
         if (!motionPath.empty()) motion = pt.downloadTemporalMotion();
         for (size_t i = 3; i < temporal.size(); i += 4) temporalLength += temporal[i];
         temporalLength /= (double)width * height;
@@ -523,6 +546,10 @@ int main(int argc, char** argv) {
       }
       std::printf("temporal: %d frame%s of %u spp, %g degrees per frame, mean history length %.2f -> %s%s%s\n", temporalFrames, temporalFrames == 1 ? "" : "s",
                   spp, (double)temporalOrbit, temporalLength, temporalPath.c_str(), dn.empty() ? "" : ", ", dn.c_str());
+      if (temporalDemodulate) std::printf("temporal: the history holds illumination (colour / albedo); %s is its image read-out\n", temporalPath.c_str());
+      if (svgfFeedback)
+        std::printf("svgf feedback: the first %ld level%s fed back into the history on each of %d frame%s\n", svgfFeedback, svgfFeedback == 1 ? "" : "s",
+                    temporalFrames, temporalFrames == 1 ? "" : "s");
       if (!motionPath.empty()) {
         size_t followed = 0;
         for (size_t i = 3; i < motion.size(); i += 4) {

@@ -63,6 +63,11 @@ EXPORTS = (
     "gsp_temporal_follow_instances",
     "gsp_download_temporal_motion",
     "gsp_temporal_motion_to_device",
+    "gsp_temporal_demodulate",
+    "gsp_download_temporal_image",
+    "gsp_temporal_image_to_device",
+    "gsp_temporal_svgf_feedback",
+    "gsp_temporal_svgf_feedback_to_device",
     "gsp_frame_sample_base",
     "gsp_get_stats",
     "gsp_reset_stats",
@@ -174,6 +179,11 @@ def load():
     L.gsp_temporal_follow_instances.argtypes = [vp, C.c_int]
     L.gsp_download_temporal_motion.argtypes = [vp, vp]
     L.gsp_temporal_motion_to_device.argtypes = [vp, vp, u64]
+    L.gsp_temporal_demodulate.argtypes = [vp, C.c_int]
+    L.gsp_download_temporal_image.argtypes = [vp, vp]
+    L.gsp_temporal_image_to_device.argtypes = [vp, vp, u64]
+    L.gsp_temporal_svgf_feedback.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp]
+    L.gsp_temporal_svgf_feedback_to_device.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp, u64]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -224,7 +234,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -542,6 +552,49 @@ class Context:
         else:
             ptr = dst
         self._check(self._L.gsp_temporal_motion_to_device(self._h, ptr, nbytes), "gsp_temporal_motion_to_device")
+
+    # ---- illumination history (gpuspectral_pt.h "Illumination history") ----
+    def temporal_demodulate(self, on=True):
+        """gsp_temporal_demodulate: the history accumulates colour / first-hit albedo; a change drops the history."""
+        self._check(self._L.gsp_temporal_demodulate(self._h, 1 if on else 0), "gsp_temporal_demodulate")
+
+    def download_temporal_image(self):
+        """gsp_download_temporal_image: what a viewer shows of the newest history -- re-modulated by this frame's albedo while
+        demodulation is on, the history itself otherwise; (height, width, 4) float32, .w = the history length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_temporal_image(self._h, out.ctypes.data), "gsp_download_temporal_image")
+        return out
+
+    def temporal_image_to_device(self, dst, nbytes=None):
+        """gsp_temporal_image_to_device: the same into device memory, width*height*16 bytes.  dst: a torch tensor on the context's
+        device (its bytes from its storage offset on), or a device pointer with nbytes."""
+        if hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsp_temporal_image_to_device(self._h, ptr, nbytes), "gsp_temporal_image_to_device")
+
+    def temporal_svgf_feedback(self, denoise=None, svgf=None, levels=1, out=True):
+        """gsp_temporal_svgf_feedback: download_temporal_svgf, and the output of the first `levels` levels becomes the colour of
+        the newest history (once per temporal_accumulate).  out=False passes NULL: no output, returns None."""
+        res = np.zeros((self.height, self.width, 4), np.float32) if out else None
+        self._check(self._L.gsp_temporal_svgf_feedback(self._h, C.byref(denoise) if denoise is not None else None,
+                                                       C.byref(svgf) if svgf is not None else None, levels, res.ctypes.data if out else None),
+                    "gsp_temporal_svgf_feedback")
+        return res
+
+    def temporal_svgf_feedback_to_device(self, dst, nbytes=None, denoise=None, svgf=None, levels=1):
+        """gsp_temporal_svgf_feedback_to_device: the same with the output in device memory.  dst: a torch tensor, a device pointer
+        with nbytes, or None (no output)."""
+        if dst is None:
+            ptr, nbytes = None, 0
+        elif hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsp_temporal_svgf_feedback_to_device(self._h, C.byref(denoise) if denoise is not None else None,
+                                                                 C.byref(svgf) if svgf is not None else None, levels, ptr, nbytes),
+                    "gsp_temporal_svgf_feedback_to_device")
 
     def pixel_stats(self):
         """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of

@@ -77,7 +77,9 @@ extern "C" {
                                 gsp_temporal_track_moments, gsp_download_temporal_moments, gsp_download_temporal_svgf,
                                 gsp_temporal_svgf_to_device, gsp_download_temporal_svgf_display (see "Variance-guided filter");
                                 gsp_temporal_follow_instances, gsp_download_temporal_motion, gsp_temporal_motion_to_device
-                                (see "Temporal accumulation: moved instances") */
+                                (see "Temporal accumulation: moved instances");
+                                gsp_temporal_demodulate, gsp_download_temporal_image, gsp_temporal_image_to_device,
+                                gsp_temporal_svgf_feedback, gsp_temporal_svgf_feedback_to_device (see "Illumination history") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -828,7 +830,7 @@ int gsp_download_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, 
  * Out of scope.  By default the world is taken as static between two frames: an instance that moved is handled only by rejection
  * (the instance-index, depth and normal tests); "Temporal accumulation: moved instances" below follows it.  There are no gsp_multi_* variants: a
  * share has no neighbours, and gathering the ids plane is a change of its own -- a frame begun with pixel_ids is refused.  The
- * filtered output is not fed back into the history.
+ * filtered output is not fed back into the history by the calls of this section ("Illumination history" below adds that).
  */
 typedef struct gsp_temporal {
   uint32_t struct_size; /* sizeof(gsp_temporal) of the host's header; same rule as gsp_denoise (fields beyond it are 0; NULL and
@@ -859,7 +861,8 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal);
 int gsp_temporal_reset(gsp_context* ctx);
 /* The four read-outs below return GSP_ERR_INVALID when no gsp_temporal_accumulate has succeeded since the history was last
  * invalidated (or since the context was made). */
-/* H of the newest set: width*height*4 floats, .w = the history length.  Through the staged read-back. */
+/* H of the newest set as stored: width*height*4 floats, .w = the history length.  Through the staged read-back.  With
+ * gsp_temporal_demodulate on, H.rgb is illumination (see "Illumination history"; gsp_download_temporal_image is the image). */
 int gsp_download_temporal(gsp_context* ctx, float* out_rgba);
 /* The same into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
 int gsp_temporal_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
@@ -918,7 +921,8 @@ int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* 
  * per pixel, allocated by the first call.  The calls change no state of the frame or of the history.  GSP_ERR_INVALID: what
  * gsp_download_temporal_denoised refuses; tracking off; min_history 1 or above 65536; a negative or NaN sigma_variance.
  *
- * Out of scope.  The filtered frame is not fed back into the history; there are no gsp_multi_* variants.
+ * Out of scope.  These calls do not feed the filtered frame back into the history (gsp_temporal_svgf_feedback, "Illumination
+ * history" below, does); there are no gsp_multi_* variants.
  */
 typedef struct gsp_svgf {
   uint32_t struct_size; /* sizeof(gsp_svgf) of the host's header; same rule as gsp_denoise (NULL and struct_size 0 = every default) */
@@ -996,6 +1000,71 @@ int gsp_temporal_follow_instances(gsp_context* ctx, int on);
 int gsp_download_temporal_motion(gsp_context* ctx, float* out_rgba);
 /* The same into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
 int gsp_temporal_motion_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
+
+/*
+ * Illumination history.  The two parts of SVGF that decide what a 1-spp viewer shows after a few frames: the history accumulates
+ * the frame's colour divided by its first-hit albedo (illumination is smooth where textures are not, so the four bilinear taps
+ * stop low-passing every texel edge once per frame), and the output of the filter's first level(s) is written back into the
+ * history, so that the next frame starts from a filtered estimate.  Both are opt-in; without them every call of the sections
+ * above runs the kernels it runs without this section and returns the same bits.  Arithmetic is float32 in the order written
+ * (no contraction); / is correctly rounded.
+ *
+ * Demodulation.  gsp_temporal_demodulate(ctx, on) -- context state, off by default; a CHANGE of the value clears history_valid; a
+ * call with the current value does nothing.  It allocates no plane: H then holds illumination in the same 16 bytes.  With it on,
+ * gsp_temporal_accumulate forms per pixel (e, A) = "Denoiser: Prepare" of this frame's accumulate record c and albedo record:
+ *     a'_k = albedo.k + (1 - cov);   A_k = max(a'_k, 0.01f);   e.k = c.k / A_k;   L = the luminance of e
+ *     u = c.r, c.g, c.b finite and e.r, e.g, e.b finite        (the second half guards a quotient that overflows)
+ * and "Temporal accumulation: Blend", "Variance-guided filter: 1. Moments" and "Temporal accumulation: moved instances" apply as
+ * written with u for "c finite" and e.k for c.k:
+ *     with history, u:         H'.k = prev.k + (e.k - prev.k) * a,  H'.len = N
+ *     with history, not u:     H' = prev, the length capped as there
+ *     without history, u:      H' = {e.r, e.g, e.b, 1}
+ *     without history, not u:  H' = {c.r, c.g, c.b, 0}            (the raw record: nobody's history)
+ * l of the moments already is L, the luminance of e, so M's formulas do not change (their "c finite" is u).  Steps 1-7, the
+ * taps, their weights and tests, len, G', I' and the motion plane V are untouched: demodulation composes with
+ * gsp_temporal_track_moments and gsp_temporal_follow_instances in every combination.
+ *
+ * Read-outs.  gsp_download_temporal and gsp_temporal_to_device return H as stored: illumination while demodulation is on.
+ * gsp_download_temporal_image / gsp_temporal_image_to_device return what a viewer shows.  With demodulation on,
+ *     out.k = H.k * A_k  where H.len > 0;   out = H as stored  where H.len == 0;   out.w = H.len
+ * with A from THIS frame's albedo record; through a scratch plane of 16 bytes per pixel (the denoiser's output plane) where the
+ * result is not written straight into an aligned destination.  With demodulation off they return H bit for bit, so one viewer
+ * loop serves both settings.  Both need a gsp_temporal_accumulate in the current frame -- otherwise the albedo plane belongs to
+ * another frame -- and return GSP_ERR_INVALID without one; null pointer and size are refused as by gsp_download_temporal /
+ * gsp_temporal_to_device.
+ *
+ * Filters on a demodulated history (gsp_download_temporal_denoised*, gsp_*_temporal_svgf*, the feedback calls below).  Prepare
+ * takes e = H.rgb as it is, valid = H's three channels finite, A and a' from the albedo record as always, L from e.  Everything
+ * after Prepare is unchanged: the output is e_final.k * A_k for a valid pixel and H's record bit for bit for an invalid one,
+ * out.w = H.len.
+ *
+ * Feedback.  gsp_temporal_svgf_feedback / _to_device run the variance-guided filter exactly as gsp_download_temporal_svgf /
+ * gsp_temporal_svgf_to_device do (validation, defaults, scratch; tracking must be on) and, in addition, overwrite the colour
+ * of the NEWEST history set with the output of the first `levels` levels, e_after = E of level levels - 1:
+ *     valid pixel, demodulation on:    H.k = e_after.k
+ *     valid pixel, demodulation off:   H.k = e_after.k * A_k
+ * H.len, G, I, M, V, every invalid pixel and the older set keep their bits.  levels must be within 1 .. iterations, the
+ * iterations being those the call resolves (5 for gsp_denoise.iterations = 0).  The call's output -- out_rgba / device_dst may
+ * be NULL: then there is none, and the levels after the fed-back one are not run -- is the full filter of the history as it was
+ * before the write: bit for bit what gsp_download_temporal_svgf would have returned in its place.  At most one feedback per
+ * accumulate: it needs a gsp_temporal_accumulate in the current frame, and a second call before the next one is
+ * GSP_ERR_INVALID ("... fed back already"): a history filtered twice is not what anyone means.
+ *
+ * Limits.  After a feedback every read-out of H, and the next accumulate, sees the fed-back history.  M is not filtered: the
+ * variance it gives then describes the unfiltered history and is an upper bound of the fed-back one's.  Out of scope:
+ * gsp_multi_* variants, separate direct and indirect histories, temporal gradients (A-SVGF).
+ */
+/* on != 0: the history holds illumination.  Never fails on a context; frees nothing. */
+int gsp_temporal_demodulate(gsp_context* ctx, int on);
+/* The image of the newest history (see "Read-outs"): width*height*4 floats, .w = the history length. */
+int gsp_download_temporal_image(gsp_context* ctx, float* out_rgba);
+/* The same into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
+int gsp_temporal_image_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
+/* gsp_download_temporal_svgf plus the feedback of its first `levels` levels into the newest history. */
+int gsp_temporal_svgf_feedback(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, float* out_rgba /* may be NULL */);
+/* gsp_temporal_svgf_to_device plus the feedback; `bytes` is checked when device_dst is not NULL. */
+int gsp_temporal_svgf_feedback_to_device(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels,
+                                         void* device_dst /* may be NULL */, uint64_t bytes);
 
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
