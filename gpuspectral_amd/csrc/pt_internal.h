@@ -93,13 +93,6 @@ __attribute__((visibility("hidden"))) hipError_t denoise_run(hipStream_t stream,
                                                              uint32_t width, uint32_t height, const DenoiseConsts& k, void* e0, void* e1, void* a, void* out,
                                                              bool illum = false);
 
-// ---- temporal accumulation (pt_temporal.h) on a full frame of k.cur.width x k.cur.height: `accum`, `albedo`, `geom`, `ids` are the
-// frame's 16-byte planes, {h, g, i}_prev the history set read (not read when k.history_valid == 0) and {h, g, i}_out the set
-// written (16, 16 and 4 bytes per pixel).  Queues one launch of k_temporal_reproject on `stream`; does not synchronise.
-__attribute__((visibility("hidden"))) hipError_t temporal_run(hipStream_t stream, const void* accum, const void* albedo, const void* geom, const void* ids,
-                                                              const void* h_prev, const void* g_prev, const void* i_prev, void* h_out, void* g_out,
-                                                              void* i_out, const TemporalConsts& k);
-
 // Bakes the instances' triangles to world space and builds the wide BVH (PLOC + reinsertion + collapse) on `stream`.
 // Returns GSP_OK or an error code with `err` set.
 int build_bvh(hipStream_t stream, const BuildInput& in, DeviceBvh& out, std::string& err);

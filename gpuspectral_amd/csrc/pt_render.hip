@@ -545,4 +545,4 @@ void gsp_ctx_destroy(gsp_context* ctx) {
 }
 
 #include "pt_render_scene.inc"     // scene upload and per-frame edits
-#include "pt_render_pipeline.inc"  // the streaming pipeline and the rest of the C ABI
+#include "pt_render_pipeline.inc"  // the streaming pipeline and the rest of the C ABI (includes pt_render_post.inc: the stages behind the tracer)

@@ -1,7 +1,8 @@
 // pt_render_kernels.inc -- part of the translation unit pt_render.hip (included there; not compiled on its own).
 // The DEVICE side of the wavefront tracer: queue layouts, the ray sources / result sinks of k_trace (pt_wavetrace.h), k_generate,
 // k_shade, k_finish, k_resolve, the table / uv bake kernels, and DevBuf.  Host code: pt_render.hip (context, options),
-// pt_render_scene.inc (upload + per-frame edits), pt_render_pipeline.inc (the streaming pipeline + the rest of the C ABI).
+// pt_render_scene.inc (upload + per-frame edits), pt_render_pipeline.inc (the streaming pipeline + the rest of the C ABI),
+// pt_render_post.inc (the stages behind the path tracer: LDR film, denoiser, temporal accumulation, filters).
 
 namespace gsp {
 

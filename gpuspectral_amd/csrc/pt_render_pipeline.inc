@@ -1,6 +1,7 @@
 // pt_render_pipeline.inc -- part of the translation unit pt_render.hip (included there; not compiled on its own).
 // The streaming path pool: ensure_pool, lane_enqueue / lane_collect (one iteration = extend, shade, connect over the queues),
-// pipeline_run; gsp_render, gsp_sync, the read-back calls, statistics, gsp_trace.  (Continues the extern "C" block.)
+// pipeline_run; gsp_render, gsp_sync, the read-back calls, statistics, gsp_trace.  (Continues the extern "C" block.)  The LDR film,
+// the denoiser, temporal accumulation and its filters are in pt_render_post.inc, included in front of gsp_debug_visit_histograms.
 
 static int ensure_pool(gsp_context* ctx, gsp_context::Lane& L, uint64_t cap, uint64_t result_entries) {
   if (result_entries > L.result_cap) {
@@ -536,6 +537,16 @@ int gsp_render(gsp_context* ctx, const gsp_render_params* rp_host) {
   if (adaptive) return render_adaptive(ctx, rp);
   ctx->frame_mode = gsp_context::kFrameUniform;
   return render_enqueue(ctx, rp);
+}
+
+int gsp_frame_sample_base(gsp_context* ctx, uint32_t base) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (!ctx->have_frame || ctx->frame_mode != gsp_context::kFrameUndecided) {
+    ctx->err = "gsp_frame_sample_base belongs between gsp_frame_begin and the frame's first gsp_render";
+    return GSP_ERR_INVALID;
+  }
+  ctx->sample_base = base;
+  return GSP_OK;
 }
 
 // Queues rp->spp samples of every pixel the lanes sample (all owned pixels, or an adaptive frame's active lists) without waiting
@@ -1236,827 +1247,13 @@ int gsp_focus_distance(gsp_context* ctx, uint32_t width, uint32_t height, float 
   return GSP_OK;
 }
 
-
 }  // extern "C"
 
-// ---- LDR film (include/gpuspectral_pt.h, "LDR film"; per-pixel code: pt_display.h) ----
-hipError_t gsp::display_measure(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, DisplayStatsRec* d_rec, DisplayStatsRec* h_rec,
-                                gsp_luminance* out) {
-  hipError_t e = hipMemsetAsync(d_rec, 0, sizeof(DisplayStatsRec), stream);
-  if (e != hipSuccess) return e;
-  if (n) {
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 4));
-    hipLaunchKernelGGL(k_display_stats, dim3(grid), dim3(kBlock), 0, stream, (const v4f*)src, n, d_rec);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if ((e = hipMemcpyAsync(h_rec, d_rec, sizeof(DisplayStatsRec), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
-  if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-  *out = display_luminance(*h_rec);
-  return hipSuccess;
-}
-
-hipError_t gsp::display_map(hipStream_t stream, uint32_t num_cus, const void* src, uint64_t n, const DisplayConsts& k, uint32_t* dst) {
-  if (n == 0) return hipSuccess;
-  const uint64_t groups = (n + 3) / 4;
-  const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((groups + kBlock - 1) / kBlock, (uint64_t)num_cus * 8))), block(kBlock);
-  const v4f* s = (const v4f*)src;
-#define GSP_DISPLAY_LAUNCH(T, S) hipLaunchKernelGGL((k_display_map<T, S>), grid, block, 0, stream, s, n, k, dst)
-  if (k.srgb) {
-    if (k.tonemap == GSP_TONEMAP_ACES) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_ACES, true);
-    else if (k.tonemap == GSP_TONEMAP_REINHARD) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_REINHARD, true);
-    else GSP_DISPLAY_LAUNCH(GSP_TONEMAP_CLAMP, true);
-  } else {
-    if (k.tonemap == GSP_TONEMAP_ACES) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_ACES, false);
-    else if (k.tonemap == GSP_TONEMAP_REINHARD) GSP_DISPLAY_LAUNCH(GSP_TONEMAP_REINHARD, false);
-    else GSP_DISPLAY_LAUNCH(GSP_TONEMAP_CLAMP, false);
-  }
-#undef GSP_DISPLAY_LAUNCH
-  return hipGetLastError();
-}
-
-// gsp_peek's ordering: the folds queued so far finish, the paths in flight keep their state
-static int display_peek_sync(gsp_context* ctx, uint32_t* samples_folded) {
-  uint32_t folded = 0xffffffffu;
-  for (uint32_t l = 0; l < ctx->num_lanes; ++l) {
-    gsp_context::Lane& L = ctx->lanes[l];
-    if (L.num_pixels == 0) continue;
-    CTX_TRY(ctx, hipStreamSynchronize(L.stream));
-    folded = std::min(folded, ctx->pipe_active && L.pipe.active ? L.pipe.folded_end : ctx->folded_idle);
-  }
-  if (samples_folded) *samples_folded = folded == 0xffffffffu ? 0u : (folded >= ctx->sample_base ? folded - ctx->sample_base : folded);
-  return GSP_OK;
-}
-
-static int display_measure_ctx(gsp_context* ctx, gsp_luminance* out, const void* src = nullptr) {
-  CTX_TRY(ctx, ctx->display_rec.ensure(1, &ctx->bytes));
-  if (!ctx->h_display_rec) CTX_TRY(ctx, hipHostMalloc((void**)&ctx->h_display_rec, sizeof(DisplayStatsRec), hipHostMallocDefault));
-  CTX_TRY(ctx, display_measure(ctx->stream, (uint32_t)ctx->num_cus, src ? src : ctx->accum.p, ctx->num_pixels, ctx->display_rec.p, ctx->h_display_rec, out));
-  return GSP_OK;
-}
-
-// validates `display_host`, measures the frame where the display asks for it and queues the map of the compact accumulate
-// buffer (or of `src`: the denoised frame) into `dst` (device, 16-byte aligned; nullptr = the context's own RGBA8 buffer) on
-// ctx->stream
-static int display_run(gsp_context* ctx, const gsp_display* display_host, uint32_t* dst, const void* src = nullptr) {
-  gsp_display d;
-  if (const char* why = resolve_display(display_host, d)) {
-    ctx->err = why;
-    return GSP_ERR_INVALID;
-  }
-  gsp_luminance lum{};
-  if (display_needs_stats(d)) {
-    int rc = display_measure_ctx(ctx, &lum, src);
-    if (rc != GSP_OK) return rc;
-  }
-  if (!dst) {
-    CTX_TRY(ctx, ctx->display_out.ensure((ctx->num_pixels + 3) / 4 * 4, &ctx->bytes));
-    dst = ctx->display_out.p;
-  }
-  CTX_TRY(ctx, display_map(ctx->stream, (uint32_t)ctx->num_cus, src ? src : ctx->accum.p, ctx->num_pixels, display_consts(d, lum), dst));
-  return GSP_OK;
-}
-
-// ---- denoiser (include/gpuspectral_pt.h, "Denoiser"; per-pixel code: pt_denoise.h) ----
-hipError_t gsp::denoise_run(hipStream_t stream, uint32_t num_cus, const void* accum, const void* albedo, const void* geom, uint32_t width, uint32_t height,
-                            const DenoiseConsts& k, void* e0, void* e1, void* a, void* out, bool illum) {
-  const uint64_t n = (uint64_t)width * height;
-  if (n == 0) return hipSuccess;
-  const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 8));
-  if (illum) hipLaunchKernelGGL(k_illum_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)accum, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
-  else hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)accum, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH), block(kBlock);
-  v4f* E[2] = {(v4f*)e0, (v4f*)e1};
-  for (uint32_t i = 0; i < k.iterations; ++i) {
-    const bool last = i + 1 == k.iterations;
-    const v4f* in = E[i & 1u];
-    v4f* dst = last ? (v4f*)out : E[(i + 1u) & 1u];
-#define GSP_DENOISE_LAUNCH(S, LAST) \
-  hipLaunchKernelGGL((k_denoise_atrous<S, LAST>), grid, block, 0, stream, in, (const v4f*)a, (const v4f*)geom, (const v4f*)accum, dst, k, i, (int)width, (int)height)
-    // levels 0 and 1 (steps 1 and 2) stage tile + halo in LDS, the wider steps read their taps from global memory
-    if (i == 0) {
-      if (last) GSP_DENOISE_LAUNCH(1, true);
-      else GSP_DENOISE_LAUNCH(1, false);
-    } else if (i == 1) {
-      if (last) GSP_DENOISE_LAUNCH(2, true);
-      else GSP_DENOISE_LAUNCH(2, false);
-    } else {
-      if (last) GSP_DENOISE_LAUNCH(0, true);
-      else GSP_DENOISE_LAUNCH(0, false);
-    }
-#undef GSP_DENOISE_LAUNCH
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// Validates, completes the queued samples and queues the filter of the frame into `dst` (device, 16-byte aligned; nullptr = the
-// context's own buffer) on ctx->stream.  `out_ptr` is the caller's output pointer (checked for NULL only).
-static int denoise_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const char* who, const void* out_ptr, void* dst) {
-  if (!out_ptr) {
-    ctx->err = std::string(who) + ": null output pointer";
-    return GSP_ERR_INVALID;
-  }
-  if (!ctx->have_frame) {
-    ctx->err = std::string(who) + " needs gsp_frame_begin first";
-    return GSP_ERR_INVALID;
-  }
-  if (ctx->subset) {
-    ctx->err = std::string(who) + ": the frame was begun with pixel_ids; a share has no neighbours (use gsp_multi_download_denoised)";
-    return GSP_ERR_INVALID;
-  }
-  if (!ctx->features_rendered) {
-    ctx->err = std::string(who) + " needs a gsp_render_features call since gsp_frame_begin";
-    return GSP_ERR_INVALID;
-  }
-  DenoiseConsts k;
-  if (const char* why = resolve_denoise(denoise_host, k)) {
-    ctx->err = why;
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  {
-    int rc_ = pipeline_drain(ctx);
-    if (rc_ != GSP_OK) return rc_;
-  }
-  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
-  for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
-  CTX_TRY(ctx, denoise_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->width, ctx->height, k,
-                           ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, dst ? dst : (void*)ctx->dn_out.p));
-  return GSP_OK;
-}
+// The stages behind the path tracer.  Included here and not behind this file: kernel templates are instantiated in the order of
+// their first launch in the translation unit, and the k_trace<.., TestIO> of gsp_trace below stay the last of the device code.
+#include "pt_render_post.inc"
 
 extern "C" {
-
-int gsp_download_denoised(gsp_context* ctx, const gsp_denoise* denoise, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = denoise_ctx(ctx, denoise, "gsp_download_denoised", out, nullptr);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
-}
-
-int gsp_denoise_to_device(gsp_context* ctx, const gsp_denoise* denoise, void* dst, uint64_t bytes) {
-  if (!ctx) return GSP_ERR_INVALID;
-  if (dst && ctx->have_frame && bytes < ctx->num_pixels * sizeof(q4)) {
-    ctx->err = "destination too small";
-    return GSP_ERR_INVALID;
-  }
-  // the kernels store 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
-  const bool direct = ((uintptr_t)dst & 15u) == 0;
-  int rc = denoise_ctx(ctx, denoise, "gsp_denoise_to_device", dst, direct ? dst : nullptr);
-  if (rc != GSP_OK) return rc;
-  if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), hipMemcpyDeviceToDevice, ctx->stream));
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-int gsp_download_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  {  // (an invalid display is refused before anything is queued)
-    gsp_display d;
-    if (const char* why = resolve_display(display, d)) {
-      ctx->err = why;
-      return GSP_ERR_INVALID;
-    }
-  }
-  int rc = denoise_ctx(ctx, denoise, "gsp_download_denoised_display", out, nullptr);
-  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
-}
-
-}  // extern "C"
-
-// ---- temporal accumulation (include/gpuspectral_pt.h, "Temporal accumulation"; per-pixel code: pt_temporal.h) ----
-hipError_t gsp::temporal_run(hipStream_t stream, const void* accum, const void* albedo, const void* geom, const void* ids, const void* h_prev,
-                             const void* g_prev, const void* i_prev, void* h_out, void* g_out, void* i_out, const TemporalConsts& k) {
-  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
-  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
-  hipLaunchKernelGGL(k_temporal_reproject, grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids,
-                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (v4f*)h_out, (v4f*)g_out, (uint32_t*)i_out, k);
-  return hipGetLastError();
-}
-
-// ... with the moments plane beside the history (k_temporal_reproject_moments; pt_svgf.h)
-static hipError_t temporal_moments_run(hipStream_t stream, const void* accum, const void* albedo, const void* geom, const void* ids, const void* h_prev,
-                                       const void* g_prev, const void* i_prev, const void* m_prev, void* h_out, void* g_out, void* i_out, void* m_out,
-                                       const TemporalConsts& k) {
-  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
-  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
-  hipLaunchKernelGGL(k_temporal_reproject_moments, grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids,
-                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (const v4f*)m_prev, (v4f*)h_out, (v4f*)g_out, (uint32_t*)i_out,
-                     (v4f*)m_out, k);
-  return hipGetLastError();
-}
-
-// ... with the moved instances followed (k_temporal_reproject_follow; pt_motion.h): m_prev / m_out may be nullptr when !moments
-static hipError_t temporal_follow_run(hipStream_t stream, bool moments, const void* accum, const void* albedo, const void* geom, const void* ids,
-                                      const void* h_prev, const void* g_prev, const void* i_prev, const void* m_prev, const void* table, uint32_t num_records,
-                                      void* h_out, void* g_out, void* i_out, void* m_out, void* v_out, const TemporalConsts& k) {
-  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
-  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
-#define GSP_FOLLOW_LAUNCH(M)                                                                                                                       \
-  hipLaunchKernelGGL((k_temporal_reproject_follow<M>), grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids, \
-                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (const v4f*)m_prev, (const v4f*)table, num_records, (v4f*)h_out,     \
-                     (v4f*)g_out, (uint32_t*)i_out, (v4f*)m_out, (v4f*)v_out, k)
-  if (moments) GSP_FOLLOW_LAUNCH(true);
-  else GSP_FOLLOW_LAUNCH(false);
-#undef GSP_FOLLOW_LAUNCH
-  return hipGetLastError();
-}
-
-// ... with the frame demodulated (k_temporal_reproject_illum; pt_illum.h): temporal_run, temporal_moments_run or
-// temporal_follow_run by `moments` and `follow`; the planes a form does not have may be nullptr
-static hipError_t temporal_illum_run(hipStream_t stream, bool moments, bool follow, const void* accum, const void* albedo, const void* geom, const void* ids,
-                                     const void* h_prev, const void* g_prev, const void* i_prev, const void* m_prev, const void* table, uint32_t num_records,
-                                     void* h_out, void* g_out, void* i_out, void* m_out, void* v_out, const TemporalConsts& k) {
-  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
-  const dim3 grid((k.cur.width + kDnTileW - 1) / kDnTileW, (k.cur.height + kDnTileH - 1) / kDnTileH), block(kBlock);
-#define GSP_ILLUM_LAUNCH(M, F)                                                                                                                        \
-  hipLaunchKernelGGL((k_temporal_reproject_illum<M, F>), grid, block, 0, stream, (const v4f*)accum, (const v4f*)albedo, (const v4f*)geom, (const v4u*)ids, \
-                     (const v4f*)h_prev, (const v4f*)g_prev, (const uint32_t*)i_prev, (const v4f*)m_prev, (const v4f*)table, num_records, (v4f*)h_out,      \
-                     (v4f*)g_out, (uint32_t*)i_out, (v4f*)m_out, (v4f*)v_out, k)
-  if (follow) {
-    if (moments) GSP_ILLUM_LAUNCH(true, true);
-    else GSP_ILLUM_LAUNCH(false, true);
-  } else {
-    if (moments) GSP_ILLUM_LAUNCH(true, false);
-    else GSP_ILLUM_LAUNCH(false, false);
-  }
-#undef GSP_ILLUM_LAUNCH
-  return hipGetLastError();
-}
-
-// what every temporal read-out asks first (null_ok: the call may do without an output)
-static int temporal_have_history(gsp_context* ctx, const char* who, const void* out_ptr, bool null_ok = false) {
-  if (!out_ptr && !null_ok) {
-    ctx->err = std::string(who) + ": null output pointer";
-    return GSP_ERR_INVALID;
-  }
-  if (!ctx->tp_valid) {
-    ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since the history was last invalidated";
-    return GSP_ERR_INVALID;
-  }
-  return GSP_OK;
-}
-
-// Validates and queues the denoiser with the newest history as its colour source into `dst` (nullptr = the context's own buffer)
-static int temporal_denoise_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const char* who, const void* out_ptr) {
-  int rc = temporal_have_history(ctx, who, out_ptr);
-  if (rc != GSP_OK) return rc;
-  // (tp_valid: the history has the size of the frame -- gsp_frame_begin invalidates any other -- and the frame is a full one)
-  if (!ctx->have_frame || ctx->subset || !ctx->features_rendered) {
-    ctx->err = std::string(who) + " needs a full frame (no pixel_ids) and a gsp_render_features call since gsp_frame_begin";
-    return GSP_ERR_INVALID;
-  }
-  DenoiseConsts k;
-  if (const char* why = resolve_denoise(denoise_host, k)) {
-    ctx->err = why;
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
-  for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
-  CTX_TRY(ctx, denoise_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->tp_h[ctx->tp_cur].p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->width, ctx->height, k,
-                           ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, ctx->dn_out.p, ctx->tp_demod));
-  return GSP_OK;
-}
-
-extern "C" {
-
-int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
-  if (!ctx) return GSP_ERR_INVALID;
-  const char* who = "gsp_temporal_accumulate";
-  if (!ctx->have_frame) {
-    ctx->err = std::string(who) + " needs gsp_frame_begin first";
-    return GSP_ERR_INVALID;
-  }
-  if (ctx->subset) {
-    ctx->err = std::string(who) + ": the frame was begun with pixel_ids; a share has no neighbours and there is no multi-GPU variant";
-    return GSP_ERR_INVALID;
-  }
-  if (!ctx->features_rendered) {
-    ctx->err = std::string(who) + " needs a gsp_render_features call since gsp_frame_begin";
-    return GSP_ERR_INVALID;
-  }
-  if (ctx->tp_done) {
-    ctx->err = std::string(who) + ": the frame has been accumulated already (one call per gsp_frame_begin)";
-    return GSP_ERR_INVALID;
-  }
-  if (ctx->tp_follow && ctx->inst_edits != ctx->feat_inst_edits) {
-    ctx->err = std::string(who) + ": gsp_update_instances has changed the instances since the frame's gsp_render_features; with "
-               "gsp_temporal_follow_instances on, an edit belongs before the frame's gsp_render_features";
-    return GSP_ERR_INVALID;
-  }
-  TemporalParams tp;
-  if (const char* why = resolve_temporal(temporal, tp)) {
-    ctx->err = why;
-    return GSP_ERR_INVALID;
-  }
-  // (gsp_frame_begin has invalidated a history of another size)
-  TemporalConsts k;
-  if (const char* why = temporal_consts(ctx->camera, &ctx->tp_camera, ctx->tp_valid, ctx->width, ctx->height, tp, k)) {
-    ctx->err = std::string(who) + ": " + why;
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  {
-    int rc_ = pipeline_drain(ctx);
-    if (rc_ != GSP_OK) return rc_;
-  }
-  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
-  for (int s = 0; s < 2; ++s) {
-    CTX_TRY(ctx, ctx->tp_h[s].ensure(n, &ctx->bytes));
-    CTX_TRY(ctx, ctx->tp_g[s].ensure(n, &ctx->bytes));
-    CTX_TRY(ctx, ctx->tp_i[s].ensure(n, &ctx->bytes));
-    if (ctx->tp_moments) CTX_TRY(ctx, ctx->tp_m[s].ensure(n, &ctx->bytes));
-  }
-  const int from = ctx->tp_cur, to = from ^ 1;
-  std::vector<float> cur;  // (following: the instances' transforms of this frame)
-  if (ctx->tp_follow) {
-    // the records of the instances between the history's frame and this one: formed in the pinned buffer, copied on the stream
-    // in front of the launch.  Without a history (or without a snapshot of its transforms) the table is not read.
-    const uint32_t ni = (uint32_t)ctx->h_inst.size();
-    const bool have_prev = ctx->tp_valid && ctx->tp_xforms.size() == 16ull * ni;
-    if (!have_prev) k.history_valid = 0;
-    cur.resize(16ull * ni);
-    for (uint32_t i = 0; i < ni; ++i) std::memcpy(&cur[16ull * i], ctx->h_inst[i].transform, 16 * sizeof(float));
-    CTX_TRY(ctx, ctx->tp_v.ensure(n, &ctx->bytes));
-    CTX_TRY(ctx, ctx->tp_table.ensure((size_t)std::max<uint32_t>(ni, 1) * kMotionRecordQuads, &ctx->bytes));
-    if (ctx->h_motion_cap < std::max<uint32_t>(ni, 1)) {
-      if (ctx->h_motion) (void)hipHostFree(ctx->h_motion);
-      ctx->h_motion = nullptr;
-      ctx->h_motion_cap = 0;
-      CTX_TRY(ctx, hipHostMalloc((void**)&ctx->h_motion, (size_t)std::max<uint32_t>(ni, 1) * sizeof(MotionRecord), hipHostMallocDefault));
-      ctx->h_motion_cap = std::max<uint32_t>(ni, 1);
-    }
-    uint32_t records = 0;
-    if (k.history_valid && ni) {
-      motion_table(ctx->tp_xforms.data(), cur.data(), ni, ctx->h_motion);
-      CTX_TRY(ctx, hipMemcpyAsync(ctx->tp_table.p, ctx->h_motion, (size_t)ni * sizeof(MotionRecord), hipMemcpyHostToDevice, ctx->stream));
-      records = ni;
-    }
-    if (ctx->tp_demod)
-      CTX_TRY(ctx, temporal_illum_run(ctx->stream, ctx->tp_moments, true, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p,
-                                      ctx->tp_h[from].p, ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_table.p, records, ctx->tp_h[to].p,
-                                      ctx->tp_g[to].p, ctx->tp_i[to].p, ctx->tp_m[to].p, ctx->tp_v.p, k));
-    else
-      CTX_TRY(ctx, temporal_follow_run(ctx->stream, ctx->tp_moments, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
-                                     ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_table.p, records, ctx->tp_h[to].p, ctx->tp_g[to].p,
-                                     ctx->tp_i[to].p, ctx->tp_m[to].p, ctx->tp_v.p, k));
-  } else if (ctx->tp_demod)
-    CTX_TRY(ctx, temporal_illum_run(ctx->stream, ctx->tp_moments, false, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
-                                    ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, nullptr, 0u, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p,
-                                    ctx->tp_m[to].p, nullptr, k));
-  else if (ctx->tp_moments)
-    CTX_TRY(ctx, temporal_moments_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p,
-                                      ctx->tp_g[from].p, ctx->tp_i[from].p, ctx->tp_m[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p,
-                                      ctx->tp_m[to].p, k));
-  else
-    CTX_TRY(ctx, temporal_run(ctx->stream, ctx->accum.p, ctx->feat_albedo.p, ctx->feat_geom.p, ctx->feat_ids.p, ctx->tp_h[from].p, ctx->tp_g[from].p,
-                              ctx->tp_i[from].p, ctx->tp_h[to].p, ctx->tp_g[to].p, ctx->tp_i[to].p, k));
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (complete when the call returns: a camera or scene edit may follow at once)
-  ctx->tp_cur = to;
-  ctx->tp_camera = ctx->camera;
-  if (ctx->tp_follow) ctx->tp_xforms.swap(cur);
-  ctx->tp_width = ctx->width;
-  ctx->tp_height = ctx->height;
-  ctx->tp_valid = true;
-  ctx->tp_done = true;
-  ctx->tp_fed = false;  // (gsp_temporal_svgf_feedback: at most one per accumulate)
-  return GSP_OK;
-}
-
-int gsp_frame_sample_base(gsp_context* ctx, uint32_t base) {
-  if (!ctx) return GSP_ERR_INVALID;
-  if (!ctx->have_frame || ctx->frame_mode != gsp_context::kFrameUndecided) {
-    ctx->err = "gsp_frame_sample_base belongs between gsp_frame_begin and the frame's first gsp_render";
-    return GSP_ERR_INVALID;
-  }
-  ctx->sample_base = base;
-  return GSP_OK;
-}
-
-int gsp_temporal_reset(gsp_context* ctx) {
-  if (!ctx) return GSP_ERR_INVALID;
-  ctx->tp_valid = false;
-  return GSP_OK;
-}
-
-int gsp_download_temporal(gsp_context* ctx, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_have_history(ctx, "gsp_download_temporal", out);
-  if (rc != GSP_OK) return rc;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  return read_back_bytes(ctx, ctx->tp_h[ctx->tp_cur].p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
-}
-
-int gsp_temporal_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_have_history(ctx, "gsp_temporal_to_device", dst);
-  if (rc != GSP_OK) return rc;
-  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
-  if (bytes < need) {
-    ctx->err = "destination too small";
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->tp_h[ctx->tp_cur].p, need, hipMemcpyDeviceToDevice, ctx->stream));  // (a copy: any alignment)
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-int gsp_download_temporal_denoised(gsp_context* ctx, const gsp_denoise* denoise, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_denoise_ctx(ctx, denoise, "gsp_download_temporal_denoised", out);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
-}
-
-int gsp_download_temporal_denoised_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_display* display, uint32_t* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  {  // (an invalid display is refused before anything is queued)
-    gsp_display d;
-    if (const char* why = resolve_display(display, d)) {
-      ctx->err = why;
-      return GSP_ERR_INVALID;
-    }
-  }
-  int rc = temporal_denoise_ctx(ctx, denoise, "gsp_download_temporal_denoised_display", out);
-  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
-}
-
-}  // extern "C"
-
-// ---- variance-guided filter (include/gpuspectral_pt.h, "Variance-guided filter"; per-pixel code: pt_svgf.h) ----
-// The filter of the history `hist` with moments `moments` on a full frame: k_denoise_prepare, k_svgf_variance and k.iterations
-// launches of k_svgf_atrous on `stream`; does not synchronise.  e0, e1, a, out: 16 bytes per pixel; v0, v1: 4 bytes per pixel.
-// illum: hist is a demodulated history (k_illum_prepare for k_denoise_prepare).  fb_levels > 0 (gsp_temporal_svgf_feedback): level
-// fb_levels - 1 is k_svgf_atrous_feedback and writes its colour into `hist`; with !want_out the levels after it are not run.
-static hipError_t svgf_run(hipStream_t stream, uint32_t num_cus, void* hist, const void* moments, const void* albedo, const void* geom, uint32_t width,
-                           uint32_t height, const SvgfConsts& k, void* e0, void* e1, void* a, void* v0, void* v1, void* out, bool illum = false,
-                           uint32_t fb_levels = 0, bool want_out = true) {
-  const uint64_t n = (uint64_t)width * height;
-  if (n == 0) return hipSuccess;
-  const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)num_cus * 8));
-  if (illum) hipLaunchKernelGGL(k_illum_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)hist, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
-  else hipLaunchKernelGGL(k_denoise_prepare, dim3(pgrid), dim3(kBlock), 0, stream, (const v4f*)hist, (const v4f*)albedo, n, (v4f*)e0, (v4f*)a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const dim3 grid((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH), block(kBlock);
-  hipLaunchKernelGGL(k_svgf_variance, grid, block, 0, stream, (const v4f*)e0, (const v4f*)a, (const v4f*)geom, (const v4f*)hist, (const v4f*)moments,
-                     (float*)v0, k, (int)width, (int)height);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  v4f* E[2] = {(v4f*)e0, (v4f*)e1};
-  float* V[2] = {(float*)v0, (float*)v1};
-  const uint32_t run_levels = fb_levels && !want_out ? fb_levels : k.iterations;
-  for (uint32_t i = 0; i < run_levels; ++i) {
-    const bool last = i + 1 == k.iterations;
-    v4f* dst = last ? (v4f*)out : E[(i + 1u) & 1u];
-    if (fb_levels && i + 1 == fb_levels) {
-#define GSP_SVGF_FB_LAUNCH(S, LAST, D)                                                                                                                    \
-  hipLaunchKernelGGL((k_svgf_atrous_feedback<S, LAST, D>), grid, block, 0, stream, (const v4f*)E[i & 1u], (const v4f*)a, (const v4f*)geom,                  \
-                     (const float*)V[i & 1u], (v4f*)hist, dst, V[(i + 1u) & 1u], k, i, (int)width, (int)height)
-#define GSP_SVGF_FB_STEP(S)                        \
-  do {                                             \
-    if (last) {                                    \
-      if (illum) GSP_SVGF_FB_LAUNCH(S, true, true);  \
-      else GSP_SVGF_FB_LAUNCH(S, true, false);       \
-    } else {                                       \
-      if (illum) GSP_SVGF_FB_LAUNCH(S, false, true); \
-      else GSP_SVGF_FB_LAUNCH(S, false, false);      \
-    }                                              \
-  } while (0)
-      if (i == 0) GSP_SVGF_FB_STEP(1);
-      else if (i == 1) GSP_SVGF_FB_STEP(2);
-      else GSP_SVGF_FB_STEP(0);
-#undef GSP_SVGF_FB_STEP
-#undef GSP_SVGF_FB_LAUNCH
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      continue;
-    }
-#define GSP_SVGF_LAUNCH(S, LAST)                                                                                                                    \
-  hipLaunchKernelGGL((k_svgf_atrous<S, LAST>), grid, block, 0, stream, (const v4f*)E[i & 1u], (const v4f*)a, (const v4f*)geom, (const float*)V[i & 1u], \
-                     (const v4f*)hist, dst, V[(i + 1u) & 1u], k, i, (int)width, (int)height)
-    // as denoise_run: levels 0 and 1 stage tile + halo in LDS, the wider steps read their taps from global memory
-    if (i == 0) {
-      if (last) GSP_SVGF_LAUNCH(1, true);
-      else GSP_SVGF_LAUNCH(1, false);
-    } else if (i == 1) {
-      if (last) GSP_SVGF_LAUNCH(2, true);
-      else GSP_SVGF_LAUNCH(2, false);
-    } else {
-      if (last) GSP_SVGF_LAUNCH(0, true);
-      else GSP_SVGF_LAUNCH(0, false);
-    }
-#undef GSP_SVGF_LAUNCH
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// Validates and queues the filter into `dst` (device, 16-byte aligned; nullptr = the context's own buffer) on ctx->stream
-// fb: the call is a gsp_temporal_svgf_feedback of `fb_levels` levels -- out_ptr may be NULL (then nothing is written to dst), the
-// frame must have been accumulated and not fed back yet, and the newest history takes the colour of level fb_levels - 1
-static int svgf_ctx(gsp_context* ctx, const gsp_denoise* denoise_host, const gsp_svgf* svgf_host, const char* who, const void* out_ptr, void* dst,
-                    bool fb = false, uint32_t fb_levels = 0) {
-  int rc = temporal_have_history(ctx, who, out_ptr, fb);
-  if (rc != GSP_OK) return rc;
-  if (!ctx->tp_moments) {
-    ctx->err = std::string(who) + " needs gsp_temporal_track_moments(ctx, 1) before the history was accumulated";
-    return GSP_ERR_INVALID;
-  }
-  if (!ctx->have_frame || ctx->subset || !ctx->features_rendered) {
-    ctx->err = std::string(who) + " needs a full frame (no pixel_ids) and a gsp_render_features call since gsp_frame_begin";
-    return GSP_ERR_INVALID;
-  }
-  SvgfConsts k;
-  if (const char* why = resolve_svgf(denoise_host, svgf_host, k)) {
-    ctx->err = why;
-    return GSP_ERR_INVALID;
-  }
-  if (fb) {
-    if (fb_levels < 1 || fb_levels > k.iterations) {
-      ctx->err = std::string(who) + ": levels must be within 1 .. " + std::to_string(k.iterations) + " (the filter's iterations)";
-      return GSP_ERR_INVALID;
-    }
-    if (!ctx->tp_done) {
-      ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since gsp_frame_begin";
-      return GSP_ERR_INVALID;
-    }
-    if (ctx->tp_fed) {
-      ctx->err = std::string(who) + ": the history has been fed back already (one call per gsp_temporal_accumulate)";
-      return GSP_ERR_INVALID;
-    }
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
-  for (DevBuf<q4>* b : {&ctx->dn_e0, &ctx->dn_e1, &ctx->dn_a, &ctx->dn_out}) CTX_TRY(ctx, b->ensure(n, &ctx->bytes));
-  for (DevBuf<float>& b : ctx->sv_v) CTX_TRY(ctx, b.ensure(n, &ctx->bytes));
-  CTX_TRY(ctx, svgf_run(ctx->stream, (uint32_t)ctx->num_cus, ctx->tp_h[ctx->tp_cur].p, ctx->tp_m[ctx->tp_cur].p, ctx->feat_albedo.p, ctx->feat_geom.p,
-                        ctx->width, ctx->height, k, ctx->dn_e0.p, ctx->dn_e1.p, ctx->dn_a.p, ctx->sv_v[0].p, ctx->sv_v[1].p,
-                        dst ? dst : (void*)ctx->dn_out.p, ctx->tp_demod, fb ? fb_levels : 0u, !fb || out_ptr != nullptr));
-  if (fb) ctx->tp_fed = true;
-  return GSP_OK;
-}
-
-extern "C" {
-
-int gsp_temporal_track_moments(gsp_context* ctx, int on) {
-  if (!ctx) return GSP_ERR_INVALID;
-  const bool want = on != 0;
-  if (want == ctx->tp_moments) return GSP_OK;
-  ctx->tp_moments = want;
-  ctx->tp_valid = false;  // (moments and history have the same age)
-  return GSP_OK;
-}
-
-int gsp_temporal_follow_instances(gsp_context* ctx, int on) {
-  if (!ctx) return GSP_ERR_INVALID;
-  const bool want = on != 0;
-  if (want == ctx->tp_follow) return GSP_OK;
-  ctx->tp_follow = want;
-  ctx->tp_valid = false;  // (the transforms the history belongs to are recorded only while following is on)
-  ctx->tp_xforms.clear();
-  return GSP_OK;
-}
-
-// what the two read-outs of the motion plane ask first
-static int temporal_have_motion(gsp_context* ctx, const char* who, const void* out_ptr) {
-  int rc = temporal_have_history(ctx, who, out_ptr);
-  if (rc != GSP_OK) return rc;
-  if (!ctx->tp_follow) {
-    ctx->err = std::string(who) + " needs gsp_temporal_follow_instances(ctx, 1) before the history was accumulated";
-    return GSP_ERR_INVALID;
-  }
-  return GSP_OK;
-}
-
-int gsp_download_temporal_motion(gsp_context* ctx, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_have_motion(ctx, "gsp_download_temporal_motion", out);
-  if (rc != GSP_OK) return rc;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  return read_back_bytes(ctx, ctx->tp_v.p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
-}
-
-int gsp_temporal_motion_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_have_motion(ctx, "gsp_temporal_motion_to_device", dst);
-  if (rc != GSP_OK) return rc;
-  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
-  if (bytes < need) {
-    ctx->err = "destination too small";
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->tp_v.p, need, hipMemcpyDeviceToDevice, ctx->stream));  // (a copy: any alignment)
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-int gsp_download_temporal_moments(gsp_context* ctx, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_have_history(ctx, "gsp_download_temporal_moments", out);
-  if (rc != GSP_OK) return rc;
-  if (!ctx->tp_moments) {
-    ctx->err = "gsp_download_temporal_moments needs gsp_temporal_track_moments(ctx, 1) before the history was accumulated";
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  return read_back_bytes(ctx, ctx->tp_m[ctx->tp_cur].p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
-}
-
-int gsp_download_temporal_svgf(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_download_temporal_svgf", out, nullptr);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
-}
-
-int gsp_temporal_svgf_to_device(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, void* dst, uint64_t bytes) {
-  if (!ctx) return GSP_ERR_INVALID;
-  if (dst && ctx->have_frame && bytes < ctx->num_pixels * sizeof(q4)) {
-    ctx->err = "destination too small";
-    return GSP_ERR_INVALID;
-  }
-  // the kernels store 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
-  const bool direct = ((uintptr_t)dst & 15u) == 0;
-  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_temporal_svgf_to_device", dst, direct ? dst : nullptr);
-  if (rc != GSP_OK) return rc;
-  if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), hipMemcpyDeviceToDevice, ctx->stream));
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-int gsp_download_temporal_svgf_display(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, const gsp_display* display, uint32_t* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  {  // (an invalid display is refused before anything is queued)
-    gsp_display d;
-    if (const char* why = resolve_display(display, d)) {
-      ctx->err = why;
-      return GSP_ERR_INVALID;
-    }
-  }
-  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_download_temporal_svgf_display", out, nullptr);
-  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr, ctx->dn_out.p);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
-}
-
-}  // extern "C"
-
-// ---- illumination history (include/gpuspectral_pt.h, "Illumination history"; per-pixel code: pt_illum.h) ----
-// what the two image read-outs ask first
-static int temporal_have_image(gsp_context* ctx, const char* who, const void* out_ptr) {
-  int rc = temporal_have_history(ctx, who, out_ptr);
-  if (rc != GSP_OK) return rc;
-  if (!ctx->tp_done) {
-    ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since gsp_frame_begin";
-    return GSP_ERR_INVALID;
-  }
-  return GSP_OK;
-}
-
-// queues the re-modulated newest history into `dst` (device, 16-byte aligned) on ctx->stream
-static int temporal_image_run(gsp_context* ctx, void* dst) {
-  const uint64_t n = (uint64_t)ctx->tp_width * ctx->tp_height;
-  if (n == 0) return GSP_OK;
-  const uint32_t pgrid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)ctx->num_cus * 8));
-  hipLaunchKernelGGL(k_illum_image, dim3(pgrid), dim3(kBlock), 0, ctx->stream, (const v4f*)ctx->tp_h[ctx->tp_cur].p, (const v4f*)ctx->feat_albedo.p, n,
-                     (v4f*)dst);
-  CTX_TRY(ctx, hipGetLastError());
-  return GSP_OK;
-}
-
-extern "C" {
-
-int gsp_temporal_demodulate(gsp_context* ctx, int on) {
-  if (!ctx) return GSP_ERR_INVALID;
-  const bool want = on != 0;
-  if (want == ctx->tp_demod) return GSP_OK;
-  ctx->tp_demod = want;
-  ctx->tp_valid = false;  // (a history of colour is no history of illumination)
-  return GSP_OK;
-}
-
-int gsp_download_temporal_image(gsp_context* ctx, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_have_image(ctx, "gsp_download_temporal_image", out);
-  if (rc != GSP_OK) return rc;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
-  if (!ctx->tp_demod) return read_back_bytes(ctx, ctx->tp_h[ctx->tp_cur].p, bytes, out);
-  CTX_TRY(ctx, ctx->dn_out.ensure(std::max<uint64_t>(ctx->num_pixels, 1), &ctx->bytes));
-  rc = temporal_image_run(ctx, ctx->dn_out.p);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->dn_out.p, bytes, out);
-}
-
-int gsp_temporal_image_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = temporal_have_image(ctx, "gsp_temporal_image_to_device", dst);
-  if (rc != GSP_OK) return rc;
-  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
-  if (bytes < need) {
-    ctx->err = "destination too small";
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  if (!ctx->tp_demod) {
-    CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->tp_h[ctx->tp_cur].p, need, hipMemcpyDeviceToDevice, ctx->stream));  // (a copy: any alignment)
-  } else {
-    // the kernel stores 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
-    const bool direct = ((uintptr_t)dst & 15u) == 0;
-    if (!direct) CTX_TRY(ctx, ctx->dn_out.ensure(std::max<uint64_t>(ctx->num_pixels, 1), &ctx->bytes));
-    rc = temporal_image_run(ctx, direct ? dst : (void*)ctx->dn_out.p);
-    if (rc != GSP_OK) return rc;
-    if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, need, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-int gsp_temporal_svgf_feedback(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, float* out) {
-  if (!ctx) return GSP_ERR_INVALID;
-  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_temporal_svgf_feedback", out, nullptr, true, levels);
-  if (rc != GSP_OK) return rc;
-  if (out) return read_back_bytes(ctx, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), out);
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-int gsp_temporal_svgf_feedback_to_device(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, void* dst, uint64_t bytes) {
-  if (!ctx) return GSP_ERR_INVALID;
-  if (dst && ctx->have_frame && bytes < ctx->num_pixels * sizeof(q4)) {
-    ctx->err = "destination too small";
-    return GSP_ERR_INVALID;
-  }
-  // the kernels store 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
-  const bool direct = dst && ((uintptr_t)dst & 15u) == 0;
-  int rc = svgf_ctx(ctx, denoise, svgf, "gsp_temporal_svgf_feedback_to_device", dst, direct ? dst : nullptr, true, levels);
-  if (rc != GSP_OK) return rc;
-  if (dst && !direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->dn_out.p, ctx->num_pixels * sizeof(q4), hipMemcpyDeviceToDevice, ctx->stream));
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int gsp_frame_luminance(gsp_context* ctx, int drain, gsp_luminance* out) {
-  if (!ctx || !out || !ctx->have_frame) return GSP_ERR_INVALID;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = drain ? pipeline_drain(ctx) : display_peek_sync(ctx, nullptr);
-  if (rc != GSP_OK) return rc;
-  return display_measure_ctx(ctx, out);
-}
-
-int gsp_peek_display(gsp_context* ctx, const gsp_display* display, uint32_t* out, uint32_t* samples_folded) {
-  if (!ctx || !out || !ctx->have_frame) return GSP_ERR_INVALID;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = display_peek_sync(ctx, samples_folded);
-  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr);
-  if (rc != GSP_OK) return rc;
-  return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
-}
-
-int gsp_peek_display_to_device(gsp_context* ctx, const gsp_display* display, void* dst, uint64_t bytes, uint32_t* samples_folded) {
-  if (!ctx || !dst || !ctx->have_frame) return GSP_ERR_INVALID;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  if (bytes < ctx->num_pixels * sizeof(uint32_t)) {
-    ctx->err = "destination too small";
-    return GSP_ERR_INVALID;
-  }
-  int rc = display_peek_sync(ctx, samples_folded);
-  if (rc != GSP_OK) return rc;
-  // the kernel stores 16 bytes at a time: a destination that is not aligned so gets a copy of the context's own buffer
-  const bool direct = ((uintptr_t)dst & 15u) == 0;
-  rc = display_run(ctx, display, direct ? (uint32_t*)dst : nullptr);
-  if (rc != GSP_OK) return rc;
-  if (!direct) CTX_TRY(ctx, hipMemcpyAsync(dst, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return GSP_OK;
-}
-
-int gsp_download_display(gsp_context* ctx, const gsp_display* display, uint32_t* out) {
-  if (!ctx || !out || !ctx->have_frame) return GSP_ERR_INVALID;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = pipeline_drain(ctx);
-  if (rc == GSP_OK) rc = display_run(ctx, display, nullptr);
-  if (rc != GSP_OK) return rc;
-  if (!ctx->subset) return read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), out);
-  std::vector<uint32_t> tmp(ctx->num_pixels);
-  rc = read_back_bytes(ctx, ctx->display_out.p, ctx->num_pixels * sizeof(uint32_t), tmp.data());
-  if (rc != GSP_OK) return rc;
-  std::memset(out, 0, sizeof(uint32_t) * (size_t)ctx->width * ctx->height);
-  for (uint64_t i = 0; i < ctx->num_pixels; ++i) out[ctx->pixel_ids_host[i]] = tmp[i];
-  return GSP_OK;
-}
 
 int gsp_debug_visit_histograms(gsp_context* ctx, uint32_t* node_counts, uint64_t num_nodes, uint32_t* slot_counts, uint64_t num_slots) {
   if (!ctx) return GSP_ERR_INVALID;

@@ -16,6 +16,17 @@ DEFAULTS = dict(max_history=32, alpha=0.2, depth_tolerance=0.02, normal_min=0.9)
 U32 = 2.0 ** -24  # unit roundoff of float32
 
 
+def refusals(ctx, cases):
+    """Every (export, its arguments behind the context, text) of `cases`: the call on the library itself returns GSP_ERR_INVALID (1)
+    and leaves a gsp_last_error that contains `text`.  A case breaks two of the export's conditions at once and `text` is that of the
+    one the export tests first, so two refusals that change places fail here.  (A device destination of such a call is never written:
+    16 stands for one.)"""
+    for export, args, text in cases:
+        rc = getattr(ctx._L, export)(ctx._h, *args)
+        err = ctx._L.gsp_last_error(ctx._h).decode()
+        assert rc == 1 and text in err, (export, text, rc, err)
+
+
 def same(a, b):
     return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
 

@@ -2,6 +2,7 @@
 on the host (csrc/pt_denoise.h through tests/emu/denoise_emu.cpp, itself checked against a float64 restatement in
 tests/test_denoise_cpu.py).  gsp_download_denoised equals the emulation applied to gsp_download + gsp_download_features BIT FOR
 BIT: both fetch paths of the kernel (LDS for steps 1 and 2, global memory above), ragged tiles, steps beyond the frame."""
+import ctypes as C
 import subprocess
 import sys
 
@@ -11,6 +12,7 @@ import pytest
 from conftest import ROOT
 from denoise_util import INF, DenoiseEmu, same
 from display_util import DisplayEmu
+from temporal_util import refusals
 
 pytestmark = pytest.mark.gpu
 
@@ -240,6 +242,29 @@ def test_validation(rigs, scenes_):
         with pytest.raises(g.GspError, match="gsp_frame_begin"):
             ctx.download_denoised(None)  # no frame
         ctx.upload_scene(scenes_["cornell"])
+        # the order of the refusals, two broken conditions per call (temporal_util.refusals): first without a frame ...
+        buf = np.zeros((16, 16, 4), np.float32).ctypes.data
+        bad_dn, tone = C.byref(abi.denoise(iterations=9)), C.byref(abi.display(tonemap=7))
+        names = ("gsp_download_denoised", "gsp_denoise_to_device", "gsp_download_denoised_display")
+        null, frame, share, feats = (dict((n, n + t) for n in names) for t in (
+            ": null output pointer", " needs gsp_frame_begin first",
+            ": the frame was begun with pixel_ids; a share has no neighbours (use gsp_multi_download_denoised)",
+            " needs a gsp_render_features call since gsp_frame_begin"))
+        n0, n1, n2 = names
+        refusals(ctx, [(n0, (bad_dn, None), null[n0]), (n0, (bad_dn, buf), frame[n0]),
+                       (n1, (bad_dn, None, 0), null[n1]), (n1, (bad_dn, 16, 0), frame[n1]),
+                       (n2, (None, tone, None), "tonemap"), (n2, (bad_dn, None, None), null[n2]), (n2, (bad_dn, None, buf), frame[n2])])
+        # ... in a share's frame without a feature pass ...
+        ctx.frame_begin(16, 16, pixel_ids=g.pt.tile_partition(16, 16, 0, 2))
+        refusals(ctx, [(n0, (None, buf), share[n0]), (n1, (None, 16, 4), "destination too small"), (n1, (None, None, 0), null[n1]),
+                       (n1, (None, 16, 1 << 20), share[n1]), (n2, (None, None, None), null[n2]), (n2, (None, None, buf), share[n2])])
+        ctx.frame_begin(16, 16)
+        ctx.render(1)
+        # ... in a full frame without one, and with one
+        refusals(ctx, [(n0, (bad_dn, buf), feats[n0]), (n1, (bad_dn, 16, 1 << 20), feats[n1]), (n2, (bad_dn, None, buf), feats[n2])])
+        ctx.render_features(1)
+        refusals(ctx, [(n1, (bad_dn, 16, 4), "destination too small"), (n2, (bad_dn, tone, buf), "tonemap"),
+                       (n2, (bad_dn, None, buf), "iterations")])
         ctx.frame_begin(16, 16)
         ctx.render(1)
         with pytest.raises(g.GspError, match="gsp_render_features"):

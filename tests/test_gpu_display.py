@@ -4,6 +4,7 @@ k_display_map / k_display_stats against the same text run on the host (csrc/pt_d
 gsp_download_display equals the emulation applied to gsp_download BYTE FOR BYTE and gsp_frame_luminance equals it integer for
 integer, for every tonemap x encode x exposure, on full frames, pixel_ids shares, adaptive frames and frames with NaN / Inf; the
 peek variants; the gathered frame of gsp_multi; the CLI's PNG."""
+import ctypes as C
 import os
 import subprocess
 
@@ -262,6 +263,9 @@ def test_invalid_display_is_refused(ctx, cornell):
             ctx.download_display(bad)
         with pytest.raises(g.GspError, match=word):
             ctx.peek_display(bad)
+    # gsp_peek_display_to_device asks for the room before it looks at the display (a device destination that is never written)
+    assert ctx._L.gsp_peek_display_to_device(ctx._h, C.byref(abi.display(tonemap=9)), 16, 4 * 256 - 4, None) == 1
+    assert ctx._L.gsp_last_error(ctx._h).decode() == "destination too small"
     assert (ctx.download_display(None) == 0xFF000000).all()  # a frame without samples: black, alpha 255
     assert ctx.frame_luminance()["pixels"] == 256
 

@@ -5,6 +5,7 @@ feedback's output and the history after the feedback equal the emulation applied
 emulated history BIT FOR BIT, frame after frame; then parity with the feature off, state, bytes and refusals, two quality orderings,
 the device-memory read-outs, the host layer and the CLI."""
 import copy
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -15,7 +16,7 @@ import pytest
 import temporal_util as tu
 from conftest import GOLDEN, ROOT
 from illum_util import IllumEmu
-from temporal_util import FLT_MIN, same
+from temporal_util import FLT_MIN, refusals, same
 from test_gpu_motion import MOVERS, ORBIT, moved_instances, orbit, words
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +25,9 @@ pytestmark = pytest.mark.gpu
 # its taps from global memory)
 CASES = [(d, m, lv) for d in (False, True) for m, lv in (("plain", 0), ("moments", 1), ("moments", 3), ("moments+follow", 1), ("moments+follow", 3))]
 CASE_IDS = ["%s-%s-fb%d" % ("demod" if d else "colour", m, lv) for d, m, lv in CASES]
+# the feedback level by (levels, iterations): level 1 (the second step that stages its taps in LDS) and a last level of each kind --
+# iterations None = the default of 5
+FB_LEVELS = [(2, None), (1, 1), (2, 2), (3, 3)]
 
 
 @pytest.fixture(scope="module")
@@ -54,8 +58,8 @@ def rigs(scenes_):
         ctx.update_camera(scenes_[name].to_world, scenes_[name].fov)
         ctx.update_instances(scenes_[name].instances)
         ctx.temporal_demodulate(demod)
-        ctx.temporal_track_moments(mode != "plain")
-        ctx.temporal_follow_instances(mode == "moments+follow")
+        ctx.temporal_track_moments("moments" in mode)
+        ctx.temporal_follow_instances("follow" in mode)
         ctx.temporal_reset()
         return ctx
 
@@ -80,12 +84,12 @@ def begin(ctx, size, ts, cam=None, fov=None, inst=None):
     ctx.render_features(1, ts)
 
 
-def frame(ctx, emu, hist, cam, fov, size, ts, inst, demod, mode, levels, what=""):
+def frame(ctx, emu, hist, cam, fov, size, ts, inst, demod, mode, levels, what="", dn=None):
     """One frame of the viewer loop -- the edit, the camera, the frame, its feature pass, the accumulate, the image read-out and (levels)
     the feedback -- on the GPU and by the emulation from `hist`.  Returns the emulated history the next frame starts from."""
     from gpuspectral_amd import abi
 
-    moments, follow = mode != "plain", mode == "moments+follow"
+    moments, follow = "moments" in mode, "follow" in mode
     begin(ctx, size, ts, cam, fov, inst)
     ctx.temporal_accumulate(None)
     c = ctx.download()
@@ -99,8 +103,8 @@ def frame(ctx, emu, hist, cam, fov, size, ts, inst, demod, mode, levels, what=""
     check(what, "the image", ctx.download_temporal_image(), emu.image(new.H, a, demod))
     if levels:
         sv = abi.svgf(min_history=2)
-        out, fb = emu.svgf(None, sv, new.H, new.M, a, g, demod=demod, levels=levels)
-        check(what, "the feedback's output", ctx.temporal_svgf_feedback(None, sv, levels), out)
+        out, fb = emu.svgf(dn, sv, new.H, new.M, a, g, demod=demod, levels=levels)
+        check(what, "the feedback's output", ctx.temporal_svgf_feedback(dn, sv, levels), out)
         check(what, "H after the feedback", ctx.download_temporal(), fb)
         check(what, "the image after the feedback", ctx.download_temporal_image(), emu.image(fb, a, demod))
         check(what, "M after the feedback", ctx.download_temporal_moments(), new.M)
@@ -108,10 +112,10 @@ def frame(ctx, emu, hist, cam, fov, size, ts, inst, demod, mode, levels, what=""
     return new
 
 
-def sequence(ctx, emu, sc, size, movers, demod, mode, levels, degrees=ORBIT, what=""):
+def sequence(ctx, emu, sc, size, movers, demod, mode, levels, degrees=ORBIT, what="", dn=None):
     hist = None
     for k, cam in enumerate(orbit(sc, degrees)):
-        hist = frame(ctx, emu, hist, cam, sc.fov, size, k, moved_instances(sc.instances, movers, k), demod, mode, levels, "%s frame %d" % (what, k))
+        hist = frame(ctx, emu, hist, cam, sc.fov, size, k, moved_instances(sc.instances, movers, k), demod, mode, levels, "%s frame %d" % (what, k), dn)
     return hist
 
 
@@ -128,6 +132,25 @@ def test_cornell_orbit_with_the_tall_box_moving(rigs, emu, scenes_, demod, mode,
 @pytest.mark.parametrize("size", [(33, 17), (5, 3), (1, 1)])
 def test_materials_scene(rigs, emu, scenes_, size, demod, mode, levels):
     sequence(rigs("materials", demod, mode), emu, scenes_["materials"], size, MOVERS["materials"], demod, mode, levels, what="materials %dx%d" % size)
+
+
+@pytest.mark.parametrize("demod", [False, True], ids=["colour", "demod"])
+@pytest.mark.parametrize("levels,iterations", FB_LEVELS)
+def test_materials_scene_feedback_levels(rigs, emu, scenes_, demod, levels, iterations):
+    """33 x 17 (two tiles across, three down, ragged both ways): the feedback on the filter's second level and on its last one."""
+    from gpuspectral_amd import abi
+
+    dn = abi.denoise(iterations=iterations) if iterations else None
+    sequence(rigs("materials", demod, "moments"), emu, scenes_["materials"], (33, 17), MOVERS["materials"], demod, "moments", levels, degrees=ORBIT[:4],
+             what="materials 33x17, level %d of %s" % (levels, iterations), dn=dn)
+
+
+@pytest.mark.parametrize("demod", [False, True], ids=["colour", "demod"])
+def test_materials_scene_following_without_moments(rigs, emu, scenes_, demod):
+    """The one state of the three switches that CASES leaves out, at 33 x 17: instances followed, no moments plane."""
+    hist = sequence(rigs("materials", demod, "follow"), emu, scenes_["materials"], (33, 17), MOVERS["materials"], demod, "follow", 0, degrees=ORBIT[:4],
+                    what="materials 33x17, following without moments")
+    assert hist.M is None and hist.V is not None
 
 
 @pytest.mark.parametrize("demod,mode,levels", CASES, ids=CASE_IDS)
@@ -236,6 +259,27 @@ def test_state_bytes_and_refusals(scenes_):
         assert all(s1[2][k] == v for k, v in s0[2].items() if k not in skip)
         return res
 
+    buf = np.zeros((h, w, 4), np.float32).ctypes.data
+    bads = C.byref(abi.svgf(min_history=1))
+    names = ("gsp_download_temporal_image", "gsp_temporal_image_to_device", "gsp_temporal_svgf_feedback", "gsp_temporal_svgf_feedback_to_device")
+    null, hist, track, full, done, fed = (dict((n, n + t) for n in names) for t in (
+        ": null output pointer", " needs a gsp_temporal_accumulate call since the history was last invalidated",
+        " needs gsp_temporal_track_moments(ctx, 1) before the history was accumulated",
+        " needs a full frame (no pixel_ids) and a gsp_render_features call since gsp_frame_begin",
+        " needs a gsp_temporal_accumulate call since gsp_frame_begin", ": the history has been fed back already (one call per gsp_temporal_accumulate)"))
+    span = lambda n, k: "%s: levels must be within 1 .. %d (the filter's iterations)" % (n, k)
+    n0, n1, n2, n3 = names
+    with g.Context(0) as ctx:
+        ctx.upload_scene(sc)
+        # the order of the refusals, two broken conditions per call (temporal_util.refusals): without a frame and a history ...
+        refusals(ctx, [(n0, (None,), null[n0]), (n0, (buf,), hist[n0]), (n1, (None, 0), null[n1]), (n1, (16, 0), hist[n1]),
+                      (n2, (None, None, 0, None), hist[n2]), (n3, (None, None, 0, 16, 0), hist[n3])])
+        # ... with a history without moments, in the next frame before its feature pass ...
+        begin(ctx, size, 0)
+        ctx.temporal_accumulate(None)
+        ctx.frame_begin(*size)
+        refusals(ctx, [(n0, (None,), null[n0]), (n0, (buf,), done[n0]), (n1, (None, 4), null[n1]), (n1, (16, 4), done[n1]), (n2, (None, None, 0, buf), track[n2]),
+                      (n3, (None, None, 0, 16, 4), "destination too small"), (n3, (None, None, 0, 16, 1 << 30), track[n3])])
     with g.Context(0) as on, g.Context(0) as off:
         for ctx in (on, off):
             ctx.upload_scene(sc)
@@ -292,6 +336,13 @@ def test_state_bytes_and_refusals(scenes_):
         assert ctx._L.gsp_temporal_image_to_device(ctx._h, 16, 1 << 30) == 1 and "since gsp_frame_begin" in ctx._L.gsp_last_error(ctx._h).decode()
         with pytest.raises(g.GspError, match="gsp_temporal_svgf_feedback needs a gsp_temporal_accumulate call since gsp_frame_begin"):
             ctx.temporal_svgf_feedback(None, None, 1)
+        # ... with moments, in a frame before its accumulate: the filter's parameters, then the levels, then the accumulate ...
+        refusals(ctx, [(n2, (None, bads, 0, buf), "gsp_svgf.min_history"), (n2, (None, None, 0, buf), span(n2, 5)), (n2, (None, None, 1, buf), done[n2]),
+                       (n3, (None, bads, 0, 16, 1 << 30), "gsp_svgf.min_history"), (n3, (None, None, 6, 16, 1 << 30), span(n3, 5)),
+                       (n3, (None, None, 0, 16, 4), "destination too small")])
+        ctx.frame_begin(*size)  # ... and before its feature pass
+        refusals(ctx, [(n2, (None, bads, 0, buf), full[n2]), (n3, (None, bads, 0, 16, 1 << 30), full[n3])])
+        begin(ctx, size, 4)
         ctx.temporal_accumulate(None)
         # levels outside 1 .. iterations (those the call resolves: 5 by default)
         for dn, levels in ((None, 0), (None, 6), (abi.denoise(iterations=2), 3)):
@@ -308,6 +359,8 @@ def test_state_bytes_and_refusals(scenes_):
         assert "destination too small" in ctx._L.gsp_last_error(ctx._h).decode()
         assert np.all(ctx.download_temporal()[..., 3] == 2.0)
         untouched(ctx, lambda: ctx.temporal_svgf_feedback(None, None, 5))  # (none of the refused calls counted as the frame's feedback)
+        refusals(ctx, [(n2, (None, None, 0, buf), span(n2, 5)), (n2, (None, None, 1, None), fed[n2]), (n3, (None, None, 6, 16, 1 << 30), span(n3, 5)),
+                       (n3, (None, None, 1, 16, 4), "destination too small")])  # ... and after the frame's feedback
         # feedback with tracking off
         ctx.temporal_track_moments(False)
         begin(ctx, size, 5)

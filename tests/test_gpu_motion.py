@@ -14,7 +14,7 @@ import temporal_util as tu
 from conftest import ROOT
 from motion_util import MotionEmu
 from svgf_util import SvgfEmu
-from temporal_util import same
+from temporal_util import refusals, same
 
 pytestmark = pytest.mark.gpu
 
@@ -329,6 +329,14 @@ def test_state_bytes_refusal_and_restarts(scenes_, emu):
         for call in (ctx.download_temporal_motion,):
             with pytest.raises(g.GspError, match="gsp_temporal_accumulate"):
                 call()  # before any accumulate
+        # the order of the refusals, two broken conditions per call (temporal_util.refusals): without a history and following off ...
+        buf = np.zeros((h, w, 4), np.float32).ctypes.data
+        names = ("gsp_download_temporal_motion", "gsp_temporal_motion_to_device")
+        null, hist, follow = (dict((n, n + t) for n in names) for t in (
+            ": null output pointer", " needs a gsp_temporal_accumulate call since the history was last invalidated",
+            " needs gsp_temporal_follow_instances(ctx, 1) before the history was accumulated"))
+        n0, n1 = names
+        refusals(ctx, [(n0, (None,), null[n0]), (n0, (buf,), hist[n0]), (n1, (None, 0), null[n1]), (n1, (16, 0), hist[n1])])
         # following off: the motion read-outs are refused also with a history, and nothing of the feature is allocated
         ctx.frame_begin(w, h)
         ctx.render(1, 0)
@@ -339,6 +347,7 @@ def test_state_bytes_refusal_and_restarts(scenes_, emu):
         with pytest.raises(g.GspError, match="gsp_temporal_follow_instances"):
             ctx.download_temporal_motion()
         assert ctx._L.gsp_temporal_motion_to_device(ctx._h, 16, 1 << 30) == 1 and "gsp_temporal_follow_instances" in ctx._L.gsp_last_error(ctx._h).decode()
+        refusals(ctx, [(n0, (None,), null[n0]), (n0, (buf,), follow[n0]), (n1, (None, 4), null[n1]), (n1, (16, 4), follow[n1])])  # ... with one ...
         # with following off a late edit is nobody's business
         assert np.all(one(ctx, 1, size, late_edit=moved1)[ctx.download_features()[2][..., 2] != 6] == 2.0)
         ctx.update_instances(sc.instances)
@@ -365,6 +374,7 @@ def test_state_bytes_refusal_and_restarts(scenes_, emu):
         assert np.all(one(ctx, 3, size) == 2.0)
         assert ctx._L.gsp_download_temporal_motion(ctx._h, None) == 1 and "null output" in ctx._L.gsp_last_error(ctx._h).decode()
         assert ctx._L.gsp_temporal_motion_to_device(ctx._h, None, 1 << 20) == 1 and "null output" in ctx._L.gsp_last_error(ctx._h).decode()
+        refusals(ctx, [(n0, (None,), null[n0]), (n1, (None, 4), null[n1])])  # ... and following on
         # the edit counter: an edit after the frame's feature pass is refused, with the text that says where it belongs ...
         with pytest.raises(g.GspError, match="before the frame's gsp_render_features"):
             one(ctx, 4, size, late_edit=moved1)

@@ -2,6 +2,7 @@
 k_svgf_variance and k_svgf_atrous against the same text run on the host (csrc/pt_svgf.h through tests/emu/svgf_emu.cpp, itself
 checked against a float64 restatement in tests/test_svgf_cpu.py).  The history, its moments and the filtered frame equal the
 emulation applied to gsp_download + gsp_download_features + the previous emulated history BIT FOR BIT, frame after frame."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -13,7 +14,7 @@ import temporal_util as tu
 from conftest import ROOT
 from display_util import DisplayEmu
 from svgf_util import INF, SvgfEmu, same
-from temporal_util import FLT_MIN
+from temporal_util import FLT_MIN, refusals
 
 pytestmark = pytest.mark.gpu
 
@@ -314,10 +315,28 @@ def test_validation(scenes_):
                 call()  # before any accumulate
         assert ctx._L.gsp_temporal_svgf_to_device(ctx._h, None, None, 16, 1 << 30) == 1 and "gsp_temporal_accumulate" in ctx._L.gsp_last_error(ctx._h).decode()
         ctx.upload_scene(scenes_["cornell"])
+        # the order of the refusals, two broken conditions per call (temporal_util.refusals): first without a frame and a history ...
+        buf = np.zeros((16, 16, 4), np.float32).ctypes.data
+        bad_dn, tone, bads = C.byref(abi.denoise(iterations=9)), C.byref(abi.display(tonemap=7)), C.byref(abi.svgf(min_history=1))
+        names = ("gsp_download_temporal_moments", "gsp_download_temporal_svgf", "gsp_temporal_svgf_to_device", "gsp_download_temporal_svgf_display")
+        null, hist, track, full = (dict((n, n + t) for n in names) for t in (
+            ": null output pointer", " needs a gsp_temporal_accumulate call since the history was last invalidated",
+            " needs gsp_temporal_track_moments(ctx, 1) before the history was accumulated",
+            " needs a full frame (no pixel_ids) and a gsp_render_features call since gsp_frame_begin"))
+        n0, n1, n2, n3 = names
+        refusals(ctx, [(n0, (None,), null[n0]), (n0, (buf,), hist[n0]), (n1, (bad_dn, None, None), null[n1]), (n1, (bad_dn, None, buf), hist[n1]),
+                       (n2, (None, None, None, 0), null[n2]), (n2, (None, None, 16, 0), hist[n2]), (n3, (None, None, tone, None), "tonemap"),
+                       (n3, (None, None, None, None), null[n3]), (n3, (None, None, None, buf), hist[n3])])
         ctx.frame_begin(16, 16)
         ctx.render(1)
         ctx.render_features(1)
         ctx.temporal_accumulate(None)  # tracking is off
+        # ... then with a history without moments, in the next frame before its feature pass ...
+        ctx.frame_begin(16, 16)
+        refusals(ctx, [(n0, (None,), null[n0]), (n0, (buf,), track[n0]), (n1, (bad_dn, None, buf), track[n1]), (n2, (None, None, 16, 4), "destination too small"),
+                       (n2, (None, None, 16, 1 << 20), track[n2]), (n3, (None, None, None, buf), track[n3])])
+        ctx.render(1)
+        ctx.render_features(1)
         for call in calls:
             with pytest.raises(g.GspError, match="gsp_temporal_track_moments"):
                 call()
@@ -344,8 +363,11 @@ def test_validation(scenes_):
         with pytest.raises(g.GspError, match="tonemap"):
             ctx.download_temporal_svgf_display(None, None, abi.display(tonemap=7))
         ctx.download_temporal_svgf(None, None)
+        refusals(ctx, [(n1, (bad_dn, None, buf), "iterations"), (n1, (None, bads, buf), "min_history"), (n2, (bad_dn, None, 16, 4), "destination too small"),
+                       (n3, (bad_dn, None, tone, buf), "tonemap")])
         ctx.frame_begin(16, 16)  # a new frame of the same size: the history stays, the feature planes are stale
         assert np.all(ctx.download_temporal_moments()[..., 2] == 1.0)
+        refusals(ctx, [(n1, (bad_dn, None, buf), full[n1]), (n2, (bad_dn, None, 16, 1 << 20), full[n2]), (n3, (bad_dn, None, None, buf), full[n3])])
         with pytest.raises(g.GspError, match="gsp_render_features"):
             ctx.download_temporal_svgf(None, None)
         ctx.frame_begin(16, 16, pixel_ids=g.pt.tile_partition(16, 16, 0, 2))

@@ -2,6 +2,7 @@
 run on the host (csrc/pt_temporal.h through tests/emu/temporal_emu.cpp, itself checked against a float64 restatement in
 tests/test_temporal_cpu.py).  gsp_download_temporal equals the emulation applied to gsp_download + gsp_download_features + the
 previous emulated history BIT FOR BIT, frame after frame."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -13,7 +14,7 @@ import temporal_util as tu
 from conftest import ROOT
 from denoise_util import DenoiseEmu
 from display_util import DisplayEmu
-from temporal_util import FLT_MIN, TemporalEmu, same
+from temporal_util import FLT_MIN, TemporalEmu, refusals, same
 
 pytestmark = pytest.mark.gpu
 
@@ -381,6 +382,35 @@ def test_validation(scenes_):
         with pytest.raises(g.GspError, match="gsp_frame_begin"):
             ctx.temporal_accumulate(None)  # no frame
         ctx.upload_scene(scenes_["cornell"])
+        # the order of the refusals, two broken conditions per call (temporal_util.refusals): first without a frame and a history ...
+        buf = np.zeros((16, 16, 4), np.float32).ctypes.data
+        bad_dn, tone, badt = C.byref(abi.denoise(iterations=9)), C.byref(abi.display(tonemap=7)), C.byref(abi.temporal(max_history=65537))
+        acc = "gsp_temporal_accumulate"
+        names = ("gsp_download_temporal", "gsp_temporal_to_device", "gsp_download_temporal_denoised", "gsp_download_temporal_denoised_display")
+        null, hist, full = (dict((n, n + t) for n in names) for t in (
+            ": null output pointer", " needs a gsp_temporal_accumulate call since the history was last invalidated",
+            " needs a full frame (no pixel_ids) and a gsp_render_features call since gsp_frame_begin"))
+        n0, n1, n2, n3 = names
+        refusals(ctx, [(acc, (badt,), acc + " needs gsp_frame_begin first"), (n0, (None,), null[n0]), (n1, (None, 0), null[n1]), (n1, (16, 0), hist[n1]),
+                       (n2, (bad_dn, None), null[n2]), (n2, (bad_dn, buf), hist[n2]), (n3, (None, tone, None), "tonemap"), (n3, (bad_dn, None, None), null[n3]),
+                       (n3, (bad_dn, None, buf), hist[n3])])
+        # ... then the accumulate in a share's frame and in a full one, both without a feature pass ...
+        ctx.frame_begin(16, 16, pixel_ids=g.pt.tile_partition(16, 16, 0, 2))
+        refusals(ctx, [(acc, (badt,), acc + ": the frame was begun with pixel_ids; a share has no neighbours and there is no multi-GPU variant")])
+        ctx.frame_begin(16, 16)
+        ctx.render(1)
+        refusals(ctx, [(acc, (badt,), acc + " needs a gsp_render_features call since gsp_frame_begin")])
+        # ... then with a history: in its frame, in the next one before the feature pass, and in a share's frame after one
+        ctx.render_features(1)
+        ctx.temporal_accumulate(None)
+        refusals(ctx, [(acc, (badt,), acc + ": the frame has been accumulated already (one call per gsp_frame_begin)"),
+                       (n2, (bad_dn, buf), "iterations"), (n3, (bad_dn, tone, buf), "tonemap"), (n3, (bad_dn, None, buf), "iterations")])
+        ctx.frame_begin(16, 16)
+        refusals(ctx, [(n2, (bad_dn, buf), full[n2]), (n3, (bad_dn, None, buf), full[n3])])
+        ctx.frame_begin(16, 16, pixel_ids=g.pt.tile_partition(16, 16, 0, 2))
+        ctx.render_features(1)
+        refusals(ctx, [(n2, (bad_dn, buf), full[n2]), (n3, (bad_dn, None, buf), full[n3])])
+        ctx.temporal_reset()
         ctx.frame_begin(16, 16)
         ctx.render(1)
         with pytest.raises(g.GspError, match="gsp_render_features"):
@@ -422,6 +452,7 @@ def test_validation(scenes_):
         ctx.frame_begin(16, 16)
         ctx.render(1)
         ctx.render_features(1)
+        refusals(ctx, [(acc, (badt,), "max_history")])  # (the parameters before the cameras)
         with pytest.raises(g.GspError, match="singular"):
             ctx.temporal_accumulate(None)
         ctx.temporal_reset()
