@@ -1,6 +1,7 @@
 """Ray hits against a BVH-free geometric reference (tests/trace_reference.py), on the CPU: first the reference's own inputs are
 checked from the reference alone, then the oracle and the host emulation of the product's traversal (tests/emu: node_test /
-intersect_tri) are held to it.  The GPU run of the same properties is tests/test_gpu_trace_reference.py."""
+intersect_tri) are held to it.  The GPU run of the same properties is tests/test_gpu_trace_reference.py; the cases that arrive
+through a transform are the controls of tests/test_gpu_trace_edits.py, which reaches them by edits of a resident scene."""
 import math
 
 import numpy as np
@@ -57,6 +58,45 @@ def test_crumpled_slivers_are_closed_but_not_convex(name, placement):
         print("%s at %s%s: %.2f float32 spacings thick, concave by %.2f spacings" % (name, placement, " (instanced)" if instanced else "", ulps, dent))
         assert ulps < 4 and dent > 1 and case.outside_rays is None
     assert R.concavity_in_spacings(R.leak_case(name, "unit", False).world_tris) < 1  # (the same mesh, resolved: convex)
+
+
+@pytest.mark.parametrize("name,target", R.EDIT_CASES)
+def test_edit_case_origins_are_interior(name, target):
+    """The cases of tests/test_gpu_trace_edits.py: the unit mesh under each target transform.  Whether a case keeps its fixed
+    origins and its outside rays follows from the two figures printed here and from nothing else; a case with fewer than 4
+    interior origins is one the GPU tests leave out, and R.EDIT_DROPPED must say so."""
+    case = R.edit_case(name, target)
+    world = R.transform_points_f32(R.EDIT_TARGETS[target], case.mesh.verts)[case.mesh.faces]
+    assert np.array_equal(case.world_tris.view(np.uint32), world.view(np.uint32)) and case.mesh.placement == "unit"
+    ulps, dent = R.thickness_in_ulps(world.reshape(-1, 3)), R.concavity_in_spacings(world)
+    resolved = ulps > 16 and (name not in R.CONVEX or dent < 1)
+    print("%s under %s: %.2f float32 spacings thick, concave by %.2f spacings -> %s; %d origins, %d inside rays, %d slab-grazing rays, %s"
+          % (name, target, ulps, dent, "resolved" if resolved else "crumpled", len(case.origins), len(case.inside_rays), len(case.grazing_rays),
+             "no outside rays" if case.outside_rays is None else "%d outside rays" % len(case.outside_rays)))
+    assert (ulps, dent, resolved) == (case.thickness, case.concavity, case.resolved)
+    dropped = len(case.origins) < 4
+    if dropped:
+        print("%s under %s is left out of the GPU tests: %d interior origins" % (name, target, len(case.origins)))
+    assert dropped == ((name, target) in R.EDIT_DROPPED)
+    assert len(case.origins) <= 8 and (len(case.origins) == 8 or not resolved) and R.crossing_parity(case.world_tris, case.origins).all()
+    full = len(case.origins) * (len(case.mesh.verts) + 4 * len(case.mesh.edges))
+    assert np.isfinite(case.inside_rays).all() and (len(case.inside_rays) == full if resolved else 0.9 * full < len(case.inside_rays) <= full)
+    assert np.isfinite(case.grazing_rays).all() and len(case.grazing_rays) <= (len(case.mesh.verts) + 4 * len(case.mesh.edges) + 3) // 4
+    if len(case.grazing_rays):
+        assert R.crossing_parity(case.world_tris, case.grazing_rays[:, 0:3], ndirs=2).all()
+    assert (case.outside_rays is not None) == (name in R.CONVEX and resolved)
+    if case.outside_rays is not None:
+        assert len(case.outside_rays) == len(case.mesh.verts) + 4 * len(case.mesh.edges)
+        assert not R.crossing_parity(case.world_tris, case.outside_rays[::97, 0:3], ndirs=1).any()
+
+
+@pytest.mark.parametrize("placement", list(R.LATTICE_PLACEMENTS))
+@pytest.mark.parametrize("n,seed", [(8, 1), (12, 2)])
+def test_lattice_through_a_transform_is_the_lattice(n, seed, placement):
+    """The integer lattice triangles under the placement's transform, in float32 with the renderer's association, are
+    world_tris(scale, offset) bit for bit: the integer march stays the reference for a lattice that was moved there by an edit."""
+    obj, world = R.lattice_tris_through_transform(R.voxel_solid(n, seed), placement)
+    assert obj.dtype == np.float32 and world.shape == obj.shape
 
 
 @pytest.mark.parametrize("n,seed", [(8, 1), (12, 2)])
@@ -122,6 +162,54 @@ def test_float32_reference_deviation_defines_the_tolerance():
 def test_closed_meshes_do_not_leak(tracer, who, name, placement, instanced):
     case = R.leak_case(name, placement, instanced)
     R.check_no_leaks(case, tracer(who, case.key, case.instances), who)
+
+
+@pytest.mark.parametrize("name,target", R.EDIT_CASES)
+@pytest.mark.parametrize("who", WHO)
+def test_edit_cases_do_not_leak_in_a_fresh_scene(tracer, who, name, target):
+    """The control of tests/test_gpu_trace_edits.py: every edit case as a scene built for it, the target as the instance
+    transform.  Where this passes and the GPU test of the same case fails, the edit road is at fault and not the case."""
+    case = R.edit_case(name, target)
+    n = R.check_no_leaks(case, tracer(who, case.key, case.instances), who, prim_range=(0, len(case.obj_tris)))
+    print("%s, %s under %s: %d rays" % (who, name, target, n))
+
+
+@pytest.mark.parametrize("who", WHO)
+def test_split_scene_cases_in_a_fresh_scene(tracer, who):
+    """The control of the split-scene GPU test: lattice and mover as two objects of a scene built for the mover's last placement.
+    The mover's rays name its triangles only (a leak would name the lattice's), and no lattice ray meets the mover: every ray of
+    check_lattice that has left the lattice goes on to miss, as it does with the lattice alone."""
+    ref = R.lattice_reference(*R.SPLIT_LATTICE)
+    lat = ref.solid.world_tris(1.0, 0.0)
+    for name, step in (("icosphere", 4), ("icosphere", 70), ("torus", 4)):
+        case = R.split_mover_case(name, step)
+        trace = tracer(who, ("split", name, step), [(lat, None)] + case.instances)
+        n = R.check_no_leaks(case, trace, who, prim_range=(len(lat), len(case.obj_tris)))
+        R.check_lattice(ref, 1.0, 0.0, trace, who)
+        print("%s, split scene, %s after %d edits: %d mover rays, 4 x %d lattice rays" % (who, name, step, n, len(ref.first)))
+
+
+def test_split_mover_stays_clear_of_the_lattice_and_its_rays():
+    """From the reference alone: at every edit step the mover's bounding ball lies beside the lattice with the origins of its
+    outside rays (3 radii out) clear of the lattice box, and no lattice ray passes through the ball."""
+    solid = R.voxel_solid(*R.SPLIT_LATTICE)
+    rays = solid.world_rays(1.0, 0.0).astype(np.float64)
+    o, d = rays[:, 0:3], rays[:, 4:7] / np.linalg.norm(rays[:, 4:7], axis=1, keepdims=True)
+    worst = np.inf
+    for name in ("icosphere", "torus"):
+        mesh = R.ClosedMesh(name, "unit")
+        for step in range(0, 71 if name == "icosphere" else 5):
+            v = R.transform_points_f32(R.split_mover_transform(name, step), mesh.verts).astype(np.float64)
+            c = R.split_mover_transform(name, step).astype(np.float64)[12:15]
+            radius = np.linalg.norm(v - c, axis=1).max()
+            # (radius: up to rounding of the vertices, a spacing of 1e-6 at coordinate 8; the lattice is [0, 12]^3)
+            assert radius <= R.SPLIT_MOVER_RADIUS + 1e-5 and c[0] + 3 * radius < 0.0
+            w = c - o
+            along = np.maximum((w * d).sum(1), 0.0)
+            gap = np.linalg.norm(w - along[:, None] * d, axis=1).min() - radius
+            worst = min(worst, gap)
+            assert gap > 0, (name, step, gap)
+    print("closest approach of a lattice ray to the mover's bounding ball: %.3f" % worst)
 
 
 @pytest.mark.parametrize("placement", list(R.LATTICE_PLACEMENTS))

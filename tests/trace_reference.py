@@ -6,6 +6,9 @@ Three independent sources of truth:
     through face diagonals, lattice edges and lattice vertices;
   * closed meshes with bit-identical shared vertices (icosphere, torus, two slivers), for the "a ray from inside must hit"
     properties that need no number at all.
+
+The same cases with their geometry arriving through an instance transform (edit_case, lattice_transform, the split scene's mover)
+are what tests/test_gpu_trace_edits.py brings about by edits of a resident scene.
 """
 import functools
 import math
@@ -516,20 +519,24 @@ class LeakCase:
     for the reference-only checks."""
 
     def __init__(self, name, placement, instanced):
-        mesh = ClosedMesh(name, placement)
-        self.key, self.mesh, self.obj_tris = (name, placement, instanced), mesh, mesh.tris
-        if instanced:
-            self.transform = instance_transform()
+        self.key = (name, placement, instanced)
+        self._derive(ClosedMesh(name, placement), instance_transform() if instanced else None, (name, placement) in CRUMPLED)
+
+    def _derive(self, mesh, transform, crumpled):
+        """Everything but the key, from the object-space mesh, its transform (None = identity) and whether rounding has crumpled
+        the world-space mesh (origins by crossing parity, no outside rays)."""
+        name = mesh.name
+        self.mesh, self.obj_tris, self.transform = mesh, mesh.tris, transform
+        if transform is not None:
             m = self.transform.astype(np.float64).reshape(4, 4).T
             to_world = lambda p: np.asarray(p, np.float64) @ m[:3, :3].T + m[:3, 3]
             world_verts = transform_points_f32(self.transform, mesh.verts)
         else:
-            self.transform, to_world, world_verts = None, (lambda p: np.asarray(p, np.float64)), mesh.verts
+            to_world, world_verts = (lambda p: np.asarray(p, np.float64)), mesh.verts
         self.world_tris = world_verts[mesh.faces]
         # origins: the first 8 of a fixed sequence of candidates that the float64 brute force finds interior (odd crossing
         # parity in three directions); for a well resolved mesh those are simply the first 8
         # (the float32 points inside a crumpled sliver are few and candidates round onto each other: distinct ones, up to 8)
-        crumpled = (name, placement) in CRUMPLED
         cand = to_world(mesh.interior_points(n=16384 if crumpled else 8, radius=0.9 if crumpled else 0.3).astype(np.float64)).astype(F)
         if crumpled:
             cand = cand[np.sort(np.unique(cand, axis=0, return_index=True)[1])]
@@ -550,7 +557,7 @@ class LeakCase:
         moved[np.arange(len(t4)), k] = t4[np.arange(len(t4)), k] - 1e-3 * np.abs(world_verts - to_world(mesh.centre)).max()
         g = np.concatenate([rays_towards(moved[i:i + 1], t4[i:i + 1]) for i in range(len(t4))])
         self.grazing_rays = g[np.isfinite(g).all(1) & crossing_parity(self.world_tris, g[:, 0:3], ndirs=2)]
-        if name in CONVEX and (name, placement) not in CRUMPLED:
+        if name in CONVEX and not crumpled:
             self.outside_rays, self.outside_limit = rays_from_outside(to_world(mesh.centre), targets)
 
     @property
@@ -589,15 +596,122 @@ def thickness_in_ulps(verts):
     return float((proj.max() - proj.min()) / np.spacing(F(np.abs(v).max())))
 
 
-def check_no_leaks(case, trace, who):
-    """trace(rays, any_hit) -> hit records.  Returns the number of rays checked."""
+# ---- cases whose geometry arrives through a transform: what an edit of the instance table leaves behind ---------------------------
+def affine(linear, offset=(0.0, 0.0, 0.0)):
+    """Column-major 16 float32 of x -> linear x + offset."""
+    m = np.eye(4)
+    m[:3, :3], m[:3, 3] = linear, offset
+    return m.T.astype(F).reshape(16).copy()
+
+
+def _edit_targets():
+    r = random_rotation(11)
+    return {"rotated": affine(random_rotation(12)),  # (the mesh's own rotation is random_rotation(5))
+            "mirrored-stretched": instance_transform(),
+            "shrunk-far": affine(r * 1e-3, (100.0, 100.0, 100.0)),
+            "huge": affine(r * 1e4),
+            "flattened": affine(r @ np.diag([1.0, 1e-4, 1.0]), (0.5, 0.5, 0.5))}
+
+
+EDIT_TARGETS = _edit_targets()
+EDIT_CASES = [(m, t) for m in MESHES for t in EDIT_TARGETS]
+# Cases whose world-space mesh has fewer than 4 float32 points of odd crossing parity among the 16384 candidates: nothing to shoot
+# from.  A list, so that collecting the GPU tests costs nothing; tests/test_trace_reference_cpu.py::test_edit_case_origins_are_
+# interior measures every case and asserts that this list is exactly the cases it finds so.
+EDIT_DROPPED = []
+
+
+class EditCase(LeakCase):
+    """ClosedMesh(name, "unit") as the object-space mesh of one instance under EDIT_TARGETS[target]; rays as LeakCase derives
+    them for its instanced case.  Whether the world-space mesh is still what its name says is measured, not looked up: it keeps
+    its 8 fixed origins and (if convex by construction) its outside rays where it is more than 16 float32 spacings thick and, for
+    the meshes of CONVEX, no vertex lies a spacing or more beyond a face plane.  (The torus is concave by construction, by half
+    its size: the concavity figure says nothing about rounding there, and it has no outside rays to lose, so thickness alone
+    decides for it.)  Otherwise the case is treated as CRUMPLED is: origins by crossing parity, no outside rays."""
+
+    def __init__(self, name, target, transform=None):
+        mesh = ClosedMesh(name, "unit")
+        self.key, self.target = (name, "edit", target), target
+        transform = EDIT_TARGETS[target] if transform is None else transform
+        world = transform_points_f32(transform, mesh.verts)[mesh.faces]
+        self.thickness, self.concavity = thickness_in_ulps(world.reshape(-1, 3)), concavity_in_spacings(world)
+        self.resolved = self.thickness > 16 and (name not in CONVEX or self.concavity < 1)
+        self._derive(mesh, transform, not self.resolved)
+
+
+@functools.lru_cache(maxsize=None)
+def edit_case(name, target):
+    return EditCase(name, target)
+
+
+# The split scene: the lattice (12, seed 2) at scale 1 stays where it is, a small closed mesh beside its x = 0 face is edited.
+# The mover's bounding ball (radius <= SPLIT_MOVER_RADIUS around a centre within SPLIT_MOVER_WOBBLE per axis of SPLIT_MOVER_CENTRE)
+# is met by NO ray of the lattice's world_rays, so check_lattice holds in the scene of both as it does for the lattice alone, and the
+# origins of the mover's outside rays, 3 radii out, lie short of x = 0 (tests/test_trace_reference_cpu.py::test_split_mover_stays_
+# clear_of_the_lattice_and_its_rays).  Seen from the mover the lattice fills nearly the half space x > 0 (44 % of the outside rays and
+# 47 % of the inside rays have it on their line beyond the mover): a ray that leaks out of the mover on that side names a lattice
+# triangle, on the other side it misses.
+SPLIT_LATTICE = (12, 2)
+SPLIT_MOVER_RADIUS = 0.16
+SPLIT_MOVER_WOBBLE = 0.03
+SPLIT_MOVER_CENTRE = (-0.6, 8.0, 4.0)
+
+
+def split_mover_transform(name, step):
+    """The mover's transform after `step` edits: turned by 0.37 rad per step about (1, 2, 3), scaled between 0.8 and 1.0 of its
+    start, moved within the wobble.  Step 0 is the placement the scene is uploaded with."""
+    axis = np.array([1.0, 2.0, 3.0]) / math.sqrt(14.0)
+    k = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    rot = np.eye(3) + math.sin(0.37 * step) * k + (1 - math.cos(0.37 * step)) * (k @ k)
+    scale = SPLIT_MOVER_RADIUS / (1.35 if name == "torus" else 1.0) * (1.0 - 0.2 * ((7 * step) % 11) / 10.0)
+    wobble = np.array([(3 * step) % 7 / 3.0 - 1.0, (5 * step) % 11 / 5.0 - 1.0, (2 * step) % 5 / 2.0 - 1.0]) * SPLIT_MOVER_WOBBLE
+    return affine(rot * scale, np.array(SPLIT_MOVER_CENTRE) + (wobble if step else 0.0))
+
+
+@functools.lru_cache(maxsize=None)
+def split_mover_case(name, step):
+    case = EditCase(name, "split-%d" % step, split_mover_transform(name, step))
+    assert case.resolved
+    return case
+
+
+def lattice_transform(placement):
+    """The 16 floats that bring the integer lattice to LATTICE_PLACEMENTS[placement]."""
+    scale, offset = LATTICE_PLACEMENTS[placement]
+    return affine(np.eye(3) * scale, (offset, offset, offset))
+
+
+def lattice_tris_through_transform(solid, placement):
+    """The lattice triangles in lattice units as a float32 object-space mesh, brought to the world the way a float32 renderer
+    does it -- and the assertion that this IS world_tris(scale, offset), bit for bit (powers of two and small integers: every
+    product and every sum is exact), which is what lets the integer march stay the reference after an edit."""
+    obj = solid.lattice_tris.astype(F)
+    assert np.array_equal(obj.astype(np.int64), solid.lattice_tris)
+    world = transform_points_f32(lattice_transform(placement), obj)
+    want = solid.world_tris(*LATTICE_PLACEMENTS[placement])
+    assert world.dtype == F and np.array_equal(world.view(np.uint32), want.view(np.uint32))
+    return obj, world
+
+
+def check_no_leaks(case, trace, who, prim_range=None):
+    """trace(rays, any_hit) -> hit records.  Returns the number of rays checked.  prim_range = (first, count): every closest
+    hit must name a triangle of that range -- in a scene with other objects a ray that leaks out of the mesh hits one of them."""
+
+    def in_range(h, what):
+        if prim_range is not None:
+            bad = (h["prim"] < prim_range[0]) | (h["prim"] >= prim_range[0] + prim_range[1])
+            assert not bad.any(), "%s %s: %d of %d %s hit a triangle outside [%d, %d) (first: ray %d, triangle %d)" % (
+                who, case.key, bad.sum(), len(bad), what, prim_range[0], prim_range[0] + prim_range[1], np.nonzero(bad)[0][0], h["prim"][bad][0])
+
     h = trace(case.inside_rays, False)
     bad = h["prim"] < 0
     assert not bad.any(), "%s %s: %d of %d rays from inside leak out (first: ray %d)" % (who, case.key, bad.sum(), len(bad), np.nonzero(bad)[0][0])
+    in_range(h, "rays from inside")
     a = trace(case.inside_rays, True)
     assert (a["prim"] == 0).all(), "%s %s: %d shadow rays from inside are not occluded" % (who, case.key, (a["prim"] != 0).sum())
     g = trace(case.grazing_rays, False)
     assert (g["prim"] >= 0).all(), "%s %s: %d of %d slab-grazing rays from inside leak out" % (who, case.key, (g["prim"] < 0).sum(), len(g))
+    in_range(g, "slab-grazing rays from inside")
     assert (trace(case.grazing_rays, True)["prim"] == 0).all(), "%s %s: slab-grazing shadow rays from inside are not occluded" % (who, case.key)
     n = len(h) + len(g)
     if case.outside_rays is not None:
@@ -607,6 +721,7 @@ def check_no_leaks(case, trace, who):
         bad = (h["prim"] < 0) | ~(dist < case.outside_limit)
         assert not bad.any(), "%s %s: %d of %d rays from outside pass the near surface (first: ray %d)" % (
             who, case.key, bad.sum(), len(bad), np.nonzero(bad)[0][0])
+        in_range(h, "rays from outside")
         sh = r.copy()
         sh[:, 7] = (case.outside_limit / np.linalg.norm(r[:, 4:7].astype(np.float64), axis=1)).astype(F)  # up to the centre only
         a = trace(sh, True)

@@ -1,4 +1,4 @@
-"""Scene assembly shared by tests/test_trace_reference_cpu.py and tests/test_gpu_trace_reference.py (tests/trace_reference.py
+"""Scene assembly shared by tests/test_trace_reference_cpu.py, tests/test_gpu_trace_reference.py and tests/test_gpu_trace_edits.py (tests/trace_reference.py
 itself imports nothing of the product)."""
 import numpy as np
 
