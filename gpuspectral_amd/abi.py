@@ -237,6 +237,21 @@ def svgf(min_history=0, sigma_variance=0.0):
     return Svgf(C.sizeof(Svgf), min_history, sigma_variance)
 
 
+class Antilag(C.Structure):
+    """gsp_antilag: the parameters of the temporal anti-lag (gsp_temporal_antilag); all zero = every default."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("fast_history", C.c_uint32),  # 0 = 4; otherwise 1..64
+        ("radius", C.c_uint32),  # 0 = 2 (5 x 5); otherwise 1..3
+        ("sigma_scale", C.c_float),  # 0 = 2.0; otherwise > 0 and finite
+    ]
+
+
+def antilag(fast_history=0, radius=0, sigma_scale=0.0):
+    return Antilag(C.sizeof(Antilag), fast_history, radius, sigma_scale)
+
+
 class Luminance(C.Structure):
     """gsp_luminance: the frame statistics of the Reinhard operator (gsp_frame_luminance)."""
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/gpuspectral_pt.h"
+#include "pt_antilag.h"
 #include "pt_denoise.h"
 #include "pt_display.h"
 #include "pt_illum.h"

@@ -181,6 +181,20 @@ struct gsp_context {
   DevBuf<q4> tp_table, tp_v;
   MotionRecord* h_motion = nullptr;
   size_t h_motion_cap = 0;
+  // temporal anti-lag (gsp_temporal_antilag): what the newest accumulate ran with -- its constants, the number of motion records
+  // it copied to tp_table, its flags and its number in the context's count of accumulates -- and the two ping-pong fast planes,
+  // made by the first gsp_temporal_antilag of the context; al_cur = the newest one, al_serial = the accumulate it belongs to
+  // (0 = none).  The fast history is valid for an accumulate when al_serial is the accumulate before it and that accumulate
+  // itself ran with a valid history.
+  struct AccumulateRecord {
+    TemporalConsts k{};
+    uint32_t records = 0;
+    bool follow = false, demod = false;
+    uint64_t serial = 0;
+  } tp_acc;
+  DevBuf<q4> al_f[2];
+  int al_cur = 0;
+  uint64_t al_serial = 0;
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;

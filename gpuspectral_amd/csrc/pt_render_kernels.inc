@@ -1560,6 +1560,87 @@ __global__ __launch_bounds__(kBlock) void k_svgf_atrous_feedback(const v4f* __re
   dn_store(hist + p, illum_feedback<DEMOD>(r.E, a, h));
 }
 
+// ---- temporal anti-lag (pt_antilag.h; include/gpuspectral_pt.h "Temporal anti-lag") ---------------------------------------------
+// Step A, the fast history: the frame's accumulate once more with F of the older fast plane in H's place and no plane but F'
+// written -- k_temporal_reproject (FOLLOW, DEMOD = false, false), k_temporal_reproject_follow<false> (true, false) and
+// k_temporal_reproject_illum<false, FOLLOW> (DEMOD) stand behind it, with their tile, their loads and their order.  G and I of
+// the taps come from the older history set, which the accumulate left as it was.  Kernels of their own, launched only by
+// gsp_temporal_antilag: the accumulate runs the instruction streams it ran before.
+template <bool FOLLOW, bool DEMOD>
+__global__ __launch_bounds__(kBlock) void k_antilag_fast(const v4f* __restrict__ accum, const v4f* __restrict__ albedo, const v4f* __restrict__ geom,
+                                                         const v4u* __restrict__ ids, const v4f* __restrict__ Fprev, const v4f* __restrict__ Gprev,
+                                                         const uint32_t* __restrict__ Iprev, const v4f* __restrict__ table, uint32_t num_records,
+                                                         v4f* __restrict__ Fout, TemporalConsts k) {
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  const int width = (int)k.cur.width;
+  if (px >= width || py >= (int)k.cur.height) return;
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  const uint32_t inst = ids[p].z;
+  const dn4 c = dn_load(accum + p), alb = dn_load(albedo + p), g = dn_load(geom + p);
+  MotionRecord rec = motion_record_of_class(FOLLOW ? kMotionNoHistory : kMotionStatic);
+  bool wave_moved = false;
+  if constexpr (FOLLOW) {
+    if (inst < num_records) {
+      const v4f* r = table + (size_t)inst * kMotionRecordQuads;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        rec.b[i] = dn_load(r + i);
+        rec.n[i] = dn_load(r + 3 + i);
+      }
+    }
+    wave_moved = __ballot(motion_class(rec) == kMotionMoved) != 0;
+  }
+  dn_store(Fout + p, antilag_fast_pixel<FOLLOW, DEMOD>(k, px, py, c, alb, g, inst, rec, wave_moved, [&](int x, int y, dn4& F_, dn4& G_, uint32_t& I_) {
+             const size_t q = (size_t)y * (size_t)width + (size_t)x;  // a pixel of the frame
+             F_ = dn_load(Fprev + q);
+             G_ = dn_load(Gprev + q);
+             I_ = Iprev[q];
+           }));
+}
+
+// Step B, the clamp of the newest history into the box of F's window statistics, in place.  A block owns a tile of 32 x 8 pixels
+// and stages tile + apron of R -- (32 + 2 R) x (8 + 2 R) records, 38 x 14 at R = 3 -- in LDS by row-major 16-byte loads, one per
+// lane and plane as k_svgf_variance does: F' as it is, and of G the normal with the instance word I in the place of the depth,
+// which the window does not read -- two 16-byte records per pixel, 17 024 bytes per block at R = 3, and two ds_read_b128 per
+// tap.  A tap of a wave is two rows of 32 consecutive records: the 16 lanes of a ds_read_b128 group lie in one row at 16
+// distinct 16-byte slots of the 256-byte bank row, so the reads are free of bank conflicts at any row pitch, and no padding is
+// needed.  Out-of-frame records are zero and never read (antilag_clamp_pixel skips the tap first).  H is read once per pixel
+// and written only where it left its box.
+template <int R>
+__global__ __launch_bounds__(kBlock) void k_antilag_clamp(const v4f* __restrict__ F, const v4f* __restrict__ G, const uint32_t* __restrict__ I,
+                                                          v4f* __restrict__ H, AntilagParams a, float normal_min, int width, int height) {
+  constexpr int PW = kDnTileW + 2 * R, PH = kDnTileH + 2 * R;
+  __shared__ v4f sF[PW * PH], sN[PW * PH];
+  const int x0 = (int)blockIdx.x * kDnTileW - R, y0 = (int)blockIdx.y * kDnTileH - R;
+  for (int i = (int)threadIdx.x; i < PW * PH; i += kBlock) {
+    const int ly = i / PW, lx = i - ly * PW;
+    const int gx = x0 + lx, gy = y0 + ly;
+    v4f f = {0.0f, 0.0f, 0.0f, 0.0f}, n = f;
+    if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+      const size_t idx = (size_t)gy * (size_t)width + (size_t)gx;
+      f = F[idx];
+      n = G[idx];
+      n.w = u2f(I[idx]);
+    }
+    sF[i] = f;
+    sN[i] = n;
+  }
+  __syncthreads();
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  if (px >= width || py >= height) return;  // (no barrier below)
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  a.radius = R;
+  const AntilagClampOut o = antilag_clamp_pixel(a, normal_min, width, height, px, py, dn_load(H + p), [&](int x, int y, dn4& F_, dn4& G_, uint32_t& I_) {
+    const int i = (y - y0) * PW + (x - x0);  // |x - px| <= R and |y - py| <= R: inside the staged rectangle
+    F_ = dn_load(&sF[i]);
+    G_ = dn_load(&sN[i]);
+    I_ = f2u(G_.w);
+  });
+  if (o.changed) dn_store(H + p, o.H);
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

@@ -1,6 +1,6 @@
 // pt_render_post.inc -- part of the translation unit pt_render.hip (through pt_render_pipeline.inc; not compiled on its
 // own).  The host side of the stages behind the path tracer: the LDR film, the denoiser, temporal accumulation, the
-// variance-guided filter and the illumination history -- their launchers, guards, read-out tails and exports.
+// variance-guided filter, the illumination history and the temporal anti-lag -- their launchers, guards, read-out tails and exports.
 
 // ---- what the stages share: launch shapes, guards with one text, the tails of the *_to_device exports ----
 // a grid-stride launch over `n` items: enough blocks for them, at most `per_cu` per compute unit
@@ -426,6 +426,7 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
   ctx->tp_valid = true;
   ctx->tp_done = true;
   ctx->tp_fed = false;  // (gsp_temporal_svgf_feedback: at most one per accumulate)
+  ctx->tp_acc = {k, records, ctx->tp_follow, ctx->tp_demod, ctx->tp_acc.serial + 1};  // (gsp_temporal_antilag: what this accumulate ran with)
   return GSP_OK;
 }
 
@@ -702,6 +703,108 @@ int gsp_temporal_svgf_feedback_to_device(gsp_context* ctx, const gsp_denoise* de
   if (dst && ctx->have_frame && refuse_too_small(ctx, bytes, need) != GSP_OK) return GSP_ERR_INVALID;
   return to_device_tail(ctx, dst, need, ctx->dn_out,
                         [&](void* target) { return svgf_ctx(ctx, denoise, svgf, "gsp_temporal_svgf_feedback_to_device", dst, target, true, levels); });
+}
+
+}  // extern "C"
+
+// ---- temporal anti-lag (include/gpuspectral_pt.h, "Temporal anti-lag"; per-pixel code: pt_antilag.h) ----
+// Queues the two launches of a gsp_temporal_antilag on `stream`: Step A -- `frame`, F of `fprev` and G, I of the older set `prev`
+// (none of the three read when k.history_valid == 0) into `fout` under the accumulate's flags -- and Step B, the clamp of out.h
+// into the box of `fout` with out.g and out.i; does not synchronise.  k = antilag_fast_consts of the accumulate's constants;
+// table, num_records: the accumulate's motion records (`follow` alone).
+static hipError_t antilag_run(hipStream_t stream, TemporalFlags f, const TemporalFrame& frame, const v4f* fprev, const TemporalSet& prev, const TemporalSet& out,
+                              const v4f* table, uint32_t num_records, v4f* fout, const TemporalConsts& k, const AntilagParams& a) {
+  if (k.cur.width == 0 || k.cur.height == 0) return hipSuccess;
+  const dim3 grid = tile_grid(k.cur.width, k.cur.height), block(kBlock);
+#define GSP_ANTILAG_LAUNCH(FOLLOW, DEMOD)                                                                                                       \
+  hipLaunchKernelGGL((k_antilag_fast<FOLLOW, DEMOD>), grid, block, 0, stream, frame.accum, frame.albedo, frame.geom, frame.ids, fprev, prev.g, prev.i, \
+                     table, num_records, fout, k)
+  if (f.demod) {
+    if (f.follow) GSP_ANTILAG_LAUNCH(true, true);
+    else GSP_ANTILAG_LAUNCH(false, true);
+  } else {
+    if (f.follow) GSP_ANTILAG_LAUNCH(true, false);
+    else GSP_ANTILAG_LAUNCH(false, false);
+  }
+#undef GSP_ANTILAG_LAUNCH
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+#define GSP_ANTILAG_LAUNCH(R) \
+  hipLaunchKernelGGL((k_antilag_clamp<R>), grid, block, 0, stream, (const v4f*)fout, (const v4f*)out.g, (const uint32_t*)out.i, out.h, a, k.p.normal_min, \
+                     (int)k.cur.width, (int)k.cur.height)
+  if (a.radius == 1) GSP_ANTILAG_LAUNCH(1);
+  else if (a.radius == 2) GSP_ANTILAG_LAUNCH(2);
+  else GSP_ANTILAG_LAUNCH(3);
+#undef GSP_ANTILAG_LAUNCH
+  return hipGetLastError();
+}
+
+// what the two read-outs of the fast history ask first
+static int temporal_have_fast(gsp_context* ctx, const char* who, const void* out_ptr) {
+  int rc = temporal_have_history(ctx, who, out_ptr);
+  if (rc != GSP_OK) return rc;
+  if (ctx->al_serial != ctx->tp_acc.serial) {
+    ctx->err = std::string(who) + " needs a gsp_temporal_antilag call since the newest gsp_temporal_accumulate";
+    return GSP_ERR_INVALID;
+  }
+  return GSP_OK;
+}
+
+extern "C" {
+
+int gsp_temporal_antilag(gsp_context* ctx, const gsp_antilag* antilag) {
+  if (!ctx) return GSP_ERR_INVALID;
+  const char* who = "gsp_temporal_antilag";
+  int rc = temporal_have_history(ctx, who, nullptr, true);
+  if (rc != GSP_OK) return rc;
+  AntilagParams a;
+  if (const char* why = resolve_antilag(antilag, a)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  if (!ctx->tp_done) {
+    ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since gsp_frame_begin";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->al_serial == ctx->tp_acc.serial) {
+    ctx->err = std::string(who) + ": the history has been clamped already (one call per gsp_temporal_accumulate)";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->tp_fed) {
+    ctx->err = std::string(who) + ": the history has been fed back already (the call belongs before gsp_temporal_svgf_feedback)";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  rc = pipeline_drain(ctx);
+  if (rc != GSP_OK) return rc;
+  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
+  for (DevBuf<q4>& b : ctx->al_f) CTX_TRY(ctx, b.ensure(n, &ctx->bytes));
+  const gsp_context::AccumulateRecord& acc = ctx->tp_acc;
+  const bool fast_valid = ctx->al_serial != 0 && ctx->al_serial + 1 == acc.serial;
+  const TemporalConsts k = antilag_fast_consts(acc.k, a, fast_valid);
+  const int from = ctx->al_cur, to = from ^ 1;
+  const TemporalFrame frame{(const v4f*)ctx->accum.p, (const v4f*)ctx->feat_albedo.p, (const v4f*)ctx->feat_geom.p, (const v4u*)ctx->feat_ids.p};
+  CTX_TRY(ctx, antilag_run(ctx->stream, TemporalFlags{false, acc.follow, acc.demod}, frame, (const v4f*)ctx->al_f[from].p, temporal_set(ctx, ctx->tp_cur ^ 1),
+                           temporal_set(ctx, ctx->tp_cur), acc.follow ? (const v4f*)ctx->tp_table.p : nullptr, acc.records, (v4f*)ctx->al_f[to].p, k, a));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (complete when the call returns, like the accumulate)
+  ctx->al_cur = to;
+  ctx->al_serial = acc.serial;
+  return GSP_OK;
+}
+
+int gsp_download_temporal_fast(gsp_context* ctx, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_fast(ctx, "gsp_download_temporal_fast", out);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  return read_back_bytes(ctx, ctx->al_f[ctx->al_cur].p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
+}
+
+int gsp_temporal_fast_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_fast(ctx, "gsp_temporal_fast_to_device", dst);
+  if (rc != GSP_OK) return rc;
+  return plane_to_device(ctx, dst, bytes, ctx->al_f[ctx->al_cur].p);
 }
 
 }  // extern "C"

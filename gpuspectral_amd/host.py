@@ -104,6 +104,9 @@ def load():
     L.gsph_pathtracer_temporal_image_to_device.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_temporal_svgf_feedback.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp, u64]
     L.gsph_pathtracer_temporal_svgf_feedback_to_device.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp, u64]
+    L.gsph_pathtracer_temporal_antilag.argtypes = [vp, C.POINTER(abi.Antilag)]
+    L.gsph_pathtracer_download_temporal_fast.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_temporal_fast_to_device.argtypes = [vp, vp, u64]
     _LIB = L
     return L
 
@@ -453,6 +456,25 @@ class PathTracer:
         self._check(self._L.gsph_pathtracer_temporal_svgf_feedback_to_device(self._h, C.byref(denoise) if denoise is not None else None,
                                                                              C.byref(svgf) if svgf is not None else None, levels, ptr, nbytes),
                     "temporalSvgfFeedbackToDevice")
+
+    def temporal_antilag(self, antilag=None):
+        """PathTracer::temporalAntilag: the fast history of this frame's temporal_accumulate and the clamp of the long one into its
+        box (once per temporal_accumulate, before any temporal_svgf_feedback).  antilag: an abi.Antilag, None = every default."""
+        self._check(self._L.gsph_pathtracer_temporal_antilag(self._h, C.byref(antilag) if antilag is not None else None), "temporalAntilag")
+
+    def download_temporal_fast(self):
+        """PathTracer::downloadTemporalFast: (h, w, 4) float32, the fast history; .w = its length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_temporal_fast(self._h, out.ctypes.data, out.size), "downloadTemporalFast")
+        return out
+
+    def temporal_fast_to_device(self, dst, nbytes=None):
+        """PathTracer::temporalFastToDevice: dst = a torch tensor on the device, or a device pointer with nbytes."""
+        if hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsph_pathtracer_temporal_fast_to_device(self._h, ptr, nbytes), "temporalFastToDevice")
 
     def stats(self):
         s = abi.Stats()

@@ -347,6 +347,18 @@ void PathTracer::temporalSvgfFeedbackToDevice(const gsp_denoise* denoise, const 
   check(gsp_temporal_svgf_feedback_to_device(ctx, denoise, svgf, levels, deviceDst, bytes), "gsp_temporal_svgf_feedback_to_device");
 }
 
+void PathTracer::temporalAntilag(const gsp_antilag* antilag) { check(gsp_temporal_antilag(ctx, antilag), "gsp_temporal_antilag"); }
+
+std::vector<float> PathTracer::downloadTemporalFast() {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_temporal_fast(ctx, out.data()), "gsp_download_temporal_fast");
+  return out;
+}
+
+void PathTracer::temporalFastToDevice(void* deviceDst, uint64_t bytes) {
+  check(gsp_temporal_fast_to_device(ctx, deviceDst, bytes), "gsp_temporal_fast_to_device");
+}
+
 void PathTracer::nextFrame() {
   featureTimestamp = timestamp;  // (the feature samples of the new frame are those of its beauty samples)
   check(gsp_frame_begin(ctx, width, height, pixelIds.empty() ? nullptr : pixelIds.data(), pixelIds.size()), "gsp_frame_begin");

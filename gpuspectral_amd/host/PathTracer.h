@@ -137,6 +137,12 @@ class PathTracer : public RenderPassCreator {
   void temporalImageToDevice(void* deviceDst, uint64_t bytes);
   std::vector<float> temporalSvgfFeedback(const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, bool wantOutput = true);
   void temporalSvgfFeedbackToDevice(const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels, void* deviceDst, uint64_t bytes);
+  // Temporal anti-lag (gpuspectral_pt.h "Temporal anti-lag"): temporalAntilag keeps a short history beside the long one and clamps
+  // the long one into the box of its window statistics, so that a change of the lighting is forgotten in a few frames.  Once per
+  // temporalAccumulate, before any temporalSvgfFeedback.  downloadTemporalFast / temporalFastToDevice: the short history.
+  void temporalAntilag(const gsp_antilag* antilag = nullptr);
+  std::vector<float> downloadTemporalFast();
+  void temporalFastToDevice(void* deviceDst, uint64_t bytes);
   void nextFrame();  // a new frame (accumulate buffer and feature planes cleared) whose samples continue the timestamp sequence
   void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }

@@ -396,6 +396,20 @@ int gsph_pathtracer_temporal_svgf_feedback_to_device(void* pt, const gsp_denoise
                                                      uint64_t bytes) {
   return guard([&] { ((PathTracer*)pt)->temporalSvgfFeedbackToDevice(denoise, svgf, levels, device_dst, bytes); });
 }
+// temporal anti-lag of a PathTracer (gpuspectral_pt.h "Temporal anti-lag")
+int gsph_pathtracer_temporal_antilag(void* pt, const gsp_antilag* antilag) {
+  return guard([&] { ((PathTracer*)pt)->temporalAntilag(antilag); });
+}
+int gsph_pathtracer_download_temporal_fast(void* pt, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTemporalFast();
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_temporal_fast_to_device(void* pt, void* device_dst, uint64_t bytes) {
+  return guard([&] { ((PathTracer*)pt)->temporalFastToDevice(device_dst, bytes); });
+}
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {
     std::vector<uint8_t> v;

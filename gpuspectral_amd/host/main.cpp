@@ -34,6 +34,9 @@
 //   history") and out.pfm of --temporal receives the image read-out (the history re-modulated by the last frame's albedo).
 //   --svgf-feedback LEVELS (with --svgf): on every frame of --temporal-frames the output of the filter's first LEVELS levels is
 //   written back into the history (gsp_temporal_svgf_feedback); the files of --temporal and --denoise show the fed-back history.
+//   --temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S] (with --temporal): on every frame, between the
+//   accumulate and any --svgf-feedback, a fast history of at most N frames is kept beside the long one and the long one is clamped
+//   into the box of its statistics over (2 R + 1)^2 pixels, S standard deviations wide (gpuspectral_pt.h "Temporal anti-lag").
 //   --svgf out.pfm [--svgf-sigma S] [--svgf-min-history N] (with --temporal): the history keeps its luminance moments and out.pfm
 //   receives its variance-guided filter (gpuspectral_pt.h "Variance-guided filter"; S = sigma_variance, inf = the term off; N =
 //   2..65536), with the levels and guide sigmas of --denoise-iterations / --denoise-sigma where --denoise is given.
@@ -78,6 +81,9 @@ int main(int argc, char** argv) {
   std::string motionPath;
   bool temporalDemodulate = false;
   long svgfFeedback = 0;  // (0 = not given)
+  bool temporalAntilag = false, antilagOptions = false;
+  gsp_antilag antilag{};
+  antilag.struct_size = (uint32_t)sizeof(gsp_antilag);
   std::string svgfPath;
   gsp_svgf svgf{};
   svgf.struct_size = (uint32_t)sizeof(gsp_svgf);
@@ -162,6 +168,24 @@ int main(int argc, char** argv) {
         return 2;
       }
       used = 2;
+    } else if (flag == "--temporal-antilag") temporalAntilag = true, used = 1;
+    else if ((flag == "--antilag-fast" || flag == "--antilag-radius") && argc > 2) {
+      const bool fast = flag == "--antilag-fast";
+      char* end = nullptr;
+      const long v = std::strtol(argv[2], &end, 10);
+      if (end == argv[2] || *end != 0 || v < 1 || v > (fast ? 64 : 3)) {
+        if (fast) std::fprintf(stderr, "gsp_render: bad antilag fast history '%s' (expected the cap of the fast history's length, 1..64)\n", argv[2]);
+        else std::fprintf(stderr, "gsp_render: bad antilag radius '%s' (expected the half-width of the window, 1..3)\n", argv[2]);
+        return 2;
+      }
+      (fast ? antilag.fast_history : antilag.radius) = (uint32_t)v;
+      antilagOptions = true, used = 2;
+    } else if (flag == "--antilag-sigma" && argc > 2) {
+      if (!parseFloat(argv[2], antilag.sigma_scale) || !(antilag.sigma_scale > 0.0f) || !std::isfinite(antilag.sigma_scale)) {
+        std::fprintf(stderr, "gsp_render: bad antilag sigma '%s' (expected the half-width of the box in standard deviations, > 0)\n", argv[2]);
+        return 2;
+      }
+      antilagOptions = true, used = 2;
     } else if (flag == "--svgf" && argc > 2) svgfPath = argv[2], used = 2;
     else if (flag == "--svgf-sigma" && argc > 2) {
       if (std::string(argv[2]) == "inf") svgf.sigma_variance = INFINITY;
@@ -339,6 +363,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --temporal-demodulate needs --temporal out.pfm\n");
     return 2;
   }
+  if (temporalPath.empty() && temporalAntilag) {
+    std::fprintf(stderr, "gsp_render: --temporal-antilag needs --temporal out.pfm\n");
+    return 2;
+  }
+  if (!temporalAntilag && antilagOptions) {
+    std::fprintf(stderr, "gsp_render: --antilag-fast, --antilag-radius and --antilag-sigma need --temporal-antilag\n");
+    return 2;
+  }
   if (svgfPath.empty() && svgfOptions) {
     std::fprintf(stderr, "gsp_render: --svgf-sigma and --svgf-min-history need --svgf out.pfm\n");
     return 2;
@@ -348,7 +380,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -414,6 +446,7 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> ldr, denoisedLdr;
     std::vector<float> img, featAlbedo, featGeom, denoised, temporal, temporalDenoised, temporalSvgf, motion;
     double temporalLength = 0.0;
+    double fastLength = 0.0;
     const uint32_t fspp = featureSpp > 0 ? (uint32_t)featureSpp : spp;
     gsp_stats st;
     double s;
@@ -437,6 +470,7 @@ int main(int argc, char** argv) {
         pt.render(scene, spp);
         pt.renderFeatures(scene, spp);
         pt.temporalAccumulate();
+        if (temporalAntilag) pt.temporalAntilag(&antilag);
         if (svgfFeedback) pt.temporalSvgfFeedback(&denoise, &svgf, (uint32_t)svgfFeedback, false);
         const float a = temporalOrbit * 3.14159265358979323846f / 180.0f, cs = std::cos(a), sn = std::sin(a);
         const mat4 m = scene.camera.getToWorld();
@@ -471,6 +505,12 @@ int main(int argc, char** argv) {
       if (!temporalPath.empty()) {  // the last frame into the history, on the planes above or on a pass of its own
         if (featuresPrefix.empty() && denoisePath.empty()) pt.renderFeatures(scene, spp);
         pt.temporalAccumulate();
+        if (temporalAntilag) {  // (before the feedback: the filter starts from the clamped history)
+          pt.temporalAntilag(&antilag);
+          const std::vector<float> fast = pt.downloadTemporalFast();
+          for (size_t i = 3; i < fast.size(); i += 4) fastLength += fast[i];
+          fastLength /= (double)width * height;
+        }
         if (svgfFeedback) temporalSvgf = pt.temporalSvgfFeedback(&denoise, &svgf, (uint32_t)svgfFeedback);  // (first: the files below show the fed-back history)
         temporal = temporalDemodulate ? pt.downloadTemporalImage() : pt.downloadTemporal();
         if (!denoisePath.empty()) temporalDenoised = pt.downloadTemporalDenoised(&denoise);
@@ -547,6 +587,9 @@ int main(int argc, char** argv) {
       std::printf("temporal: %d frame%s of %u spp, %g degrees per frame, mean history length %.2f -> %s%s%s\n", temporalFrames, temporalFrames == 1 ? "" : "s",
                   spp, (double)temporalOrbit, temporalLength, temporalPath.c_str(), dn.empty() ? "" : ", ", dn.c_str());
       if (temporalDemodulate) std::printf("temporal: the history holds illumination (colour / albedo); %s is its image read-out\n", temporalPath.c_str());
+      if (temporalAntilag)
+        std::printf("temporal antilag: the history clamped into the box of the fast history on each of %d frame%s, mean fast history length %.2f\n", temporalFrames,
+                    temporalFrames == 1 ? "" : "s", fastLength);
       if (svgfFeedback)
         std::printf("svgf feedback: the first %ld level%s fed back into the history on each of %d frame%s\n", svgfFeedback, svgfFeedback == 1 ? "" : "s",
                     temporalFrames, temporalFrames == 1 ? "" : "s");

@@ -68,6 +68,9 @@ EXPORTS = (
     "gsp_temporal_image_to_device",
     "gsp_temporal_svgf_feedback",
     "gsp_temporal_svgf_feedback_to_device",
+    "gsp_temporal_antilag",
+    "gsp_download_temporal_fast",
+    "gsp_temporal_fast_to_device",
     "gsp_frame_sample_base",
     "gsp_get_stats",
     "gsp_reset_stats",
@@ -184,6 +187,9 @@ def load():
     L.gsp_temporal_image_to_device.argtypes = [vp, vp, u64]
     L.gsp_temporal_svgf_feedback.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp]
     L.gsp_temporal_svgf_feedback_to_device.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), C.c_uint32, vp, u64]
+    L.gsp_temporal_antilag.argtypes = [vp, C.POINTER(abi.Antilag)]
+    L.gsp_download_temporal_fast.argtypes = [vp, vp]
+    L.gsp_temporal_fast_to_device.argtypes = [vp, vp, u64]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -234,7 +240,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -595,6 +601,28 @@ class Context:
         self._check(self._L.gsp_temporal_svgf_feedback_to_device(self._h, C.byref(denoise) if denoise is not None else None,
                                                                  C.byref(svgf) if svgf is not None else None, levels, ptr, nbytes),
                     "gsp_temporal_svgf_feedback_to_device")
+
+    # ---- temporal anti-lag (gpuspectral_pt.h "Temporal anti-lag") ----
+    def temporal_antilag(self, antilag=None):
+        """gsp_temporal_antilag: accumulates the fast history of the frame's temporal_accumulate and clamps the newest history into
+        the box of its window statistics (once per temporal_accumulate, before any temporal_svgf_feedback).  antilag: an
+        abi.Antilag, None = every default."""
+        self._check(self._L.gsp_temporal_antilag(self._h, C.byref(antilag) if antilag is not None else None), "gsp_temporal_antilag")
+
+    def download_temporal_fast(self):
+        """gsp_download_temporal_fast: the newest fast history, (height, width, 4) float32, .w = its length."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_temporal_fast(self._h, out.ctypes.data), "gsp_download_temporal_fast")
+        return out
+
+    def temporal_fast_to_device(self, dst, nbytes=None):
+        """gsp_temporal_fast_to_device: the same into device memory, width*height*16 bytes.  dst: a torch tensor on the context's
+        device (its bytes from its storage offset on), or a device pointer with nbytes."""
+        if hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsp_temporal_fast_to_device(self._h, ptr, nbytes), "gsp_temporal_fast_to_device")
 
     def pixel_stats(self):
         """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of

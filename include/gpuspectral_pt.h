@@ -79,7 +79,9 @@ extern "C" {
                                 gsp_temporal_follow_instances, gsp_download_temporal_motion, gsp_temporal_motion_to_device
                                 (see "Temporal accumulation: moved instances");
                                 gsp_temporal_demodulate, gsp_download_temporal_image, gsp_temporal_image_to_device,
-                                gsp_temporal_svgf_feedback, gsp_temporal_svgf_feedback_to_device (see "Illumination history") */
+                                gsp_temporal_svgf_feedback, gsp_temporal_svgf_feedback_to_device (see "Illumination history");
+                                gsp_temporal_antilag, gsp_download_temporal_fast, gsp_temporal_fast_to_device (see "Temporal
+                                anti-lag") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -1065,6 +1067,64 @@ int gsp_temporal_svgf_feedback(gsp_context* ctx, const gsp_denoise* denoise, con
 /* gsp_temporal_svgf_to_device plus the feedback; `bytes` is checked when device_dst is not NULL. */
 int gsp_temporal_svgf_feedback_to_device(gsp_context* ctx, const gsp_denoise* denoise, const gsp_svgf* svgf, uint32_t levels,
                                          void* device_dst /* may be NULL */, uint64_t bytes);
+
+/*
+ * Temporal anti-lag.  A tap of the history is rejected by geometry alone (instance index, depth, normal), so when the LIGHTING
+ * changes -- gsp_update_tables dims a light, a moved object drags its shadow across a wall -- every tap passes and the stale
+ * illumination decays only as (1 - alpha)^frames.  gsp_temporal_antilag keeps a second, short history F beside the long one
+ * (the responsive history of ReLAX-style denoisers), takes the mean and the standard deviation of F over a small window and
+ * clamps the long history into that box; a clamped pixel's history length is cut to the short one's.  It is a call of its own
+ * after gsp_temporal_accumulate: a context that never makes it runs the kernels it ran before, holds no plane of this section
+ * and returns the same bits.  Arithmetic is float32 in the order written (no contraction); / and sqrt are correctly rounded.
+ *
+ * State.  Two ping-pong planes F = {r, g, b, len}, 16 bytes per pixel each, made by the first gsp_temporal_antilag of the
+ * context and counted in its bytes.  fast_valid is true exactly when the accumulate BEFORE the current one was followed by a
+ * gsp_temporal_antilag and history_valid has not been cleared since; everything that clears history_valid clears fast_valid.
+ *
+ * Call order.  The call needs a gsp_temporal_accumulate in the current frame, at most one call per accumulate, and it comes
+ * before the gsp_temporal_svgf_feedback* of that accumulate; otherwise GSP_ERR_INVALID.
+ *
+ * Step A, the fast history.  Per pixel F' is what the frame's gsp_temporal_accumulate computed for H' -- the same context state,
+ * the same resolved gsp_temporal, the same cameras and motion records: steps 1-7, taps, weights and tests, following and
+ * demodulation -- with
+ *     F_q of the OLDER fast plane for H_q, in the "len > 0, rgb finite" test of a tap and in the sums;
+ *     G_q and I_q of the OLDER history set, which the accumulate left as it was;
+ *     min(fast_history, max_history) for max_history;
+ *     history_valid && fast_valid for history_valid.
+ * Without a fast history F' = {x.r, x.g, x.b, 1} for a finite x and {c.r, c.g, c.b, 0} otherwise, x = c, or e under
+ * demodulation: what "Blend" says.  The frame's records are read as they are at the call.
+ *
+ * Step B, the clamp, in place on H of the NEWEST set; G and I below are the newest set's.  A pixel p is processed when
+ * H_p.len > 0, F'_p.len > 0 and both have finite rgb.  The window is q = p + (dx, dy), dy = -radius .. radius outer and dx
+ * inner; a q counts when it is inside the frame, F'_q.len > 0 with rgb finite, I_q == I_p and, for a surface pixel (I_p is not
+ * the background's 0xffffffff), (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z >= normal_min -- the accumulate's normal_min:
+ *     n += 1.0f;  s1.k += F'_q.k;  s2.k += F'_q.k * F'_q.k                                   (k = r, g, b)
+ *     n < 2 radius + 1:  the pixel is left alone
+ *     m.k = s1.k / n;  v.k = max(s2.k / n - m.k * m.k, 0);  sd.k = sqrt(v.k)
+ *     lo.k = m.k - sigma_scale * sd.k;  hi.k = m.k + sigma_scale * sd.k
+ *     H.k = H.k < lo.k ? lo.k : (H.k > hi.k ? hi.k : H.k)
+ *     if any channel changed:  H.len = min(H.len, F'_p.len)
+ * G, I, M, V, the older set, every pixel that is not processed and every pixel that already lies inside its box keep their bits.
+ *
+ * Read-outs.  gsp_download_temporal_fast / gsp_temporal_fast_to_device return F' of the newest fast plane, .w = its length;
+ * they need a gsp_temporal_antilag since the history was last invalidated and after the newest accumulate.
+ *
+ * Limits.  M is not clamped: with fast_history < gsp_svgf.min_history a clamped pixel falls back to the variance-guided
+ * filter's spatial variance estimate.  Values whose square overflows float32 are outside the domain.  Out of scope:
+ * gsp_multi_* variants, separate direct and indirect histories, temporal gradients (A-SVGF).
+ */
+typedef struct gsp_antilag {
+  uint32_t struct_size;  /* sizeof(gsp_antilag) of the host's header; same rule as gsp_denoise / gsp_temporal (NULL and struct_size 0 = every default) */
+  uint32_t fast_history; /* cap of the fast history's length; 0 = 4; otherwise 1 .. 64 */
+  uint32_t radius;       /* half-width of the window; 0 = 2 (5 x 5); otherwise 1 .. 3 */
+  float sigma_scale;     /* half-width of the box in standard deviations; 0 = 2.0; otherwise > 0 and finite */
+} gsp_antilag;
+/* Steps A and B on the frame's accumulate; complete when the call returns. */
+int gsp_temporal_antilag(gsp_context* ctx, const gsp_antilag* antilag);
+/* F' of the newest fast plane: width*height*4 floats, .w = its length. */
+int gsp_download_temporal_fast(gsp_context* ctx, float* out_rgba);
+/* The same into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
+int gsp_temporal_fast_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
 
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
