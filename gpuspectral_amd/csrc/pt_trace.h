@@ -12,8 +12,8 @@
 //     pointer per child;
 //   * the visiting order of a node's children is fixed at build time for each of the 8 sign octants of the ray
 //     direction (children sorted by the projection of their box centre, in units of the node's extent, on the
-//     octant's diagonal).  Measured on the CPU (scripts/experiments/wide_bvh_probe.cpp, 200 k-triangle interior,
-//     quantised boxes): 10.46 node visits per ray against 10.46 with an exact distance sort per node.
+//     octant's diagonal).  What that order costs against an exact distance sort per node, per octant, is held by
+//     tests/test_trace_work_cpu.py (figures: profiles/trace_work_cpu.txt, DESIGN.md "Work per ray").
 // The node width is 4.  (An 8-wide variant after Ylitie, Karras, Laine 2017 was built and measured in r03 -- slower on
 // every scene, LAB_NOTES.md -- and lives on in scripts/experiments/ and in the history, not here.)
 //

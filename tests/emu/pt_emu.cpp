@@ -204,9 +204,12 @@ struct Emu {
     isect.assign(3ull * (n + kWide), mkq(0, 0, 0, 0));  // slots n..: all-zero triangles (det == 0: never hit), as build_bvh appends
     shade.assign(4ull * (n + kWide), mkq(0, 0, 0, 0));
     slot_to_global.assign(n + kWide, 0);
+    lo.assign(3ull * (n + kWide), 0.0f);  // (the padding slots: the all-zero triangle's box)
+    hi.assign(3ull * (n + kWide), 0.0f);
     for (uint32_t s = 0; s < n; ++s) {
       uint32_t gg = slots[s];
       slot_to_global[s] = gg;
+      for (int c = 0; c < 3; ++c) lo[3ull * s + c] = glo[3ull * gg + c], hi[3ull * s + c] = ghi[3ull * gg + c];
       for (int k = 0; k < 3; ++k) isect[3ull * s + k] = gi[3ull * gg + k];
       for (int k = 0; k < 4; ++k) shade[4ull * s + k] = gs[4ull * gg + k];
     }
@@ -256,6 +259,20 @@ bool trace1(const SceneView& S, f3 o, f3 d, float tmin, float tmax, HitRec& h, u
   HostStack stk;
   return trace_ray<ANY>(S.nodes, S.tri_isect, o, d, tmin, tmax, h, aux, stk, kTab);
 }
+
+// The step table behind a counter (emu_trace_work).  node_step<false> reads the table exactly once per node record, and the entry it
+// gets names the hit leaf positions of that record (e >> 9): one triangle test each.  So the closest-hit work of a ray is counted
+// here, outside the product's headers.
+struct CountingTable {
+  StepTableRef tab;
+  mutable uint32_t nodes = 0, tris = 0;
+  uint32_t operator()(uint32_t byte_off) const {
+    const uint32_t e = tab(byte_off);
+    ++nodes;
+    tris += (uint32_t)__builtin_popcount(e >> 9);
+    return e;
+  }
+};
 
 template <class T>
 void copyv(std::vector<T>& d, const T* s, size_t n) {
@@ -390,6 +407,49 @@ int emu_trace(void* h, const float* rays, uint64_t n, int any_hit, void* hits_ou
     else out[i] = hit ? HR{hh.t, hh.u, hh.v, (int32_t)e->slot_to_global[hh.slot]} : HR{0, 0, 0, -1};
   }
   return 0;
+}
+
+// emu_trace + the work of every ray: node records read and triangle packets tested by trace_ray<false> (CountingTable).  Closest
+// hit only: trace_ray<true> reads no table, and any-hit work is measured on the GPU (tests/test_gpu_trace_work.py); any_hit != 0
+// returns -1 and writes nothing.
+int emu_trace_work(void* h, const float* rays, uint64_t n, int any_hit, void* hits_out, uint32_t* nodes_per_ray, uint32_t* tris_per_ray) {
+  if (any_hit) return -1;
+  Emu* e = (Emu*)h;
+  struct HR {
+    float t, u, v;
+    int32_t prim;
+  };
+  HR* out = (HR*)hits_out;
+  const SceneView& S = e->view;
+  const bool empty = e->sc.num_vertices == 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const float* r = rays + 8 * i;
+    HitRec hh;
+    uint32_t aux;
+    HostStack stk;
+    CountingTable tab{kTab};
+    bool hit = trace_ray<false>(S.nodes, S.tri_isect, mk3(r[0], r[1], r[2]), mk3(r[4], r[5], r[6]), r[3], r[7], hh, aux, stk, tab);
+    if (empty) hit = false;
+    out[i] = hit ? HR{hh.t, hh.u, hh.v, (int32_t)e->slot_to_global[hh.slot]} : HR{0, 0, 0, -1};
+    nodes_per_ray[i] = tab.nodes;
+    tris_per_ray[i] = tab.tris;
+  }
+  return 0;
+}
+// The emulation's tree, for a decoder written from the layout comment of pt_trace.h (tests/trace_work.py): the node records (16 words
+// each), the triangle packets (12 words per slot, the kWide all-zero padding slots included), the padded box of every slot and its
+// global triangle id.  The pointers stay valid until emu_destroy.
+void emu_tree(void* h, const void** nodes, uint64_t* num_nodes, const void** packets, uint64_t* num_slots, uint64_t* num_real_slots,
+              const float** lo, const float** hi, const uint32_t** slot_to_global) {
+  Emu* e = (Emu*)h;
+  *nodes = e->nodes.data();
+  *num_nodes = e->nodes.size() / kNodeQuads;
+  *packets = e->isect.data();
+  *num_slots = e->isect.size() / 3;
+  *num_real_slots = e->isect.size() / 3 - kWide;
+  *lo = e->lo.data();
+  *hi = e->hi.data();
+  *slot_to_global = e->slot_to_global.data();
 }
 
 void emu_bsdf_sample(void* h, uint32_t handle, const float* wo, uint32_t seed, float* out9) {
