@@ -252,6 +252,20 @@ def antilag(fast_history=0, radius=0, sigma_scale=0.0):
     return Antilag(C.sizeof(Antilag), fast_history, radius, sigma_scale)
 
 
+class Taa(C.Structure):
+    """gsp_taa: the parameters of temporal anti-aliasing (gsp_temporal_taa); all zero = every default."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("alpha", C.c_float),  # weight of the new frame; 0 = 0.1; otherwise (0, 1]
+        ("sigma_clip", C.c_float),  # half-width of the neighbourhood box in standard deviations; 0 = 1.0; otherwise > 0 and finite
+    ]
+
+
+def taa(alpha=0.0, sigma_clip=0.0):
+    return Taa(C.sizeof(Taa), alpha, sigma_clip)
+
+
 class Luminance(C.Structure):
     """gsp_luminance: the frame statistics of the Reinhard operator (gsp_frame_luminance)."""
 

@@ -56,9 +56,9 @@ GSP_HD float display_encode(float v, float inv_gamma) {
 
 GSP_HD float display_aces(float x) { return (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f); }
 
-// steps 1-6 for one pixel: the RGBA8 word, R in bits 0-7, A = 255
-template <uint32_t TONEMAP, bool SRGB>
-GSP_HD uint32_t display_pixel_t(float r, float g, float b, const DisplayConsts& k) {
+// steps 1-4 for one pixel, in place: display-linear colour, every channel finite in [0, 1]
+template <uint32_t TONEMAP>
+GSP_HD void display_tone_t(float& r, float& g, float& b, const DisplayConsts& k) {
   r = display_channel(r) * k.exposure_scale;
   g = display_channel(g) * k.exposure_scale;
   b = display_channel(b) * k.exposure_scale;
@@ -79,12 +79,27 @@ GSP_HD uint32_t display_pixel_t(float r, float g, float b, const DisplayConsts& 
       b = b * ratio;
     }
   }
-  r = display_encode<SRGB>(display_clamp01(r), k.inv_gamma);
-  g = display_encode<SRGB>(display_clamp01(g), k.inv_gamma);
-  b = display_encode<SRGB>(display_clamp01(b), k.inv_gamma);
+  r = display_clamp01(r);
+  g = display_clamp01(g);
+  b = display_clamp01(b);
+}
+
+// steps 5-6 for one display-linear pixel (channels in [0, 1]): the RGBA8 word, R in bits 0-7, A = 255
+template <bool SRGB>
+GSP_HD uint32_t display_encode_word(float r, float g, float b, const DisplayConsts& k) {
+  r = display_encode<SRGB>(r, k.inv_gamma);
+  g = display_encode<SRGB>(g, k.inv_gamma);
+  b = display_encode<SRGB>(b, k.inv_gamma);
   // (the encode of a value in [0, 1] stays in [0, 1 + 1 ulp]: the casts below cannot leave 0..255)
   const uint32_t R = (uint32_t)(r * 255.0f + 0.5f), G = (uint32_t)(g * 255.0f + 0.5f), B = (uint32_t)(b * 255.0f + 0.5f);
   return R | (G << 8) | (B << 16) | 0xff000000u;
+}
+
+// steps 1-6 for one pixel: the tone half, then the encode half
+template <uint32_t TONEMAP, bool SRGB>
+GSP_HD uint32_t display_pixel_t(float r, float g, float b, const DisplayConsts& k) {
+  display_tone_t<TONEMAP>(r, g, b, k);
+  return display_encode_word<SRGB>(r, g, b, k);
 }
 
 // the same through a run-time choice (host emulation, tests)

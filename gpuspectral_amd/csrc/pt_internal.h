@@ -14,6 +14,7 @@
 #include "pt_stages.h"
 #include "pt_motion.h"
 #include "pt_svgf.h"
+#include "pt_taa.h"
 #include "pt_temporal.h"
 
 namespace gsp {

@@ -195,6 +195,14 @@ struct gsp_context {
   DevBuf<q4> al_f[2];
   int al_cur = 0;
   uint64_t al_serial = 0;
+  // temporal anti-aliasing (gsp_temporal_taa): the two ping-pong planes D of display-linear colour, made by the first resolve of
+  // the context; ta_cur = the newest one, ta_serial = the accumulate it belongs to (0 = none), ta_display = the resolved display
+  // of that resolve.  D is valid for an accumulate when ta_serial is the accumulate before it and that accumulate itself ran with
+  // a valid history.  tp_epoch = the newest accumulate that ran without one: a read-out needs a resolve no older than it.
+  DevBuf<q4> ta_d[2];
+  int ta_cur = 0;
+  uint64_t ta_serial = 0, tp_epoch = 0;
+  gsp_display ta_display{};
   DevBuf<float> trace_rays;  // gsp_trace: grow-only staging, kept across calls
   DevBuf<q4> trace_hits;
   DevBuf<uint32_t> trace_work;

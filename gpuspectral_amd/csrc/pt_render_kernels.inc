@@ -1641,6 +1641,47 @@ __global__ __launch_bounds__(kBlock) void k_antilag_clamp(const v4f* __restrict_
   if (o.changed) dn_store(H + p, o.H);
 }
 
+// ---- temporal anti-aliasing (pt_taa.h; include/gpuspectral_pt.h "Temporal anti-aliasing") ---------------------------------------
+// One launch per resolve.  A block owns a tile of 32 x 8 pixels and stages X -- YCoCg of the toned source -- of tile + halo of 1,
+// 34 x 10 records of 16 bytes (5440 bytes), in LDS: every source pixel is read once with a 16-byte load and toned once, and the
+// nine taps of the box are ds_read_b128 of rows of 32 consecutive records, free of bank conflicts at any row pitch as in
+// k_antilag_clamp.  A record outside the frame is marked by .w = 0 (inside: 1) and never read: taa_pixel skips the tap first, the
+// definition counts only pixels inside the frame.  V is one 16-byte load, issued in front of the staging; the four history taps
+// are 16-byte global loads of neighbouring records of the older D, served by L2; D' is one 16-byte store.  No atomics, one
+// barrier.  The curve is a template parameter: the CLAMP instantiation carries no Reinhard registers.
+template <uint32_t TONEMAP>
+__global__ __launch_bounds__(kBlock) void k_taa_resolve(const v4f* __restrict__ src, const v4f* __restrict__ V, const v4f* __restrict__ Dprev,
+                                                        v4f* __restrict__ Dout, TaaParams a, DisplayConsts k, int taa_valid, int width, int height) {
+  constexpr int PW = kDnTileW + 2, PH = kDnTileH + 2;
+  __shared__ v4f sX[PW * PH];
+  const int x0 = (int)blockIdx.x * kDnTileW - 1, y0 = (int)blockIdx.y * kDnTileH - 1;
+  const int px = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x & (kDnTileW - 1));
+  const int py = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  const bool inside = px < width && py < height;
+  const size_t p = (size_t)py * (size_t)width + (size_t)px;
+  dn4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (inside) v = dn_load(V + p);
+  for (int i = (int)threadIdx.x; i < PW * PH; i += kBlock) {
+    const int ly = i / PW, lx = i - ly * PW;
+    const int gx = x0 + lx, gy = y0 + ly;
+    v4f x = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+      const dn4 X = taa_source_t<TONEMAP>(dn_load(src + ((size_t)gy * (size_t)width + (size_t)gx)), k);
+      x.x = X.x;
+      x.y = X.y;
+      x.z = X.z;
+      x.w = 1.0f;
+    }
+    sX[i] = x;
+  }
+  __syncthreads();
+  if (!inside) return;  // (no barrier below)
+  dn_store(Dout + p, taa_pixel(
+                         a, taa_valid != 0, width, height, px, py, v,
+                         [&](int x, int y) { return dn_load(&sX[(y - y0) * PW + (x - x0)]); },  // |x - px| <= 1 and |y - py| <= 1: inside the staged rectangle
+                         [&](int x, int y) { return dn_load(Dprev + ((size_t)y * (size_t)width + (size_t)x)); }));  // a pixel of the frame
+}
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;

@@ -1,6 +1,7 @@
 // pt_render_post.inc -- part of the translation unit pt_render.hip (through pt_render_pipeline.inc; not compiled on its
 // own).  The host side of the stages behind the path tracer: the LDR film, the denoiser, temporal accumulation, the
-// variance-guided filter, the illumination history and the temporal anti-lag -- their launchers, guards, read-out tails and exports.
+// variance-guided filter, the illumination history, the temporal anti-lag and temporal anti-aliasing -- their launchers, guards,
+// read-out tails and exports.
 
 // ---- what the stages share: launch shapes, guards with one text, the tails of the *_to_device exports ----
 // a grid-stride launch over `n` items: enough blocks for them, at most `per_cu` per compute unit
@@ -427,6 +428,7 @@ int gsp_temporal_accumulate(gsp_context* ctx, const gsp_temporal* temporal) {
   ctx->tp_done = true;
   ctx->tp_fed = false;  // (gsp_temporal_svgf_feedback: at most one per accumulate)
   ctx->tp_acc = {k, records, ctx->tp_follow, ctx->tp_demod, ctx->tp_acc.serial + 1};  // (gsp_temporal_antilag: what this accumulate ran with)
+  if (!k.history_valid) ctx->tp_epoch = ctx->tp_acc.serial;  // (gsp_temporal_taa: a history begins here)
   return GSP_OK;
 }
 
@@ -805,6 +807,167 @@ int gsp_temporal_fast_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
   int rc = temporal_have_fast(ctx, "gsp_temporal_fast_to_device", dst);
   if (rc != GSP_OK) return rc;
   return plane_to_device(ctx, dst, bytes, ctx->al_f[ctx->al_cur].p);
+}
+
+}  // extern "C"
+
+// ---- temporal anti-aliasing (include/gpuspectral_pt.h, "Temporal anti-aliasing"; per-pixel code: pt_taa.h) ----
+// Queues the one launch of a resolve on `stream`: the source plane `src`, the motion plane `motion` and the older plane `dprev`
+// (not read when !taa_valid) into `dout`; does not synchronise.
+static hipError_t taa_run(hipStream_t stream, const v4f* src, const v4f* motion, const v4f* dprev, v4f* dout, const TaaParams& a, const DisplayConsts& k,
+                          bool taa_valid, uint32_t width, uint32_t height) {
+  if (width == 0 || height == 0) return hipSuccess;
+  const dim3 grid = tile_grid(width, height), block(kBlock);
+#define GSP_TAA_LAUNCH(T) hipLaunchKernelGGL((k_taa_resolve<T>), grid, block, 0, stream, src, motion, dprev, dout, a, k, taa_valid ? 1 : 0, (int)width, (int)height)
+  if (k.tonemap == GSP_TONEMAP_ACES) GSP_TAA_LAUNCH(GSP_TONEMAP_ACES);
+  else if (k.tonemap == GSP_TONEMAP_REINHARD) GSP_TAA_LAUNCH(GSP_TONEMAP_REINHARD);
+  else GSP_TAA_LAUNCH(GSP_TONEMAP_CLAMP);
+#undef GSP_TAA_LAUNCH
+  return hipGetLastError();
+}
+
+// A resolve with its source in host memory (host_src), in the caller's device memory (device_src, `bytes`) or, with both NULL, the
+// image of the newest history.  A source the kernel cannot read where it lies -- host memory, a device address that is not
+// 16-byte aligned, the image of a demodulated history -- passes through the filters' output plane dn_out.
+static int taa_ctx(gsp_context* ctx, const char* who, const gsp_taa* taa_host, const gsp_display* display_host, const float* host_src, const void* device_src,
+                   uint64_t bytes) {
+  if (!ctx->have_frame) {
+    ctx->err = std::string(who) + " needs gsp_frame_begin first";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->subset) {
+    ctx->err = std::string(who) + ": the frame was begun with pixel_ids; a share has no neighbours and there is no multi-GPU variant";
+    return GSP_ERR_INVALID;
+  }
+  int rc = temporal_have_history(ctx, who, nullptr, true);
+  if (rc != GSP_OK) return rc;
+  if (!ctx->tp_done) {
+    ctx->err = std::string(who) + " needs a gsp_temporal_accumulate call since gsp_frame_begin";
+    return GSP_ERR_INVALID;
+  }
+  const gsp_context::AccumulateRecord& acc = ctx->tp_acc;
+  if (!acc.follow || !ctx->tp_follow) {
+    ctx->err = std::string(who) + " needs gsp_temporal_follow_instances(ctx, 1) before the frame was accumulated: the motion plane is made only then";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->ta_serial == acc.serial) {
+    ctx->err = std::string(who) + ": the frame has been resolved already (one call per gsp_temporal_accumulate)";
+    return GSP_ERR_INVALID;
+  }
+  TaaParams a;
+  if (const char* why = resolve_taa(taa_host, a)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  gsp_display d;
+  if (const char* why = resolve_display(display_host, d)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(q4);
+  if (device_src && bytes < need) {
+    ctx->err = std::string(who) + ": source too small";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t n = std::max<uint64_t>(ctx->num_pixels, 1);
+  for (DevBuf<q4>& b : ctx->ta_d) CTX_TRY(ctx, b.ensure(n, &ctx->bytes));
+  const void* src = nullptr;
+  if (host_src || (device_src && ((uintptr_t)device_src & 15u) != 0)) {
+    CTX_TRY(ctx, ctx->dn_out.ensure(n, &ctx->bytes));
+    if (need) CTX_TRY(ctx, hipMemcpyAsync(ctx->dn_out.p, host_src ? (const void*)host_src : device_src, need, host_src ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    src = ctx->dn_out.p;
+  } else if (device_src) {
+    src = device_src;
+  } else if (ctx->tp_demod) {
+    rc = temporal_image_run(ctx, nullptr);
+    if (rc != GSP_OK) return rc;
+    src = ctx->dn_out.p;
+  } else {
+    src = ctx->tp_h[ctx->tp_cur].p;  // (the history is the image)
+  }
+  gsp_luminance lum{};
+  if (display_needs_stats(d)) {
+    rc = display_measure_ctx(ctx, &lum, src);
+    if (rc != GSP_OK) return rc;
+  }
+  const bool taa_valid = ctx->ta_serial != 0 && ctx->ta_serial + 1 == acc.serial && acc.k.history_valid != 0;
+  const int from = ctx->ta_cur, to = from ^ 1;
+  CTX_TRY(ctx, taa_run(ctx->stream, (const v4f*)src, (const v4f*)ctx->tp_v.p, (const v4f*)ctx->ta_d[from].p, (v4f*)ctx->ta_d[to].p, a, display_consts(d, lum), taa_valid,
+                       ctx->tp_width, ctx->tp_height));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (complete when the call returns, like the accumulate)
+  ctx->ta_cur = to;
+  ctx->ta_serial = acc.serial;
+  ctx->ta_display = d;
+  return GSP_OK;
+}
+
+// what the three read-outs of D ask first
+static int temporal_have_taa(gsp_context* ctx, const char* who, const void* out_ptr) {
+  int rc = temporal_have_history(ctx, who, out_ptr);
+  if (rc != GSP_OK) return rc;
+  if (ctx->ta_serial == 0 || ctx->ta_serial < ctx->tp_epoch) {
+    ctx->err = std::string(who) + " needs a gsp_temporal_taa call since the history was last invalidated";
+    return GSP_ERR_INVALID;
+  }
+  return GSP_OK;
+}
+
+// queues the encode of the newest D under the stored display into `dst` (device, 16-byte aligned; nullptr = the context's own RGBA8
+// buffer) on ctx->stream: k_display_map's CLAMP instantiation at exposure 0, whose tone half leaves a value of [0, 1] as it is --
+// display_channel(v) * 1.0f and display_clamp01 of it are v -- so that the word is the encode half of D' and no kernel is added
+static int taa_display_run(gsp_context* ctx, uint32_t* dst) {
+  const uint64_t n = (uint64_t)ctx->tp_width * ctx->tp_height;
+  if (!dst) {
+    CTX_TRY(ctx, ctx->display_out.ensure((std::max<uint64_t>(n, 1) + 3) / 4 * 4, &ctx->bytes));
+    dst = ctx->display_out.p;
+  }
+  gsp_display d = ctx->ta_display;
+  d.tonemap = GSP_TONEMAP_CLAMP;
+  d.exposure = 0.0f;
+  CTX_TRY(ctx, display_map(ctx->stream, (uint32_t)ctx->num_cus, ctx->ta_d[ctx->ta_cur].p, n, display_consts(d, gsp_luminance{}), dst));
+  return GSP_OK;
+}
+
+extern "C" {
+
+int gsp_temporal_taa(gsp_context* ctx, const gsp_taa* taa, const gsp_display* display, const float* src) {
+  if (!ctx) return GSP_ERR_INVALID;
+  return taa_ctx(ctx, "gsp_temporal_taa", taa, display, src, nullptr, 0);
+}
+
+int gsp_temporal_taa_from_device(gsp_context* ctx, const gsp_taa* taa, const gsp_display* display, const void* device_src, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  return taa_ctx(ctx, "gsp_temporal_taa_from_device", taa, display, nullptr, device_src, bytes);
+}
+
+int gsp_download_taa(gsp_context* ctx, float* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_taa(ctx, "gsp_download_taa", out);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  return read_back_bytes(ctx, ctx->ta_d[ctx->ta_cur].p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(q4), out);
+}
+
+int gsp_download_taa_display(gsp_context* ctx, uint32_t* out) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_taa(ctx, "gsp_download_taa_display", out);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  rc = taa_display_run(ctx, nullptr);
+  if (rc != GSP_OK) return rc;
+  return read_back_bytes(ctx, ctx->display_out.p, (size_t)ctx->tp_width * ctx->tp_height * sizeof(uint32_t), out);
+}
+
+int gsp_taa_display_to_device(gsp_context* ctx, void* dst, uint64_t bytes) {
+  if (!ctx) return GSP_ERR_INVALID;
+  int rc = temporal_have_taa(ctx, "gsp_taa_display_to_device", dst);
+  if (rc != GSP_OK) return rc;
+  const uint64_t need = (uint64_t)ctx->tp_width * ctx->tp_height * sizeof(uint32_t);
+  rc = refuse_too_small(ctx, bytes, need);
+  if (rc != GSP_OK) return rc;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  return to_device_tail(ctx, dst, need, ctx->display_out, [&](void* target) { return taa_display_run(ctx, (uint32_t*)target); });
 }
 
 }  // extern "C"

@@ -107,6 +107,11 @@ def load():
     L.gsph_pathtracer_temporal_antilag.argtypes = [vp, C.POINTER(abi.Antilag)]
     L.gsph_pathtracer_download_temporal_fast.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_temporal_fast_to_device.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_temporal_taa.argtypes = [vp, C.POINTER(abi.Taa), C.POINTER(abi.Display), vp, u64]
+    L.gsph_pathtracer_temporal_taa_from_device.argtypes = [vp, C.POINTER(abi.Taa), C.POINTER(abi.Display), vp, u64]
+    L.gsph_pathtracer_download_taa.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_download_taa_display.argtypes = [vp, vp, u64]
+    L.gsph_pathtracer_taa_display_to_device.argtypes = [vp, vp, u64]
     _LIB = L
     return L
 
@@ -475,6 +480,48 @@ class PathTracer:
         else:
             ptr = dst
         self._check(self._L.gsph_pathtracer_temporal_fast_to_device(self._h, ptr, nbytes), "temporalFastToDevice")
+
+    def temporal_taa(self, taa=None, display=None, src=None):
+        """PathTracer::temporalTaa: resolves the tone-mapped frame over its own history (once per temporal_accumulate, with
+        temporal_follow_instances on).  taa: an abi.Taa, None = every default; display: an abi.Display, None = the PathTracer's LDR
+        film; src: (h, w, 4) float32, the HDR frame to resolve, None = the image of the newest history."""
+        n = 0
+        if src is not None:
+            src = np.ascontiguousarray(src, np.float32)
+            n = src.size
+        self._check(self._L.gsph_pathtracer_temporal_taa(self._h, C.byref(taa) if taa is not None else None, C.byref(display) if display is not None else None,
+                                                         src.ctypes.data if src is not None else None, n), "temporalTaa")
+
+    def temporal_taa_from_device(self, src, nbytes=None, taa=None, display=None):
+        """PathTracer::temporalTaaFromDevice: src = a torch tensor on the device, a device pointer with nbytes, or None."""
+        if src is None:
+            ptr, nbytes = None, 0
+        elif hasattr(src, "data_ptr"):
+            ptr, nbytes = src.data_ptr(), src.numel() * src.element_size()
+        else:
+            ptr = src
+        self._check(self._L.gsph_pathtracer_temporal_taa_from_device(self._h, C.byref(taa) if taa is not None else None,
+                                                                     C.byref(display) if display is not None else None, ptr, nbytes), "temporalTaaFromDevice")
+
+    def download_taa(self):
+        """PathTracer::downloadTaa: (h, w, 4) float32, the resolved display-linear frame; .w = 1 where the history was used."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsph_pathtracer_download_taa(self._h, out.ctypes.data, out.size), "downloadTaa")
+        return out
+
+    def download_taa_display(self):
+        """PathTracer::downloadTaaDisplay: (h, w) uint32 RGBA8 words, the encode of the resolved frame."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsph_pathtracer_download_taa_display(self._h, out.ctypes.data, out.size), "downloadTaaDisplay")
+        return out
+
+    def taa_display_to_device(self, dst, nbytes=None):
+        """PathTracer::taaDisplayToDevice: dst = a torch tensor on the device, or a device pointer with nbytes."""
+        if hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsph_pathtracer_taa_display_to_device(self._h, ptr, nbytes), "taaDisplayToDevice")
 
     def stats(self):
         s = abi.Stats()

@@ -359,6 +359,29 @@ void PathTracer::temporalFastToDevice(void* deviceDst, uint64_t bytes) {
   check(gsp_temporal_fast_to_device(ctx, deviceDst, bytes), "gsp_temporal_fast_to_device");
 }
 
+void PathTracer::temporalTaa(const gsp_taa* taa, const gsp_display* displayOverride, const float* src, uint64_t srcFloats) {
+  if (src && srcFloats < (uint64_t)width * height * 4) throw std::runtime_error("temporalTaa: source buffer too small");
+  check(gsp_temporal_taa(ctx, taa, displayOverride ? displayOverride : &display, src), "gsp_temporal_taa");
+}
+
+void PathTracer::temporalTaaFromDevice(const gsp_taa* taa, const gsp_display* displayOverride, const void* deviceSrc, uint64_t bytes) {
+  check(gsp_temporal_taa_from_device(ctx, taa, displayOverride ? displayOverride : &display, deviceSrc, bytes), "gsp_temporal_taa_from_device");
+}
+
+std::vector<float> PathTracer::downloadTaa() {
+  std::vector<float> out((size_t)width * height * 4);
+  check(gsp_download_taa(ctx, out.data()), "gsp_download_taa");
+  return out;
+}
+
+std::vector<uint32_t> PathTracer::downloadTaaDisplay() {
+  std::vector<uint32_t> out((size_t)width * height);
+  check(gsp_download_taa_display(ctx, out.data()), "gsp_download_taa_display");
+  return out;
+}
+
+void PathTracer::taaDisplayToDevice(void* deviceDst, uint64_t bytes) { check(gsp_taa_display_to_device(ctx, deviceDst, bytes), "gsp_taa_display_to_device"); }
+
 void PathTracer::nextFrame() {
   featureTimestamp = timestamp;  // (the feature samples of the new frame are those of its beauty samples)
   check(gsp_frame_begin(ctx, width, height, pixelIds.empty() ? nullptr : pixelIds.data(), pixelIds.size()), "gsp_frame_begin");

@@ -143,6 +143,15 @@ class PathTracer : public RenderPassCreator {
   void temporalAntilag(const gsp_antilag* antilag = nullptr);
   std::vector<float> downloadTemporalFast();
   void temporalFastToDevice(void* deviceDst, uint64_t bytes);
+  // Temporal anti-aliasing (gpuspectral_pt.h "Temporal anti-aliasing"): temporalTaa resolves the tone-mapped frame over its own
+  // history -- src = an HDR frame of width*height*4 floats (the output of temporalSvgf / temporalSvgfFeedback, say), nullptr = the
+  // image of the newest history (srcFloats: what the caller's buffer holds); displayOverride nullptr = the LDR film `display`.  Once per temporalAccumulate, with
+  // temporalFollowInstances on.  downloadTaa: the resolved display-linear frame; downloadTaaDisplay / taaDisplayToDevice: its RGBA8 encode.
+  void temporalTaa(const gsp_taa* taa = nullptr, const gsp_display* displayOverride = nullptr, const float* src = nullptr, uint64_t srcFloats = ~0ull);
+  void temporalTaaFromDevice(const gsp_taa* taa, const gsp_display* displayOverride, const void* deviceSrc, uint64_t bytes);
+  std::vector<float> downloadTaa();
+  std::vector<uint32_t> downloadTaaDisplay();
+  void taaDisplayToDevice(void* deviceDst, uint64_t bytes);
   void nextFrame();  // a new frame (accumulate buffer and feature planes cleared) whose samples continue the timestamp sequence
   void reset();  // timestamp = 0, accumulate buffer and feature planes cleared
   int getTimestamp() const { return timestamp; }

@@ -410,6 +410,30 @@ int gsph_pathtracer_download_temporal_fast(void* pt, float* out, uint64_t floats
 int gsph_pathtracer_temporal_fast_to_device(void* pt, void* device_dst, uint64_t bytes) {
   return guard([&] { ((PathTracer*)pt)->temporalFastToDevice(device_dst, bytes); });
 }
+// temporal anti-aliasing of a PathTracer (gpuspectral_pt.h "Temporal anti-aliasing"); taa, display and src may be NULL
+int gsph_pathtracer_temporal_taa(void* pt, const gsp_taa* taa, const gsp_display* display, const float* src, uint64_t floats) {
+  return guard([&] { ((PathTracer*)pt)->temporalTaa(taa, display, src, floats); });
+}
+int gsph_pathtracer_temporal_taa_from_device(void* pt, const gsp_taa* taa, const gsp_display* display, const void* device_src, uint64_t bytes) {
+  return guard([&] { ((PathTracer*)pt)->temporalTaaFromDevice(taa, display, device_src, bytes); });
+}
+int gsph_pathtracer_download_taa(void* pt, float* out, uint64_t floats) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTaa();
+    if (floats < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(float));
+  });
+}
+int gsph_pathtracer_download_taa_display(void* pt, uint32_t* out, uint64_t count) {
+  return guard([&] {
+    auto img = ((PathTracer*)pt)->downloadTaaDisplay();
+    if (count < img.size()) throw std::runtime_error("output buffer too small");
+    std::memcpy(out, img.data(), img.size() * sizeof(uint32_t));
+  });
+}
+int gsph_pathtracer_taa_display_to_device(void* pt, void* device_dst, uint64_t bytes) {
+  return guard([&] { ((PathTracer*)pt)->taaDisplayToDevice(device_dst, bytes); });
+}
 int gsph_tone_map(const float* rgba, uint32_t width, uint32_t height, int tone_map, uint8_t* rgb8) {
   return guard([&] {
     std::vector<uint8_t> v;

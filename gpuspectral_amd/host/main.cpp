@@ -37,6 +37,11 @@
 //   --temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S] (with --temporal): on every frame, between the
 //   accumulate and any --svgf-feedback, a fast history of at most N frames is kept beside the long one and the long one is clamped
 //   into the box of its statistics over (2 R + 1)^2 pixels, S standard deviations wide (gpuspectral_pt.h "Temporal anti-lag").
+//   --taa out.png [--taa-alpha A] [--taa-sigma S] (with --temporal and --temporal-follow): on every frame the tone-mapped frame is
+//   resolved over its own history (gpuspectral_pt.h "Temporal anti-aliasing"; A = the weight of the new frame in (0, 1], S = the
+//   half-width of the neighbourhood box in standard deviations) -- the output of --svgf (of --svgf-feedback where given) as its
+//   source, else the image of the history -- under the display of --tonemap / --exposure / --gamma; out.png receives the last
+//   frame's resolve.
 //   --svgf out.pfm [--svgf-sigma S] [--svgf-min-history N] (with --temporal): the history keeps its luminance moments and out.pfm
 //   receives its variance-guided filter (gpuspectral_pt.h "Variance-guided filter"; S = sigma_variance, inf = the term off; N =
 //   2..65536), with the levels and guide sigmas of --denoise-iterations / --denoise-sigma where --denoise is given.
@@ -84,6 +89,10 @@ int main(int argc, char** argv) {
   bool temporalAntilag = false, antilagOptions = false;
   gsp_antilag antilag{};
   antilag.struct_size = (uint32_t)sizeof(gsp_antilag);
+  std::string taaPath;
+  bool taaOptions = false;
+  gsp_taa taa{};
+  taa.struct_size = (uint32_t)sizeof(gsp_taa);
   std::string svgfPath;
   gsp_svgf svgf{};
   svgf.struct_size = (uint32_t)sizeof(gsp_svgf);
@@ -186,6 +195,19 @@ int main(int argc, char** argv) {
         return 2;
       }
       antilagOptions = true, used = 2;
+    } else if (flag == "--taa" && argc > 2) taaPath = argv[2], used = 2;
+    else if (flag == "--taa-alpha" && argc > 2) {
+      if (!parseFloat(argv[2], taa.alpha) || !(taa.alpha > 0.0f) || !(taa.alpha <= 1.0f)) {
+        std::fprintf(stderr, "gsp_render: bad taa alpha '%s' (expected the weight of the new frame, within (0, 1])\n", argv[2]);
+        return 2;
+      }
+      taaOptions = true, used = 2;
+    } else if (flag == "--taa-sigma" && argc > 2) {
+      if (!parseFloat(argv[2], taa.sigma_clip) || !(taa.sigma_clip > 0.0f)) {
+        std::fprintf(stderr, "gsp_render: bad taa sigma '%s' (expected the half-width of the neighbourhood box in standard deviations, > 0)\n", argv[2]);
+        return 2;
+      }
+      taaOptions = true, used = 2;
     } else if (flag == "--svgf" && argc > 2) svgfPath = argv[2], used = 2;
     else if (flag == "--svgf-sigma" && argc > 2) {
       if (std::string(argv[2]) == "inf") svgf.sigma_variance = INFINITY;
@@ -331,7 +353,7 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --aperture needs --focus-distance D, --focus-pixel X,Y or --scene-lens\n");
     return 2;
   }
-  if (ldrPath.empty() && (tonemap >= 0 || haveExposure || gamma >= 0.0f || options.readFilm)) {
+  if (ldrPath.empty() && taaPath.empty() && (tonemap >= 0 || haveExposure || gamma >= 0.0f || options.readFilm)) {
     std::fprintf(stderr, "gsp_render: --tonemap, --exposure, --gamma and --scene-film need --ldr out.png\n");
     return 2;
   }
@@ -371,6 +393,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "gsp_render: --antilag-fast, --antilag-radius and --antilag-sigma need --temporal-antilag\n");
     return 2;
   }
+  if (taaPath.empty() && taaOptions) {
+    std::fprintf(stderr, "gsp_render: --taa-alpha and --taa-sigma need --taa out.png\n");
+    return 2;
+  }
+  if (!taaPath.empty() && (temporalPath.empty() || !temporalFollow)) {
+    std::fprintf(stderr, "gsp_render: --taa needs --temporal out.pfm and --temporal-follow (it fetches its history through the motion plane)\n");
+    return 2;
+  }
   if (svgfPath.empty() && svgfOptions) {
     std::fprintf(stderr, "gsp_render: --svgf-sigma and --svgf-min-history need --svgf out.pfm\n");
     return 2;
@@ -380,7 +410,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -443,7 +473,8 @@ int main(int argc, char** argv) {
     if (gamma >= 0.0f) display.gamma = gamma;
     if (!denoisePath.empty() && !ldrPath.empty() && devices.size() > 1)
       throw std::runtime_error("--denoise with --ldr needs a single device (the LDR film of the denoised frame is a single-context call)");
-    std::vector<uint32_t> ldr, denoisedLdr;
+    std::vector<uint32_t> ldr, denoisedLdr, taaLdr;
+    double taaUsed = 0.0;
     std::vector<float> img, featAlbedo, featGeom, denoised, temporal, temporalDenoised, temporalSvgf, motion;
     double temporalLength = 0.0;
     double fastLength = 0.0;
@@ -471,7 +502,12 @@ int main(int argc, char** argv) {
         pt.renderFeatures(scene, spp);
         pt.temporalAccumulate();
         if (temporalAntilag) pt.temporalAntilag(&antilag);
-        if (svgfFeedback) pt.temporalSvgfFeedback(&denoise, &svgf, (uint32_t)svgfFeedback, false);
+        std::vector<float> filtered;  // (the source of --taa: the filter's output where --svgf is given)
+        if (svgfFeedback) filtered = pt.temporalSvgfFeedback(&denoise, &svgf, (uint32_t)svgfFeedback, !taaPath.empty());
+        if (!taaPath.empty()) {
+          if (!svgfPath.empty() && !svgfFeedback) filtered = pt.downloadTemporalSvgf(&denoise, &svgf);
+          pt.temporalTaa(&taa, &display, svgfPath.empty() ? nullptr : filtered.data(), filtered.size());
+        }
         const float a = temporalOrbit * 3.14159265358979323846f / 180.0f, cs = std::cos(a), sn = std::sin(a);
         const mat4 m = scene.camera.getToWorld();
         mat4 r = m;
@@ -516,6 +552,13 @@ int main(int argc, char** argv) {
         if (!denoisePath.empty()) temporalDenoised = pt.downloadTemporalDenoised(&denoise);
         if (!svgfPath.empty() && !svgfFeedback) temporalSvgf = pt.downloadTemporalSvgf(&denoise, &svgf);
         if (!motionPath.empty()) motion = pt.downloadTemporalMotion();
+        if (!taaPath.empty()) {  // (last: the filter's output is its source)
+          pt.temporalTaa(&taa, &display, svgfPath.empty() ? nullptr : temporalSvgf.data(), temporalSvgf.size());
+          taaLdr = pt.downloadTaaDisplay();
+          const std::vector<float> d = pt.downloadTaa();
+          for (size_t i = 3; i < d.size(); i += 4) taaUsed += d[i];
+          taaUsed /= (double)width * height;
+        }
         for (size_t i = 3; i < temporal.size(); i += 4) temporalLength += temporal[i];
         temporalLength /= (double)width * height;
       }
@@ -593,6 +636,12 @@ int main(int argc, char** argv) {
       if (svgfFeedback)
         std::printf("svgf feedback: the first %ld level%s fed back into the history on each of %d frame%s\n", svgfFeedback, svgfFeedback == 1 ? "" : "s",
                     temporalFrames, temporalFrames == 1 ? "" : "s");
+      if (!taaPath.empty()) {
+        writePng(taaPath, taaLdr.data(), width, height, false);
+        std::printf("taa: %s resolved over its history on each of %d frame%s, alpha %g, sigma %g, %.1f %% of the last frame's pixels blended -> %s\n",
+                    svgfPath.empty() ? "the image of the history" : "the filter's output", temporalFrames, temporalFrames == 1 ? "" : "s",
+                    taa.alpha != 0.0f ? (double)taa.alpha : 0.1, taa.sigma_clip != 0.0f ? (double)taa.sigma_clip : 1.0, 100.0 * taaUsed, taaPath.c_str());
+      }
       if (!motionPath.empty()) {
         size_t followed = 0;
         for (size_t i = 3; i < motion.size(); i += 4) {

@@ -71,6 +71,11 @@ EXPORTS = (
     "gsp_temporal_antilag",
     "gsp_download_temporal_fast",
     "gsp_temporal_fast_to_device",
+    "gsp_temporal_taa",
+    "gsp_temporal_taa_from_device",
+    "gsp_download_taa",
+    "gsp_download_taa_display",
+    "gsp_taa_display_to_device",
     "gsp_frame_sample_base",
     "gsp_get_stats",
     "gsp_reset_stats",
@@ -190,6 +195,11 @@ def load():
     L.gsp_temporal_antilag.argtypes = [vp, C.POINTER(abi.Antilag)]
     L.gsp_download_temporal_fast.argtypes = [vp, vp]
     L.gsp_temporal_fast_to_device.argtypes = [vp, vp, u64]
+    L.gsp_temporal_taa.argtypes = [vp, C.POINTER(abi.Taa), C.POINTER(abi.Display), vp]
+    L.gsp_temporal_taa_from_device.argtypes = [vp, C.POINTER(abi.Taa), C.POINTER(abi.Display), vp, u64]
+    L.gsp_download_taa.argtypes = [vp, vp]
+    L.gsp_download_taa_display.argtypes = [vp, vp]
+    L.gsp_taa_display_to_device.argtypes = [vp, vp, u64]
     L.gsp_get_stats.argtypes = [vp, C.POINTER(abi.Stats)]
     L.gsp_reset_stats.argtypes = [vp]
     L.gsp_trace.argtypes = [vp, vp, u64, C.c_int, vp]
@@ -240,7 +250,7 @@ def build_info():
 
 # the files csrc/Makefile hashes into the digest, in its order
 DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "../../include/gpuspectral_pt.h")
+                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -623,6 +633,53 @@ class Context:
         else:
             ptr = dst
         self._check(self._L.gsp_temporal_fast_to_device(self._h, ptr, nbytes), "gsp_temporal_fast_to_device")
+
+    # ---- temporal anti-aliasing (gpuspectral_pt.h "Temporal anti-aliasing") ----
+    def temporal_taa(self, taa=None, display=None, src=None):
+        """gsp_temporal_taa: resolves the tone-mapped frame over its history D (once per temporal_accumulate, following on).  taa: an
+        abi.Taa, display: an abi.Display, None = every default.  src: the HDR frame, (height, width, 4) float32 in host memory; None
+        = the image of the newest history."""
+        if src is not None:
+            src = np.ascontiguousarray(src, np.float32)
+            if src.size != self.height * self.width * 4:
+                raise ValueError("temporal_taa: src must hold height*width*4 floats")
+        self._check(self._L.gsp_temporal_taa(self._h, C.byref(taa) if taa is not None else None, C.byref(display) if display is not None else None,
+                                             src.ctypes.data if src is not None else None), "gsp_temporal_taa")
+
+    def temporal_taa_from_device(self, src, nbytes=None, taa=None, display=None):
+        """gsp_temporal_taa_from_device: the same with the HDR frame in device memory, width*height*16 bytes of any alignment.  src:
+        a torch tensor on the context's device (its bytes from its storage offset on), a device pointer with nbytes, or None (the
+        image of the newest history)."""
+        if src is None:
+            ptr, nbytes = None, 0
+        elif hasattr(src, "data_ptr"):
+            ptr, nbytes = src.data_ptr(), src.numel() * src.element_size()
+        else:
+            ptr = src
+        self._check(self._L.gsp_temporal_taa_from_device(self._h, C.byref(taa) if taa is not None else None,
+                                                         C.byref(display) if display is not None else None, ptr, nbytes), "gsp_temporal_taa_from_device")
+
+    def download_taa(self):
+        """gsp_download_taa: the newest resolved frame D', (height, width, 4) float32 of display-linear colour, .w = 1 where the pixel
+        was blended with its history."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.gsp_download_taa(self._h, out.ctypes.data), "gsp_download_taa")
+        return out
+
+    def download_taa_display(self):
+        """gsp_download_taa_display: the encode of D' under the display of the last resolve, (height, width) uint32 RGBA8 words."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.gsp_download_taa_display(self._h, out.ctypes.data), "gsp_download_taa_display")
+        return out
+
+    def taa_display_to_device(self, dst, nbytes=None):
+        """gsp_taa_display_to_device: the same into device memory, width*height*4 bytes.  dst: a torch tensor on the context's device
+        (its bytes from its storage offset on), or a device pointer with nbytes."""
+        if hasattr(dst, "data_ptr"):
+            ptr, nbytes = dst.data_ptr(), dst.numel() * dst.element_size()
+        else:
+            ptr = dst
+        self._check(self._L.gsp_taa_display_to_device(self._h, ptr, nbytes), "gsp_taa_display_to_device")
 
     def pixel_stats(self):
         """Adaptive frame (ABI 9): (m2[n] float32, spp[n] uint32) of the owned pixels in pixel_ids order -- the running mean of

@@ -81,7 +81,8 @@ extern "C" {
                                 gsp_temporal_demodulate, gsp_download_temporal_image, gsp_temporal_image_to_device,
                                 gsp_temporal_svgf_feedback, gsp_temporal_svgf_feedback_to_device (see "Illumination history");
                                 gsp_temporal_antilag, gsp_download_temporal_fast, gsp_temporal_fast_to_device (see "Temporal
-                                anti-lag") */
+                                anti-lag"); gsp_temporal_taa, gsp_temporal_taa_from_device, gsp_download_taa,
+                                gsp_download_taa_display, gsp_taa_display_to_device (see "Temporal anti-aliasing") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -1125,6 +1126,87 @@ int gsp_temporal_antilag(gsp_context* ctx, const gsp_antilag* antilag);
 int gsp_download_temporal_fast(gsp_context* ctx, float* out_rgba);
 /* The same into caller-owned device memory of `bytes` >= width*height*16 (any alignment); complete when the call returns. */
 int gsp_temporal_fast_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
+
+/*
+ * Temporal anti-aliasing.  The last stage of SVGF: the tone-mapped frame resolved over its own history.  The edge stops of the
+ * filters are steered by one-sample feature planes, so under a pixel filter a silhouette pixel keeps or drops its neighbours
+ * differently each frame and object edges shimmer.  The histories H cannot settle that: they are HDR, they sit in front of the
+ * filter and the tone curve, and a tone curve applied to an average is not the average of tone-mapped samples.
+ * gsp_temporal_taa keeps a history D of DISPLAY-LINEAR colour -- after the tone curve and the clamp to [0, 1], before the encode
+ * -- fetches it through the motion plane V of the frame's accumulate, clamps it into the box of the frame's 3 x 3 neighbourhood
+ * in YCoCg and blends the frame in.  It is a call of its own after gsp_temporal_accumulate: a context that never makes it runs the
+ * kernels it ran before, holds no plane of this section and returns the same bits.  Arithmetic is float32 in the order written
+ * (no contraction); / and sqrt are correctly rounded.
+ *
+ * Source.  The frame to resolve is an HDR frame of width*height*4 floats: what gsp_download_temporal_svgf,
+ * gsp_temporal_svgf_feedback, gsp_download_temporal_denoised or gsp_download_temporal_image wrote, in host memory
+ * (gsp_temporal_taa) or in caller-owned device memory of any alignment (gsp_temporal_taa_from_device: what the *_to_device calls
+ * wrote).  A NULL source is the image of the newest history as it is at the call: what gsp_download_temporal_image would
+ * return.  src.w is not read.
+ *
+ * State.  Two ping-pong planes D = {r, g, b, used}, 16 bytes per pixel each over the full frame, made by the first resolve of the
+ * context and counted in gsp_stats.device_bytes.  (A source in host memory, a device source that is not 16-byte aligned and the
+ * NULL source of a demodulated history pass through the filters' 16-byte output plane, made on first use like every plane.)
+ * taa_valid is true exactly when the accumulate BEFORE the current one was followed by a resolve and history_valid has not been
+ * cleared since; everything that clears history_valid clears taa_valid.  The context keeps the resolved gsp_display of the last
+ * resolve for the two display read-outs.
+ *
+ * Call order.  A resolve needs a successful gsp_temporal_accumulate in the current frame with gsp_temporal_follow_instances on
+ * (V is made only then: it holds, for every pixel, where the surface point was in the frame D belongs to, and the reprojection
+ * is not derived a second time), at most one resolve per accumulate; otherwise GSP_ERR_INVALID.  Where the resolve sits
+ * relative to gsp_temporal_antilag and the feedback calls matters only for the NULL source.  The call completes before it
+ * returns and changes nothing else: the accumulate buffer, the feature planes, H, G, I, M, V, F, the primary-hit memo and
+ * gsp_stats keep their bits (device_bytes grows at the first call).
+ *
+ * Per pixel p = (px, py):
+ *  1. Tone.  T_q = steps 1-4 of "LDR film" on source pixel q with the resolved display: NaN and negative channels to 0,
+ *     exposure, the tone curve, the clamp to [0, 1] with a NaN becoming 1.  Every T is finite in [0, 1].  REINHARD with a
+ *     statistic left 0 measures "Frame statistics" over all width*height source pixels; a viewer should pass fixed
+ *     log_avg_luminance / max_luminance, otherwise the exposure itself flickers from frame to frame.
+ *  2. YCoCg.  X.y = (0.25f*r + 0.5f*g) + 0.25f*b;  X.co = 0.5f*r - 0.5f*b;  X.cg = (-0.25f*r + 0.5f*g) - 0.25f*b  of T.
+ *     Back: t = y - cg;  r = t + co;  g = y + cg;  b = t - co.
+ *  3. Neighbourhood box.  q = p + (dx, dy), dy = -1..1 outer and dx inner, for q inside the frame (k = y, co, cg):
+ *         n += 1.0f;  s1.k += X_q.k;  s2.k += X_q.k * X_q.k
+ *         m.k = s1.k / n;  v.k = max(s2.k / n - m.k * m.k, 0);  sd.k = sqrt(v.k)
+ *         lo.k = m.k - sigma_clip * sd.k;  hi.k = m.k + sigma_clip * sd.k
+ *  4. History.  V_p = {mx, my, sw, cls}, the motion record of this frame's accumulate.  No history when !taa_valid, cls == 0 or
+ *     sw < 0.01f.  Otherwise fx = (float)px + mx;  fy = (float)py + my;  x0 = floor(fx);  wx = fx - x0, likewise for y; the
+ *     four taps, their order and their weights are those of "Temporal accumulation" step 7, read from the OLDER D plane.  A
+ *     tap is skipped when its weight is 0 or it lies outside the frame (no tap lies inside it unless fx is within (-1, W) and
+ *     fy within (-1, H)).  Over the kept taps, in tap order:  sw2 += w;  s.k += w * D_q.k  (k = r, g, b).  sw2 < 0.01f: no
+ *     history.  Otherwise h.k = s.k / sw2 and Hc = YCoCg of h.
+ *  5. Without history:  D' = {rgb(X_p) clamped to [0, 1] per channel, 0}.
+ *  6. With history:  c.k = Hc.k < lo.k ? lo.k : (Hc.k > hi.k ? hi.k : Hc.k);  o.k = c.k + (X_p.k - c.k) * alpha -- and, for
+ *     alpha == 1, o.k = X_p.k itself: c.k + (X_p.k - c.k) may round away from X_p.k, and a frame of full weight keeps no trace
+ *     of the history.  D' = {rgb(o) clamped to [0, 1] per channel (the clamp of "LDR film" step 4), 1}.
+ *  7. Read-out.  The RGBA8 word is steps 5-6 of "LDR film" on D'.rgb under the stored display, A = 255.
+ *
+ * GSP_ERR_INVALID (text at gsp_last_error) for: no frame, or a frame begun with pixel_ids; no gsp_temporal_accumulate in this
+ * frame; following off; a second resolve for the same accumulate; alpha outside [0, 1] or NaN; a negative, NaN or infinite
+ * sigma_clip; whatever the gsp_display of "LDR film" is refused for; device_src non-NULL with `bytes` < width*height*16; a
+ * read-out before any resolve since the history was last invalidated; NULL destinations and short sizes as in
+ * gsp_download_temporal / gsp_temporal_to_device.
+ *
+ * Limits.  The history is fetched bilinearly, so it softens under sub-pixel motion; a sharper (Catmull-Rom) fetch is out of
+ * scope.  Disocclusion is handled by V.z (the summed weight of the accumulate's kept taps) and the clamp alone.  Out of scope:
+ * deforming meshes and gsp_multi_* variants, as in the rest of the temporal family.
+ */
+typedef struct gsp_taa {
+  uint32_t struct_size; /* sizeof(gsp_taa) of the host's header; same rule as gsp_antilag (NULL and struct_size 0 = every default) */
+  float alpha;          /* weight of the new frame; 0 = 0.1; otherwise (0, 1] */
+  float sigma_clip;     /* half-width of the neighbourhood box in standard deviations; 0 = 1.0; otherwise > 0 and finite */
+} gsp_taa;
+/* The resolve of src_rgba (host memory, width*height*4 floats; NULL = the image of the newest history); complete when it returns. */
+int gsp_temporal_taa(gsp_context* ctx, const gsp_taa* taa, const gsp_display* display, const float* src_rgba);
+/* The same with the source in caller-owned device memory of `bytes` >= width*height*16 (any alignment); device_src NULL = the same
+ * default, `bytes` then not read. */
+int gsp_temporal_taa_from_device(gsp_context* ctx, const gsp_taa* taa, const gsp_display* display, const void* device_src, uint64_t bytes);
+/* D' as stored: width*height*4 floats, .w = used. */
+int gsp_download_taa(gsp_context* ctx, float* out_rgba);
+/* The encode of D' under the display of the last resolve: width*height RGBA8 words. */
+int gsp_download_taa_display(gsp_context* ctx, uint32_t* out_rgba8);
+/* The same into caller-owned device memory of `bytes` >= width*height*4 (any alignment); complete when the call returns. */
+int gsp_taa_display_to_device(gsp_context* ctx, void* device_dst, uint64_t bytes);
 
 int gsp_get_stats(gsp_context* ctx, gsp_stats* out);
 int gsp_reset_stats(gsp_context* ctx);
