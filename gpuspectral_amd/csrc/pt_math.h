@@ -87,9 +87,23 @@ GSP_HD f3 xform_dir(const float* m, f3 n) {
 // minimax kernels (S. Moshier, public domain) evaluated with explicit fmaf, so
 // the values are the same on any IEEE-754 machine.  ~1 ulp on the ranges used
 // (|x| <= 2*pi for sin/cos, (0,1] for log, <= 0 for exp).
+// Domain of det_sincosf: |x * 2/pi| < 2^31.  Beyond it (int)k overflows -- undefined in C++, and the two targets differed: x86
+// converts to INT_MIN, the gfx950 conversion (v_cvt_i32_f32) saturates, so the quadrant was another one (seen on the GPU: -inf
+// against a finite value at x = 3.45e12, tests/test_gpu_devfn.py).  The conversion is therefore stated once, gcvt_i32, as
+// the device performs it; the host compile spells the saturation out and the device code is unchanged.  The reduction is
+// meaningless that far out anyway; what matters is that the function is the same function on every target.  No bit inside
+// the domain depends on this.
 // ---------------------------------------------------------------------------
 GSP_HD float gfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 GSP_HD float grint(float x) { return __builtin_rintf(x); }
+// (int)x as v_cvt_i32_f32 converts: towards zero, saturating, NaN -> 0 (inside the int range: C++'s conversion)
+GSP_HD int gcvt_i32(float x) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+  if (!(x > -2147483648.0f)) return x != x ? 0 : -2147483647 - 1;
+  if (!(x < 2147483648.0f)) return 2147483647;
+#endif
+  return (int)x;
+}
 
 GSP_HD void det_sincosf(float x, float& s_out, float& c_out) {
   const float kTwoOverPi = 0.63661977236758134308f;
@@ -105,7 +119,7 @@ GSP_HD void det_sincosf(float x, float& s_out, float& c_out) {
   float pc = gfma(2.443315711809948e-5f, z, -1.388731625493765e-3f);
   pc = gfma(pc, z, 4.166664568298827e-2f);
   float c = gfma(pc * z, z, gfma(-0.5f, z, 1.0f));
-  int q = ((int)k) & 3;
+  int q = gcvt_i32(k) & 3;
   float ss = (q & 1) ? c : s;
   float cc = (q & 1) ? s : c;
   if (q == 1 || q == 2) cc = -cc;

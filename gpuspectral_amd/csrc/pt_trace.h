@@ -210,8 +210,22 @@ GSP_HD bool intersect_tri_rot(f3 v0, f3 v1, f3 v2, f3 o, const RayShearRot& rs, 
 
 // min/max here are the NaN-dropping IEEE forms, so a NaN from 0*inf (origin on a slab plane, zero direction
 // component) leaves that slab unconstrained: conservative.
-GSP_HD float fmin_(float a, float b) { return __builtin_fminf(a, b); }
-GSP_HD float fmax_(float a, float b) { return __builtin_fmaxf(a, b); }
+// Two zeros of different sign: -0 orders below +0 (IEEE 754-2019 minimumNumber / maximumNumber), which is what v_min_f32 /
+// v_max_f32 return on gfx950.  C's fminf / fmaxf leave that choice open, and the x86 code picks by operand order (a node
+// whose child boxes held -0 and +0 got a -0 origin on the device and a +0 one on the host, tests/test_gpu_devfn.py), so the
+// host compile states the device's rule; the device code is unchanged.
+GSP_HD float fmin_(float a, float b) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+  if (a == b) return u2f(f2u(a) | f2u(b));  // the same value twice, or two zeros: the negative one if there is one
+#endif
+  return __builtin_fminf(a, b);
+}
+GSP_HD float fmax_(float a, float b) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+  if (a == b) return u2f(f2u(a) & f2u(b));
+#endif
+  return __builtin_fmaxf(a, b);
+}
 
 GSP_HD q4 make_q4(float x, float y, float z, float w) {
   q4 r;

@@ -152,6 +152,16 @@ static inline float u2f(uint32_t u) {
 
 // sin and cos of x, |x| <~ 1e4 (used for |x| <= 2*pi).  Cody-Waite reduction by
 // pi/2, Cephes sinf/cosf kernels on [-pi/4, pi/4].
+// Domain: |x * 2/pi| < 2^31.  Beyond it (int)k overflows -- undefined in C, and the targets differed: x86 converts to INT_MIN,
+// the gfx950 conversion (v_cvt_i32_f32) saturates, so the quadrant was another one (seen on the GPU: -inf against a finite
+// value at x = 3.45e12, tests/test_gpu_devfn.py).  The conversion is therefore spelled out as the device performs it
+// (det_cvt_i32; pt_math.h gcvt_i32).  The reduction is meaningless that far out anyway; what matters is that the function is
+// the same function on every target.  No bit inside the domain depends on this.
+static inline int det_cvt_i32(float x) {  // towards zero, saturating, NaN -> 0
+  if (!(x > -2147483648.0f)) return x != x ? 0 : -2147483647 - 1;
+  if (!(x < 2147483648.0f)) return 2147483647;
+  return (int)x;
+}
 static inline void det_sincosf(float x, float* s_out, float* c_out) {
   const float kTwoOverPi = 0.63661977236758134308f;
   const float kPio2Hi = 1.57079637050628662109375f;       // float(pi/2)
@@ -166,7 +176,7 @@ static inline void det_sincosf(float x, float* s_out, float* c_out) {
   float pc = fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
   pc = fmaf(pc, z, 4.166664568298827e-2f);
   float c = fmaf(pc * z, z, fmaf(-0.5f, z, 1.0f));
-  int q = ((int)k) & 3;
+  int q = det_cvt_i32(k) & 3;
   float ss = (q & 1) ? c : s;
   float cc = (q & 1) ? s : c;
   if (q == 1 || q == 2) cc = -cc;

@@ -20,6 +20,12 @@
 
 #include "../../gpuspectral_amd/csrc/pt_hostmath.h"
 #include "../../gpuspectral_amd/csrc/pt_stages.h"
+// the call bodies shared with the device harness (tests/devfn); a copy of this file alone, as tests/test_trace_work_cpu.py makes for
+// its mutants, builds without the emu_devfn_* twins
+#if __has_include("../devfn/devfn_bodies.h")
+#include "../devfn/devfn_bodies.h"
+#define EMU_HAS_DEVFN 1
+#endif
 
 using namespace gsp;
 
@@ -583,4 +589,106 @@ int emu_is_transmission(uint32_t handle) { return bsdf_transmits(handle) ? 1 : 0
 uint32_t emu_seed(uint32_t width, uint32_t px, uint32_t py, uint32_t timestamp) {
   return pcg_hash(tea(width * py + px, timestamp));
 }
+
+#if defined(EMU_HAS_DEVFN)
+// ---- batch twins of tests/devfn/pt_devfn.hip: the same bodies (tests/devfn/devfn_bodies.h), the same index checks and the same
+// return codes, in a loop on the host.  Array shapes as documented there.
+#define EMU_EACH(n, call) \
+  for (uint64_t i = 0; i < (n); ++i) { call; }
+int emu_devfn_math(const float* x, uint64_t n, float* s, float* c, float* lg, float* ex, float* sq, float* rc) {
+  EMU_EACH(n, devfn::math1(i, x, s, c, lg, ex, sq, rc))
+  return 0;
+}
+int emu_devfn_atan2(const float* y, const float* x, uint64_t n, float* out) {
+  EMU_EACH(n, devfn::atan2_1(i, y, x, out))
+  return 0;
+}
+int emu_devfn_normalize(const float* v, uint64_t n, float* out3) {
+  EMU_EACH(n, devfn::normalize1(i, v, out3))
+  return 0;
+}
+int emu_devfn_rng(const uint32_t* a, const uint32_t* b, uint64_t n, uint32_t* out7) {
+  EMU_EACH(n, devfn::rng1(i, a, b, out7))
+  return 0;
+}
+int emu_devfn_onb(const float* nrm, const float* v, uint64_t n, float* out15) {
+  EMU_EACH(n, devfn::onb1(i, nrm, v, out15))
+  return 0;
+}
+int emu_devfn_helpers(const float* f, const float* g, const uint32_t* h, uint64_t n, uint32_t* out3) {
+  EMU_EACH(n, devfn::helpers1(i, f, g, h, out3))
+  return 0;
+}
+int emu_devfn_samplers(const uint32_t* seeds, const float* alpha, uint64_t n, float* out8) {
+  EMU_EACH(n, devfn::samplers1(i, seeds, alpha, out8))
+  return 0;
+}
+int emu_devfn_bsdf(const void* const* recs, const uint32_t* num, const uint32_t* handles, const float* wo, const uint32_t* seeds,
+                   const float* wi, uint64_t n, float* out9, float* out5, uint8_t* image) {
+  for (int t = 0; t < GSP_BSDF_TYPE_COUNT; ++t)
+    if (num[t] > 0x10000u) return devfn::kBadIndex;
+  if (!devfn::ok_handles(handles, n, num)) return devfn::kBadIndex;
+  const devfn::TableLayout L = devfn::table_layout(num);
+  std::memset(image, 0, L.total);
+  uint32_t most = 0;
+  for (int t = 0; t < GSP_BSDF_TYPE_COUNT; ++t) {
+    if (num[t]) std::memcpy(image + L.rec_off[t], recs[t], (size_t)num[t] * devfn::kRecBytes[t]);
+    most = std::max(most, num[t]);
+  }
+  EMU_EACH(most, devfn::bake_tables1(i, image, L))
+  const BsdfTables T = devfn::tables_at(image, L);
+  EMU_EACH(n, devfn::bsdf1(i, T, handles, wo, seeds, wi, out9, out5))
+  return 0;
+}
+int emu_devfn_lights(gsp_triangle_light* lights, uint32_t capacity, uint32_t num_lights, const float* pos, const uint32_t* seeds,
+                     uint64_t n, float* out8) {
+  if (num_lights > capacity) return devfn::kBadIndex;
+  EMU_EACH(capacity, devfn::bake_light1(i, lights))
+  const float inv = num_lights ? 1.0f / (float)num_lights : 0.0f;
+  EMU_EACH(n, devfn::light1(i, lights, num_lights, inv, pos, seeds, out8))
+  return 0;
+}
+int emu_devfn_texture(const gsp_texture* textures, uint32_t num_textures, const uint32_t* texels, uint64_t num_texels, const float* decode,
+                      const uint32_t* ids, const float* uv, uint64_t n, float* out3) {
+  if (!devfn::ok_textures(textures, num_textures, num_texels, ids, n)) return devfn::kBadIndex;
+  TextureView T;
+  T.textures = textures;
+  T.texels = texels;
+  T.decode = decode;
+  T.num_textures = num_textures;
+  EMU_EACH(n, devfn::texture1(i, T, ids, uv, out3))
+  return 0;
+}
+int emu_devfn_envmap(const float* env_texels, uint32_t width, uint32_t height, const float* to_local, const float* dirs, uint64_t n,
+                     float* out3) {
+  if (width == 0 || height == 0 || width > 32768u || height > 32768u) return devfn::kBadIndex;
+  TextureView T;
+  T.env_texels = env_texels;
+  T.env_width = width;
+  T.env_height = height;
+  for (int k = 0; k < 16; ++k) T.env_to_local[k] = to_local[k];
+  EMU_EACH(n, devfn::envmap1(i, T, dirs, out3))
+  return 0;
+}
+int emu_devfn_tri_tests(const float* rays, const float* tris, uint64_t n, float* out_ref, float* out_rot) {
+  EMU_EACH(n, devfn::tri1(i, rays, tris, out_ref, out_rot))
+  return 0;
+}
+int emu_devfn_shears(const float* d3, uint64_t n, uint32_t* out12) {
+  EMU_EACH(n, devfn::shear1(i, d3, out12))
+  return 0;
+}
+int emu_devfn_encode_nodes(const float* boxes, const int32_t* counts, uint64_t n, uint32_t* out_ref, uint32_t* out_fast) {
+  if (!devfn::ok_child_counts(counts, n)) return devfn::kBadIndex;
+  EMU_EACH(n, devfn::encode1(i, boxes, counts, out_ref, out_fast))
+  return 0;
+}
+int emu_devfn_node_tests(const uint32_t* nodes, uint64_t num_nodes, const uint32_t* node_idx, const float* rays, uint64_t n,
+                         uint32_t* out12) {
+  if (!devfn::ok_node_indices(node_idx, n, num_nodes)) return devfn::kBadIndex;
+  EMU_EACH(n, devfn::nodetest1(i, nodes, node_idx, rays, out12))
+  return 0;
+}
+#undef EMU_EACH
+#endif  // EMU_HAS_DEVFN
 }

@@ -158,36 +158,12 @@ def test_leaf_step_triangle_test_equals_the_oracle_statement(emu):
     lane masks and without make_shear's kx / ky exchange (pt_trace.h intersect_tri_rot).  Same verdict and the same t, u, v bit
     for bit as the oracle's statement (intersect_tri) -- for rays of every dominant axis and sign, rays through shared edges and
     vertices (the double-precision fallback), axis-parallel rays, degenerate and far-away triangles."""
-    rng = np.random.RandomState(77)
-    n = 400000
-    tris = rng.uniform(-2, 2, (n, 9)).astype(np.float32)
-    tris[: n // 8] *= np.float32(1e-3)  # tiny
-    tris[n // 8: n // 4] += np.float32(1e4)  # far from the origin
-    o = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
-    k = rng.randint(0, 4, n)
-    bary = rng.dirichlet((1, 1, 1), n).astype(np.float32)
-    bary[k == 1] = np.eye(3, dtype=np.float32)[rng.randint(0, 3, (k == 1).sum())]  # through a vertex
-    e = k == 2
-    bary[e, 2] = 0
-    bary[e, 0] = rng.uniform(0, 1, e.sum()).astype(np.float32)
-    bary[e, 1] = np.float32(1) - bary[e, 0]  # through an edge
-    tgt = (tris.reshape(n, 3, 3) * bary[:, :, None]).sum(1)
-    tgt[k == 3] = rng.uniform(-3, 3, ((k == 3).sum(), 3)).astype(np.float32)  # anywhere: mostly misses
-    d = tgt - o
-    ax = rng.randint(0, 12, n)
-    for a in range(3):  # axis-parallel rays (two zero components), both signs
-        m = ax == a
-        z = np.zeros((m.sum(), 3), np.float32)
-        z[:, a] = np.where(rng.rand(m.sum()) < 0.5, -1, 1)
-        d[m] = z
-    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-30).astype(np.float32)
-    rays = np.zeros((n, 8), np.float32)
-    rays[:, 0:3], rays[:, 3:6] = o, d
-    rays[:, 6] = np.where(rng.rand(n) < 0.5, 0.0, 0.01)
-    rays[:, 7] = np.where(rng.rand(n) < 0.5, 1e10, rng.uniform(0.1, 8, n))
-    tris[-1000:, 6:9] = tris[-1000:, 0:3]  # zero-area triangles
+    import devfn_vectors
+
+    rays, tris = devfn_vectors.tri_test_cases()  # (shared with tests/test_gpu_devfn.py)
+    n = len(rays)
+    assert n == 400000
     a, b = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
-    rays, tris = np.ascontiguousarray(rays), np.ascontiguousarray(tris)
     emu.L.emu_tri_tests(rays.ctypes.data, tris.ctypes.data, n, a.ctypes.data, b.ctypes.data)
     assert a[:, 0].sum() > n // 5  # (the case set does hit)
     assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
@@ -199,26 +175,11 @@ def test_node_encoder_forms_agree(emu):
     insertion sort of the per-octant keys as six chained compare-exchanges, the order code in closed form, power-of-two divisions
     as multiplications).  Same record, bit for bit: every child count, boxes of every size from 1e-30 to 1e30, children that
     coincide (ties in every octant), flat and point-like nodes, huge offsets from the origin."""
-    rng = np.random.RandomState(20250)
-    n = 400_000
-    centre = rng.uniform(-1, 1, (n, 1, 3)) * 10.0 ** rng.uniform(-3, 6, (n, 1, 1))
-    size = 10.0 ** rng.uniform(-30, 30, (n, 1, 1)) * (rng.rand(n, 1, 1) < 0.1) + 10.0 ** rng.uniform(-4, 3, (n, 1, 1)) * 1.0
-    size = np.minimum(size, 1e30)
-    lo = centre + rng.uniform(-1, 1, (n, 4, 3)) * size
-    ext = rng.uniform(0, 1, (n, 4, 3)) * size * (rng.rand(n, 4, 3) > 0.1)  # flat children on some axes
-    hi = lo + ext
-    boxes = np.concatenate([lo, hi], axis=2).astype(np.float32)
-    dup = rng.rand(n) < 0.2  # ties: children 1.. repeat child 0 (or each other)
-    boxes[dup, 1] = boxes[dup, 0]
-    dup2 = rng.rand(n) < 0.1
-    boxes[dup2, 3] = boxes[dup2, 2]
-    snap = rng.rand(n) < 0.1  # centres on a coarse grid: equal keys in some octants only
-    boxes[snap] = np.round(boxes[snap] * 4) / 4
-    boxes[snap, :, 3:] = np.maximum(boxes[snap, :, 3:], boxes[snap, :, :3])
-    cnt = rng.randint(0, 5, n)
-    ni = (rng.rand(n) * (cnt + 1)).astype(np.int32)
-    counts = np.stack([ni, cnt - ni], axis=1).astype(np.int32)
-    boxes, counts = np.ascontiguousarray(boxes), np.ascontiguousarray(counts)
+    import devfn_vectors
+
+    boxes, counts = devfn_vectors.node_encoder_cases()  # (shared with tests/test_gpu_devfn.py)
+    n = len(boxes)
+    assert n == 400000
     a, b = np.zeros((n, 16), np.uint32), np.zeros((n, 16), np.uint32)
     emu.L.emu_encode_nodes(boxes.ctypes.data, counts.ctypes.data, n, a.ctypes.data, b.ctypes.data)
     assert len(np.unique(a[:, 12])) > 1000  # (many different order words)
