@@ -55,12 +55,63 @@
 
 using namespace gsp;
 
+// triangle slots a tree's intersection / shading arrays hold: leading all-zero slots, the triangles, the tail a wide leaf may read
+static uint64_t tree_slots(const DeviceBvh& t) { return (uint64_t)t.num_tris + t.first_slot + (kWide - 1); }
+
+// The three geometry arrays -- node records, intersection triangles, shading packets -- as ONE allocation unit addressed by
+// TRIANGLE SLOT: slot s starts at quad s * kPerSlot[k] of array k (a tree has at most one node per slot, so it fits where its
+// triangles do).  The context's geometry ring is one of these; nothing else spells the per-slot quad counts.
+struct TreeArrays {
+  DevBuf<q4> nodes, isect, shade;
+  static constexpr size_t kPerSlot[3] = {kNodeQuads, 3, 4};  // quads per triangle slot: nodes, isect, shade
+  // bytes of the three arrays of a tree that owns them, as build_bvh counts them in DeviceBvh::bytes
+  static size_t bytes_owned_by(const DeviceBvh& t) { return (size_t)t.num_nodes * kNodeBytes + tree_slots(t) * (kPerSlot[1] + kPerSlot[2]) * sizeof(q4); }
+  size_t bytes() const { return (nodes.count + isect.count + shade.count) * sizeof(q4); }
+  // all-zero everywhere: the leading / trailing triangle slots of every version (build_bvh), node records nothing refers to.
+  // Counted in no ledger: the caller adds bytes() once the arrays are the context's.
+  hipError_t alloc_zeroed(size_t total_slots, hipStream_t st) {
+    DevBuf<q4>* const arr[3] = {&nodes, &isect, &shade};
+    for (int k = 0; k < 3; ++k) {
+      hipError_t e = arr[k]->ensure(total_slots * kPerSlot[k], nullptr);
+      if (e == hipSuccess) e = hipMemsetAsync(arr[k]->p, 0, total_slots * kPerSlot[k] * sizeof(q4), st);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  // the tree's arrays := slot at_slot onwards (not the tree's to free: arrays_external)
+  void point(DeviceBvh& t, size_t at_slot) const {
+    t.nodes = nodes.p + at_slot * kPerSlot[0];
+    t.tri_isect = isect.p + at_slot * kPerSlot[1];
+    t.tri_shade = shade.p + at_slot * kPerSlot[2];
+    t.arrays_external = true;
+  }
+  // the contents of the tree's three arrays -> slot at_slot onwards (queued on st)
+  hipError_t copy_tree_in(size_t at_slot, const DeviceBvh& t, hipStream_t st) const {
+    DeviceBvh to;
+    point(to, at_slot);
+    hipError_t e = hipMemcpyAsync(to.nodes, t.nodes, (size_t)t.num_nodes * kNodeBytes, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(to.tri_isect, t.tri_isect, tree_slots(t) * kPerSlot[1] * sizeof(q4), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(to.tri_shade, t.tri_shade, tree_slots(t) * kPerSlot[2] * sizeof(q4), hipMemcpyDeviceToDevice, st);
+    return e;
+  }
+  void swap(TreeArrays& o) {
+    nodes.swap(o.nodes);
+    isect.swap(o.isect);
+    shade.swap(o.shade);
+  }
+  void release() {
+    nodes.release();
+    isect.release();
+    shade.release();
+  }
+};
+
 struct gsp_context {
   int device = 0;
   int num_cus = 256;
   hipStream_t stream = nullptr;
   std::string err;
-  size_t bytes = 0;
+  ByteLedger bytes;  // gsp_stats.device_bytes (pt_versions.h)
 
   // scene
   bool have_scene = false;
@@ -80,7 +131,7 @@ struct gsp_context {
   // triangles, shading packets -- so that gsp_update_instances need not wait for the samples in flight either: the refit goes
   // into the next slot, new samples are stamped with it, the old ones finish in theirs.  Made by the first gsp_update_instances
   // of a tree (which drains, as every one did until r04); `bvh.nodes / tri_isect / tri_shade` then point at the NEWEST slot.
-  DevBuf<q4> ring_nodes, ring_isect, ring_shade;
+  TreeArrays ring;
   GeoVersions geo;  // stride (0 = no ring), log2 of the slots, current version, base slot (pt_versions.h)
   bool geo_ring_failed = false;  // no memory for it: edits drain, as before
   // r05: SPLIT scene (gsp_update_instances): the instances the host has edited since the last full build live in a tree of their
@@ -110,6 +161,8 @@ struct gsp_context {
   DevBuf<float> d_invt, d_pos, d_nrm, d_uv;
   DevBuf<uint32_t> d_first;
   std::vector<gsp_instance> h_inst;
+  std::vector<float> h_invt;  // h_invt, h_tabs: what d_invt / d_first were last uploaded from (the copies are queued: their
+  InstanceTables h_tabs;      // source stays alive)
   std::vector<uint8_t> h_tables;  // host copy of the table image (counts + tables): gsp_update_tables compares before it drains
   uint32_t num_bsdfs[GSP_BSDF_TYPE_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t num_vertices = 0, total_tris = 0;
@@ -325,12 +378,12 @@ struct gsp_context {
   SceneView view(bool versioned = false, bool newest_tables = false) const {
     SceneView v;
     if (split) versioned = true;  // (a split scene has no array a plain kernel could walk)
-    const bool ring = versioned && geo.stride != 0;
+    const bool in_ring = versioned && geo.stride != 0;
     const bool tab_versions = versioned && !newest_tables && oldest_live_version() != tab.ver;  // (else: one version of the tables, wherever it sits)
-    v.nodes = ring ? ring_nodes.p : bvh.nodes;
-    v.tri_isect = ring ? ring_isect.p : bvh.tri_isect;
-    v.tri_shade = ring ? ring_shade.p : bvh.tri_shade;
-    v.geo = ring ? pack_geo(geo.base, geo.stride, geo.log2) : 0u;
+    v.nodes = in_ring ? ring.nodes.p : bvh.nodes;  // (slot 0 of the ring: the base the <VER> kernels add their offset to)
+    v.tri_isect = in_ring ? ring.isect.p : bvh.tri_isect;
+    v.tri_shade = in_ring ? ring.shade.p : bvh.tri_shade;
+    v.geo = in_ring ? pack_geo(geo.base, geo.stride, geo.log2) : 0u;
     v.static_slots = split ? static_slots : 0u;
     // slot 0 = the base the <VER> kernels add their offset to, or the slot of the one live version (slot 0 again whenever the
     // plain kernels run: lane_enqueue moves it there)

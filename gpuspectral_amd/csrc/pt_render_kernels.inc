@@ -1692,19 +1692,23 @@ struct DevBuf {
     p = nullptr;
     count = 0;
   }
-  hipError_t ensure(size_t n, size_t* tally) {
+  void swap(DevBuf& o) {
+    std::swap(p, o.p);
+    std::swap(count, o.count);
+  }
+  hipError_t ensure(size_t n, ByteLedger* tally) {
     if (n <= count && p) return hipSuccess;
-    if (tally && p) *tally -= count * sizeof(T);
+    if (tally && p) tally->sub(count * sizeof(T));
     release();
     n = n ? n : 1;
     hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
     if (e == hipSuccess) {
       count = n;
-      if (tally) *tally += n * sizeof(T);
+      if (tally) tally->add(n * sizeof(T));
     }
     return e;
   }
-  hipError_t upload(const T* src, size_t n, hipStream_t s, size_t* tally) {
+  hipError_t upload(const T* src, size_t n, hipStream_t s, ByteLedger* tally) {
     hipError_t e = ensure(n, tally);
     if (e != hipSuccess || n == 0 || !src) return e;
     return hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, s);

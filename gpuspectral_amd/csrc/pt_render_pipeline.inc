@@ -1186,7 +1186,7 @@ int gsp_get_stats(gsp_context* ctx, gsp_stats* out) {
   ctx->stats.num_triangles = ctx->bvh.num_tris;  // (a split scene: the static tree keeps a slot for every triangle of the scene)
   ctx->stats.num_bvh_nodes = ctx->bvh.num_nodes + (ctx->split ? ctx->dyn.num_nodes : 0u);
   ctx->stats.bvh_depth = std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u);
-  ctx->stats.device_bytes = ctx->bytes;
+  ctx->stats.device_bytes = ctx->bytes.bytes;
   ctx->stats.adaptive_active_pixels = ctx->frame_mode == gsp_context::kFrameAdaptive ? ctx->active_pixels() : 0u;
   ctx->stats.algorithmic_bytes = 48ull * ctx->stats.stat_rays + (uint64_t)kNodeBytes * ctx->stats.nodes_visited + 48ull * ctx->stats.tris_tested +
                                  32ull * ctx->stats.shadow_stat_rays + 36ull * ctx->stats.shadow_stat_occluded +
@@ -1284,7 +1284,7 @@ int gsp_debug_visit_histograms(gsp_context* ctx, uint32_t* node_counts, uint64_t
   }
   if (node_counts) CTX_TRY(ctx, hipMemcpy(node_counts, ctx->node_hist.p, std::min<uint64_t>(num_nodes, ctx->node_hist.count) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (slot_counts) CTX_TRY(ctx, hipMemcpy(slot_counts, ctx->tri_hist.p, std::min<uint64_t>(num_slots, ctx->tri_hist.count) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  ctx->bytes -= (ctx->node_hist.count + ctx->tri_hist.count) * sizeof(uint32_t);
+  ctx->bytes.sub((ctx->node_hist.count + ctx->tri_hist.count) * sizeof(uint32_t));
   ctx->node_hist.release();
   ctx->tri_hist.release();
   return GSP_OK;

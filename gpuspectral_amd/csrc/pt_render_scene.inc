@@ -44,6 +44,22 @@ static int check_texture_words(gsp_context* ctx, const gsp_scene_desc* sc, uint3
   return GSP_OK;
 }
 
+// the primary-hit memos hold hits of the scene / camera / frame as it was: re-traced on the lane's stream before its next batch
+static void invalidate_memos(gsp_context* ctx) {
+  for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
+}
+// The one place an edit waits: the samples already queued belong to the scene as it was and finish first.  Counted in
+// gsp_stats.scene_drains when there is something to wait for.
+static int drain_for_edit(gsp_context* ctx) {
+  if (!ctx->pipe_active) return GSP_OK;
+  ++ctx->stats.scene_drains;
+  return pipeline_drain(ctx);
+}
+
+// record sizes of the eight BSDF tables (in GSP_BSDF_* order), then of the lights
+static constexpr size_t kRecordBytes[9] = {sizeof(gsp_diffuse_bsdf), sizeof(gsp_smooth_dielectric_bsdf), sizeof(gsp_smooth_conductor_bsdf),
+                                           sizeof(gsp_smooth_plastic_bsdf), sizeof(gsp_rough_conductor_bsdf), sizeof(gsp_smooth_floor_bsdf),
+                                           sizeof(gsp_rough_floor_bsdf), sizeof(gsp_rough_plastic_bsdf), sizeof(gsp_triangle_light)};
 // The eight BSDF arrays + the lights of `sc`, packed back to back (16-B aligned each) as they sit in the context's one table
 // allocation; the counts ride in front of the image so that "equal images" means equal tables.
 struct TableImage {
@@ -54,15 +70,12 @@ struct TableImage {
 static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& img) {
   const void* src[9] = {sc->diffuse_bsdfs, sc->smooth_dielectric_bsdfs, sc->smooth_conductor_bsdfs, sc->smooth_plastic_bsdfs,
                         sc->rough_conductor_bsdfs, sc->smooth_floor_bsdfs, sc->rough_floor_bsdfs, sc->rough_plastic_bsdfs, sc->lights};
-  const size_t rec[9] = {sizeof(gsp_diffuse_bsdf), sizeof(gsp_smooth_dielectric_bsdf), sizeof(gsp_smooth_conductor_bsdf),
-                         sizeof(gsp_smooth_plastic_bsdf), sizeof(gsp_rough_conductor_bsdf), sizeof(gsp_smooth_floor_bsdf),
-                         sizeof(gsp_rough_floor_bsdf), sizeof(gsp_rough_plastic_bsdf), sizeof(gsp_triangle_light)};
   size_t bytes[9];
   uint64_t counts[9];
   img.total = 0;
   for (int k = 0; k < 9; ++k) {
     counts[k] = k < 8 ? sc->num_bsdfs[k] : sc->num_lights;
-    bytes[k] = rec[k] * counts[k];
+    bytes[k] = kRecordBytes[k] * counts[k];
     if (bytes[k] && !src[k]) {
       ctx->err = "null array with non-zero count";
       return GSP_ERR_SCENE;
@@ -90,7 +103,7 @@ static int upload_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage&
     // behind a drain (or the first upload): ONE slot -- the ring is made by the first edit that arrives with samples in flight
     // (grow_table_ring), not at upload: 64 slots of a large light table are gigabytes (r05 review)
     if (ctx->tab.upload_behind_drain(slot) || !ctx->tables.p) {  // (another slot size starts with one slot again)
-      if (ctx->tables.p) ctx->bytes -= std::min(ctx->bytes, ctx->tables.count);
+      ctx->bytes.sub(ctx->tables.count);
       ctx->tables.release();
       CTX_TRY(ctx, ctx->tables.ensure(ctx->tab.allocation_bytes(), &ctx->bytes));
     }
@@ -107,12 +120,9 @@ static int upload_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage&
   // the resident light and diffuse records carry what a vertex would compute from them alone (pt_shading.h bake_light / bake_diffuse)
   uint32_t nb = sc->num_lights;
   BakeTables bt;
-  const uint32_t rec_bytes[GSP_BSDF_TYPE_COUNT] = {sizeof(gsp_diffuse_bsdf), sizeof(gsp_smooth_dielectric_bsdf), sizeof(gsp_smooth_conductor_bsdf),
-                                                   sizeof(gsp_smooth_plastic_bsdf), sizeof(gsp_rough_conductor_bsdf), sizeof(gsp_smooth_floor_bsdf),
-                                                   sizeof(gsp_rough_floor_bsdf), sizeof(gsp_rough_plastic_bsdf)};
   for (uint32_t t = 0; t < GSP_BSDF_TYPE_COUNT; ++t) {
     bt.rec[t] = base + img.off[t];
-    bt.rec_bytes[t] = rec_bytes[t];
+    bt.rec_bytes[t] = (uint32_t)kRecordBytes[t];
     bt.num[t] = sc->num_bsdfs[t];
     nb = std::max(nb, sc->num_bsdfs[t]);
   }
@@ -139,37 +149,51 @@ static int grow_table_ring(gsp_context* ctx, uint32_t slots) {
   }
   CTX_TRY(ctx, hipMemcpyAsync(ring.p, ctx->tables.p, ctx->tab.slot_bytes, hipMemcpyDeviceToDevice, ctx->stream));
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->bytes -= std::min(ctx->bytes, ctx->tables.count);
-  std::swap(ctx->tables.p, ring.p);  // (`ring` now holds the one-slot allocation and frees it on return)
-  std::swap(ctx->tables.count, ring.count);
-  ctx->bytes += ctx->tables.count;
+  ctx->bytes.sub(ctx->tables.count);
+  ctx->tables.swap(ring);  // (`ring` now holds the one-slot allocation and frees it on return)
+  ctx->bytes.add(ctx->tables.count);
   ctx->tab.on_grown(slots);
   return GSP_OK;
 }
 
-// ---- geometry ring (gsp_context::ring_*) ----------------------------------------------------------------------------------
-// Both need an idle pipeline: nothing queued may name the arrays that go away.
+// ---- geometry ring (gsp_context::ring, a TreeArrays) ------------------------------------------------------------------------
+// the tree gives back the three arrays it owns (as build_bvh counted them in DeviceBvh::bytes, which the context's ledger holds)
+static void release_own_arrays(gsp_context* ctx, DeviceBvh& t) {
+  const size_t freed = TreeArrays::bytes_owned_by(t);
+  (void)hipFree(t.nodes);
+  (void)hipFree(t.tri_isect);
+  (void)hipFree(t.tri_shade);
+  t.nodes = t.tri_isect = t.tri_shade = nullptr;
+  t.bytes -= std::min(t.bytes, freed);
+  ctx->bytes.sub(freed);
+}
+// the tree lets go of its slot of the ring (free_bvh would free what it points at)
+static void detach_from_ring(DeviceBvh& t) {
+  t.nodes = t.tri_isect = t.tri_shade = nullptr;
+  t.arrays_external = false;
+}
+// the edited instances' tree of a split scene goes: its arrays were a slot of the ring, the rest was its own
+static void drop_edited_tree(gsp_context* ctx) {
+  detach_from_ring(ctx->dyn);
+  ctx->bytes.sub(ctx->dyn.bytes);
+  free_bvh(ctx->dyn);
+}
+// tree T := its slot of version v (T = ctx->dyn: behind the static tree of a split scene; T = ctx->bvh: a ring of whole trees)
+static void point_tree_at(gsp_context* ctx, DeviceBvh& T, uint32_t v) {
+  ctx->ring.point(T, (&T == &ctx->dyn ? (size_t)ctx->static_slots : 0) + (size_t)ctx->geo.phys(v) * ctx->geo.stride);
+}
+
+// drop_geo_ring and make_geo_ring need an idle pipeline: nothing queued may name the arrays that go away.
 static void drop_geo_ring(gsp_context* ctx) {
-  if (ctx->bvh.arrays_external) {  // the tree's arrays were a slot of the ring
-    ctx->bvh.nodes = ctx->bvh.tri_isect = ctx->bvh.tri_shade = nullptr;
-    ctx->bvh.arrays_external = false;
-  }
-  if (ctx->split) {  // ... and so were the edited instances' tree's
-    ctx->dyn.nodes = ctx->dyn.tri_isect = ctx->dyn.tri_shade = nullptr;
-    ctx->dyn.arrays_external = false;
-    ctx->bytes -= std::min(ctx->bytes, ctx->dyn.bytes);
-    free_bvh(ctx->dyn);
+  if (ctx->bvh.arrays_external) detach_from_ring(ctx->bvh);  // the tree's arrays were a slot of the ring
+  if (ctx->split) {                                          // ... and so were the edited instances' tree's
+    drop_edited_tree(ctx);
     ctx->split = false;
     ctx->static_slots = 0;
   }
-  for (DevBuf<q4>* b : {&ctx->ring_nodes, &ctx->ring_isect, &ctx->ring_shade}) {
-    if (b->p) ctx->bytes -= b->count * sizeof(q4);
-    b->release();
-  }
-  ctx->geo.stride = 0;
-  ctx->geo.log2 = 0;
-  ctx->geo.ver = 0;
-  ctx->geo.base = 0;
+  ctx->bytes.sub(ctx->ring.bytes());
+  ctx->ring.release();
+  ctx->geo.reset();
 }
 // Moves the tree's three arrays into slot 0 of a new ring of as many versions (a power of two, at most kGeoVersions) as 32-bit node
 // offsets and a quarter of the free device memory allow: 176 B per triangle and version, 11 GB for 64 versions of a million
@@ -178,101 +202,136 @@ static void drop_geo_ring(gsp_context* ctx) {
 static int make_geo_ring(gsp_context* ctx) {
   DeviceBvh& b = ctx->bvh;
   if (ctx->geo.stride != 0 || ctx->geo_ring_failed || !b.nodes || b.num_tris == 0 || b.arrays_external) return GSP_OK;
-  const uint64_t slots = (uint64_t)b.num_tris + b.first_slot + (kWide - 1);
   size_t free_b = 0, total_b = 0;
   CTX_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
   // log2 of the slots: at most what the options allow (default kGeoVersions), 32-bit node offsets, a quarter of the free memory
-  const GeoRingPlan plan = plan_geo_ring(0, 0, slots, b.num_nodes, ctx->opt.geometry_versions, free_b, kNodeAllocMin / kNodeBytes, kGeoMaxStride, kNodeBytes);
+  const GeoRingPlan plan = plan_geo_ring(0, 0, tree_slots(b), b.num_nodes, ctx->opt.geometry_versions, free_b, kNodeAllocMin / kNodeBytes, kGeoMaxStride, kNodeBytes);
   if (plan.log2 < 2) return GSP_OK;
-  const uint64_t stride = plan.stride_ring;
-  const uint32_t lg = (uint32_t)plan.log2;
   hipStream_t st = ctx->stream;
-  const size_t total = (size_t)stride << lg;
-  if (ctx->ring_nodes.ensure(total * kNodeQuads, &ctx->bytes) != hipSuccess || ctx->ring_isect.ensure(total * 3, &ctx->bytes) != hipSuccess ||
-      ctx->ring_shade.ensure(total * 4, &ctx->bytes) != hipSuccess) {
+  const hipError_t e = ctx->ring.alloc_zeroed((size_t)plan.stride_ring << plan.log2, st);
+  if (e == hipErrorOutOfMemory) {
     (void)hipGetLastError();
-    drop_geo_ring(ctx);
+    ctx->ring.release();
     ctx->geo_ring_failed = true;
     return GSP_OK;
   }
-  // all-zero everywhere: the leading / trailing triangle slots of every version (build_bvh), node records nothing refers to
-  CTX_TRY(ctx, hipMemsetAsync(ctx->ring_nodes.p, 0, total * kNodeQuads * sizeof(q4), st));
-  CTX_TRY(ctx, hipMemsetAsync(ctx->ring_isect.p, 0, total * 3 * sizeof(q4), st));
-  CTX_TRY(ctx, hipMemsetAsync(ctx->ring_shade.p, 0, total * 4 * sizeof(q4), st));
-  ctx->geo.ver = 0;
-  ctx->geo.base = 0;
-  ctx->geo.log2 = lg;
-  q4* nn = ctx->ring_nodes.p;  // (slot 0)
-  q4* ni = ctx->ring_isect.p;
-  q4* ns = ctx->ring_shade.p;
-  const size_t b_nodes = (size_t)b.num_nodes * kNodeBytes, b_is = slots * 3 * sizeof(q4), b_sh = slots * 4 * sizeof(q4);
-  CTX_TRY(ctx, hipMemcpyAsync(nn, b.nodes, b_nodes, hipMemcpyDeviceToDevice, st));
-  CTX_TRY(ctx, hipMemcpyAsync(ni, b.tri_isect, b_is, hipMemcpyDeviceToDevice, st));
-  CTX_TRY(ctx, hipMemcpyAsync(ns, b.tri_shade, b_sh, hipMemcpyDeviceToDevice, st));
+  CTX_TRY(ctx, e);
+  CTX_TRY(ctx, ctx->ring.copy_tree_in(0, b, st));
   CTX_TRY(ctx, hipStreamSynchronize(st));
-  (void)hipFree(b.nodes);
-  (void)hipFree(b.tri_isect);
-  (void)hipFree(b.tri_shade);
-  const size_t freed = b_nodes + b_is + b_sh;  // (as build_bvh counted them)
-  b.bytes -= std::min(b.bytes, freed);
-  ctx->bytes -= std::min(ctx->bytes, freed);
-  b.nodes = nn;
-  b.tri_isect = ni;
-  b.tri_shade = ns;
-  b.arrays_external = true;
-  ctx->geo.stride = (uint32_t)stride;
+  ctx->bytes.add(ctx->ring.bytes());
+  release_own_arrays(ctx, b);
+  ctx->ring.point(b, 0);
+  ctx->geo.reset();
+  ctx->geo.log2 = (uint32_t)plan.log2;
+  ctx->geo.stride = (uint32_t)plan.stride_ring;
   return GSP_OK;
 }
-// the tree's arrays := the slot of version v
-static void point_bvh_at(gsp_context* ctx, uint32_t v) {
-  const size_t off = (size_t)ctx->geo.phys(v) * ctx->geo.stride;
-  ctx->bvh.nodes = ctx->ring_nodes.p + off * kNodeQuads;
-  ctx->bvh.tri_isect = ctx->ring_isect.p + off * 3;
-  ctx->bvh.tri_shade = ctx->ring_shade.p + off * 4;
+
+// ---- instance tables -> device ------------------------------------------------------------------------------------------------
+// transformInvT per instance (PathTracer::prepareScene, PathTracer.cpp:58-93)
+static void inverse_transposes(const std::vector<gsp_instance>& inst, std::vector<float>& inv_t) {
+  inv_t.resize(16ull * inst.size());
+  for (size_t i = 0; i < inst.size(); ++i) {
+    float tr[16];
+    transpose4(inst[i].transform, tr);
+    inverse4(tr, &inv_t[16ull * i]);
+  }
+}
+static BuildInput build_input(const gsp_context* ctx, const gsp_instance* inst, const float* inv_t, const uint32_t* tri_first, const uint32_t* tri_id_first,
+                              size_t num_instances, uint32_t num_tris) {
+  BuildInput bi{};
+  bi.instances = inst;
+  bi.inv_t = inv_t;
+  bi.tri_first = tri_first;
+  bi.tri_id_first = tri_id_first;
+  bi.num_instances = (uint32_t)num_instances;
+  bi.positions = ctx->d_pos.p;
+  bi.normals = ctx->d_nrm.p;
+  bi.num_tris = num_tris;
+  bi.reinsert_rounds = (int)ctx->opt.reinsert_rounds - 1;
+  return bi;
+}
+// the whole instance list (ctx->h_inst) for build_bvh / refit_bvh of the scene's one tree.  The copies are queued: their sources
+// are the context's (h_inst, h_invt, h_tabs)
+static int upload_scene_instances(gsp_context* ctx, BuildInput& bi) {
+  hipStream_t st = ctx->stream;
+  inverse_transposes(ctx->h_inst, ctx->h_invt);
+  ctx->h_tabs = instance_tables(ctx->h_inst);
+  CTX_TRY(ctx, ctx->d_inst.upload(ctx->h_inst.data(), ctx->h_inst.size(), st, &ctx->bytes));
+  CTX_TRY(ctx, ctx->d_invt.upload(ctx->h_invt.data(), ctx->h_invt.size(), st, &ctx->bytes));
+  CTX_TRY(ctx, ctx->d_first.upload(ctx->h_tabs.tri_first.data(), ctx->h_tabs.tri_first.size(), st, &ctx->bytes));
+  bi = build_input(ctx, ctx->d_inst.p, ctx->d_invt.p, ctx->d_first.p, nullptr, ctx->h_inst.size(), (uint32_t)ctx->total_tris);
+  return GSP_OK;
+}
+// ... and one subset of it (which = 0 static / 1 edited, ctx->sub_index) for the trees of a split scene
+static int upload_subset(gsp_context* ctx, int which, BuildInput& bi) {
+  const std::vector<uint32_t>& idx = ctx->sub_index[which];
+  std::vector<gsp_instance> inst(idx.size());
+  for (size_t k = 0; k < idx.size(); ++k) inst[k] = ctx->h_inst[idx[k]];
+  std::vector<float> inv_t;
+  inverse_transposes(inst, inv_t);
+  const InstanceTables t = instance_tables(ctx->h_inst, &idx);
+  hipStream_t st = ctx->stream;
+  CTX_TRY(ctx, ctx->d_inst_sub[which].upload(inst.data(), inst.size(), st, &ctx->bytes));
+  CTX_TRY(ctx, ctx->d_invt_sub[which].upload(inv_t.data(), inv_t.size(), st, &ctx->bytes));
+  CTX_TRY(ctx, ctx->d_first_sub[which].upload(t.tri_first.data(), t.tri_first.size(), st, &ctx->bytes));
+  CTX_TRY(ctx, ctx->d_idfirst_sub[which].upload(t.tri_id_first.data(), t.tri_id_first.size(), st, &ctx->bytes));
+  CTX_TRY(ctx, hipStreamSynchronize(st));  // (the host vectors go out of scope)
+  bi = build_input(ctx, ctx->d_inst_sub[which].p, ctx->d_invt_sub[which].p, ctx->d_first_sub[which].p, ctx->d_idfirst_sub[which].p, idx.size(), t.total);
+  return GSP_OK;
 }
 
 // ---- split scene -----------------------------------------------------------------------------------------------------------
-// device tables of one subset of ctx->h_inst (which = 0 static / 1 edited) for build_bvh / refit_bvh
-static int upload_subset(gsp_context* ctx, int which, BuildInput& bi) {
-  const std::vector<uint32_t>& idx = ctx->sub_index[which];
-  const uint32_t ni = (uint32_t)idx.size();
-  std::vector<gsp_instance> inst(ni);
-  std::vector<float> inv_t(16ull * ni);
-  std::vector<uint32_t> first(ni + 1ull), idfirst(ni + 1ull);
-  std::vector<uint32_t> scene_first(ctx->h_inst.size() + 1ull);
-  uint32_t acc = 0;
-  for (size_t i = 0; i < ctx->h_inst.size(); ++i) scene_first[i] = acc, acc += ctx->h_inst[i].vertex_count / 3;
-  acc = 0;
-  for (uint32_t k = 0; k < ni; ++k) {
-    inst[k] = ctx->h_inst[idx[k]];
-    float tr[16];
-    transpose4(inst[k].transform, tr);
-    inverse4(tr, &inv_t[16ull * k]);
-    first[k] = acc;
-    idfirst[k] = scene_first[idx[k]];
-    acc += inst[k].vertex_count / 3;
-  }
-  first[ni] = acc;
-  idfirst[ni] = 0;
+// The second half of make_split: the small tree D is built and owns its arrays; the new layout [static tree | ring of D] is
+// allocated, filled and swapped in.  *made = false (and nothing changed; D is still the caller's) when there is no room for it.
+static int lay_out_split(gsp_context* ctx, DeviceBvh& D, bool* made) {
+  DeviceBvh& S = ctx->bvh;
   hipStream_t st = ctx->stream;
-  CTX_TRY(ctx, ctx->d_inst_sub[which].upload(inst.data(), ni, st, &ctx->bytes));
-  CTX_TRY(ctx, ctx->d_invt_sub[which].upload(inv_t.data(), inv_t.size(), st, &ctx->bytes));
-  CTX_TRY(ctx, ctx->d_first_sub[which].upload(first.data(), first.size(), st, &ctx->bytes));
-  CTX_TRY(ctx, ctx->d_idfirst_sub[which].upload(idfirst.data(), idfirst.size(), st, &ctx->bytes));
-  CTX_TRY(ctx, hipStreamSynchronize(st));  // (the host vectors go out of scope)
-  bi = BuildInput{};
-  bi.instances = ctx->d_inst_sub[which].p;
-  bi.inv_t = ctx->d_invt_sub[which].p;
-  bi.tri_first = ctx->d_first_sub[which].p;
-  bi.tri_id_first = ctx->d_idfirst_sub[which].p;
-  bi.num_instances = ni;
-  bi.positions = ctx->d_pos.p;
-  bi.normals = ctx->d_nrm.p;
-  bi.num_tris = acc;
-  bi.reinsert_rounds = (int)ctx->opt.reinsert_rounds - 1;
-  return GSP_OK;
+  size_t free_b = 0, total_b = 0;
+  CTX_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+  const GeoRingPlan plan = plan_geo_ring(tree_slots(S), S.num_nodes, tree_slots(D), D.num_nodes, ctx->opt.geometry_versions, free_b, kNodeAllocMin / kNodeBytes, kGeoMaxStride, kNodeBytes);
+  if (plan.log2 < 2) return GSP_OK;
+  // ---- the new layout: [static | ring]; the static tree's arrays are copied into it, wherever they were ----
+  TreeArrays next;  // (releases the old arrays on return, once they have been swapped into it)
+  const hipError_t e = next.alloc_zeroed((size_t)plan.total_slots, st);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    ctx->geo_ring_failed = true;
+    return GSP_OK;  // (nothing has changed: the scene stays one tree)
+  }
+  CTX_TRY(ctx, e);
+  CTX_TRY(ctx, next.copy_tree_in(0, S, st));
+  CTX_TRY(ctx, next.copy_tree_in((size_t)plan.stride_static, D, st));
+  {  // the edited instances' triangles leave the static tree
+    const InstanceTables scene = instance_tables(ctx->h_inst);
+    CTX_TRY(ctx, ctx->d_first.upload(scene.tri_first.data(), scene.tri_first.size(), st, &ctx->bytes));
+    CTX_TRY(ctx, ctx->d_retired.upload(ctx->inst_dynamic.data(), ctx->inst_dynamic.size(), st, &ctx->bytes));
+    hipLaunchKernelGGL(k_retire_triangles, dim3((uint32_t)((S.num_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, S.num_tris, S.first_slot,
+                       (const uint32_t*)S.slot_to_global, (const uint32_t*)ctx->d_first.p, (uint32_t)ctx->h_inst.size(),
+                       (const uint8_t*)ctx->d_retired.p, next.isect.p);
+    CTX_TRY(ctx, hipGetLastError());
+    CTX_TRY(ctx, hipStreamSynchronize(st));  // (`scene` goes out of scope)
+  }
+  // ---- swap the new arrays in ----
+  if (ctx->split) drop_edited_tree(ctx);               // a re-split: the old edited tree goes
+  if (!S.arrays_external) release_own_arrays(ctx, S);  // the first split: the tree owned its arrays
+  ctx->bytes.sub(ctx->ring.bytes());
+  ctx->ring.swap(next);
+  ctx->bytes.add(ctx->ring.bytes());
+  ctx->ring.point(S, 0);
+  ctx->bytes.add(D.bytes);  // the small tree becomes the context's: its arrays are a slot of the ring, the rest stays its own
+  release_own_arrays(ctx, D);
+  ctx->ring.point(D, (size_t)plan.stride_static);
+  ctx->dyn = std::move(D);
+  ctx->split = true;
+  ctx->static_slots = (uint32_t)plan.stride_static;
+  ctx->geo.reset();
+  ctx->geo.stride = (uint32_t)plan.stride_ring;
+  ctx->geo.log2 = (uint32_t)plan.log2;
+  ctx->s2g_all_valid = false;  // (gsp_trace makes it when it needs it)
+  *made = true;
+  return ctx->ensure_spill();
 }
-
 // Makes (or re-makes, when an edit touches an instance not edited before) the two trees of a split scene and lays them out:
 // [static tree | ring of the edited instances' tree].  The static tree IS the tree of the whole scene as it stands, minus the
 // triangles of the edited instances (k_retire_triangles: their slots become all-zero triangles; the boxes above them keep what
@@ -281,10 +340,13 @@ static int upload_subset(gsp_context* ctx, int which, BuildInput& bi) {
 // at least four versions.
 static int make_split(gsp_context* ctx, bool* made) {
   *made = false;
-  if (ctx->num_textures != 0 || ctx->opt.refit_growth <= 1.0 || ctx->opt.geometry_versions < 4 || ctx->geo_ring_failed) return GSP_OK;
+  // split_declined is passed as false: make_split has never looked at it, and it CAN be set on entry -- a re-split that is
+  // declined sets it while the scene is still split, and if the drain that follows fails, the next edit of that split scene asks
+  // again (edit_wants_split: is_split).  The callers' gate is edit_wants_split; a host that keeps touching new objects stops at
+  // kMaxSceneSplits (a wait per edit is no bargain).
+  if (!may_split(false, (uint32_t)ctx->stats.scene_splits, ctx->opt.refit_growth, ctx->opt.geometry_versions, ctx->num_textures, ctx->geo_ring_failed)) return GSP_OK;
   if (ctx->geo.stride != 0 && !ctx->split) return GSP_OK;  // (the scene lives in a ring of whole trees already)
-  if (ctx->stats.scene_splits >= kMaxSceneSplits) return GSP_OK;  // a host that keeps touching new objects: a wait per edit is no bargain
-  DeviceBvh& S = ctx->bvh;
+  const DeviceBvh& S = ctx->bvh;
   if (!S.nodes || S.num_tris != ctx->total_tris || ctx->total_tris == 0) return GSP_OK;  // (the tree of the WHOLE scene: first split or a re-split)
   uint64_t tris[2] = {0, 0};
   ctx->sub_index[0].clear();
@@ -295,145 +357,33 @@ static int make_split(gsp_context* ctx, bool* made) {
     tris[w] += ctx->h_inst[i].vertex_count / 3;
   }
   if (!split_worthwhile(tris[0], tris[1])) return GSP_OK;
-  hipStream_t st = ctx->stream;
-  // ---- the edited instances' tree ----
+  // ---- the edited instances' tree: this function's until lay_out_split has moved it into ctx->dyn ----
   BuildInput bi;
   DeviceBvh D;
   int rc = upload_subset(ctx, 1, bi);
-  if (rc == GSP_OK) rc = build_bvh(st, bi, D, ctx->err);
-  if (rc != GSP_OK) {
-    (void)hipStreamSynchronize(st);
+  if (rc == GSP_OK) rc = build_bvh(ctx->stream, bi, D, ctx->err);
+  if (rc == GSP_OK) rc = lay_out_split(ctx, D, made);
+  if (!*made) {
+    if (rc != GSP_OK) (void)hipStreamSynchronize(ctx->stream);
     free_bvh(D);
-    return rc;
   }
-  struct Guard {  // (an early return below gives the small tree back)
-    DeviceBvh* d;
-    ~Guard() {
-      if (d) free_bvh(*d);
-    }
-  } guard{&D};
-  CTX_TRY(ctx, hipStreamSynchronize(st));
-  const uint64_t slots_s = (uint64_t)S.num_tris + S.first_slot + (kWide - 1), slots_d = (uint64_t)D.num_tris + D.first_slot + (kWide - 1);
-  size_t free_b = 0, total_b = 0;
-  CTX_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-  const GeoRingPlan plan = plan_geo_ring(slots_s, S.num_nodes, slots_d, D.num_nodes, ctx->opt.geometry_versions, free_b, kNodeAllocMin / kNodeBytes, kGeoMaxStride, kNodeBytes);
-  if (plan.log2 < 2) return GSP_OK;
-  const uint64_t stride_s = plan.stride_static, stride_d = plan.stride_ring;
-  const uint32_t lg = (uint32_t)plan.log2;
-  auto total_slots = [&](uint32_t l) { return stride_s + (stride_d << l); };
-  // ---- the new layout: [static | ring]; the static tree's arrays are copied into it, wherever they were ----
-  const size_t total = (size_t)total_slots(lg);
-  DevBuf<q4> nn, ni, ns;
-  if (nn.ensure(total * kNodeQuads, nullptr) != hipSuccess || ni.ensure(total * 3, nullptr) != hipSuccess || ns.ensure(total * 4, nullptr) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->geo_ring_failed = true;
-    return GSP_OK;  // (nothing has changed: the scene stays one tree)
-  }
-  CTX_TRY(ctx, hipMemsetAsync(nn.p, 0, total * kNodeQuads * sizeof(q4), st));
-  CTX_TRY(ctx, hipMemsetAsync(ni.p, 0, total * 3 * sizeof(q4), st));
-  CTX_TRY(ctx, hipMemsetAsync(ns.p, 0, total * 4 * sizeof(q4), st));
-  CTX_TRY(ctx, hipMemcpyAsync(nn.p, S.nodes, (size_t)S.num_nodes * kNodeBytes, hipMemcpyDeviceToDevice, st));
-  CTX_TRY(ctx, hipMemcpyAsync(ni.p, S.tri_isect, slots_s * 3 * sizeof(q4), hipMemcpyDeviceToDevice, st));
-  CTX_TRY(ctx, hipMemcpyAsync(ns.p, S.tri_shade, slots_s * 4 * sizeof(q4), hipMemcpyDeviceToDevice, st));
-  CTX_TRY(ctx, hipMemcpyAsync(nn.p + stride_s * kNodeQuads, D.nodes, (size_t)D.num_nodes * kNodeBytes, hipMemcpyDeviceToDevice, st));
-  CTX_TRY(ctx, hipMemcpyAsync(ni.p + stride_s * 3, D.tri_isect, slots_d * 3 * sizeof(q4), hipMemcpyDeviceToDevice, st));
-  CTX_TRY(ctx, hipMemcpyAsync(ns.p + stride_s * 4, D.tri_shade, slots_d * 4 * sizeof(q4), hipMemcpyDeviceToDevice, st));
-  // the edited instances' triangles leave the static tree
-  {
-    std::vector<uint32_t> first(ctx->h_inst.size() + 1ull);
-    uint32_t acc = 0;
-    for (size_t i = 0; i < ctx->h_inst.size(); ++i) first[i] = acc, acc += ctx->h_inst[i].vertex_count / 3;
-    first[ctx->h_inst.size()] = acc;
-    CTX_TRY(ctx, ctx->d_first.upload(first.data(), first.size(), st, &ctx->bytes));
-    CTX_TRY(ctx, ctx->d_retired.upload(ctx->inst_dynamic.data(), ctx->inst_dynamic.size(), st, &ctx->bytes));
-    hipLaunchKernelGGL(k_retire_triangles, dim3((uint32_t)((S.num_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, S.num_tris, S.first_slot,
-                       (const uint32_t*)S.slot_to_global, (const uint32_t*)ctx->d_first.p, (uint32_t)ctx->h_inst.size(),
-                       (const uint8_t*)ctx->d_retired.p, ni.p);
-    CTX_TRY(ctx, hipGetLastError());
-  }
-  CTX_TRY(ctx, hipStreamSynchronize(st));
-  // ---- swap the new arrays in ----
-  if (ctx->split) {  // a re-split: the old edited tree goes
-    ctx->dyn.nodes = ctx->dyn.tri_isect = ctx->dyn.tri_shade = nullptr;
-    ctx->dyn.arrays_external = false;
-    ctx->bytes -= std::min(ctx->bytes, ctx->dyn.bytes);
-    free_bvh(ctx->dyn);
-  }
-  if (!S.arrays_external) {  // the first split: the tree owned its arrays
-    const size_t freed = (size_t)S.num_nodes * kNodeBytes + slots_s * 7 * sizeof(q4);
-    (void)hipFree(S.nodes);
-    (void)hipFree(S.tri_isect);
-    (void)hipFree(S.tri_shade);
-    S.bytes -= std::min(S.bytes, freed);
-    ctx->bytes -= std::min(ctx->bytes, freed);
-  }
-  for (DevBuf<q4>* old : {&ctx->ring_nodes, &ctx->ring_isect, &ctx->ring_shade})
-    if (old->p) ctx->bytes -= std::min(ctx->bytes, old->count * sizeof(q4));
-  std::swap(ctx->ring_nodes.p, nn.p), std::swap(ctx->ring_nodes.count, nn.count);  // (nn, ni, ns release the old arrays on return)
-  std::swap(ctx->ring_isect.p, ni.p), std::swap(ctx->ring_isect.count, ni.count);
-  std::swap(ctx->ring_shade.p, ns.p), std::swap(ctx->ring_shade.count, ns.count);
-  ctx->bytes += (ctx->ring_nodes.count + ctx->ring_isect.count + ctx->ring_shade.count) * sizeof(q4);
-  S.nodes = ctx->ring_nodes.p;
-  S.tri_isect = ctx->ring_isect.p;
-  S.tri_shade = ctx->ring_shade.p;
-  S.arrays_external = true;
-  {
-    const size_t freed = (size_t)D.num_nodes * kNodeBytes + slots_d * 7 * sizeof(q4);
-    (void)hipFree(D.nodes);
-    (void)hipFree(D.tri_isect);
-    (void)hipFree(D.tri_shade);
-    D.bytes -= std::min(D.bytes, freed);
-    D.nodes = ctx->ring_nodes.p + stride_s * kNodeQuads;
-    D.tri_isect = ctx->ring_isect.p + stride_s * 3;
-    D.tri_shade = ctx->ring_shade.p + stride_s * 4;
-    D.arrays_external = true;
-    ctx->bytes += D.bytes;
-  }
-  ctx->dyn = std::move(D);
-  guard.d = nullptr;
-  ctx->split = true;
-  ctx->static_slots = (uint32_t)stride_s;
-  ctx->geo.stride = (uint32_t)stride_d;
-  ctx->geo.log2 = lg;
-  ctx->geo.ver = 0;
-  ctx->geo.base = 0;
-  ctx->s2g_all_valid = false;  // (gsp_trace makes it when it needs it)
-  *made = true;
-  return ctx->ensure_spill();
+  return rc;
 }
 
 // slot counted through both trees -> scene triangle index, for gsp_trace on a split scene (made on first use)
 static int make_split_s2g(gsp_context* ctx) {
   hipStream_t st = ctx->stream;
   std::vector<uint32_t> all((size_t)ctx->static_slots + ctx->geo.stride, 0xffffffffu);
-  {  // the static tree is the tree of the whole scene: its slots name scene triangles already
-    const uint64_t nslots = (uint64_t)ctx->bvh.num_tris + ctx->bvh.first_slot + (kWide - 1);
-    CTX_TRY(ctx, hipMemcpyAsync(all.data(), ctx->bvh.slot_to_global, nslots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CTX_TRY(ctx, hipStreamSynchronize(st));
-  }
+  // the static tree is the tree of the whole scene: its slots name scene triangles already
+  CTX_TRY(ctx, hipMemcpyAsync(all.data(), ctx->bvh.slot_to_global, tree_slots(ctx->bvh) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CTX_TRY(ctx, hipStreamSynchronize(st));
   {  // the edited instances' tree counts the triangles of ITS instance list
     const DeviceBvh& D = ctx->dyn;
-    const uint64_t nslots = (uint64_t)D.num_tris + D.first_slot + (kWide - 1);
-    std::vector<uint32_t> s2g(nslots);
-    CTX_TRY(ctx, hipMemcpyAsync(s2g.data(), D.slot_to_global, nslots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> s2g(tree_slots(D));
+    CTX_TRY(ctx, hipMemcpyAsync(s2g.data(), D.slot_to_global, s2g.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     CTX_TRY(ctx, hipStreamSynchronize(st));
-    std::vector<uint32_t> scene_first(ctx->h_inst.size() + 1ull);
-    uint32_t acc = 0;
-    for (size_t i = 0; i < ctx->h_inst.size(); ++i) scene_first[i] = acc, acc += ctx->h_inst[i].vertex_count / 3;
-    const std::vector<uint32_t>& idx = ctx->sub_index[1];
-    std::vector<uint32_t> first(idx.size() + 1), idfirst(idx.size());
-    acc = 0;
-    for (size_t k = 0; k < idx.size(); ++k) {
-      first[k] = acc;
-      idfirst[k] = scene_first[idx[k]];
-      acc += ctx->h_inst[idx[k]].vertex_count / 3;
-    }
-    first[idx.size()] = acc;
-    for (uint64_t sl = D.first_slot; sl < (uint64_t)D.first_slot + D.num_tris; ++sl) {
-      const uint32_t lt = s2g[sl];
-      const size_t k = (size_t)(std::upper_bound(first.begin(), first.end(), lt) - first.begin()) - 1;
-      all[(size_t)ctx->static_slots + sl] = idfirst[k] + (lt - first[k]);
-    }
+    const InstanceTables t = instance_tables(ctx->h_inst, &ctx->sub_index[1]);
+    for (uint64_t sl = D.first_slot; sl < (uint64_t)D.first_slot + D.num_tris; ++sl) all[(size_t)ctx->static_slots + sl] = scene_triangle_of(t, s2g[sl]);
   }
   CTX_TRY(ctx, ctx->s2g_all.upload(all.data(), all.size(), st, &ctx->bytes));
   CTX_TRY(ctx, hipStreamSynchronize(st));
@@ -441,128 +391,62 @@ static int make_split_s2g(gsp_context* ctx) {
   return GSP_OK;
 }
 
-// the edited instances' tree := its slot of version v
-static void point_dyn_at(gsp_context* ctx, uint32_t v) {
-  const size_t off = (size_t)ctx->static_slots + (size_t)ctx->geo.phys(v) * ctx->geo.stride;
-  ctx->dyn.nodes = ctx->ring_nodes.p + off * kNodeQuads;
-  ctx->dyn.tri_isect = ctx->ring_isect.p + off * 3;
-  ctx->dyn.tri_shade = ctx->ring_shade.p + off * 4;
-}
-
-// instance table (ctx->h_inst) -> device, transformInvT per instance, world-space bake + BVH build from the RESIDENT vertex
-// arrays, per-slot uv gather of a textured scene, traversal spill region
-// refit == true (gsp_update_instances): keep the tree's topology if its boxes stay within gsp_ctx_options.refit_growth of what
-// they were after the last full build; *refitted says which of the two happened
-static int bake_and_build(gsp_context* ctx, bool refit = false, bool* refitted = nullptr) {
+// A new tree of the whole scene from the instance tables of `bi` (upload_scene_instances): world-space bake + BVH build from the
+// RESIDENT vertex arrays, per-slot uv gather of a textured scene, traversal spill region
+static int build_whole_tree(gsp_context* ctx, const BuildInput& bi) {
   hipStream_t st = ctx->stream;
-  const uint32_t ni = (uint32_t)ctx->h_inst.size();
-  if (refitted) *refitted = false;
-  // ---- PathTracer::prepareScene (PathTracer.cpp:58-93): per-instance table ----
-  std::vector<float> inv_t(16ull * ni);
-  std::vector<uint32_t> tri_first(ni + 1ull);
-  uint32_t acc = 0;
-  for (uint32_t i = 0; i < ni; ++i) {
-    const gsp_instance& in = ctx->h_inst[i];
-    float tr[16];
-    transpose4(in.transform, tr);
-    inverse4(tr, &inv_t[16ull * i]);
-    tri_first[i] = acc;
-    acc += in.vertex_count / 3;
-  }
-  tri_first[ni] = acc;
-  CTX_TRY(ctx, ctx->d_inst.upload(ctx->h_inst.data(), ni, st, &ctx->bytes));
-  CTX_TRY(ctx, ctx->d_invt.upload(inv_t.data(), inv_t.size(), st, &ctx->bytes));
-  CTX_TRY(ctx, ctx->d_first.upload(tri_first.data(), tri_first.size(), st, &ctx->bytes));
-  BuildInput bi;
-  bi.instances = ctx->d_inst.p;
-  bi.inv_t = ctx->d_invt.p;
-  bi.tri_first = ctx->d_first.p;
-  bi.num_instances = ni;
-  bi.positions = ctx->d_pos.p;
-  bi.normals = ctx->d_nrm.p;
-  bi.num_tris = (uint32_t)ctx->total_tris;
-  bi.reinsert_rounds = (int)ctx->opt.reinsert_rounds - 1;
-  if (refit && !ctx->split && ctx->opt.refit_growth > 1.0 && ctx->bvh.nodes && ctx->bvh.num_tris == bi.num_tris && bi.num_tris > 0) {  // (a split scene goes back to one tree by a build)
-    double growth = 0.0;
-    const size_t held = ctx->bvh.bytes;
-    int rc = refit_bvh(st, bi, ctx->bvh, &growth, ctx->err);  // (synchronises the stream)
-    ctx->bytes += ctx->bvh.bytes - held;                      // (the first refit of a tree allocates its scratch)
-    if (rc != GSP_OK) {
-      (void)hipStreamSynchronize(st);
-      return rc;
-    }
-    if (growth <= ctx->opt.refit_growth) {  // (per-slot uv of a textured scene: the slot order has not changed)
-      if (refitted) *refitted = true;
-      return GSP_OK;
-    }
-  }
   // a new tree: its arrays are its own again, and whatever is in flight ends on the old ones first (the committed version's:
   // a refit into the next slot of the ring that grew too much is abandoned here)
-  if (ctx->geo.stride && !ctx->split) point_bvh_at(ctx, ctx->geo.ver);
-  if (ctx->pipe_active) {
-    ++ctx->stats.scene_drains;
-    int rc_ = pipeline_drain(ctx);
-    if (rc_ != GSP_OK) return rc_;
-  }
+  if (ctx->geo.stride && !ctx->split) point_tree_at(ctx, ctx->bvh, ctx->geo.ver);
+  int rc = drain_for_edit(ctx);
+  if (rc != GSP_OK) return rc;
   drop_geo_ring(ctx);
-  ctx->bytes -= ctx->bvh.bytes;
-  if (ctx->node_hist.p) ctx->bytes -= (ctx->node_hist.count + ctx->tri_hist.count) * sizeof(uint32_t);
+  ctx->bytes.sub(ctx->bvh.bytes);
+  ctx->bytes.sub((ctx->node_hist.count + ctx->tri_hist.count) * sizeof(uint32_t));
   ctx->node_hist.release();
   ctx->tri_hist.release();
-  int rc = build_bvh(st, bi, ctx->bvh, ctx->err);  // (synchronises the stream: inv_t / tri_first may go out of scope)
+  rc = build_bvh(st, bi, ctx->bvh, ctx->err);  // (synchronises the stream)
   if (rc != GSP_OK) {
-    (void)hipStreamSynchronize(st);  // ... also on a failed build: the uploads above read host vectors of this frame
+    (void)hipStreamSynchronize(st);  // ... also on a failed build: the uploads before it are queued
     free_bvh(ctx->bvh);              // whatever the failed build had allocated: nothing of it is counted in ctx->bytes (ADVICE r04)
     return rc;
   }
-  ctx->bytes += ctx->bvh.bytes;
+  ctx->bytes.add(ctx->bvh.bytes);
   if (ctx->num_textures) {  // the collapse defines the slot order: the per-slot uv follow it
     CTX_TRY(ctx, ctx->tri_uv.ensure(8ull * (ctx->total_tris + ctx->bvh.first_slot + kWide), &ctx->bytes));
     if (ctx->total_tris) {
       hipLaunchKernelGGL(k_gather_uv, dim3((uint32_t)((ctx->total_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (uint32_t)ctx->total_tris,
-                         ctx->bvh.first_slot, ctx->bvh.slot_to_global, ctx->d_first.p, ni, ctx->d_inst.p, ctx->d_uv.p, ctx->tri_uv.p);
+                         ctx->bvh.first_slot, ctx->bvh.slot_to_global, ctx->d_first.p, bi.num_instances, ctx->d_inst.p, ctx->d_uv.p, ctx->tri_uv.p);
       CTX_TRY(ctx, hipGetLastError());
     }
   }
   CTX_TRY(ctx, hipStreamSynchronize(st));
   return ctx->ensure_spill();
 }
+// instance table (ctx->h_inst) -> device, transformInvT per instance, then the tree of the whole scene
+static int bake_and_build(gsp_context* ctx) {
+  BuildInput bi;
+  int rc = upload_scene_instances(ctx, bi);
+  return rc == GSP_OK ? build_whole_tree(ctx, bi) : rc;
+}
 
-int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
-  if (!ctx || !sc) return GSP_ERR_INVALID;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  {
-    int rc_ = pipeline_drain(ctx);
-    if (rc_ != GSP_OK) return rc_;
-  }
-  ctx->have_scene = false;
-  ctx->tp_valid = false;  // (temporal accumulation: a new scene has no history)
-  ctx->tp_xforms.clear();
-  for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
-  ctx->geo_ring_failed = false;
-  ctx->inst_dynamic.clear();
-  ctx->split_declined = false;
-  // ---- validate ----
+// null arrays, instance ranges and handles, the triangle limit, texture / environment-map sizes: before any device work
+static int check_scene(gsp_context* ctx, const gsp_scene_desc* sc, uint64_t* total_tris) {
   if ((sc->num_instances && !sc->instances) || (sc->num_vertices && (!sc->positions || !sc->normals)) ||
       (sc->num_lights && !sc->lights)) {
     ctx->err = "null array with non-zero count";
     return GSP_ERR_SCENE;
   }
-  uint64_t total_tris = 0;
-  {
-    int rc_ = check_instances(ctx, sc->instances, sc->num_instances, sc->num_bsdfs, sc->num_vertices, &total_tris);
-    if (rc_ != GSP_OK) return rc_;
-  }
+  int rc = check_instances(ctx, sc->instances, sc->num_instances, sc->num_bsdfs, sc->num_vertices, total_tris);
+  if (rc != GSP_OK) return rc;
   // the wide tree of n triangles has fewer than n nodes and the traversal's stack entry holds node indices below kMaxNodes
-  // (pt_trace.h): checked here, before any device work
-  if (total_tris >= (uint64_t)kMaxNodes) {
-    ctx->err = "too many triangles: " + std::to_string(total_tris) + " (limit 2^25 - 1 = 33 554 431)";
+  // (pt_trace.h)
+  if (*total_tris >= (uint64_t)kMaxNodes) {
+    ctx->err = "too many triangles: " + std::to_string(*total_tris) + " (limit 2^25 - 1 = 33 554 431)";
     return GSP_ERR_SCENE;
   }
   // dormant-feature extension: textures / environment map
-  const bool want_tex = sc->num_textures != 0;
-  const bool want_env = sc->envmap.texels != nullptr;
-  if (want_tex) {
+  if (sc->num_textures != 0) {
     if (!sc->textures || !sc->texels || (sc->num_vertices && !sc->uvs)) {
       ctx->err = "textures need the textures, texels and uvs arrays";
       return GSP_ERR_SCENE;
@@ -575,29 +459,19 @@ int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
         return GSP_ERR_SCENE;
       }
     }
-    int rc_ = check_texture_words(ctx, sc, sc->num_textures);
-    if (rc_ != GSP_OK) return rc_;
+    rc = check_texture_words(ctx, sc, sc->num_textures);
+    if (rc != GSP_OK) return rc;
   }
-  if (want_env && (sc->envmap.width == 0 || sc->envmap.height == 0 || sc->envmap.width > (1u << 15) || sc->envmap.height > (1u << 15))) {
+  if (sc->envmap.texels && (sc->envmap.width == 0 || sc->envmap.height == 0 || sc->envmap.width > (1u << 15) || sc->envmap.height > (1u << 15))) {
     ctx->err = "environment map: size 0 or above 32768";
     return GSP_ERR_SCENE;
   }
-  auto t0 = std::chrono::steady_clock::now();
+  return GSP_OK;
+}
+// dormant-feature extension: texel arrays, uv, environment map
+static int upload_textures(gsp_context* ctx, const gsp_scene_desc* sc) {
   hipStream_t st = ctx->stream;
-  {
-    TableImage img;
-    int rc_ = pack_tables(ctx, sc, img);
-    if (rc_ == GSP_OK) rc_ = upload_tables(ctx, sc, img);
-    if (rc_ != GSP_OK) return rc_;
-  }
-  ctx->camera = sc->camera;
-  // ---- resident geometry (the "BLAS inputs": object-space vertices; Mesh.cpp:7-51) ----
-  CTX_TRY(ctx, ctx->d_pos.upload(sc->positions, 3ull * sc->num_vertices, st, &ctx->bytes));
-  CTX_TRY(ctx, ctx->d_nrm.upload(sc->normals, 3ull * sc->num_vertices, st, &ctx->bytes));
-  ctx->num_vertices = sc->num_vertices;
-  ctx->total_tris = total_tris;
-  ctx->h_inst.assign(sc->instances, sc->instances + sc->num_instances);
-  // ---- dormant-feature extension: texel arrays, uv, environment map ----
+  const bool want_tex = sc->num_textures != 0, want_env = sc->envmap.texels != nullptr;
   ctx->textured = want_tex || want_env;
   ctx->num_textures = want_tex ? sc->num_textures : 0;
   ctx->env_width = want_env ? sc->envmap.width : 0;
@@ -615,8 +489,40 @@ int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
     CTX_TRY(ctx, ctx->env_texels.upload(sc->envmap.texels, 4ull * sc->envmap.width * sc->envmap.height, st, &ctx->bytes));
     for (int k = 0; k < 16; ++k) ctx->env_to_local[k] = sc->envmap.to_local[k];
   }
-  // ---- bake + device BVH build ----
-  int rc = bake_and_build(ctx);
+  return GSP_OK;
+}
+
+int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
+  if (!ctx || !sc) return GSP_ERR_INVALID;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = pipeline_drain(ctx);
+  if (rc != GSP_OK) return rc;
+  ctx->have_scene = false;
+  ctx->tp_valid = false;  // (temporal accumulation: a new scene has no history)
+  ctx->tp_xforms.clear();
+  invalidate_memos(ctx);
+  ctx->geo_ring_failed = false;
+  ctx->inst_dynamic.clear();
+  ctx->split_declined = false;
+  uint64_t total_tris = 0;
+  rc = check_scene(ctx, sc, &total_tris);
+  if (rc != GSP_OK) return rc;
+  auto t0 = std::chrono::steady_clock::now();
+  {
+    TableImage img;
+    rc = pack_tables(ctx, sc, img);
+    if (rc == GSP_OK) rc = upload_tables(ctx, sc, img);
+    if (rc != GSP_OK) return rc;
+  }
+  ctx->camera = sc->camera;
+  // ---- resident geometry (the "BLAS inputs": object-space vertices; Mesh.cpp:7-51) ----
+  CTX_TRY(ctx, ctx->d_pos.upload(sc->positions, 3ull * sc->num_vertices, ctx->stream, &ctx->bytes));
+  CTX_TRY(ctx, ctx->d_nrm.upload(sc->normals, 3ull * sc->num_vertices, ctx->stream, &ctx->bytes));
+  ctx->num_vertices = sc->num_vertices;
+  ctx->total_tris = total_tris;
+  ctx->h_inst.assign(sc->instances, sc->instances + sc->num_instances);
+  rc = upload_textures(ctx, sc);
+  if (rc == GSP_OK) rc = bake_and_build(ctx);
   if (rc != GSP_OK) return rc;
   ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->stats.scene_updates = 0;
@@ -645,16 +551,173 @@ static int begin_update(gsp_context* ctx, const char* what) {
 // (profiles/r04_update_latency.txt: 500x500, one sample per frame).
 int gsp_update_camera(gsp_context* ctx, const gsp_camera* camera) {
   if (!ctx || !camera) return GSP_ERR_INVALID;
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  if (!ctx->have_scene) {
-    ctx->err = "gsp_update_camera needs gsp_upload_scene first";
-    return GSP_ERR_INVALID;
-  }
+  int rc = begin_update(ctx, "gsp_update_camera");
+  if (rc != GSP_OK) return rc;
   if (std::memcmp(&ctx->camera, camera, sizeof(gsp_camera)) == 0) return GSP_OK;
   ctx->camera = *camera;  // (render_consts reads it at the next gsp_render)
-  for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;  // the memo holds the hits of the OLD camera rays: re-traced
-                                                                 // on the lane's stream before the next batch is generated
+  invalidate_memos(ctx);  // the memo holds the hits of the OLD camera rays
   ++ctx->stats.scene_updates;
+  return GSP_OK;
+}
+
+// ---- gsp_update_instances ---------------------------------------------------------------------------------------------------
+// An edit that changes something is offered to three arms in the order pt_versions.h documents -- (1) refit of the edited tree,
+// (2) split / re-split, (3) the whole tree -- each of which waits for what it must (drain_for_edit), opens the edit (begin_edit),
+// and either commits (*committed = true) or leaves it to the next arm.
+struct InstanceEdit {
+  const gsp_instance* instances;
+  uint32_t n;
+  bool only_edited;  // it touches only instances that already live in the edited instances' tree of a split scene
+  std::chrono::steady_clock::time_point t0;
+  bool changes(const gsp_context* ctx, uint32_t i) const { return std::memcmp(&instances[i], &ctx->h_inst[i], sizeof(gsp_instance)) != 0; }
+};
+// From here until gsp_update_instances commits, the context has no scene (a failed rebuild leaves no half-built tree in use), the
+// memos are stale and the clock of bvh_build_ms runs (the wait before it is not build time).  adopt: the new table becomes h_inst.
+static void begin_edit(gsp_context* ctx, InstanceEdit& e, bool adopt = true) {
+  e.t0 = std::chrono::steady_clock::now();
+  ctx->have_scene = false;
+  invalidate_memos(ctx);
+  if (adopt) ctx->h_inst.assign(e.instances, e.instances + e.n);
+}
+
+// Refit tree T (the edited instances' tree of a split scene, or the whole tree) to the instance tables of `bi` as version v.
+// v == geo.ver: in place (nothing in flight reads it).  v == geo.ver + 1: into the next slot of the ring -- the topology (child
+// links, triangle ranges) of the current version is copied there and refit_bvh rewrites every box and packet.  T points at v
+// afterwards: the CALLER commits (geo.ver = v) or, when *growth says the tree has degraded, points T back.  On failure T points
+// at the committed version again.
+static int refit_tree_into(gsp_context* ctx, DeviceBvh& T, const BuildInput& bi, uint32_t v, double* growth) {
+  hipStream_t st = ctx->stream;
+  hipError_t e = hipSuccess;
+  if (v != ctx->geo.ver) {
+    const q4* from = T.nodes;
+    point_tree_at(ctx, T, v);
+    e = hipMemcpyAsync(T.nodes, from, (size_t)T.num_nodes * kNodeBytes, hipMemcpyDeviceToDevice, st);
+  }
+  int rc = GSP_ERR_DEVICE;
+  if (e == hipSuccess) {
+    const size_t held = T.bytes;
+    rc = refit_bvh(st, bi, T, growth, ctx->err);  // (synchronises the stream)
+    ctx->bytes.add(T.bytes - held);               // (the first refit of a tree allocates its scratch)
+  }
+  if (rc != GSP_OK) {
+    (void)hipStreamSynchronize(st);
+    if (v != ctx->geo.ver) point_tree_at(ctx, T, ctx->geo.ver);
+    if (e != hipSuccess) CTX_TRY(ctx, e);
+  }
+  return rc;
+}
+
+// (1) r05, split scene.  The host that edits while samples are in flight (a viewer) usually moves a few objects of many: the first
+// such edit -- and every later one that touches an instance not edited before -- builds TWO trees, one over the instances that
+// have never changed and one over the edited ones (make_split: behind a drain, two builds); from then on an edit of those
+// instances refits the small tree only, into the next slot of its ring, and the versions in flight share the large one.
+static int refit_edited_tree(gsp_context* ctx, InstanceEdit& e, bool* committed) {
+  if (!ctx->split || !e.only_edited) return GSP_OK;
+  const bool in_slot = edited_tree_refit_needs_no_wait(ctx->pipe_active, ctx->caps_allow_versions(), ctx->geo, ctx->oldest_live_geo());
+  int rc = in_slot ? GSP_OK : drain_for_edit(ctx);
+  if (rc != GSP_OK) return rc;
+  begin_edit(ctx, e);
+  BuildInput bi;
+  rc = upload_subset(ctx, 1, bi);
+  if (rc != GSP_OK) return rc;
+  double growth = 0.0;
+  rc = refit_tree_into(ctx, ctx->dyn, bi, ctx->geo.ver + (in_slot ? 1 : 0), &growth);
+  if (rc != GSP_OK) return rc;
+  if (growth > ctx->opt.refit_growth) {  // the edited tree has degraded: both trees are built again by (2), behind a drain
+    point_tree_at(ctx, ctx->dyn, ctx->geo.ver);
+    return GSP_OK;
+  }
+  if (in_slot) ++ctx->geo.ver;
+  ++ctx->stats.scene_refits;
+  *committed = true;
+  return GSP_OK;
+}
+
+// (2) the edit asks for a split: a first one, or a re-split because it touches an instance not edited before (or because the
+// edited tree has degraded).
+static int split_scene(gsp_context* ctx, InstanceEdit& e, bool* committed) {
+  if (!edit_wants_split(ctx->split, ctx->split_declined, ctx->pipe_active, ctx->opt.refit_growth, ctx->opt.geometry_versions, ctx->num_textures)) return GSP_OK;
+  // The FIRST split needs no wait: the edited instances' tree is built where they WERE (version 0: with the static tree it is,
+  // triangle for triangle, the scene the samples in flight were generated under -- they carry stamp 0 -- and the hit records
+  // the memo has handed out name slots of the static tree whose shading packets stay), and the edit itself is version 1, a
+  // refit into the next slot like every later one.  Nothing is queued between two gsp_render calls, so the arrays can change hands.
+  const bool no_wait = first_split_needs_no_wait(ctx->split, ctx->pipe_active, ctx->caps_allow_versions(), ctx->geo);
+  int rc = no_wait ? GSP_OK : drain_for_edit(ctx);
+  if (rc != GSP_OK) return rc;
+  // (the instances count as edited from the edit that is OFFERED a split: one that arrives with nothing in flight on a scene in
+  // one tree goes to (3) and marks nothing)
+  for (uint32_t i = 0; i < e.n; ++i)
+    if (e.changes(ctx, i)) ctx->inst_dynamic[i] = 1;
+  begin_edit(ctx, e, !no_wait);
+  bool made = false;
+  rc = make_split(ctx, &made);
+  if (rc != GSP_OK && rc != GSP_ERR_NOMEM) return rc;
+  if (made && no_wait) {
+    ctx->h_inst.assign(e.instances, e.instances + e.n);
+    BuildInput bi;
+    rc = upload_subset(ctx, 1, bi);
+    if (rc != GSP_OK) return rc;
+    double growth = 0.0;
+    rc = refit_tree_into(ctx, ctx->dyn, bi, 1, &growth);
+    if (rc != GSP_OK) return rc;
+    if (growth <= ctx->opt.refit_growth) {
+      ctx->geo.ver = 1;
+    } else {  // the object has moved far in one step: the small tree is built where it IS, behind a wait after all
+      point_tree_at(ctx, ctx->dyn, 0);
+      rc = drain_for_edit(ctx);
+      if (rc != GSP_OK) return rc;
+      rc = make_split(ctx, &made);
+      if (rc != GSP_OK && rc != GSP_ERR_NOMEM) return rc;
+    }
+  }
+  if (!made) {
+    // no split to be had (too much of the scene is being edited, textures, no memory): the scene stays / becomes ONE tree with the
+    // ring of whole trees -- (3), with the pipeline idle now -- and the question is not asked again for this scene
+    ctx->split_declined = true;
+    ctx->have_scene = true;
+    return GSP_OK;
+  }
+  ++ctx->stats.scene_splits;
+  *committed = true;
+  return GSP_OK;
+}
+
+// (3) the whole tree.  r05: NO DRAIN when the tree has its geometry ring and a slot of it is free: the refit -- re-bake of every
+// packet, node boxes bottom-up in the existing topology -- goes into the NEXT slot, on the context's stream, while the lanes'
+// streams finish the samples in flight in the slots they were generated under (a path carries its slot in its flags word,
+// pt_stages.h); the next gsp_render stamps its samples with the new one.  Otherwise -- first edit of this tree (the ring is made
+// then), as many edits as the ring has slots within the life of one sample, a tree that degrades and is rebuilt -- the queued
+// samples finish first, as until r04.  The tree keeps its topology if its boxes stay within gsp_ctx_options.refit_growth of what
+// they were after the last full build (a split scene goes back to one tree by a build).
+static int edit_whole_tree(gsp_context* ctx, InstanceEdit& e, bool* committed) {
+  const bool in_ring = whole_tree_refit_needs_no_wait(ctx->pipe_active, ctx->caps_allow_versions(), ctx->opt.refit_growth, ctx->geo, ctx->oldest_live_geo());
+  int rc = in_ring ? GSP_OK : drain_for_edit(ctx);
+  if (rc != GSP_OK) return rc;
+  // (the ring of WHOLE trees only where a split scene is not to be had: an edit that arrives with nothing in flight refits in
+  // place, and the first one that arrives with samples in flight asks for the split first, (2))
+  if (!in_ring && ctx->opt.refit_growth > 1.0 && !scene_may_still_split(ctx->split_declined, ctx->opt.geometry_versions, ctx->num_textures)) {
+    rc = make_geo_ring(ctx);
+    if (rc != GSP_OK) return rc;
+  }
+  begin_edit(ctx, e);
+  BuildInput bi;
+  rc = upload_scene_instances(ctx, bi);
+  if (rc != GSP_OK) return rc;
+  bool refitted = false;
+  if (!ctx->split && ctx->opt.refit_growth > 1.0 && ctx->bvh.nodes && ctx->bvh.num_tris == bi.num_tris && bi.num_tris > 0) {
+    double growth = 0.0;
+    rc = refit_tree_into(ctx, ctx->bvh, bi, ctx->geo.ver + (in_ring ? 1 : 0), &growth);
+    if (rc != GSP_OK) return rc;
+    refitted = growth <= ctx->opt.refit_growth;  // (per-slot uv of a textured scene: the slot order has not changed)
+  }
+  if (refitted) {
+    if (in_ring) ++ctx->geo.ver;
+    ++ctx->stats.scene_refits;
+  } else {  // (the tree is rebuilt behind a drain and owns its arrays again)
+    rc = build_whole_tree(ctx, bi);
+    if (rc != GSP_OK) return rc;
+  }
+  *committed = true;
   return GSP_OK;
 }
 
@@ -676,154 +739,18 @@ int gsp_update_instances(gsp_context* ctx, const gsp_instance* instances, uint32
   if (rc != GSP_OK) return rc;
   if (num_instances == 0 || std::memcmp(ctx->h_inst.data(), instances, num_instances * sizeof(gsp_instance)) == 0) return GSP_OK;
   ++ctx->inst_edits;  // (gsp_temporal_follow_instances: the frame's features belong to the transforms before this edit)
-  // r05, split scene.  The host that edits while samples are in flight (a viewer) usually moves a few objects of many: the first
-  // such edit -- and every later one that touches an instance not edited before -- builds TWO trees, one over the instances that
-  // have never changed and one over the edited ones (make_split: behind a drain, two builds); from then on an edit of those
-  // instances refits the small tree only, into the next slot of its ring, and the versions in flight share the large one.
   if (ctx->inst_dynamic.size() != num_instances) ctx->inst_dynamic.assign(num_instances, 0);
-  bool only_edited = ctx->split;
+  InstanceEdit e{instances, num_instances, ctx->split, {}};
   for (uint32_t i = 0; i < num_instances; ++i)
-    if (std::memcmp(&instances[i], &ctx->h_inst[i], sizeof(gsp_instance)) != 0 && !ctx->inst_dynamic[i]) only_edited = false;
-  if (ctx->split && only_edited) {
-    const bool in_slot = edited_tree_refit_needs_no_wait(ctx->pipe_active, ctx->caps_allow_versions(), ctx->geo, ctx->oldest_live_geo());
-    if (!in_slot && ctx->pipe_active) {
-      ++ctx->stats.scene_drains;
-      rc = pipeline_drain(ctx);
-      if (rc != GSP_OK) return rc;
-    }
-    auto t0 = std::chrono::steady_clock::now();
-    ctx->have_scene = false;
-    for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
-    ctx->h_inst.assign(instances, instances + num_instances);
-    BuildInput bi;
-    rc = upload_subset(ctx, 1, bi);
-    if (rc != GSP_OK) return rc;
-    if (in_slot) {
-      const q4* from = ctx->dyn.nodes;
-      point_dyn_at(ctx, ctx->geo.ver + 1);
-      CTX_TRY(ctx, hipMemcpyAsync(ctx->dyn.nodes, from, (size_t)ctx->dyn.num_nodes * kNodeBytes, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    double growth = 0.0;
-    const size_t held = ctx->dyn.bytes;
-    rc = refit_bvh(ctx->stream, bi, ctx->dyn, &growth, ctx->err);
-    ctx->bytes += ctx->dyn.bytes - held;
-    if (rc != GSP_OK) {
-      (void)hipStreamSynchronize(ctx->stream);
-      point_dyn_at(ctx, ctx->geo.ver);
-      return rc;
-    }
-    if (growth <= ctx->opt.refit_growth) {
-      if (in_slot) ++ctx->geo.ver;
-      ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      ctx->have_scene = true;
-      ++ctx->stats.scene_updates;
-      ++ctx->stats.scene_refits;
-      return GSP_OK;
-    }
-    // the edited tree has degraded: both trees are built again (below), behind a drain
-    point_dyn_at(ctx, ctx->geo.ver);
-  }
-  if (edit_wants_split(ctx->split, ctx->split_declined, ctx->pipe_active, ctx->opt.refit_growth, ctx->opt.geometry_versions, ctx->num_textures)) {
-    // The FIRST split needs no wait: the edited instances' tree is built where they WERE (version 0: with the static tree it is,
-    // triangle for triangle, the scene the samples in flight were generated under -- they carry stamp 0 -- and the hit records
-    // the memo has handed out name slots of the static tree whose shading packets stay), and the edit itself is version 1, a
-    // refit into the next slot like every later one.  Nothing is queued between two gsp_render calls, so the arrays can change hands.
-    const bool no_wait = first_split_needs_no_wait(ctx->split, ctx->pipe_active, ctx->caps_allow_versions(), ctx->geo);
-    if (ctx->pipe_active && !no_wait) {
-      ++ctx->stats.scene_drains;
-      rc = pipeline_drain(ctx);
-      if (rc != GSP_OK) return rc;
-    }
-    auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t i = 0; i < num_instances; ++i)
-      if (std::memcmp(&instances[i], &ctx->h_inst[i], sizeof(gsp_instance)) != 0) ctx->inst_dynamic[i] = 1;
-    ctx->have_scene = false;
-    for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
-    if (!no_wait) ctx->h_inst.assign(instances, instances + num_instances);
-    bool made = false;
-    rc = make_split(ctx, &made);
-    if (rc != GSP_OK && rc != GSP_ERR_NOMEM) return rc;
-    if (made && no_wait) {
-      ctx->h_inst.assign(instances, instances + num_instances);
-      BuildInput bi;
-      rc = upload_subset(ctx, 1, bi);
-      if (rc != GSP_OK) return rc;
-      const q4* from = ctx->dyn.nodes;
-      point_dyn_at(ctx, 1);
-      CTX_TRY(ctx, hipMemcpyAsync(ctx->dyn.nodes, from, (size_t)ctx->dyn.num_nodes * kNodeBytes, hipMemcpyDeviceToDevice, ctx->stream));
-      double growth = 0.0;
-      const size_t held = ctx->dyn.bytes;
-      rc = refit_bvh(ctx->stream, bi, ctx->dyn, &growth, ctx->err);
-      ctx->bytes += ctx->dyn.bytes - held;
-      if (rc != GSP_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-      }
-      if (growth <= ctx->opt.refit_growth) {
-        ctx->geo.ver = 1;
-      } else {  // the object has moved far in one step: the small tree is built where it IS, behind a wait after all
-        point_dyn_at(ctx, 0);
-        ++ctx->stats.scene_drains;
-        rc = pipeline_drain(ctx);
-        if (rc != GSP_OK) return rc;
-        made = false;
-        rc = make_split(ctx, &made);
-        if (rc != GSP_OK && rc != GSP_ERR_NOMEM) return rc;
-      }
-    }
-    if (made) {
-      ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      ctx->have_scene = true;
-      ++ctx->stats.scene_updates;
-      ++ctx->stats.scene_splits;
-      return GSP_OK;
-    }
-    // no split to be had (too much of the scene is being edited, textures, no memory): the scene stays / becomes ONE tree with the
-    // ring of whole trees -- below, with the pipeline idle now -- and the question is not asked again for this scene
-    ctx->split_declined = true;
-    ctx->have_scene = true;
-    (void)t0;
-  }
-  // r05: NO DRAIN when the tree has its geometry ring and a slot of it is free: the refit -- re-bake of every packet, node boxes
-  // bottom-up in the existing topology -- goes into the NEXT slot, on the context's stream, while the lanes' streams finish the
-  // samples in flight in the slots they were generated under (a path carries its slot in its flags word, pt_stages.h); the next
-  // gsp_render stamps its samples with the new one.  Otherwise -- first edit of this tree (the ring is made then), as many edits
-  // as the ring has slots within the life of one sample, a tree that degrades and is rebuilt -- the queued samples finish first,
-  // as until r04.
-  const bool in_ring = whole_tree_refit_needs_no_wait(ctx->pipe_active, ctx->caps_allow_versions(), ctx->opt.refit_growth, ctx->geo, ctx->oldest_live_geo());
-  if (!in_ring) {
-    if (ctx->pipe_active) ++ctx->stats.scene_drains;
-    rc = pipeline_drain(ctx);
-    if (rc != GSP_OK) return rc;
-    // (the ring of WHOLE trees only where a split scene is not to be had: an edit that arrives with nothing in flight refits in
-    // place, and the first one that arrives with samples in flight asks for the split first, above)
-    const bool may_split = scene_may_still_split(ctx->split_declined, ctx->opt.geometry_versions, ctx->num_textures);
-    if (ctx->opt.refit_growth > 1.0 && !may_split) {
-      rc = make_geo_ring(ctx);
-      if (rc != GSP_OK) return rc;
-    }
-  }
-  auto t0 = std::chrono::steady_clock::now();
-  ctx->have_scene = false;  // (a failed rebuild leaves no half-built tree in use)
-  for (gsp_context::Lane& L : ctx->lanes) L.memo_valid = false;
-  ctx->h_inst.assign(instances, instances + num_instances);
-  bool refitted = false;
-  if (in_ring) {
-    // topology (child links, triangle ranges) of the current version -> next slot; refit_bvh rewrites every box and packet there
-    const q4* from = ctx->bvh.nodes;
-    point_bvh_at(ctx, ctx->geo.ver + 1);
-    CTX_TRY(ctx, hipMemcpyAsync(ctx->bvh.nodes, from, (size_t)ctx->bvh.num_nodes * kNodeBytes, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  rc = bake_and_build(ctx, true, &refitted);
-  if (rc != GSP_OK) {
-    if (ctx->geo.stride) point_bvh_at(ctx, ctx->geo.ver);
-    return rc;
-  }
-  if (in_ring && refitted) ++ctx->geo.ver;  // (not refitted: the tree was rebuilt behind a drain and owns its arrays again)
-  ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (e.changes(ctx, i) && !ctx->inst_dynamic[i]) e.only_edited = false;
+  bool committed = false;
+  rc = refit_edited_tree(ctx, e, &committed);
+  if (rc == GSP_OK && !committed) rc = split_scene(ctx, e, &committed);
+  if (rc == GSP_OK && !committed) rc = edit_whole_tree(ctx, e, &committed);
+  if (rc != GSP_OK) return rc;
+  ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - e.t0).count();
   ctx->have_scene = true;
   ++ctx->stats.scene_updates;
-  if (refitted) ++ctx->stats.scene_refits;
   return GSP_OK;
 }
 
@@ -864,8 +791,7 @@ int gsp_update_tables(gsp_context* ctx, const gsp_scene_desc* sc) {
   }
   const bool in_place = how == TableRing::Update::kInPlace;
   if (!in_place) {
-    if (ctx->pipe_active) ++ctx->stats.scene_drains;
-    rc = pipeline_drain(ctx);
+    rc = drain_for_edit(ctx);
     if (rc != GSP_OK) return rc;
   }
   rc = upload_tables(ctx, sc, img, in_place);  // (k_shade stages the tables per launch: nothing else holds a copy)
@@ -892,8 +818,8 @@ int gsp_frame_begin(gsp_context* ctx, uint32_t width, uint32_t height, const uin
     return GSP_ERR_INVALID;
   }
   ctx->have_frame = false;
+  invalidate_memos(ctx);
   for (gsp_context::Lane& L : ctx->lanes) {
-    L.memo_valid = false;
     L.adaptive = false;  // (the next gsp_render decides whether the new frame is adaptive)
     L.num_active = 0;
   }
@@ -946,4 +872,3 @@ int gsp_frame_begin(gsp_context* ctx, uint32_t width, uint32_t height, const uin
   ctx->have_frame = true;
   return GSP_OK;
 }
-

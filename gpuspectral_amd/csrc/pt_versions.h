@@ -1,8 +1,9 @@
 // pt_versions.h -- the version-ring bookkeeping of the per-frame scene edits (gsp_update_tables / gsp_update_instances without a
-// drain, pt_render.hip), as PURE host logic: no HIP call, no device pointer, no allocation.  pt_render.hip asks these structs
-// which slot to write, whether a wait is needed and how large a ring may be, and performs the copies / launches itself;
+// drain, pt_render_scene.inc), as PURE host logic: no HIP call, no device pointer, no device allocation.  pt_render_scene.inc asks
+// these structs which slot to write, whether a wait is needed and how large a ring may be, and performs the copies / launches itself;
 // tests/emu/versions_model.cpp drives the same structs from a mock pipeline on the CPU (random edit streams under ASan / UBSan:
-// no slot is written while a sample that names it is in flight, the byte ledger never wraps, split / ring limits hold).
+// no slot is written while a sample that names it is in flight, the byte ledger never wraps, split / ring limits hold, the instance
+// tables equal a brute-force count).
 //
 // Behaviour contract (S/renderer/PathTracer.cpp:58-93): the reference re-reads instances, tables and camera every frame, so an
 // edit applies to the samples generated AFTER it; the samples in flight finish on the scene they were generated under.
@@ -10,6 +11,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace gsp {
 
@@ -20,8 +22,9 @@ constexpr uint32_t kMaxGeoVersions = 64;    // = kGeoVersions
 // (include/gpuspectral_pt.h, "Per-frame edits"; gsp_stats.scene_splits)
 constexpr uint32_t kMaxSceneSplits = 16;
 
-// device bytes a context accounts for (gsp_stats.device_bytes): a subtraction never wraps -- an accounting slip shows up as
-// `underflows`, which the model test and the GPU suite assert to be 0
+// device bytes a context accounts for (gsp_stats.device_bytes; gsp_context::bytes and DevBuf's tally are this type): a subtraction
+// never wraps -- an accounting slip clamps at 0 and shows up as `underflows`, which the model test asserts to be 0 (no ABI field
+// carries it)
 struct ByteLedger {
   size_t bytes = 0;
   uint64_t underflows = 0;
@@ -184,6 +187,46 @@ inline bool may_split(bool split_declined, uint32_t splits_so_far, double refit_
 // ... and is the scene one a split pays for: something edited, something not, at most a quarter of the triangles edited
 inline bool split_worthwhile(uint64_t tris_static, uint64_t tris_edited) {
   return tris_edited != 0 && tris_static != 0 && tris_edited * 4 <= tris_static + tris_edited;
+}
+
+
+// ---- instance tables ----------------------------------------------------------------------------------------------------------
+// What build_bvh / refit_bvh need beside the instance records, from the host instance list (anything with a vertex_count) and,
+// for a tree over a SUBSET of the scene's instances, the scene indices of that subset in tree order (nullptr = the whole scene).
+struct InstanceTables {
+  std::vector<uint32_t> tri_first;     // n + 1: prefix of the listed instances' triangle counts
+  std::vector<uint32_t> tri_id_first;  // n + 1: scene-wide index of each listed instance's first triangle; [n] unused: 0 for a
+                                       // subset, the total for the whole scene (where the table IS tri_first)
+  uint32_t total = 0;                  // triangles of the listed instances
+};
+template <class Instance>
+inline InstanceTables instance_tables(const std::vector<Instance>& scene, const std::vector<uint32_t>* subset = nullptr) {
+  std::vector<uint32_t> scene_first(scene.size() + 1);
+  uint32_t acc = 0;
+  for (size_t i = 0; i < scene.size(); ++i) scene_first[i] = acc, acc += scene[i].vertex_count / 3;
+  scene_first[scene.size()] = acc;
+  InstanceTables t;
+  if (!subset) {
+    t.tri_first = scene_first;
+    t.tri_id_first.swap(scene_first);
+    t.total = acc;
+    return t;
+  }
+  const size_t n = subset->size();
+  t.tri_first.resize(n + 1);
+  t.tri_id_first.assign(n + 1, 0);
+  for (size_t k = 0; k < n; ++k) {
+    t.tri_first[k] = t.total;
+    t.tri_id_first[k] = scene_first[(*subset)[k]];
+    t.total += scene[(*subset)[k]].vertex_count / 3;
+  }
+  t.tri_first[n] = t.total;
+  return t;
+}
+// triangle `local` (< total) of the listed instances, counted through the list -> its scene-wide index
+inline uint32_t scene_triangle_of(const InstanceTables& t, uint32_t local) {
+  const size_t k = (size_t)(std::upper_bound(t.tri_first.begin(), t.tri_first.end(), local) - t.tri_first.begin()) - 1;
+  return t.tri_id_first[k] + (local - t.tri_first[k]);
 }
 
 }  // namespace gsp

@@ -1,6 +1,6 @@
 // tests/emu/versions_model.cpp -- TEST HARNESS (CPU only; built by tests/test_versions_model.py with -fsanitize=address,undefined).
 //
-// Drives the product's version-ring bookkeeping (gpuspectral_amd/csrc/pt_versions.h: the structs pt_render.hip itself asks which
+// Drives the product's version-ring bookkeeping (gpuspectral_amd/csrc/pt_versions.h: the structs pt_render_scene.inc itself asks which
 // slot to write and whether to wait) from a MOCK pipeline: random streams of gsp_render / gsp_update_tables /
 // gsp_update_instances / drains, with batches of samples in flight that carry the stamps k_generate would write.  The mock
 // "device memory" remembers which version every ring slot holds; every in-flight batch reads ITS slot on every iteration.
@@ -9,7 +9,8 @@
 //   2. a batch always reads the version it was generated under -- through collapses, ring growth, base changes and wrap-around;
 //   3. the byte ledger never underflows and ends at 0 when everything is released;
 //   4. ring plans respect the 32-bit node offsets, the 2^28 slot limit, the memory share and the stride field;
-//   5. no more than kMaxSceneSplits re-splits; may_split / split_worthwhile say no where the documentation says they do.
+//   5. no more than kMaxSceneSplits re-splits; may_split / split_worthwhile say no where the documentation says they do;
+//   6. instance_tables / scene_triangle_of equal a brute-force walk of random instance lists and subsets.
 // usage: versions_model <seed> <steps>
 #include <cstdio>
 #include <cstdlib>
@@ -267,12 +268,49 @@ static void check_plans(std::mt19937& rng) {
   CHECK(l.bytes == 0 && l.underflows == 1, "ledger clamps and counts");
 }
 
+// instance tables: random instance lists (empty instances included) and random subsets in random order against a brute-force walk
+struct MockInstance {
+  uint32_t vertex_count;
+};
+static void check_instance_tables(std::mt19937& rng) {
+  for (int round = 0; round < 200; ++round) {
+    std::vector<MockInstance> scene(rng() % 12);
+    for (MockInstance& in : scene) in.vertex_count = 3 * (rng() % 4 ? rng() % 9 : 0);
+    std::vector<uint32_t> owner, id;  // brute force: per scene triangle its instance; per listed triangle its scene index
+    for (size_t i = 0; i < scene.size(); ++i) owner.insert(owner.end(), scene[i].vertex_count / 3, (uint32_t)i);
+    const InstanceTables whole = instance_tables(scene);
+    CHECK(whole.total == owner.size() && whole.tri_first.size() == scene.size() + 1 && whole.tri_id_first == whole.tri_first && whole.tri_first.back() == whole.total,
+          "whole scene: total / sizes");
+    for (uint32_t t = 0; t < whole.total; ++t) {
+      CHECK(whole.tri_first[owner[t]] <= t && t < whole.tri_first[owner[t] + 1], "whole scene: triangle %u is not in its instance's range", t);
+      CHECK(scene_triangle_of(whole, t) == t, "whole scene: triangle %u maps to %u", t, scene_triangle_of(whole, t));
+    }
+    std::vector<uint32_t> subset;
+    for (size_t i = 0; i < scene.size(); ++i)
+      if (rng() % 2) subset.insert(subset.begin() + (subset.empty() ? 0 : rng() % (subset.size() + 1)), (uint32_t)i);
+    for (uint32_t i : subset)
+      for (uint32_t t = 0; t < owner.size(); ++t)
+        if (owner[t] == i) id.push_back(t);
+    const InstanceTables sub = instance_tables(scene, &subset);
+    CHECK(sub.total == id.size() && sub.tri_first.size() == subset.size() + 1 && sub.tri_id_first.size() == subset.size() + 1 && sub.tri_id_first.back() == 0,
+          "subset: total / sizes");
+    uint32_t acc = 0;
+    for (size_t k = 0; k < subset.size(); ++k) {
+      CHECK(sub.tri_first[k] == acc && sub.tri_id_first[k] == whole.tri_first[subset[k]], "subset: entry %zu", k);
+      acc += scene[subset[k]].vertex_count / 3;
+    }
+    CHECK(sub.tri_first[subset.size()] == acc, "subset: closing entry");
+    for (uint32_t t = 0; t < sub.total; ++t) CHECK(scene_triangle_of(sub, t) == id[t], "subset: triangle %u maps to %u, not %u", t, scene_triangle_of(sub, t), id[t]);
+  }
+}
+
 int main(int argc, char** argv) {
   const uint32_t seed = argc > 1 ? (uint32_t)std::strtoul(argv[1], nullptr, 10) : 1u;
   const uint32_t steps = argc > 2 ? (uint32_t)std::strtoul(argv[2], nullptr, 10) : 20000u;
   Mock m;
   m.rng.seed(seed);
   check_plans(m.rng);
+  check_instance_tables(m.rng);
   m.upload_scene(4096);
   for (uint32_t i = 0; i < steps; ++i) {
     const uint32_t op = m.rnd(100);

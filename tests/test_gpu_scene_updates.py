@@ -817,3 +817,102 @@ def test_table_ring_is_made_lazily_and_capped_by_bytes():
     assert abs(ring / slot_bytes - 15.0) < 0.01, ring / slot_bytes  # 15 more slots (a slot = the light records + the few BSDF records): 16 = floor(1 GiB / 64 MB)
     assert st["scene_updates"] == frames - 1 == st_ref["scene_updates"]
     assert st["scene_drains"] > 0  # (16 slots, paths of up to 52 bounces in one-sample frames: some edits wait)
+
+
+# ---- the arms of gsp_update_instances, one segment each ----------------------------------------------------------------------
+# (pt_versions.h: (1) refit of the edited tree, (2) split / re-split, (3) the whole tree.)  Two small instances of the materials
+# scene, A and B, are edited between one-sample frames with samples in flight; every frame is accumulated against the oracle
+# rendering the scene as it is at that frame, and the counters are read once, at the end (gsp_get_stats completes the samples).
+_SEGMENT_1 = [{"A": "small"}, {"A": "small"}, {"B": "small"}, {"A": "small", "B": "small"}]
+_EDIT_SEGMENTS = {
+    # steps, then scene_updates, scene_splits, scene_refits, scene_drains
+    "refit-and-resplit": (_SEGMENT_1, 4, 2, 2, 1),  # no-wait split, in-slot refit, re-split behind a wait (B is new), in-slot refit
+    "edited-tree-degrades": ([{"A": "small"}, {"A": "far"}], 2, 2, 0, 1),  # no-wait split; the small tree grows fourfold: both trees again
+    "first-edit-moves-far": ([{"A": "far"}], 1, 1, 0, 1),  # the no-wait split's refit grows fourfold: the small tree is built where it is
+}
+
+
+def _two_small_instances(sc):
+    """The two boxes of the materials scene: together at most a quarter of the triangles (what a split accepts)."""
+    vc = sc.instances["vertex_count"]
+    a, b = [int(i) for i in np.flatnonzero(vc == 36)[:2]]
+    assert (int(vc[a]) + int(vc[b])) * 4 <= int(vc.sum()), (vc[a], vc[b], vc.sum())
+    return {"A": a, "B": b}
+
+
+def _edit_instance(sc, inst, i, how):
+    t = inst["transform"][i].copy()  # column-major: t[12:15] is the translation
+    if how == "small":
+        t[12:15] += np.float32(0.03) * np.array([0.5, 0.1, -0.3], np.float32)
+    else:  # "far": scaled by 2 about its own centre -- four times the box area of a single-instance tree
+        first, count = int(inst["first_vertex"][i]), int(inst["vertex_count"][i])
+        p = np.asarray(sc.positions, np.float32).reshape(-1, 3)[first:first + count]
+        c = (p.min(0) + p.max(0)) * np.float32(0.5)
+        centre = c[0] * t[0:3] + c[1] * t[4:7] + c[2] * t[8:11] + t[12:15]
+        for col in (0, 4, 8):
+            t[col:col + 3] *= np.float32(2.0)
+        t[12:15] = centre + np.float32(2.0) * (t[12:15] - centre)
+    inst["transform"][i] = t
+
+
+def _run_edit_segment(ctx, sc, steps, oracle_mod=None, W=40, H=30):
+    """render; then per step: edit, gsp_update_instances, render (one sample each, nothing waits).  -> the oracle's accumulation"""
+    who = _two_small_instances(sc)
+    inst = sc.instances.copy()
+    acc = None
+    for k in range(len(steps) + 1):
+        if k:
+            inst = inst.copy()
+            for name, how in steps[k - 1].items():
+                _edit_instance(sc, inst, who[name], how)
+            sc.instances = inst
+            ctx.update_instances(inst)
+        ctx.render(spp=1, first_timestamp=k)
+        if oracle_mod is not None:
+            acc, _ = oracle_mod.Oracle(sc).render(W, H, spp=1, first_timestamp=k, accum=acc)
+    return acc
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("segment", sorted(_EDIT_SEGMENTS))
+def test_update_instances_arms(oracle_mod, materials_scene, segment):
+    """One segment per arm that had no exact counter check: the re-split, the edited tree that degrades, the first edit that moves
+    too far.  Frames equal the oracle's bit for bit; the four scene counters are exactly what the arms taken add up to."""
+    import copy
+
+    import gpuspectral_amd as g
+
+    steps, updates, splits, refits, drains = _EDIT_SEGMENTS[segment]
+    sc = copy.deepcopy(materials_scene)
+    W, H = 40, 30
+    with g.Context(0) as ctx:
+        ctx.upload_scene(sc)
+        ctx.frame_begin(W, H)
+        acc = _run_edit_segment(ctx, sc, steps, oracle_mod, W, H)
+        img = ctx.download().reshape(-1, 4)
+        st = ctx.stats()
+    got = tuple(int(st[k]) for k in ("scene_updates", "scene_splits", "scene_refits", "scene_drains"))
+    print("segment %s: updates, splits, refits, drains = %s" % (segment, got))
+    assert np.array_equal(img, acc), "%d pixels differ" % int((img != acc).any(1).sum())
+    assert got == (updates, splits, refits, drains), st
+
+
+@pytest.mark.gpu
+def test_device_bytes_settle_over_scene_cycles(materials_scene):
+    """One context, three cycles of upload + frame + the edits of the first segment + sync: nothing shrinks, so from the second
+    cycle on every buffer has its size and gsp_stats.device_bytes repeats."""
+    import copy
+
+    import gpuspectral_amd as g
+
+    held = []
+    with g.Context(0) as ctx:
+        for _ in range(3):
+            sc = copy.deepcopy(materials_scene)
+            ctx.upload_scene(sc)
+            ctx.frame_begin(40, 30)
+            _run_edit_segment(ctx, sc, _SEGMENT_1)
+            ctx.sync()
+            held.append(int(ctx.stats()["device_bytes"]))
+    print("device_bytes after each cycle:", held)
+    assert held[1] == held[2], held

@@ -1,4 +1,4 @@
-"""The version-ring bookkeeping of the per-frame scene edits (gpuspectral_amd/csrc/pt_versions.h -- the structs pt_render.hip asks
+"""The version-ring bookkeeping of the per-frame scene edits (gpuspectral_amd/csrc/pt_versions.h -- the structs pt_render_scene.inc asks
 which ring slot to write, whether an edit must wait, how large a ring may be), driven WITHOUT a GPU: tests/emu/versions_model.cpp
 runs random streams of render / update_tables / update_instances / drain / upload against a mock device memory, under
 AddressSanitizer + UBSan.  Invariants: no slot is written while a sample in flight names it, every sample reads the version it
@@ -59,7 +59,9 @@ def test_product_and_documentation_agree_on_the_limits():
     assert "kMaxSceneSplits = %d" % splits in api or "%d times" % splits in api, "the ABI header must quote the split limit"
     csrc = os.path.join(ROOT, "gpuspectral_amd", "csrc")
     render = "".join(open(os.path.join(csrc, f)).read() for f in ("pt_render.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc"))
-    assert "scene_splits >= kMaxSceneSplits" in render and not re.search(r"scene_splits >= \d", render)
+    # the product asks may_split() of the header with its own count of splits; the header compares that count with the one constant
+    assert re.search(r"may_split\([^;]*ctx->stats\.scene_splits", render) and "splits_so_far < kMaxSceneSplits" in hdr
+    assert not re.search(r"scene_splits >=? *\d", render) and not re.search(r"splits_so_far <=? *\d", hdr)
     stages = open(os.path.join(ROOT, "gpuspectral_amd", "csrc", "pt_stages.h")).read()
     assert int(re.search(r"kTableVersions = (\d+)", stages).group(1)) == int(re.search(r"kMaxTableVersions = (\d+);", hdr).group(1))
     assert int(re.search(r"kGeoVersions = (\d+)", stages).group(1)) == int(re.search(r"kMaxGeoVersions = (\d+);", hdr).group(1))
