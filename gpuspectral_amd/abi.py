@@ -33,9 +33,13 @@ BSDF_NAMES = (
 )
 
 
-def bsdf_handle(btype, index):
-    """(type << 16) | index -- S/renderer/Scene.h:83-97."""
-    return ((int(btype) & 0xFFFF) << 16) | (int(index) & 0xFFFF)
+MAX_MEDIA = 4095
+
+
+def bsdf_handle(btype, index, medium=0):
+    """(type << 16) | index -- S/renderer/Scene.h:83-97; medium: GSP_BSDF_HANDLE_MEDIUM, the interior medium's number in bits
+    19..30 (0 = none, k = media[k - 1] of Context.set_media)."""
+    return ((int(btype) & 0xFFFF) << 16) | (int(index) & 0xFFFF) | ((int(medium) & 0xFFF) << 19)
 
 
 # numpy record layouts (all tightly packed, 4-byte scalars)
@@ -164,6 +168,20 @@ class Lens(C.Structure):
 
 def lens(radius=0.0, focus_distance=0.0, blades=0, rotation=0.0):
     return Lens(C.sizeof(Lens), radius, focus_distance, blades, rotation)
+
+
+class Medium(C.Structure):
+    """gsp_medium (include/gpuspectral_pt.h "Interior media"): a pure absorber, sigma_a per channel in 1 / length."""
+
+    _fields_ = [("sigma_a", C.c_float * 3), ("reserved", C.c_float)]
+
+
+def media_array(sigmas):
+    """[(r, g, b), ...] -> (Medium * n), or None for an empty list."""
+    sigmas = [tuple(float(x) for x in s) for s in (sigmas if sigmas is not None else [])]
+    if not sigmas:
+        return None
+    return (Medium * len(sigmas))(*[Medium((C.c_float * 3)(*s), 0.0) for s in sigmas])
 
 
 # LDR film (include/gpuspectral_pt.h "LDR film")

@@ -46,7 +46,7 @@ template <bool TEX>
 GSP_HD FeatureSample feature_vertex(const BsdfTables& T, const TextureView& tex, const q4* sp, const q4* uv, f3 rayDir, const HitRec& hit) {
   const q4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
   const uint32_t material = f2u(s0.w);
-  const uint32_t bsdf = material & 0x7fffffffu;
+  const uint32_t bsdf = material & 0x0007ffffu;  // (without the medium number of bits 19..30: "Interior media")
   const bool twofaced = (material >> 31) != 0u;
   const f3 emission = mk3(s1.w, s2.w, s3.w);
   const float b0 = (1.0f - hit.u) - hit.v;                                // :690

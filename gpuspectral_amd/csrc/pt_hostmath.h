@@ -26,6 +26,23 @@ inline const char* resolve_lens(const gsp_lens* host, gsp_lens& out) {
   return nullptr;
 }
 
+// gsp_set_media: the table as include/gpuspectral_pt.h "Interior media" wants it (NULL or 0 entries = none).  Returns nullptr or
+// the text for gsp_last_error.
+inline const char* check_media(const gsp_medium* media, uint32_t num_media) {
+  if (!media || num_media == 0u) return nullptr;
+  if (num_media > GSP_MAX_MEDIA) return "gsp_set_media: at most 4095 media (the medium number is 12 bits of the BSDF handle)";
+  for (uint32_t k = 0; k < num_media; ++k)
+    for (int c = 0; c < 3; ++c)
+      if (!(media[k].sigma_a[c] >= 0.0f) || std::isinf(media[k].sigma_a[c])) return "gsp_medium.sigma_a must be finite and >= 0";
+  return nullptr;
+}
+// the largest medium number the instances name (bits 19..30 of gsp_instance.bsdf)
+inline uint32_t max_medium_number(const gsp_instance* inst, size_t n) {
+  uint32_t m = 0;
+  for (size_t i = 0; i < n; ++i) m = ((inst[i].bsdf >> 19) & 0xfffu) > m ? ((inst[i].bsdf >> 19) & 0xfffu) : m;
+  return m;
+}
+
 // ---- host-side linear algebra for PathTracer::prepareScene (PathTracer.cpp:62) ------
 // glm::inverse(glm::transpose(M)); cofactor expansion in glm's order so the
 // float32 result matches a glm build of the reference.

@@ -367,6 +367,11 @@ int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens) {  // (NULL = pinhole
   return for_each_share(m, [&](size_t r) { return gsp_set_lens(m->ctx[r], lens); });
 }
 
+int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_media) {  // (NULL or 0 = none, as for gsp_set_media)
+  if (!m) return GSP_ERR_INVALID;
+  return for_each_share(m, [&](size_t r) { return gsp_set_media(m->ctx[r], media, num_media); });
+}
+
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances) {
   if (!m) return GSP_ERR_INVALID;
   if (!instances && num_instances) {

@@ -153,6 +153,11 @@ struct gsp_context {
   bool s2g_all_valid = false;
   gsp_camera camera{};
   gsp_lens lens{};  // gsp_set_lens; radius 0 = the pinhole.  Context state like the camera: render_consts reads it at every gsp_render
+  // interior media (gsp_set_media): context state like the lens.  num_media != 0 selects the <MED> kernels; h_media is what the
+  // device table was last uploaded from (the copy is queued: its source stays alive)
+  DevBuf<gsp_medium> media;
+  std::vector<gsp_medium> h_media;
+  uint32_t num_media = 0;
   double bvh_build_ms = 0.0;
   // what gsp_upload_scene leaves resident for the per-frame edits (gsp_update_instances re-bakes from it, as the reference
   // keeps the BLAS of a mesh and rebuilds the TLAS, Renderer.cpp:122-131 / PathTracer.cpp:10-19): the object-space

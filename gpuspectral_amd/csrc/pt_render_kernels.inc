@@ -339,8 +339,11 @@ constexpr int kShadeWaves = kShadeBlock / 64;
 // VER: tables of several versions are live (gsp_update_tables while samples were in flight): every vertex reads the version its
 // path carries, from HBM / L2 (no LDS copy: it would have to hold every live version) -- unless the versions in flight differ only
 // in their GEOMETRY (gsp_update_instances): then the one live version of the tables is staged as usual (SceneView::ver_stride == 0)
-template <bool TEX, bool VER>
-__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(SceneView S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
+// MED: the context holds interior media (gsp_set_media): shade_vertex<.., MED = true> reads the medium number of the hit and the
+// table behind SceneViewMed::media (16 B per medium, from L2: a handful of entries that only back-face vertices of glass read).
+// Only these instantiations take the larger view: the kernels of a context without media keep their argument layout
+template <bool TEX, bool VER, bool MED>
+__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
                                                         const q4* __restrict__ hits, PathQueue nxt, ShadowQueue sq,
                                                         q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                         uint32_t* __restrict__ live,
@@ -489,7 +492,7 @@ __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(Scene
         in.weight = mk3(p2.x, p2.y, p2.z);
         in.directWeight = p2.w;
         in.flags = fl;
-        shade_vertex<TEX, VER>(S, rc, in, h, out);
+        shade_vertex<TEX, VER, MED>(S, rc, in, h, out, view_media(S));
         alive = out.alive;
         has_shadow = out.has_shadow;
         ++shaded;
@@ -644,8 +647,8 @@ struct FinishStack {
   __device__ __forceinline__ uint32_t pop() { return col[(--top) * kBlock]; }
 };
 
-template <bool TEX, bool VER>
-__global__ __launch_bounds__(kBlock) void k_finish(SceneView S, RenderConstsBase rc, uint32_t n, PathQueue q,
+template <bool TEX, bool VER, bool MED>
+__global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
                                                     q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                     uint32_t* __restrict__ live,
                                                     uint32_t slot_paths, DevStats* __restrict__ stats) {
@@ -702,7 +705,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(SceneView S, RenderConstsBase
         break;
       }
       ShadeOut out;
-      shade_vertex<TEX, VER>(S, rc, in, h, out);
+      shade_vertex<TEX, VER, MED>(S, rc, in, h, out, view_media(S));
       ++shaded;
       if (!out.has_shadow) {
         add_emitted(rc.clamp, out.emitted, res);

@@ -117,14 +117,25 @@ static void launch_trace(const gsp_context* ctx, hipStream_t st, const SceneView
   with_hit_rule(std::false_type{}, view, io);
 }
 
-// k_shade / k_finish <TEX, VER>: TEX = the scene has textures or an environment map, VER = V.multi_version; launch(TEX, VER) gets them
-// as std::integral_constant values (as atrous_level, pt_render_post.inc).  These kernels read V.vview: the versioned view exactly when VER.
+// k_shade / k_finish <TEX, VER, MED>: TEX = the scene has textures or an environment map, VER = V.multi_version, MED = the context holds
+// interior media (gsp_set_media); launch(TEX, VER, MED, view) gets them as std::integral_constant values (as atrous_level,
+// pt_render_post.inc).  These kernels read V.vview -- the versioned view exactly when VER -- and the <MED> ones the table behind it.
 template <class Launch>
-static void tex_ver_kernel(bool textured, bool multi_version, Launch&& launch) {
-  if (multi_version && textured) launch(std::true_type{}, std::true_type{});
-  else if (multi_version) launch(std::false_type{}, std::true_type{});
-  else if (textured) launch(std::true_type{}, std::false_type{});
-  else launch(std::false_type{}, std::false_type{});
+static void tex_ver_med_kernel(const gsp_context* ctx, const LiveVersions& V, Launch&& launch) {
+  const auto with_view = [&](auto TEX, auto VER) {
+    if (ctx->num_media != 0) {
+      SceneViewMed mv;
+      static_cast<SceneView&>(mv) = V.vview;
+      mv.media = ctx->media.p;
+      launch(TEX, VER, std::true_type{}, mv);
+    } else {
+      launch(TEX, VER, std::false_type{}, V.vview);
+    }
+  };
+  if (V.multi_version && ctx->textured) with_view(std::true_type{}, std::true_type{});
+  else if (V.multi_version) with_view(std::false_type{}, std::true_type{});
+  else if (ctx->textured) with_view(std::true_type{}, std::false_type{});
+  else with_view(std::false_type{}, std::false_type{});
 }
 }  // extern "C++"
 
@@ -228,8 +239,8 @@ static int finish_few_paths(gsp_context* ctx, gsp_context::Lane& L, const Render
   if (!(drain && L.queued == 0 && P.remaining == 0 && P.n > 0 && P.n <= ctx->finish_paths && ctx->pipe_params.collect_traversal_stats == 0 &&
         std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 <= kFinishLevels))
     return GSP_OK;
-  tex_ver_kernel(ctx->textured, V.multi_version, [&](auto TEX, auto VER) {
-    hipLaunchKernelGGL((k_finish<decltype(TEX)::value, decltype(VER)::value>), dim3((uint32_t)((P.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, V.vview, rcst,
+  tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, const auto& sview) {
+    hipLaunchKernelGGL((k_finish<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value>), dim3((uint32_t)((P.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, sview, rcst,
                        (uint32_t)P.n, lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq), L.counters.p + C_LIVE, (uint32_t)P.batch_paths, ctx->dstats.p);
   });
   CTX_TRY(ctx, hipGetLastError());
@@ -295,8 +306,8 @@ static int trace_shade_connect(gsp_context* ctx, gsp_context::Lane& L, const Ren
   CTX_TRY(ctx, hipGetLastError());
   if (ev) CTX_TRY(ctx, hipEventRecord(ev[1], st));
   const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + kShadeBlock - 1) / kShadeBlock, shade_resident_blocks(ctx))));
-  tex_ver_kernel(ctx->textured, V.multi_version, [&](auto TEX, auto VER) {
-    hipLaunchKernelGGL((k_shade<decltype(TEX)::value, decltype(VER)::value>), grid, dim3(kShadeBlock), 0, st, V.vview, rcst, n_ptr, cur, hits, next, sq,
+  tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, const auto& sview) {
+    hipLaunchKernelGGL((k_shade<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value>), grid, dim3(kShadeBlock), 0, st, sview, rcst, n_ptr, cur, hits, next, sq,
                        L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths, room_chunk, ctx->dstats.p);
   });
   CTX_TRY(ctx, hipGetLastError());
@@ -1225,6 +1236,31 @@ int gsp_set_lens(gsp_context* ctx, const gsp_lens* lens_host) {
     return GSP_ERR_INVALID;
   }
   ctx->lens = l;  // no drain, and the memo stays: it holds the pinhole rays' hits, which a lens call does not read
+  return GSP_OK;
+}
+
+// ---- interior media (include/gpuspectral_pt.h, "Interior media") ----
+int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (const char* why = check_media(media, num_media)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  const uint32_t n = media ? num_media : 0u;
+  if (ctx->have_scene && max_medium_number(ctx->h_inst.data(), ctx->h_inst.size()) > n) {
+    ctx->err = "gsp_set_media: the resident scene names a medium number above the new count";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight read the table as it was
+  if (rc != GSP_OK) return rc;
+  ctx->h_media.assign(media, media + n);
+  for (gsp_medium& m : ctx->h_media) m.reserved = 0.0f;
+  if (n != 0) {
+    CTX_TRY(ctx, ctx->media.upload(ctx->h_media.data(), n, ctx->stream, &ctx->bytes));
+    CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lanes' streams read it)
+  }
+  ctx->num_media = n;
   return GSP_OK;
 }
 

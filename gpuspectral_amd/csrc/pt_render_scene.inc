@@ -16,8 +16,9 @@ static int check_instances(gsp_context* ctx, const gsp_instance* inst, uint32_t 
       ctx->err = "instance " + std::to_string(i) + ": vertex range outside the position/normal arrays";
       return GSP_ERR_SCENE;
     }
-    const uint32_t type = in.bsdf >> 16, idx = in.bsdf & 0xffffu;
-    if (type >= GSP_BSDF_TYPE_COUNT || idx >= num_bsdfs[type]) {
+    // (bit 31 is not part of a handle: with it the type is out of range, as it was when the type was all of bits 16..31)
+    const uint32_t type = (in.bsdf >> 16) & 7u, idx = in.bsdf & 0xffffu, medium = (in.bsdf >> 19) & 0xfffu;
+    if ((in.bsdf >> 31) != 0u || idx >= num_bsdfs[type] || medium > ctx->num_media) {
       ctx->err = "instance " + std::to_string(i) + ": BSDF handle out of range";
       return GSP_ERR_SCENE;
     }

@@ -82,6 +82,22 @@ struct SceneView {
   uint32_t ver_stride = 0;          // <VER = true> instantiations: bytes between two versions of the tables (slot 0 is what the pointers name)
   TextureView tex;                  // dormant-feature extension; read only by the <TEX = true> instantiations
 };
+// ... and what the <MED = true> instantiations of k_shade / k_finish take in its place: the view + the table of interior media
+// (gsp_set_media).  A struct of its own, not a field of SceneView: the size of SceneView is part of the kernel argument layout of
+// every kernel that takes it, and so of the instruction streams the committed counter files belong to (profiles/pmc_bench_*.json)
+struct SceneViewMed : SceneView {
+  const gsp_medium* media = nullptr;
+};
+template <bool MED>
+struct ShadeViewOf {
+  using type = SceneView;
+};
+template <>
+struct ShadeViewOf<true> {
+  using type = SceneViewMed;
+};
+GSP_HD const gsp_medium* view_media(const SceneView&) { return nullptr; }
+GSP_HD const gsp_medium* view_media(const SceneViewMed& v) { return v.media; }
 
 // path flags word: depth [0,7] | wasDelta << 8 | countEmitted << 9 | table version << 10 [10,15] | geometry version << 16 [16,21]
 GSP_HD uint32_t pack_flags(uint32_t depth, uint32_t wasDelta, uint32_t countEmitted) {
@@ -292,9 +308,13 @@ struct ShadeOut {
 // instruction; TEX = true interpolates the hit's uv and, for a record with has_texture, takes kD from the texture.
 // VER: tables of several versions are live (an edit through gsp_update_tables while samples were in flight): the vertex reads
 // the version its path carries.  VER = false is the code of a scene that is not being edited, instruction for instruction.
-template <bool TEX = false, bool VER = false>
+// MED: the context holds interior media (include/gpuspectral_pt.h, "Interior media"): bits 19..30 of the material word name the
+// medium of the hit object, and a vertex on a BACK face scales the path weight by exp(-sigma_a * t) of the segment that ran inside
+// it.  MED = false is the code of a context without media, instruction for instruction (no handle carries those bits then);
+// `media` (MED only) = the table, view_media() of the view the kernel was handed.
+template <bool TEX = false, bool VER = false, bool MED = false>
 GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
-                         ShadeOut& out) {
+                         ShadeOut& out, const gsp_medium* media = nullptr) {
   uint32_t rng = in.seed;                                                 // rchit:668
   BsdfTables Tv;  // (VER only: this lane's version of the tables)
   const gsp_triangle_light* lights_v = nullptr;
@@ -317,7 +337,7 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
                                       (VER && (uint32_t)hit.slot >= S.static_slots ? (long long)geo_slot_offset(S.geo, geo_stamp(in.flags)) : 0ll));
   const q4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
   const uint32_t material = f2u(s0.w);                                    // :672 (instance record, baked per triangle)
-  const uint32_t bsdf = material & 0x7fffffffu;
+  const uint32_t bsdf = material & (MED ? 0x0007ffffu : 0x7fffffffu);
   const bool twofaced = (material >> 31) != 0u;
   const f3 emission = mk3(s1.w, s2.w, s3.w);
   const f3 rayDir = in.d;                                                 // :696
@@ -325,10 +345,22 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   const float b0 = (1.0f - hit.u) - hit.v;                                // :690
   f3 SN = normalize((b0 * mk3(s1.x, s1.y, s1.z) + hit.u * mk3(s2.x, s2.y, s2.z)) + hit.v * mk3(s3.x, s3.y, s3.z));
   f3 N = mk3(s0.x, s0.y, s0.z);                                           // :694 (precomputed at bake)
+  // MED: the path weight this vertex works with.  Formed here, on the geometric normal before the two-sided flip and before the
+  // BSDF's inputs are live (the three exponentials then need no register the rest of the vertex does not)
+  f3 weight = in.weight;
+  const uint32_t medium = MED ? (material >> 19) & 0xfffu : 0u;
+  bool flipped = false;  // (MED only) N below is the geometric normal turned round
+  if (MED) {
+    if (medium != 0u && dot(N, -rayDir) < 0.0f) {
+      const gsp_medium* m = media + (medium - 1u);
+      weight = in.weight * mk3(det_expf(-(m->sigma_a[0] * hit.t)), det_expf(-(m->sigma_a[1] * hit.t)), det_expf(-(m->sigma_a[2] * hit.t)));
+    }
+  }
   if (dot(N, -rayDir) < 0.0f) {                                           // :698-707
     if (twofaced && emission.x == 0.0f && emission.y == 0.0f && emission.z == 0.0f) {
       N = N * -1.0f;
       SN = SN * -1.0f;
+      if (MED) flipped = true;
     }
   }
   const Frame onb = make_frame(SN);                                       // :712
@@ -379,15 +411,15 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   f3 nee = splat(0.0f);
   if (want_shadow) {
     const float w = power_heuristic(lightPdf, bs.pdf);                    // :751
-    nee = ((((w * NoL) * lb.f) * in.weight) * ls.emission) / lightPdf;    // :752
+    nee = ((((w * NoL) * lb.f) * weight) * ls.emission) / lightPdf;       // :752
   }
   const uint32_t depth = in.flags & 0xffu;
   const uint32_t wasDelta = (in.flags >> 8) & 1u;
   const uint32_t countEmitted = (in.flags >> 9) & 1u;
   const float lightFlag = NdotV > 0.0f ? 1.0f : 0.0f;                     // :760
   f3 emis = splat(0.0f);
-  if (nee_on && countEmitted == 0 && wasDelta == 0) emis = emis + ((in.directWeight * emission) * lightFlag) * in.weight;  // :763-765
-  if (!nee_on || countEmitted == 1 || wasDelta == 1) emis = emis + (emission * lightFlag) * in.weight;                      // :766-768
+  if (nee_on && countEmitted == 0 && wasDelta == 0) emis = emis + ((in.directWeight * emission) * lightFlag) * weight;  // :763-765
+  if (!nee_on || countEmitted == 1 || wasDelta == 1) emis = emis + (emission * lightFlag) * weight;                      // :766-768
 
   bool done = false;
   if (dot(wi, N) <= 0.0f && !transmits) done = true;                      // :770-773
@@ -397,11 +429,23 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
 
   PathState nx = in;
   nx.seed = rng;                                                          // :759
+  if (MED) nx.weight = weight;
   if (!done) {
     nx.directWeight = 1.0f;                                               // :785-790 (connect overwrites when NEE happens)
     nx.o = position + 0.0001f * faceforward(N, -wi, N);                   // :793
     nx.d = wi;                                                            // :794
-    nx.weight = in.weight * ((bs.f * NoW) / bs.pdf);                      // :795
+    nx.weight = weight * ((bs.f * NoW) / bs.pdf);                         // :795
+    if (MED) {
+      // the segment that starts here runs INSIDE the object (wi points against the geometric normal): its origin sits 1e-4 below the
+      // surface along the normal (:793), so the traced ray meets the surface's plane 1e-4 / |dot(N, wi)| behind its origin and the
+      // next vertex's t is short by that much.  The missing piece is absorbed here, where the normal is known
+      const float c = dot(wi, N);
+      if (medium != 0u && (flipped ? c > 0.0f : c < 0.0f)) {
+        const gsp_medium* m = media + (medium - 1u);
+        const float s = gmin(0.0001f / gabs(c), 1e30f);
+        nx.weight = nx.weight * mk3(det_expf(-(m->sigma_a[0] * s)), det_expf(-(m->sigma_a[1] * s)), det_expf(-(m->sigma_a[2] * s)));
+      }
+    }
   }
   // back in raygen: Russian roulette reads the NEXT vertex's first variate (rgen:59,66-71)
   bool alive = true;

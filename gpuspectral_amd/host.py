@@ -63,6 +63,13 @@ def load():
     L.gsph_scene_lens.argtypes = [vp, C.POINTER(C.c_float * 4)]
     L.gsph_scene_set_lens.restype = None
     L.gsph_scene_set_lens.argtypes = [vp, C.c_float, C.c_float, u32, C.c_float]
+    L.gsph_scene_media.restype = u32
+    L.gsph_scene_media.argtypes = [vp, vp]
+    L.gsph_scene_object_medium.restype = u32
+    L.gsph_scene_object_medium.argtypes = [vp, u32]
+    L.gsph_scene_add_medium.restype = u32
+    L.gsph_scene_add_medium.argtypes = [vp, vp]
+    L.gsph_scene_set_object_medium.argtypes = [vp, u32, u32]
     L.gsph_tracker_diff.argtypes = [vp]
     L.gsph_tracker_probe.argtypes = [vp, vp]
     L.gsph_pathtracer_create.restype = vp
@@ -131,19 +138,20 @@ class Scene:
     """A C++ GPUSpectral::Scene produced by loadScene (S/engine/Loader.cpp:253-349)."""
 
     def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False,
-                 read_lens=False, read_film=False):
+                 read_lens=False, read_film=False, read_media=False):
         """dormant_features: LoadOptions::dormantFeatures (textures / environment map, SURVEY 8(f).3); builtin_shapes:
         LoadOptions::builtinShapes (`disk` and `sphere` shapes are built instead of skipped, SURVEY 8(f).1); the defaults are
         the reference's behaviour.  read_filter: LoadOptions::readFilter (the film's <rfilter> becomes `pixel_filter`, which
         PathTracer.render applies unless its params name a filter of their own).  read_lens: LoadOptions::readLens (a `thinlens`
         sensor's aperture_radius / focus_distance become the camera's lens, which PathTracer hands to the device).  read_film:
-        LoadOptions::readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn become `film`)."""
+        LoadOptions::readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn become `film`).  read_media:
+        LoadOptions::readMedia (the shapes' <medium name="interior"> become `media` and the objects' medium numbers: coloured glass)."""
         self._L = load()
         ad = asset_dir.encode() if asset_dir else None
-        if builtin_shapes or read_filter or read_lens or read_film:
+        if builtin_shapes or read_filter or read_lens or read_film or read_media:
             self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) |
                                                    (4 if builtin_shapes else 0) | (8 if read_filter else 0) | (16 if read_lens else 0) |
-                                                   (32 if read_film else 0))
+                                                   (32 if read_film else 0) | (64 if read_media else 0))
         elif dormant_features:
             self._h = self._L.gsph_load_scene_ex(path.encode(), ad, 1, 1 if srgb_textures else 0)
         else:
@@ -186,6 +194,30 @@ class Scene:
         d = abi.Display()
         ldr = self._L.gsph_scene_film(self._h, C.byref(d))
         return bool(ldr), d
+
+    @property
+    def media(self):
+        """Scene::media as an (n, 3) float32 array of absorption coefficients; empty without read_media / add_medium."""
+        n = self._L.gsph_scene_media(self._h, None)
+        out = np.zeros((n, 3), np.float32)
+        if n:
+            self._L.gsph_scene_media(self._h, out.ctypes.data)
+        return out
+
+    def object_medium(self, obj):
+        """RenderObject::interiorMedium: 0 = none, k = media[k - 1]."""
+        return int(self._L.gsph_scene_object_medium(self._h, obj))
+
+    def add_medium(self, sigma_a):
+        """Scene::addMedium: the number of the (possibly shared) entry."""
+        s = np.ascontiguousarray(sigma_a, np.float32)
+        return int(self._L.gsph_scene_add_medium(self._h, s.ctypes.data))
+
+    def set_object_medium(self, obj, number):
+        """Names entry `number` of the scene's media as the object's interior medium (0 = none) and flattens the scene again."""
+        if self._L.gsph_scene_set_object_medium(self._h, obj, number) != 0:
+            raise RuntimeError(self._L.gsph_last_error().decode())
+        self._L.gsph_scene_reflatten(self._h)
 
     def set_lens(self, radius, focus_distance, blades=0, rotation=0.0):
         """Camera::setLens: the tracer sends it with the next pass (gsp_set_lens) when its value changed."""

@@ -178,6 +178,7 @@ struct Object {
   std::map<std::string, Prop> props;
   std::vector<std::shared_ptr<Object>> children;                        // anonymousChildren()
   std::vector<std::pair<std::string, std::shared_ptr<Object>>> named;   // namedChildren()
+  std::vector<std::pair<std::string, std::string>> namedRefs;           // <ref name=".." id=".."/>: (name, id); read by LoadOptions::readMedia only
 
   bool has(const std::string& n) const { return props.count(n) != 0; }
   float number(const std::string& n, float def = 0.0f) const {
@@ -267,7 +268,7 @@ std::shared_ptr<Object> parseObject(const XmlNode& el, ParseState& ps) {
       pr.type = PT_STRING;
       pr.str = ch.get("value");
       o->props[nm] = pr;
-    } else if (ch.tag == "rgb" || ch.tag == "srgb") {
+    } else if (ch.tag == "rgb" || ch.tag == "srgb" || (ch.tag == "spectrum" && el.tag == "medium")) {  // (a medium's coefficients may be a <spectrum> triple)
       pr.type = PT_COLOR;
       auto v = numbers(ch.get("value"));
       if (v.size() == 1) v = {v[0], v[0], v[0]};
@@ -294,6 +295,7 @@ std::shared_ptr<Object> parseObject(const XmlNode& el, ParseState& ps) {
         }
       o->props[nm] = pr;
     } else if (ch.tag == "ref") {
+      if (ch.attr("name")) o->namedRefs.emplace_back(nm, ch.get("id"));
       auto it = ids.find(ch.get("id"));
       if (it != ids.end()) {
         o->children.push_back(it->second);
@@ -637,6 +639,55 @@ MeshPtr loadMesh(const std::string& path, uint32_t id) {
 }
 
 // Loader.cpp:253-349
+// LoadOptions::readMedia: the interior medium of a shape (include/gpuspectral_pt.h "Interior media"), inline or as a <ref> to a
+// top-level <medium id=..>, as its number in Scene::media; 0 = none.  sigma_a = sigmaA, or sigmaT * (1 - albedo); an optional float
+// `scale` multiplies.  What is not a pure homogeneous absorber inside the shape is skipped with one warning, as `disk` shapes are.
+static uint32_t shapeInteriorMedium(Scene& scene, const Object& shape, const ParseState& ps) {
+  std::vector<std::pair<std::string, std::shared_ptr<Object>>> found;
+  for (auto& nc : shape.named)
+    if (nc.second && nc.second->kind == "medium") found.push_back(nc);
+  for (auto& nr : shape.namedRefs) {
+    auto it = ps.ids.find(nr.second);
+    if (it != ps.ids.end() && it->second && it->second->kind == "medium") found.emplace_back(nr.first, it->second);
+  }
+  uint32_t number = 0;
+  for (auto& nm : found) {
+    const Object& m = *nm.second;
+    if (nm.first != "interior") {
+      scene.warnings.push_back("medium '" + nm.first + "' of a shape skipped (only interior media are supported)");
+      continue;
+    }
+    if (m.plugin != "homogeneous") {
+      scene.warnings.push_back("unsupported medium type '" + m.plugin + "' skipped");
+      continue;
+    }
+    auto triple = [&](const char* name, float def, float out[3]) {
+      auto it = m.props.find(name);
+      for (int c = 0; c < 3; ++c) out[c] = def;
+      if (it == m.props.end()) return false;
+      if (it->second.type == PT_COLOR) for (int c = 0; c < 3; ++c) out[c] = it->second.v[c];
+      else if (it->second.type == PT_NUMBER) for (int c = 0; c < 3; ++c) out[c] = (float)it->second.number;
+      else return false;
+      return true;
+    };
+    float sa[3], ss[3], st[3], al[3];
+    const bool hasA = triple("sigma_a", 0.0f, sa), hasT = triple("sigma_t", 0.0f, st);
+    triple("sigma_s", 0.0f, ss);
+    triple("albedo", 0.0f, al);
+    if (ss[0] != 0.0f || ss[1] != 0.0f || ss[2] != 0.0f || al[0] != 0.0f || al[1] != 0.0f || al[2] != 0.0f) {
+      scene.warnings.push_back("scattering medium skipped (sigmaS / albedo != 0: only pure absorbers are supported)");
+      continue;
+    }
+    if (!hasA && hasT)
+      for (int c = 0; c < 3; ++c) sa[c] = st[c] * (1.0f - al[c]);
+    const float scale = m.number("scale", 1.0f);
+    gsp_medium rec{};
+    for (int c = 0; c < 3; ++c) rec.sigma_a[c] = sa[c] * scale;
+    number = scene.addMedium(rec);
+  }
+  return number;
+}
+
 Scene loadScene(const std::string& path, const std::string& assetDirArg, const LoadOptions& options) {
   std::ifstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("cannot open scene file: " + path);
@@ -720,6 +771,7 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
           emitting = true;
         }
       }
+      if (options.readMedia) renderObject.interiorMedium = shapeInteriorMedium(outScene, *obj, ps);
       renderObject.mesh = mesh;
       renderObject.transform = matrix;
       renderObject.material = outScene.addMaterial(material);
@@ -851,7 +903,7 @@ void flattenInstances(const Scene& scene, std::vector<gsp_instance>& out) {
     in.emission[0] = material.emission.x;
     in.emission[1] = material.emission.y;
     in.emission[2] = material.emission.z;
-    in.bsdf = material.bsdf.handle;
+    in.bsdf = material.bsdf.handle | ((obj.interiorMedium & 0xFFFu) << 19);  // GSP_BSDF_HANDLE_MEDIUM; 0 = none: the handle as it was
     in.twofaced = material.twofaced ? 1u : 0u;
     in.first_vertex = it->second.first;
     in.vertex_count = it->second.second;

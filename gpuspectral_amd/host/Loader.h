@@ -44,6 +44,13 @@ struct LoadOptions {
   // a value gsp_display would refuse is a load error.  Any other film type leaves the record at its defaults, with a warning.
   // false (default): the film is ignored, as in the reference.
   bool readFilm = false;
+  // The reference never looks at the named children of a shape, so the <medium type="homogeneous" name="interior"> of its glass
+  // shapes (living-room, staircase2) does nothing and the glasses render clear.  readMedia = true reads them (include/
+  // gpuspectral_pt.h "Interior media"): inline or as a <ref> to a top-level <medium id=..>; `sigmaA` as an rgb or spectrum triple, or
+  // `sigmaT` with `albedo` (sigma_a = sigmaT * (1 - albedo)); an optional float `scale` multiplies.  Equal triples share one entry of
+  // Scene::media; RenderObject::interiorMedium names it.  A medium with sigmaS != 0 or albedo != 0, a name="exterior" medium and a
+  // type other than homogeneous are skipped with one warning each, as `disk` shapes are.
+  bool readMedia = false;
 };
 
 // assetDir: where rect.obj / box.obj / disk.obj live (Engine::assetPath); "" = the

@@ -73,6 +73,11 @@ bool SceneTracker::lensChanged(const Scene& scene, gsp_lens& out) const {
   return std::memcmp(&mine, &out, sizeof(out)) != 0;
 }
 
+bool SceneTracker::mediaChanged(const Scene& scene) const {
+  return scene.media.size() != media.size() ||
+         (!media.empty() && std::memcmp(scene.media.data(), media.data(), media.size() * sizeof(gsp_medium)) != 0);
+}
+
 unsigned SceneTracker::diff(const Scene& scene, std::vector<gsp_instance>& inst) const {
   flattenInstances(scene, inst);
   if (!valid || scene.renderObjects.size() != meshes.size()) return Everything;
@@ -149,9 +154,19 @@ void PathTracer::prepareScene(const Scene& scene) {
     check(gsp_set_lens(ctx, &lens), "gsp_set_lens");
     tracker.rememberLens(lens);
   }
+  // the media table goes BEFORE a scene that names more entries than the device holds and AFTER one that names fewer than the
+  // resident scene does (gsp_set_media refuses to shrink the table under it): tried first, and again behind the scene if refused
+  bool mediaPending = tracker.mediaChanged(scene);
+  if (mediaPending && gsp_set_media(ctx, scene.media.data(), (uint32_t)scene.media.size()) == GSP_OK) {
+    tracker.rememberMedia(scene);
+    mediaPending = false;
+  }
   std::vector<gsp_instance> inst;
   const unsigned change = tracker.diff(scene, inst);
-  if (change == SceneTracker::None) return;
+  if (change == SceneTracker::None) {
+    if (mediaPending) check(gsp_set_media(ctx, scene.media.data(), (uint32_t)scene.media.size()), "gsp_set_media");
+    return;
+  }
   tracker.forget();  // (a failed call below leaves nothing remembered: the next pass uploads everything)
   if (change & SceneTracker::Everything) {
     FlatScene flat;
@@ -178,6 +193,10 @@ void PathTracer::prepareScene(const Scene& scene) {
       }
     }
     if (change & SceneTracker::CameraChanged) check(gsp_update_camera(ctx, &d.camera), "gsp_update_camera");
+  }
+  if (mediaPending) {
+    check(gsp_set_media(ctx, scene.media.data(), (uint32_t)scene.media.size()), "gsp_set_media");
+    tracker.rememberMedia(scene);
   }
   tracker.remember(scene, inst);
 }
@@ -421,8 +440,15 @@ void MultiGpuPathTracer::prepareScene(const Scene& scene) {
     check(gsp_multi_set_lens(multi, &lens), "gsp_multi_set_lens");
     tracker.rememberLens(lens);
   }
+  // (the media table: as PathTracer::prepareScene; a change that has to follow the scene takes the full upload here)
+  bool mediaPending = tracker.mediaChanged(scene);
+  if (mediaPending && gsp_multi_set_media(multi, scene.media.data(), (uint32_t)scene.media.size()) == GSP_OK) {
+    tracker.rememberMedia(scene);
+    mediaPending = false;
+  }
   std::vector<gsp_instance> inst;
-  const unsigned change = tracker.diff(scene, inst);
+  const unsigned change = mediaPending ? (unsigned)SceneTracker::Everything : tracker.diff(scene, inst);
+  if (mediaPending) flattenInstances(scene, inst);
   if (change == SceneTracker::None) return;
   tracker.forget();
   // (same order as PathTracer::prepareScene; the handle-range corner cases take the full upload here)
@@ -440,6 +466,10 @@ void MultiGpuPathTracer::prepareScene(const Scene& scene) {
     FlatScene flat;
     flattenScene(scene, flat);
     check(gsp_multi_upload_scene(multi, &flat.desc), "gsp_multi_upload_scene");
+  }
+  if (mediaPending) {
+    check(gsp_multi_set_media(multi, scene.media.data(), (uint32_t)scene.media.size()), "gsp_multi_set_media");
+    tracker.rememberMedia(scene);
   }
   tracker.remember(scene, inst);
 }

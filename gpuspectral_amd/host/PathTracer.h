@@ -38,6 +38,9 @@ struct SceneTracker {
   // tracked beside the snapshot: a full upload does not resend it, a changed value does
   bool lensChanged(const Scene& scene, gsp_lens& out) const;
   void rememberLens(const gsp_lens& l) { lens = l; }
+  // the scene's interior media (Scene::media) against the table last sent; context state of its own too (gsp_set_media)
+  bool mediaChanged(const Scene& scene) const;
+  void rememberMedia(const Scene& scene) { media = scene.media; }
 
  private:
   bool valid = false;
@@ -46,6 +49,7 @@ struct SceneTracker {
   std::vector<unsigned char> tables;    // counts + the eight BSDF arrays + the lights, back to back
   gsp_camera camera{};
   gsp_lens lens{};                      // (zeroed = pinhole = a fresh context's state)
+  std::vector<gsp_medium> media;        // (empty = none = a fresh context's state)
   std::vector<uint64_t> assets;         // dormant features: texture / environment-map sizes, flags, envmap transform
 };
 

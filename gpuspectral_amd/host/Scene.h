@@ -81,6 +81,9 @@ struct RenderObject {
   mat4 transform = mat4::identity();
   MeshPtr mesh;
   MaterialHandle material = 0;
+  // interior medium, opt-in (gpuspectral_pt.h "Interior media"; the reference's loader never looks at a shape's <medium>): 0 = none,
+  // k = Scene::media[k - 1].  flattenScene puts it into bits 19..30 of the instance's BSDF handle
+  uint32_t interiorMedium = 0;
 };
 
 enum BSDFType : uint16_t {
@@ -198,6 +201,15 @@ struct Scene {
   std::vector<SmoothFloorBSDF> smoothFloorBSDFs;
   std::vector<RoughFloorBSDF> roughFloorBSDFs;
   std::vector<RoughPlasticBSDF> roughPlasticBSDFs;
+  // interior media: filled only by loadScene(..., LoadOptions{.readMedia = true}) or by the host itself; equal coefficients share
+  // one entry.  PathTracer sends the table (gsp_set_media) when its value changed
+  uint32_t addMedium(const gsp_medium& m) {
+    for (size_t k = 0; k < media.size(); ++k)
+      if (media[k].sigma_a[0] == m.sigma_a[0] && media[k].sigma_a[1] == m.sigma_a[1] && media[k].sigma_a[2] == m.sigma_a[2]) return (uint32_t)k + 1;
+    media.push_back(gsp_medium{{m.sigma_a[0], m.sigma_a[1], m.sigma_a[2]}, 0.0f});
+    return (uint32_t)media.size();
+  }
+  std::vector<gsp_medium> media;
   std::vector<std::string> warnings;  // what the loader skipped (the reference printed these to stdout)
   // the film's <rfilter>, read only with LoadOptions::readFilter: GSP_FILTER_* and its parameter (0 = the filter's default).
   // 0 = none: the renderer's own params decide.  PathTracer::render uses these when its params.pixel_filter is GSP_FILTER_NONE

@@ -65,7 +65,7 @@ void* gsph_load_scene_ex(const char* path, const char* asset_dir, int dormant, i
 }
 // flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere),
 // 8 = readFilter (the film's <rfilter>), 16 = readLens (a thinlens sensor's aperture_radius / focus_distance),
-// 32 = readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn)
+// 32 = readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn), 64 = readMedia (the shapes' interior media)
 void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned flags) {
   SceneBox* b = nullptr;
   int rc = guard([&] {
@@ -77,6 +77,7 @@ void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned fla
     opt.readFilter = (flags & 8u) != 0;
     opt.readLens = (flags & 16u) != 0;
     opt.readFilm = (flags & 32u) != 0;
+    opt.readMedia = (flags & 64u) != 0;
     b->scene = loadScene(path, asset_dir ? asset_dir : "", opt);
     flattenScene(b->scene, b->flat);
   });
@@ -124,6 +125,31 @@ void gsph_scene_lens(void* s, float* out4) {
 }
 void gsph_scene_set_lens(void* s, float radius, float focus, uint32_t blades, float rotation) {
   ((SceneBox*)s)->scene.camera.setLens(radius, focus, blades, rotation);
+}
+// the scene's interior media (LoadOptions::readMedia / Scene::media): the count; out = 3 floats (sigma_a) per medium, may be NULL
+uint32_t gsph_scene_media(void* s, float* out) {
+  const std::vector<gsp_medium>& m = ((SceneBox*)s)->scene.media;
+  if (out)
+    for (size_t k = 0; k < m.size(); ++k)
+      for (int c = 0; c < 3; ++c) out[3 * k + c] = m[k].sigma_a[c];
+  return (uint32_t)m.size();
+}
+// RenderObject::interiorMedium of an object (0 = none); set: the number of an entry of the scene's media, which
+// gsph_scene_add_medium appends (equal coefficients share one entry).  gsph_scene_reflatten rebuilds the flattened handles.
+uint32_t gsph_scene_object_medium(void* s, uint32_t object) {
+  const Scene& sc = ((SceneBox*)s)->scene;
+  return object < sc.renderObjects.size() ? sc.renderObjects[object].interiorMedium : 0u;
+}
+uint32_t gsph_scene_add_medium(void* s, const float* sigma_a3) {
+  return ((SceneBox*)s)->scene.addMedium(gsp_medium{{sigma_a3[0], sigma_a3[1], sigma_a3[2]}, 0.0f});
+}
+int gsph_scene_set_object_medium(void* s, uint32_t object, uint32_t number) {
+  return guard([&] {
+    Scene& sc = ((SceneBox*)s)->scene;
+    if (object >= sc.renderObjects.size()) throw std::runtime_error("object index out of range");
+    if (number > sc.media.size()) throw std::runtime_error("medium number beyond the scene's media");
+    sc.renderObjects[object].interiorMedium = number;
+  });
 }
 // the scene's film (LoadOptions::readFilm) as the gsp_display PathTracer::display takes; returns 1 when an ldrfilm was read
 int gsph_scene_film(void* s, gsp_display* out) {

@@ -60,6 +60,9 @@ class PathTracerHip : public RenderPassCreator {
     gsp_lens l{(uint32_t)sizeof(gsp_lens), radius, focusDistance, blades, rotation};
     check(gsp_set_lens(ctx, &l));
   }
+  // coloured glass, opt-in (gpuspectral_pt.h "Interior media"): the table of absorbers that bits 19..30 of an instance's BSDF handle
+  // name (GSP_BSDF_HANDLE_MEDIUM; 0 = none).  Context state; set it BEFORE the scene that names its entries, restart() after a change
+  void setMedia(const std::vector<gsp_medium>& media) { check(gsp_set_media(ctx, media.data(), (uint32_t)media.size())); }
   float autofocus(float fx, float fy) {
     float d = 0.0f;
     check(gsp_focus_distance(ctx, width, height, fx, fy, &d));

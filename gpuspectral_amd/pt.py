@@ -28,6 +28,7 @@ EXPORTS = (
     "gsp_update_instances",
     "gsp_update_tables",
     "gsp_set_lens",
+    "gsp_set_media",
     "gsp_focus_distance",
     "gsp_frame_begin",
     "gsp_render",
@@ -90,6 +91,7 @@ EXPORTS = (
     "gsp_multi_upload_scene",
     "gsp_multi_update_camera",
     "gsp_multi_set_lens",
+    "gsp_multi_set_media",
     "gsp_multi_update_instances",
     "gsp_multi_update_tables",
     "gsp_multi_frame_begin",
@@ -143,6 +145,8 @@ def load():
     L.gsp_set_lens.argtypes = [vp, C.POINTER(abi.Lens)]
     L.gsp_focus_distance.argtypes = [vp, u32, u32, C.c_float, C.c_float, C.POINTER(C.c_float)]
     L.gsp_multi_set_lens.argtypes = [vp, C.POINTER(abi.Lens)]
+    L.gsp_set_media.argtypes = [vp, C.POINTER(abi.Medium), u32]
+    L.gsp_multi_set_media.argtypes = [vp, C.POINTER(abi.Medium), u32]
     L.gsp_update_instances.argtypes = [vp, vp, u32]
     L.gsp_update_tables.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_ctx_destroy.argtypes = [vp]
@@ -336,6 +340,12 @@ class Context:
         if lens is None:
             lens = abi.lens(radius, focus_distance, blades, rotation)
         self._check(self._L.gsp_set_lens(self._h, C.byref(lens)), "gsp_set_lens")
+
+    def set_media(self, sigmas=None):
+        """gsp_set_media: the table of interior media (gpuspectral_pt.h "Interior media"), a list of (r, g, b) absorption
+        coefficients; medium number k of abi.bsdf_handle(.., medium=k) is sigmas[k - 1].  None or empty = no media."""
+        arr = abi.media_array(sigmas)
+        self._check(self._L.gsp_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_media")
 
     def focus_distance(self, width, height, fx, fy):
         """gsp_focus_distance: camera-space depth of what the pinhole ray through fragCoord (fx, fy) hits, 0.0 on a miss."""
@@ -783,6 +793,11 @@ class MultiContext:
         if lens is None:
             lens = abi.lens(radius, focus_distance, blades, rotation)
         self._check(self._L.gsp_multi_set_lens(self._h, C.byref(lens)), "gsp_multi_set_lens")
+
+    def set_media(self, sigmas=None):
+        """gsp_multi_set_media: Context.set_media on every share."""
+        arr = abi.media_array(sigmas)
+        self._check(self._L.gsp_multi_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_media")
 
     def update_instances(self, instances):
         inst = np.ascontiguousarray(instances, abi.INSTANCE_DT)

@@ -82,7 +82,8 @@ extern "C" {
                                 gsp_temporal_svgf_feedback, gsp_temporal_svgf_feedback_to_device (see "Illumination history");
                                 gsp_temporal_antilag, gsp_download_temporal_fast, gsp_temporal_fast_to_device (see "Temporal
                                 anti-lag"); gsp_temporal_taa, gsp_temporal_taa_from_device, gsp_download_taa,
-                                gsp_download_taa_display, gsp_taa_display_to_device (see "Temporal anti-aliasing") */
+                                gsp_download_taa_display, gsp_taa_display_to_device (see "Temporal anti-aliasing");
+                                gsp_set_media, gsp_multi_set_media (see "Interior media") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -104,6 +105,9 @@ extern "C" {
 
 /* handle = (type << 16) | index        S/renderer/Scene.h:83-97, pt_common.glsl:30-42 */
 #define GSP_BSDF_HANDLE(type, index) ((((uint32_t)(type)) << 16) | ((uint32_t)(index) & 0xFFFFu))
+/* ... with an interior medium (see "Interior media"): bits 19..30 = medium number, 0 = none, k = media[k - 1] of gsp_set_media */
+#define GSP_MAX_MEDIA 4095u
+#define GSP_BSDF_HANDLE_MEDIUM(type, index, medium) (GSP_BSDF_HANDLE(type, index) | ((((uint32_t)(medium)) & 0xFFFu) << 19))
 
 /* ---- BSDF parameter records, scalar layout = S/renderer/Scene.h:29-81 ---- */
 typedef struct gsp_diffuse_bsdf {
@@ -577,6 +581,51 @@ int gsp_set_lens(gsp_context* ctx, const gsp_lens* lens); /* NULL = pinhole */
  * gsp_lens.focus_distance -- or 0 on a miss.  Not affected by the current lens or pixel filter; needs no gsp_frame_begin.
  * Completes the samples already queued first, like gsp_sync. */
 int gsp_focus_distance(gsp_context* ctx, uint32_t width, uint32_t height, float fx, float fy, float* out);
+
+/*
+ * Interior media: opt-in Beer-Lambert absorption inside closed shapes (coloured glass).
+ *
+ * The reference's scenes declare <medium type="homogeneous" name="interior"> children on glass shapes and its loader never
+ * looks at them; every one has sigmaS = 0.  A medium here is a pure absorber: it draws no random number and bends no ray, it
+ * scales the path weight over the segment that ran inside the object.  sigma_a is in units of 1 / world-space length, finite
+ * and >= 0.
+ *
+ * The media are CONTEXT STATE: gsp_set_media(ctx, media, n) replaces the table (NULL or n == 0 = none; at most GSP_MAX_MEDIA
+ * entries), holds until changed and survives gsp_upload_scene.  The samples in flight finish first (the wait of every scene
+ * edit), so it may be called between the gsp_render calls of one frame.  GSP_ERR_INVALID for a non-finite or negative
+ * coefficient, a count above GSP_MAX_MEDIA, and when the resident scene names a medium number above the new count (the
+ * table is then unchanged and the scene still renders).
+ *
+ * Assignment: bits 19..30 of gsp_instance.bsdf (GSP_BSDF_HANDLE_MEDIUM) hold the medium number k, 0 = none, k = media[k - 1].
+ * A number above the context's count -- any nonzero number while no media are set -- is GSP_ERR_SCENE, "BSDF handle out of
+ * range", at gsp_upload_scene and gsp_update_instances.
+ *
+ * The attenuation, in the shading vertex straight after the material word and the geometric normal N are read (the test of
+ * rayhit.rchit:698 on N, BEFORE the two-sided flip), float32 in this order:
+ *     k = (material >> 19) & 0xfff;  bsdf = material & 0x0007ffff
+ *     if (k != 0 && dot(N, -rayDir) < 0)   a_c = exp(-(sigma_a[k-1].c * t)), c = r, g, b;   w = weight * a   (component-wise)
+ *     else                                 w = weight
+ * and every later use of the path weight in that vertex reads w: the NEE term, both emission terms, the next vertex's weight
+ * and through it Russian roulette.  t is the hit's parametric distance along the unit direction as traced; exp is the library's
+ * deterministic one, exp(-0) = 1 exactly, so sigma_a = 0 leaves every bit of the frame in place.
+ *
+ * The entry piece.  A segment that runs inside an object starts 1e-4 below its surface along the normal (rayhit.rchit:793), so
+ * the traced ray meets the surface's plane 1e-4 / |dot(N, wi)| behind its origin and the next vertex's t is short by that much
+ * (sigma_a = 1000 would turn it into 10 % of the weight).  The vertex that sends the path inside absorbs it: when the path
+ * continues, k != 0 and wi points against the geometric normal (c = dot(wi, N) < 0; > 0 where N is the two-sided flip of it),
+ *     s = min(1e-4 / |c|, 1e30);   weight' = weight' * exp(-(sigma_a[k-1].c * s))     behind weight' = w * f * NoW / pdf (:795)
+ * float32 in this order.  A slab of thickness d crossed at angle theta then absorbs over d / cos(theta) to float32 rounding.
+ *
+ * The rule is stateless: the object whose back face is hit is the one the segment ran inside.  That is exact for closed shapes
+ * that do not overlap.  Overlapping or open shapes, and a camera inside a shape, get exactly this rule and nothing cleverer.
+ * Shadow rays are untouched: a shadow ray through a glass object is occluded by its surface as before.  The feature buffers
+ * report the handle without the medium bits.  A context without media runs the kernels it ran before media existed.
+ */
+typedef struct gsp_medium {
+  float sigma_a[3]; /* absorption coefficient per channel, 1 / length; finite, >= 0 */
+  float reserved;   /* 0 */
+} gsp_medium;
+int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media); /* NULL or 0 = none */
 
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
@@ -1252,6 +1301,7 @@ int gsp_multi_upload_scene(gsp_multi* m, const gsp_scene_desc* scene);
 /* (ABI 5) gsp_update_camera / _instances / _tables on every share */
 int gsp_multi_update_camera(gsp_multi* m, const gsp_camera* camera);
 int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens); /* gsp_set_lens on every share */
+int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_media); /* gsp_set_media on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);
 int gsp_multi_update_tables(gsp_multi* m, const gsp_scene_desc* scene);
 int gsp_multi_frame_begin(gsp_multi* m, uint32_t width, uint32_t height);
