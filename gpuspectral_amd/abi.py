@@ -184,6 +184,21 @@ def media_array(sigmas):
     return (Medium * len(sigmas))(*[Medium((C.c_float * 3)(*s), 0.0) for s in sigmas])
 
 
+# Light selection (include/gpuspectral_pt.h "Light selection")
+LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1
+LIGHT_SAMPLING_NAMES = {"uniform": LIGHTS_UNIFORM, "power": LIGHTS_POWER}
+LIGHT_PICK_DT = np.dtype([("threshold", "<u4"), ("alias", "<u4"), ("pmf_self", "<f4"), ("pmf_alias", "<f4")])  # gsp_light_pick, 16 B
+
+
+def light_sampling_mode(mode):
+    """A mode name or number -> the number gsp_set_light_sampling takes (an unknown number goes through: the library refuses it)."""
+    if isinstance(mode, str):
+        if mode not in LIGHT_SAMPLING_NAMES:
+            raise ValueError("light sampling mode %r: one of %s" % (mode, ", ".join(sorted(LIGHT_SAMPLING_NAMES))))
+        return LIGHT_SAMPLING_NAMES[mode]
+    return int(mode)
+
+
 # LDR film (include/gpuspectral_pt.h "LDR film")
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 TONEMAP_NAMES = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}

@@ -1,0 +1,100 @@
+// Light selection by emitted power (include/gpuspectral_pt.h, "Light selection"): the HOST builder of the alias table that sits
+// behind the light records of a GSP_LIGHTS_POWER context.  Plain C++, no HIP: the library (pt_render_scene.inc pack_tables) and
+// the tests' host emulation (tests/emu/lights_emu.cpp) include this one file, so both hold the same bytes for the same records.
+// The pick that reads the table is device code: sample_light_power, pt_shading.h.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/gpuspectral_pt.h"
+
+namespace gsp {
+
+// w_i = max(Y(radiance), 0) * area, in double, from the caller's (unbaked) record; a non-finite weight counts as 0
+inline double light_pick_weight(const gsp_triangle_light& L) {
+  const double y = 0.2126 * (double)L.radiance[0] + 0.7152 * (double)L.radiance[1] + 0.0722 * (double)L.radiance[2];
+  double a[3], b[3];
+  for (int c = 0; c < 3; ++c) {
+    a[c] = (double)L.positions[2][c] - (double)L.positions[0][c];  // v2 - v0
+    b[c] = (double)L.positions[1][c] - (double)L.positions[0][c];  // v1 - v0
+  }
+  const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+  const double w = (y > 0.0 ? y : 0.0) * (0.5 * std::sqrt(cx * cx + cy * cy + cz * cz));
+  return std::isfinite(w) ? w : 0.0;
+}
+
+// Vose's alias construction over weights w[0..n) -> out[0..n).  Deterministic: both work lists are filled in ascending index
+// and consumed from the front; an entry that turns from large to small or stays large is appended at the back of its list.
+// Weights that are not finite or not positive count as 0; if every weight is 0, every weight becomes 1.
+inline void build_light_pick_from_weights(const double* w_in, uint32_t n, gsp_light_pick* out) {
+  if (n == 0) return;
+  std::vector<double> s(n);
+  double sum = 0.0;
+  for (uint32_t i = 0; i < n; ++i) {
+    s[i] = (std::isfinite(w_in[i]) && w_in[i] > 0.0) ? w_in[i] : 0.0;
+    sum += s[i];
+  }
+  if (!(sum > 0.0) || !std::isfinite(sum)) {
+    // (all zero -- or a sum beyond double: scaled down first, and all ones if that does not help)
+    double big = 0.0;
+    for (uint32_t i = 0; i < n; ++i) big = s[i] > big ? s[i] : big;
+    sum = 0.0;
+    for (uint32_t i = 0; i < n; ++i) {
+      s[i] = big > 0.0 ? s[i] / big : 1.0;
+      sum += s[i];
+    }
+  }
+  for (uint32_t i = 0; i < n; ++i) s[i] = s[i] * (double)n / sum;
+  std::vector<uint32_t> small, large, alias(n);
+  small.reserve(n);
+  large.reserve(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    alias[i] = i;
+    (s[i] < 1.0 ? small : large).push_back(i);
+  }
+  std::vector<double> self(n, 1.0);  // s'_j: the share of slot j that stays with j
+  size_t si = 0, li = 0;
+  while (si < small.size() && li < large.size()) {
+    const uint32_t a = small[si++], g = large[li];
+    self[a] = s[a];
+    alias[a] = g;
+    s[g] = (s[g] + s[a]) - 1.0;
+    if (s[g] < 1.0) {
+      ++li;
+      small.push_back(g);
+    }
+  }
+  // (what is left on either list is 1 up to rounding: always self)
+  const double two32 = 4294967296.0;
+  std::vector<double> T(n);
+  for (uint32_t j = 0; j < n; ++j) {
+    double t = std::floor(self[j] * two32 + 0.5);  // round(s'_j * 2^32)
+    if (!(t >= 0.0)) t = 0.0;
+    if (t >= 4294967295.0 || alias[j] == j) {  // saturated: always self
+      out[j].threshold = 0xffffffffu;
+      out[j].alias = j;
+      T[j] = two32;
+    } else {
+      out[j].threshold = (uint32_t)t;
+      out[j].alias = alias[j];
+      T[j] = t;
+    }
+  }
+  // the probability the integer table implies: p_i = (T_i + sum over j aliased to i of (2^32 - T_j)) / (n * 2^32)
+  std::vector<double> mass(T);
+  for (uint32_t j = 0; j < n; ++j)
+    if (out[j].alias != j) mass[out[j].alias] += two32 - T[j];
+  for (uint32_t j = 0; j < n; ++j) {
+    out[j].pmf_self = (float)(mass[j] / ((double)n * two32));
+    out[j].pmf_alias = (float)(mass[out[j].alias] / ((double)n * two32));
+  }
+}
+
+inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, gsp_light_pick* out) {
+  std::vector<double> w(n);
+  for (uint32_t i = 0; i < n; ++i) w[i] = light_pick_weight(lights[i]);
+  build_light_pick_from_weights(w.data(), n, out);
+}
+
+}  // namespace gsp

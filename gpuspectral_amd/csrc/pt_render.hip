@@ -46,6 +46,7 @@
 
 #include "pt_hostmath.h"
 #include "pt_internal.h"
+#include "pt_lightpick.h"
 #include "pt_versions.h"
 #include "pt_wavetrace.h"
 #include "pt_features.h"
@@ -158,6 +159,9 @@ struct gsp_context {
   DevBuf<gsp_medium> media;
   std::vector<gsp_medium> h_media;
   uint32_t num_media = 0;
+  // light selection (gsp_set_light_sampling): context state like the lens.  GSP_LIGHTS_POWER selects the <LSEL> kernels and makes
+  // pack_tables append the alias table behind the light records of every table image
+  uint32_t light_mode = GSP_LIGHTS_UNIFORM;
   double bvh_build_ms = 0.0;
   // what gsp_upload_scene leaves resident for the per-frame edits (gsp_update_instances re-bakes from it, as the reference
   // keeps the BLAS of a mesh and rebuilds the TLAS, Renderer.cpp:122-131 / PathTracer.cpp:10-19): the object-space

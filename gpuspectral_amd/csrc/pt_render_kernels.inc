@@ -342,7 +342,9 @@ constexpr int kShadeWaves = kShadeBlock / 64;
 // MED: the context holds interior media (gsp_set_media): shade_vertex<.., MED = true> reads the medium number of the hit and the
 // table behind SceneViewMed::media (16 B per medium, from L2: a handful of entries that only back-face vertices of glass read).
 // Only these instantiations take the larger view: the kernels of a context without media keep their argument layout
-template <bool TEX, bool VER, bool MED>
+// LSEL: the context picks its light by emitted power (gsp_set_light_sampling): shade_vertex<.., LSEL = true> reads the alias table
+// behind the light records -- part of the table image, so it is staged into LDS with it and has a copy in every version
+template <bool TEX, bool VER, bool MED, bool LSEL>
 __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
                                                         const q4* __restrict__ hits, PathQueue nxt, ShadowQueue sq,
                                                         q4* __restrict__ result, uint32_t* __restrict__ tails,
@@ -492,7 +494,7 @@ __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typen
         in.weight = mk3(p2.x, p2.y, p2.z);
         in.directWeight = p2.w;
         in.flags = fl;
-        shade_vertex<TEX, VER, MED>(S, rc, in, h, out, view_media(S));
+        shade_vertex<TEX, VER, MED, LSEL>(S, rc, in, h, out, view_media(S));
         alive = out.alive;
         has_shadow = out.has_shadow;
         ++shaded;
@@ -647,7 +649,7 @@ struct FinishStack {
   __device__ __forceinline__ uint32_t pop() { return col[(--top) * kBlock]; }
 };
 
-template <bool TEX, bool VER, bool MED>
+template <bool TEX, bool VER, bool MED, bool LSEL>
 __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
                                                     q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                     uint32_t* __restrict__ live,
@@ -705,7 +707,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED>::ty
         break;
       }
       ShadeOut out;
-      shade_vertex<TEX, VER, MED>(S, rc, in, h, out, view_media(S));
+      shade_vertex<TEX, VER, MED, LSEL>(S, rc, in, h, out, view_media(S));
       ++shaded;
       if (!out.has_shadow) {
         add_emitted(rc.clamp, out.emitted, res);

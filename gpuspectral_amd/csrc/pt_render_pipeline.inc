@@ -117,25 +117,30 @@ static void launch_trace(const gsp_context* ctx, hipStream_t st, const SceneView
   with_hit_rule(std::false_type{}, view, io);
 }
 
-// k_shade / k_finish <TEX, VER, MED>: TEX = the scene has textures or an environment map, VER = V.multi_version, MED = the context holds
-// interior media (gsp_set_media); launch(TEX, VER, MED, view) gets them as std::integral_constant values (as atrous_level,
-// pt_render_post.inc).  These kernels read V.vview -- the versioned view exactly when VER -- and the <MED> ones the table behind it.
+// k_shade / k_finish <TEX, VER, MED, LSEL>: TEX = the scene has textures or an environment map, VER = V.multi_version, MED = the context
+// holds interior media (gsp_set_media), LSEL = it picks its light by emitted power (gsp_set_light_sampling); launch(TEX, VER, MED, LSEL, view)
+// gets them as std::integral_constant values (as atrous_level, pt_render_post.inc).  These kernels read V.vview -- the versioned view
+// exactly when VER -- and the <MED> ones the table behind it.
 template <class Launch>
 static void tex_ver_med_kernel(const gsp_context* ctx, const LiveVersions& V, Launch&& launch) {
-  const auto with_view = [&](auto TEX, auto VER) {
+  const auto with_view = [&](auto TEX, auto VER, auto LSEL) {
     if (ctx->num_media != 0) {
       SceneViewMed mv;
       static_cast<SceneView&>(mv) = V.vview;
       mv.media = ctx->media.p;
-      launch(TEX, VER, std::true_type{}, mv);
+      launch(TEX, VER, std::true_type{}, LSEL, mv);
     } else {
-      launch(TEX, VER, std::false_type{}, V.vview);
+      launch(TEX, VER, std::false_type{}, LSEL, V.vview);
     }
   };
-  if (V.multi_version && ctx->textured) with_view(std::true_type{}, std::true_type{});
-  else if (V.multi_version) with_view(std::false_type{}, std::true_type{});
-  else if (ctx->textured) with_view(std::true_type{}, std::false_type{});
-  else with_view(std::false_type{}, std::false_type{});
+  const auto with_pick = [&](auto TEX, auto VER) {
+    if (ctx->light_mode == GSP_LIGHTS_POWER) with_view(TEX, VER, std::true_type{});
+    else with_view(TEX, VER, std::false_type{});
+  };
+  if (V.multi_version && ctx->textured) with_pick(std::true_type{}, std::true_type{});
+  else if (V.multi_version) with_pick(std::false_type{}, std::true_type{});
+  else if (ctx->textured) with_pick(std::true_type{}, std::false_type{});
+  else with_pick(std::false_type{}, std::false_type{});
 }
 }  // extern "C++"
 
@@ -239,8 +244,8 @@ static int finish_few_paths(gsp_context* ctx, gsp_context::Lane& L, const Render
   if (!(drain && L.queued == 0 && P.remaining == 0 && P.n > 0 && P.n <= ctx->finish_paths && ctx->pipe_params.collect_traversal_stats == 0 &&
         std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 <= kFinishLevels))
     return GSP_OK;
-  tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, const auto& sview) {
-    hipLaunchKernelGGL((k_finish<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value>), dim3((uint32_t)((P.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, sview, rcst,
+  tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
+    hipLaunchKernelGGL((k_finish<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value>), dim3((uint32_t)((P.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, sview, rcst,
                        (uint32_t)P.n, lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq), L.counters.p + C_LIVE, (uint32_t)P.batch_paths, ctx->dstats.p);
   });
   CTX_TRY(ctx, hipGetLastError());
@@ -306,8 +311,8 @@ static int trace_shade_connect(gsp_context* ctx, gsp_context::Lane& L, const Ren
   CTX_TRY(ctx, hipGetLastError());
   if (ev) CTX_TRY(ctx, hipEventRecord(ev[1], st));
   const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + kShadeBlock - 1) / kShadeBlock, shade_resident_blocks(ctx))));
-  tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, const auto& sview) {
-    hipLaunchKernelGGL((k_shade<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value>), grid, dim3(kShadeBlock), 0, st, sview, rcst, n_ptr, cur, hits, next, sq,
+  tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
+    hipLaunchKernelGGL((k_shade<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value>), grid, dim3(kShadeBlock), 0, st, sview, rcst, n_ptr, cur, hits, next, sq,
                        L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths, room_chunk, ctx->dstats.p);
   });
   CTX_TRY(ctx, hipGetLastError());
@@ -1261,6 +1266,75 @@ int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media)
     CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lanes' streams read it)
   }
   ctx->num_media = n;
+  return GSP_OK;
+}
+
+// ---- light selection (include/gpuspectral_pt.h, "Light selection") ----
+static_assert(sizeof(gsp_light_pick) == 16 && sizeof(gsp_triangle_light) % 16 == 0, "the pick table starts straight behind the light records, on a 16-byte boundary");
+int gsp_set_light_sampling(gsp_context* ctx, uint32_t mode) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (mode != GSP_LIGHTS_UNIFORM && mode != GSP_LIGHTS_POWER) {
+    ctx->err = "gsp_set_light_sampling: unknown mode";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight were generated under the mode as it was
+  if (rc != GSP_OK) return rc;
+  if (mode == ctx->light_mode) return GSP_OK;
+  const uint32_t old_mode = ctx->light_mode;
+  ctx->light_mode = mode;
+  if (!ctx->have_scene || ctx->h_tables.size() < TableImage::kHead) return GSP_OK;
+  // a resident scene: its tables are packed again from the context's host copy (the caller's records, as they came) and uploaded
+  // behind the drain, with or without the pick table
+  gsp_scene_desc sc{};
+  uint64_t counts[9];
+  std::memcpy(counts, ctx->h_tables.data(), sizeof(counts));
+  const uint8_t* tb = ctx->h_tables.data() + TableImage::kHead;
+  for (int k = 0; k < GSP_BSDF_TYPE_COUNT; ++k) sc.num_bsdfs[k] = (uint32_t)counts[k];
+  sc.diffuse_bsdfs = (const gsp_diffuse_bsdf*)(tb + ctx->table_off[0]);
+  sc.smooth_dielectric_bsdfs = (const gsp_smooth_dielectric_bsdf*)(tb + ctx->table_off[1]);
+  sc.smooth_conductor_bsdfs = (const gsp_smooth_conductor_bsdf*)(tb + ctx->table_off[2]);
+  sc.smooth_plastic_bsdfs = (const gsp_smooth_plastic_bsdf*)(tb + ctx->table_off[3]);
+  sc.rough_conductor_bsdfs = (const gsp_rough_conductor_bsdf*)(tb + ctx->table_off[4]);
+  sc.smooth_floor_bsdfs = (const gsp_smooth_floor_bsdf*)(tb + ctx->table_off[5]);
+  sc.rough_floor_bsdfs = (const gsp_rough_floor_bsdf*)(tb + ctx->table_off[6]);
+  sc.rough_plastic_bsdfs = (const gsp_rough_plastic_bsdf*)(tb + ctx->table_off[7]);
+  sc.lights = (const gsp_triangle_light*)(tb + ctx->table_off[8]);
+  sc.num_lights = (uint32_t)counts[8];
+  TableImage img;
+  rc = pack_tables(ctx, &sc, img);  // (copies out of h_tables into the new image; upload_tables then swaps the two)
+  if (rc == GSP_OK) rc = upload_tables(ctx, &sc, img);
+  if (rc != GSP_OK) {
+    ctx->light_mode = old_mode;
+    ctx->have_scene = false;
+    return rc;
+  }
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return GSP_OK;
+}
+
+int gsp_download_light_pick(gsp_context* ctx, gsp_light_pick* out, uint32_t capacity, uint32_t* count) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (count) *count = ctx->have_scene ? ctx->num_lights : 0u;
+  if (ctx->light_mode != GSP_LIGHTS_POWER) {
+    ctx->err = "gsp_download_light_pick: the context is in GSP_LIGHTS_UNIFORM mode (no table)";
+    return GSP_ERR_INVALID;
+  }
+  if (!ctx->have_scene) {
+    ctx->err = "gsp_download_light_pick: no scene";
+    return GSP_ERR_INVALID;
+  }
+  if (capacity < ctx->num_lights || (!out && ctx->num_lights)) {
+    ctx->err = "gsp_download_light_pick: capacity below the number of lights";
+    return GSP_ERR_INVALID;
+  }
+  if (ctx->num_lights == 0) return GSP_OK;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  // the resident table of the CURRENT table version (samples in flight may still read older ones)
+  const uint8_t* base = ctx->tables.p + (size_t)ctx->tab.slot_of(ctx->tab.ver) * ctx->tab.slot_bytes;
+  const size_t off = ctx->table_off[8] + sizeof(gsp_triangle_light) * (size_t)ctx->num_lights;
+  CTX_TRY(ctx, hipMemcpyAsync(out, base + off, sizeof(gsp_light_pick) * (size_t)ctx->num_lights, hipMemcpyDeviceToHost, ctx->stream));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return GSP_OK;
 }
 

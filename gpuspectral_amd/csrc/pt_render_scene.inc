@@ -61,11 +61,12 @@ static int drain_for_edit(gsp_context* ctx) {
 static constexpr size_t kRecordBytes[9] = {sizeof(gsp_diffuse_bsdf), sizeof(gsp_smooth_dielectric_bsdf), sizeof(gsp_smooth_conductor_bsdf),
                                            sizeof(gsp_smooth_plastic_bsdf), sizeof(gsp_rough_conductor_bsdf), sizeof(gsp_smooth_floor_bsdf),
                                            sizeof(gsp_rough_floor_bsdf), sizeof(gsp_rough_plastic_bsdf), sizeof(gsp_triangle_light)};
-// The eight BSDF arrays + the lights of `sc`, packed back to back (16-B aligned each) as they sit in the context's one table
+// The eight BSDF arrays + the lights (+ in GSP_LIGHTS_POWER mode their alias table) of `sc`, packed back to back (16-B aligned each) as they sit in the context's one table
 // allocation; the counts ride in front of the image so that "equal images" means equal tables.
 struct TableImage {
   std::vector<uint8_t> bytes;  // [9 x uint64 count][tables ...]: the device holds bytes.data() + kHead onwards
   size_t off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, total = 0;
+  size_t pick_off = 0;         // the light pick table (GSP_LIGHTS_POWER only): == off[8] + 64 * num_lights
   static constexpr size_t kHead = 9 * sizeof(uint64_t);
 };
 static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& img) {
@@ -87,10 +88,17 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
     img.off[k] = img.total;
     img.total += (bytes[k] + 15) & ~(size_t)15;
   }
+  // GSP_LIGHTS_POWER: a tenth sub-table, the alias table of the lights (pt_lightpick.h), straight behind the light records (64 B
+  // each: no padding in between), so that (const gsp_light_pick*)(lights + num_lights) finds it.  Absent in uniform mode: such a
+  // context keeps the image size, and so the LDS staging decision, it always had
+  const bool pick = ctx->light_mode == GSP_LIGHTS_POWER && sc->num_lights != 0;
+  img.pick_off = img.total;
+  if (pick) img.total += sizeof(gsp_light_pick) * (size_t)sc->num_lights;
   img.bytes.assign(TableImage::kHead + std::max<size_t>(img.total, 16), 0);
   std::memcpy(img.bytes.data(), counts, sizeof(counts));
   for (int k = 0; k < 9; ++k)
     if (bytes[k]) std::memcpy(img.bytes.data() + TableImage::kHead + img.off[k], src[k], bytes[k]);
+  if (pick) build_light_pick(sc->lights, sc->num_lights, (gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off));
   return GSP_OK;
 }
 // image -> device, as the NEXT version of the tables (queued on the context's stream; the image becomes the context's host copy,

@@ -719,4 +719,56 @@ GSP_HD LightSample sample_light(const gsp_triangle_light* lights, uint32_t num_l
   return ls;
 }
 
+// GSP_LIGHTS_POWER (include/gpuspectral_pt.h, "Light selection"): the light is drawn in proportion to Y(radiance) * area through
+// the alias table `pick` (num_lights entries of 16 B, built on the host: pt_lightpick.h; resident straight behind the light
+// records).  The same three draws as sample_light, so the random streams of the two modes coincide from the light sample on.
+// The 64-bit product r * num_lights gives the slot (high word) and an independent 32-bit coin (low word) from the one draw;
+// the point on the light and the solid-angle pdf are sample_light's, with the stored pmf of the picked light for 1 / num_lights.
+struct alignas(16) LightPickQuad {  // gsp_light_pick, with the alignment its place in the table image gives it
+  uint32_t threshold, alias;
+  float pmf_self, pmf_alias;
+};
+// the pick itself: draw r -> light index and its stored pmf.  num_lights != 0
+GSP_HD uint32_t light_pick_index(const gsp_light_pick* pick, uint32_t num_lights, uint32_t r, float& pmf) {
+  const uint64_t m = (uint64_t)r * (uint64_t)num_lights;
+  const uint32_t j = (uint32_t)(m >> 32), lo = (uint32_t)m;
+  const LightPickQuad E = *(const LightPickQuad*)(pick + j);  // one 16-byte load (the table starts on a 16-byte boundary)
+  const bool self = lo < E.threshold || E.threshold == 0xffffffffu;
+  pmf = self ? E.pmf_self : E.pmf_alias;
+  return self ? j : E.alias;
+}
+GSP_HD LightSample sample_light_power(const gsp_triangle_light* lights, const gsp_light_pick* pick, uint32_t num_lights, uint32_t& rng, f3 pos) {
+  LightSample ls;
+  uint32_t r = pcg_next(rng);
+  float e1 = rand_uniform(rng);
+  float e2 = rand_uniform(rng);
+  if (num_lights == 0) {  // as sample_light: no light, zero pdf
+    ls.position = pos;
+    ls.emission = splat(0.0f);
+    ls.pdf = 0.0f;
+    return ls;
+  }
+  float pmf;
+  const gsp_triangle_light* L = lights + light_pick_index(pick, num_lights, r, pmf);
+  float se1 = gsqrt(e1);
+  float u = 1.0f - se1;
+  float v = e2 * se1;
+  float w = (1.0f - u) - v;
+  f3 v0 = ld3(L->positions[0]);
+  f3 v1 = ld3(L->positions[1]);
+  f3 v2 = ld3(L->positions[2]);
+  float A = L->radiance[3];
+  f3 normal = mk3(L->positions[0][3], L->positions[1][3], L->positions[2][3]);
+  f3 lightPos = (u * v0 + v * v1) + w * v2;
+  f3 toL = lightPos - pos;
+  float ldist = length(toL);
+  f3 l = normalize(toL);
+  float c = dot(-l, normal);
+  ls.position = lightPos;
+  ls.emission = ld3(L->radiance) * (c > 0.0f ? 1.0f : 0.0f);
+  ls.pdf = (ldist * ldist) / (gabs(c) * A);
+  ls.pdf = ls.pdf * pmf;
+  return ls;
+}
+
 }  // namespace gsp

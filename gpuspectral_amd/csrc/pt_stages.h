@@ -312,7 +312,10 @@ struct ShadeOut {
 // medium of the hit object, and a vertex on a BACK face scales the path weight by exp(-sigma_a * t) of the segment that ran inside
 // it.  MED = false is the code of a context without media, instruction for instruction (no handle carries those bits then);
 // `media` (MED only) = the table, view_media() of the view the kernel was handed.
-template <bool TEX = false, bool VER = false, bool MED = false>
+// LSEL: the context picks its light by emitted power (include/gpuspectral_pt.h, "Light selection"): sample_light_power reads the
+// alias table that sits straight behind the light records of this vertex's version of the tables (LDS or global, wherever the
+// lights are).  LSEL = false is the reference's uniform pick, instruction for instruction.
+template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false>
 GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
                          ShadeOut& out, const gsp_medium* media = nullptr) {
   uint32_t rng = in.seed;                                                 // rchit:668
@@ -389,7 +392,8 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   const float NoW = gabs(wi_l.z);                                         // :717
   const f3 wi = to_world(onb, wi_l);                                      // :718
 
-  const LightSample ls = sample_light(lights, S.num_lights, S.inv_num_lights, rng, position);  // :720
+  const LightSample ls = LSEL ? sample_light_power(lights, (const gsp_light_pick*)(lights + S.num_lights), S.num_lights, rng, position)
+                              : sample_light(lights, S.num_lights, S.inv_num_lights, rng, position);  // :720
   const f3 toL = ls.position - position;
   const f3 L = normalize(toL);                                            // :722
   const f3 wL = to_local(onb, L);                                         // :723

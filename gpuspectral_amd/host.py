@@ -105,6 +105,8 @@ def load():
     L.gsph_pathtracer_download_temporal_moments.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_download_temporal_svgf.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp, u64]
     L.gsph_pathtracer_temporal_follow_instances.argtypes = [vp, C.c_int]
+    L.gsph_pathtracer_set_light_sampling.argtypes = [vp, u32]
+    L.gsph_pathtracer_download_light_pick.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.gsph_pathtracer_download_temporal_motion.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_temporal_demodulate.argtypes = [vp, C.c_int]
     L.gsph_pathtracer_download_temporal_image.argtypes = [vp, vp, u64]
@@ -443,6 +445,18 @@ class PathTracer:
         self._check(self._L.gsph_pathtracer_download_temporal_svgf(self._h, C.byref(denoise) if denoise is not None else None,
                                                                    C.byref(svgf) if svgf is not None else None, out.ctypes.data, out.size),
                     "downloadTemporalSvgf")
+        return out
+
+    def set_light_sampling(self, mode):
+        """PathTracer::setLightSampling: "uniform" (the reference's pick) or "power" (gpuspectral_pt.h "Light selection")."""
+        self._check(self._L.gsph_pathtracer_set_light_sampling(self._h, abi.light_sampling_mode(mode)), "setLightSampling")
+
+    def download_light_pick(self):
+        """PathTracer::downloadLightPick: the resident alias table as an abi.LIGHT_PICK_DT array."""
+        n = C.c_uint32(0)
+        self._L.gsph_pathtracer_download_light_pick(self._h, None, 0, C.byref(n))  # (the count)
+        out = np.zeros(n.value, abi.LIGHT_PICK_DT)
+        self._check(self._L.gsph_pathtracer_download_light_pick(self._h, out.ctypes.data if n.value else None, n.value, C.byref(n)), "downloadLightPick")
         return out
 
     def temporal_follow_instances(self, on=True):

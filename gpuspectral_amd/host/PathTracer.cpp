@@ -336,6 +336,16 @@ std::vector<float> PathTracer::downloadTemporalSvgf(const gsp_denoise* denoise, 
   return out;
 }
 
+void PathTracer::setLightSampling(uint32_t mode) { check(gsp_set_light_sampling(ctx, mode), "gsp_set_light_sampling"); }
+
+std::vector<gsp_light_pick> PathTracer::downloadLightPick() {
+  uint32_t n = 0;
+  (void)gsp_download_light_pick(ctx, nullptr, 0, &n);  // (the count; the call below reports what is wrong)
+  std::vector<gsp_light_pick> out(n);
+  check(gsp_download_light_pick(ctx, out.data(), n, &n), "gsp_download_light_pick");
+  return out;
+}
+
 void PathTracer::temporalFollowInstances(bool on) { check(gsp_temporal_follow_instances(ctx, on ? 1 : 0), "gsp_temporal_follow_instances"); }
 
 std::vector<float> PathTracer::downloadTemporalMotion() {
@@ -427,6 +437,8 @@ MultiGpuPathTracer::~MultiGpuPathTracer() { gsp_multi_destroy(multi); }
 void MultiGpuPathTracer::check(int rc, const char* what) {
   if (rc != GSP_OK) throw std::runtime_error(std::string(what) + ": " + gsp_multi_last_error(multi));
 }
+
+void MultiGpuPathTracer::setLightSampling(uint32_t mode) { check(gsp_multi_set_light_sampling(multi, mode), "gsp_multi_set_light_sampling"); }
 
 void MultiGpuPathTracer::reset() {
   timestamp = 0;

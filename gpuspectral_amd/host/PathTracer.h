@@ -82,6 +82,10 @@ class PathTracer : public RenderPassCreator {
   // Forget what was uploaded: the next pass uploads everything.  Needed only after texel CONTENTS of a texture or
   // environment map were rewritten in place (dormant features; sizes and flags are tracked, contents are not).
   void invalidateScene() { tracker.forget(); }
+  // Light selection (gpuspectral_pt.h "Light selection"): GSP_LIGHTS_UNIFORM (the reference's pick, the default) or GSP_LIGHTS_POWER
+  // (by emitted power).  Context state: it holds across scenes; reset() after a change starts a frame of one estimator.
+  void setLightSampling(uint32_t mode);
+  std::vector<gsp_light_pick> downloadLightPick();  // the resident alias table (GSP_LIGHTS_POWER with a scene uploaded)
 
   // RGBA32F, row-major, width*height*4 floats (running mean, alpha 1)
   std::vector<float> download();
@@ -193,6 +197,7 @@ class MultiGpuPathTracer : public RenderPassCreator {
   void render(const Scene& scene, uint32_t spp);
   void prepareScene(const Scene& scene);  // as PathTracer::prepareScene, on every share
   void invalidateScene() { tracker.forget(); }
+  void setLightSampling(uint32_t mode);  // as PathTracer::setLightSampling, on every share
   std::vector<float> download();  // RGBA32F, row-major, width*height*4 floats
   std::vector<uint32_t> downloadDisplay();  // as PathTracer::downloadDisplay, on the gathered frame
   void renderFeatures(const Scene& scene, uint32_t spp);  // as PathTracer::renderFeatures, on every share

@@ -386,6 +386,18 @@ int gsph_pathtracer_download_temporal_svgf(void* pt, const gsp_denoise* denoise,
   });
 }
 // moved instances of a PathTracer (gpuspectral_pt.h "Temporal accumulation: moved instances")
+// PathTracer::setLightSampling / downloadLightPick (out: `capacity` entries of 16 B; returns through *count)
+int gsph_pathtracer_set_light_sampling(void* pt, uint32_t mode) {
+  return guard([&] { ((PathTracer*)pt)->setLightSampling(mode); });
+}
+int gsph_pathtracer_download_light_pick(void* pt, gsp_light_pick* out, uint32_t capacity, uint32_t* count) {
+  return guard([&] {
+    auto t = ((PathTracer*)pt)->downloadLightPick();
+    if (count) *count = (uint32_t)t.size();
+    if (t.size() > capacity) throw std::runtime_error("downloadLightPick: capacity below the number of lights");
+    if (!t.empty()) std::memcpy(out, t.data(), t.size() * sizeof(gsp_light_pick));
+  });
+}
 int gsph_pathtracer_temporal_follow_instances(void* pt, int on) {
   return guard([&] { ((PathTracer*)pt)->temporalFollowInstances(on != 0); });
 }

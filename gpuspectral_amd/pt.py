@@ -29,6 +29,8 @@ EXPORTS = (
     "gsp_update_tables",
     "gsp_set_lens",
     "gsp_set_media",
+    "gsp_set_light_sampling",
+    "gsp_download_light_pick",
     "gsp_focus_distance",
     "gsp_frame_begin",
     "gsp_render",
@@ -92,6 +94,7 @@ EXPORTS = (
     "gsp_multi_update_camera",
     "gsp_multi_set_lens",
     "gsp_multi_set_media",
+    "gsp_multi_set_light_sampling",
     "gsp_multi_update_instances",
     "gsp_multi_update_tables",
     "gsp_multi_frame_begin",
@@ -147,6 +150,9 @@ def load():
     L.gsp_multi_set_lens.argtypes = [vp, C.POINTER(abi.Lens)]
     L.gsp_set_media.argtypes = [vp, C.POINTER(abi.Medium), u32]
     L.gsp_multi_set_media.argtypes = [vp, C.POINTER(abi.Medium), u32]
+    L.gsp_set_light_sampling.argtypes = [vp, u32]
+    L.gsp_download_light_pick.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.gsp_multi_set_light_sampling.argtypes = [vp, u32]
     L.gsp_update_instances.argtypes = [vp, vp, u32]
     L.gsp_update_tables.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_ctx_destroy.argtypes = [vp]
@@ -253,7 +259,7 @@ def build_info():
 
 
 # the files csrc/Makefile hashes into the digest, in its order
-DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_math.h", "pt_shading.h",
+DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
                   "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
 
 
@@ -346,6 +352,18 @@ class Context:
         coefficients; medium number k of abi.bsdf_handle(.., medium=k) is sigmas[k - 1].  None or empty = no media."""
         arr = abi.media_array(sigmas)
         self._check(self._L.gsp_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_media")
+
+    def set_light_sampling(self, mode):
+        """gsp_set_light_sampling (gpuspectral_pt.h "Light selection"): "uniform" / "power" or abi.LIGHTS_UNIFORM / LIGHTS_POWER."""
+        self._check(self._L.gsp_set_light_sampling(self._h, abi.light_sampling_mode(mode)), "gsp_set_light_sampling")
+
+    def download_light_pick(self):
+        """gsp_download_light_pick: the resident alias table as an abi.LIGHT_PICK_DT array, one entry per light triangle."""
+        n = C.c_uint32(0)
+        self._L.gsp_download_light_pick(self._h, None, 0, C.byref(n))  # (the count; the call itself may be refused)
+        out = np.zeros(n.value, abi.LIGHT_PICK_DT)
+        self._check(self._L.gsp_download_light_pick(self._h, out.ctypes.data if n.value else None, n.value, C.byref(n)), "gsp_download_light_pick")
+        return out
 
     def focus_distance(self, width, height, fx, fy):
         """gsp_focus_distance: camera-space depth of what the pinhole ray through fragCoord (fx, fy) hits, 0.0 on a miss."""
@@ -798,6 +816,10 @@ class MultiContext:
         """gsp_multi_set_media: Context.set_media on every share."""
         arr = abi.media_array(sigmas)
         self._check(self._L.gsp_multi_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_media")
+
+    def set_light_sampling(self, mode):
+        """gsp_multi_set_light_sampling: Context.set_light_sampling on every share."""
+        self._check(self._L.gsp_multi_set_light_sampling(self._h, abi.light_sampling_mode(mode)), "gsp_multi_set_light_sampling")
 
     def update_instances(self, instances):
         inst = np.ascontiguousarray(instances, abi.INSTANCE_DT)

@@ -83,7 +83,9 @@ extern "C" {
                                 gsp_temporal_antilag, gsp_download_temporal_fast, gsp_temporal_fast_to_device (see "Temporal
                                 anti-lag"); gsp_temporal_taa, gsp_temporal_taa_from_device, gsp_download_taa,
                                 gsp_download_taa_display, gsp_taa_display_to_device (see "Temporal anti-aliasing");
-                                gsp_set_media, gsp_multi_set_media (see "Interior media") */
+                                gsp_set_media, gsp_multi_set_media (see "Interior media");
+                                gsp_set_light_sampling, gsp_download_light_pick, gsp_multi_set_light_sampling (see "Light
+                                selection") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -626,6 +628,69 @@ typedef struct gsp_medium {
   float reserved;   /* 0 */
 } gsp_medium;
 int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media); /* NULL or 0 = none */
+
+/*
+ * Light selection: opt-in choice of the light for next-event estimation in proportion to its emitted power.
+ *
+ * The reference picks the light triangle as r % num_lights (rayhit.rchit:148): every triangle is equally likely whatever it
+ * emits.  GSP_LIGHTS_UNIFORM is that pick, bit for bit, with the kernels a context ran before this section existed.
+ * GSP_LIGHTS_POWER picks light i with a probability proportional to w_i = Y(radiance_i) * area_i through an alias table.  The
+ * rest of the vertex is the reference's: the point on the light, the solid-angle pdf, the power heuristic, the emitter-hit weight
+ * formed from the NEE sample's pdf (directWeight, rchit:786).
+ *
+ * The mode is CONTEXT STATE, like the lens and the media: gsp_set_light_sampling(ctx, mode) holds until changed and survives
+ * gsp_upload_scene.  It may be called with a scene resident: the samples in flight finish first (the wait of every scene edit),
+ * then the tables are packed again from the context's host copy and uploaded, with or without the pick table.  An unknown mode
+ * is GSP_ERR_INVALID and leaves the state unchanged.
+ *
+ * The table.  One gsp_light_pick per light triangle, straight behind the light records of the resident table image (so it is
+ * staged into LDS with them when the image is at most 8192 bytes, and every table version of gsp_update_tables has its own).
+ * Built on the host, in double, from the caller's records as they came:
+ *     w_i = max(0.2126 R + 0.7152 G + 0.0722 B, 0) * 0.5 |cross(v2 - v0, v1 - v0)|;  a non-finite or negative w_i counts as 0;
+ *     if every w_i is 0, every w_i becomes 1
+ *     s_i = w_i * n / sum(w)
+ * Vose's alias construction on s, in a fixed order: the lists "small" (s_i < 1) and "large" (s_i >= 1) are filled in ascending
+ * index; while both hold an entry, the FRONT small entry a is finished against the FRONT large entry g: s'_a = s_a, alias_a = g,
+ * s_g = (s_g + s_a) - 1; if s_g < 1 now, g leaves the front of "large" and is appended at the BACK of "small".  What is left
+ * on either list has s' = 1.  The same records therefore always give the same table bytes.  Entry j:
+ *     threshold = round(s'_j * 2^32) as an integer, saturated to 0xffffffff; 0xffffffff means "always self" (2^32)
+ *     alias     = the donor g; j itself where the threshold is saturated
+ *     pmf_self  = float32(p_j),  pmf_alias = float32(p_alias),  with the probability the INTEGER table implies, in double:
+ *     p_i = (T_i + sum over j != i with alias_j = i of (2^32 - T_j)) / (n * 2^32),   T = 2^32 for a saturated entry
+ * so the pdf the estimator divides by is the pdf it samples with, to float32 rounding; |p_i - w_i / sum(w)| is at most
+ * (1 + d_i) / (n * 2^32), d_i = the entries aliased to i.  A light of weight 0 has threshold 0 and is nobody's alias: p = 0,
+ * never picked.  So is a VERY WEAK light: one whose share of sum(w) is below about 2^-33 / n rounds to threshold 0 and is
+ * dropped.
+ *
+ * The pick, in the shading vertex where the reference draws its light (the same three draws, so the random streams of the two
+ * modes coincide from the light sample on); uint32 / uint64 integer operations and float32 in this order:
+ *     r = pcg_next(rng);  e1 = rand_uniform(rng);  e2 = rand_uniform(rng)
+ *     m = (uint64)r * num_lights;   j = (uint32)(m >> 32);   lo = (uint32)m
+ *     E = pick[j];   self = lo < E.threshold || E.threshold == 0xffffffff
+ *     k = self ? j : E.alias;        pmf = self ? E.pmf_self : E.pmf_alias
+ *     the point on light k, c and A exactly as the uniform pick forms them;   pdf = ((ldist * ldist) / (|c| * A)) * pmf
+ * The high word of the product is the slot, the low word an independent 32-bit coin.  num_lights == 0: no light, pdf 0, as before.
+ *
+ * What changes and what does not.  The path's continuation (BSDF sample, weight, Russian roulette) does not read the light
+ * sample: extension rays and shaded vertices are those of the uniform mode, only the shadow rays differ; with disable_nee the
+ * two modes give the same frame, and so they do with one light triangle (pmf = 1.0f = 1 / num_lights, j = 0).  THE EXPECTED
+ * IMAGE SHIFTS SLIGHTLY between the modes: the reference's emitter-hit weight is formed from the pdf of the vertex's own NEE
+ * sample, not from the pdf of the light that was hit (its documented departure from textbook multiple importance sampling,
+ * rchit:763-790), and that pdf depends on the selection density.  Where BSDF-sampled emitter hits matter, the two modes
+ * therefore converge to slightly different images.  Both are the reference's estimator with a selection density; neither is
+ * the textbook estimator.
+ *
+ * gsp_download_light_pick reads the resident table of the current table version: count receives the number of light
+ * triangles; GSP_ERR_INVALID in uniform mode, without a scene, or when capacity < that number.
+ */
+#define GSP_LIGHTS_UNIFORM 0u /* r % num_lights, rayhit.rchit:148: the reference */
+#define GSP_LIGHTS_POWER 1u   /* proportional to Y(radiance) * area, through an alias table */
+typedef struct gsp_light_pick {
+  uint32_t threshold, alias;
+  float pmf_self, pmf_alias;
+} gsp_light_pick; /* 16 B */
+int gsp_set_light_sampling(gsp_context* ctx, uint32_t mode);
+int gsp_download_light_pick(gsp_context* ctx, gsp_light_pick* out, uint32_t capacity, uint32_t* count);
 
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
@@ -1302,6 +1367,7 @@ int gsp_multi_upload_scene(gsp_multi* m, const gsp_scene_desc* scene);
 int gsp_multi_update_camera(gsp_multi* m, const gsp_camera* camera);
 int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens); /* gsp_set_lens on every share */
 int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_media); /* gsp_set_media on every share */
+int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode); /* gsp_set_light_sampling on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);
 int gsp_multi_update_tables(gsp_multi* m, const gsp_scene_desc* scene);
 int gsp_multi_frame_begin(gsp_multi* m, uint32_t width, uint32_t height);
