@@ -199,6 +199,20 @@ def light_sampling_mode(mode):
     return int(mode)
 
 
+# Estimator (include/gpuspectral_pt.h "Estimator")
+ESTIMATOR_REFERENCE, ESTIMATOR_TEXTBOOK = 0, 1
+ESTIMATOR_NAMES = {"reference": ESTIMATOR_REFERENCE, "textbook": ESTIMATOR_TEXTBOOK}
+
+
+def estimator_mode(mode):
+    """A mode name or number -> the number gsp_set_estimator takes (an unknown number goes through: the library refuses it)."""
+    if isinstance(mode, str):
+        if mode not in ESTIMATOR_NAMES:
+            raise ValueError("estimator %r: one of %s" % (mode, ", ".join(sorted(ESTIMATOR_NAMES))))
+        return ESTIMATOR_NAMES[mode]
+    return int(mode)
+
+
 # LDR film (include/gpuspectral_pt.h "LDR film")
 TONEMAP_CLAMP, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2
 TONEMAP_NAMES = {"clamp": TONEMAP_CLAMP, "reinhard": TONEMAP_REINHARD, "aces": TONEMAP_ACES}

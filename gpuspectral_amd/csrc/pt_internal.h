@@ -19,6 +19,32 @@
 
 namespace gsp {
 
+// GSP_ESTIMATOR_TEXTBOOK: the <EST = true> instantiations of k_shade / k_finish are compiled in a translation unit of their own
+// (pt_render_textbook.hip; the library's two large units then build side by side) and launched through these two entries.  The
+// queues travel as plain pointers: the queue records of pt_render_kernels.inc are types of an unnamed namespace.  TEX / VER / LSEL
+// and media != nullptr (MED) pick the instantiation as tex_ver_med_kernel (pt_render_pipeline.inc) does for the reference mode.
+struct TextbookLaunch {
+  bool tex, ver, lsel;
+  const gsp_medium* media;  // nullptr: the context holds no media
+  const SceneView* view;    // the view the reference-mode launch would take (the versioned one when ver)
+  const RenderConstsBase* rc;
+  hipStream_t stream;
+  uint32_t blocks;
+  const uint32_t* n_ptr;  // k_shade: the queue's size on the device;  k_finish: n
+  uint32_t n;
+  q4* cur[4];
+  const q4* hits;  // k_shade
+  q4* next[4];     // k_shade
+  q4* shadow[3];   // k_shade
+  q4* result;
+  uint32_t* tails;
+  uint32_t* live;
+  uint32_t slot_paths, chunk;  // (chunk: k_shade)
+  void* stats;                 // DevStats*
+};
+void launch_shade_textbook(const TextbookLaunch& a);
+void launch_finish_textbook(const TextbookLaunch& a);
+
 #define GSP_HIP_TRY(expr)                                                                     \
   do {                                                                                        \
     hipError_t e_ = (expr);                                                                   \

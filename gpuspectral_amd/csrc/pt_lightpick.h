@@ -91,6 +91,30 @@ inline void build_light_pick_from_weights(const double* w_in, uint32_t n, gsp_li
   }
 }
 
+// What follows the light records in the table image: the alias table (GSP_LIGHTS_POWER with at least one light), and behind it the
+// one trailing record {inv_sum_w, 0, 0, 0} when the context ALSO runs GSP_ESTIMATOR_TEXTBOOK.  Every other combination of the two
+// modes keeps the image it had before the estimator mode existed.
+inline size_t light_pick_table_bytes(uint32_t n, uint32_t light_mode) { return light_mode == GSP_LIGHTS_POWER ? sizeof(gsp_light_pick) * (size_t)n : 0; }
+inline size_t light_pick_tail_bytes(uint32_t n, uint32_t light_mode, uint32_t estimator) {
+  return light_pick_table_bytes(n, light_mode) != 0 && estimator == GSP_ESTIMATOR_TEXTBOOK ? 16 : 0;
+}
+
+// GSP_ESTIMATOR_TEXTBOOK under GSP_LIGHTS_POWER (include/gpuspectral_pt.h, "Estimator"): the float32 rounding of 1 / sum(w), the sum
+// formed as above (the same weights, in double, in ascending index).  0 when every weight was 0 (the table fell back to uniform:
+// the selection probability of a light that is hit is then 1 / n), and when the sum or its reciprocal is beyond the format
+inline float light_pick_inv_sum_from_weights(const double* w_in, uint32_t n) {
+  double sum = 0.0;
+  for (uint32_t i = 0; i < n; ++i) sum += (std::isfinite(w_in[i]) && w_in[i] > 0.0) ? w_in[i] : 0.0;
+  if (!(sum > 0.0) || !std::isfinite(sum)) return 0.0f;
+  const float r = (float)(1.0 / sum);
+  return std::isfinite(r) ? r : 0.0f;
+}
+inline float light_pick_inv_sum(const gsp_triangle_light* lights, uint32_t n) {
+  std::vector<double> w(n);
+  for (uint32_t i = 0; i < n; ++i) w[i] = light_pick_weight(lights[i]);
+  return light_pick_inv_sum_from_weights(w.data(), n);
+}
+
 inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, gsp_light_pick* out) {
   std::vector<double> w(n);
   for (uint32_t i = 0; i < n; ++i) w[i] = light_pick_weight(lights[i]);

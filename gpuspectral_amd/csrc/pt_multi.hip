@@ -381,6 +381,15 @@ int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode) {
   return for_each_share(m, [&](size_t r) { return gsp_set_light_sampling(m->ctx[r], mode); });
 }
 
+int gsp_multi_set_estimator(gsp_multi* m, uint32_t mode) {
+  if (!m) return GSP_ERR_INVALID;
+  if (mode != GSP_ESTIMATOR_REFERENCE && mode != GSP_ESTIMATOR_TEXTBOOK) {  // (checked first: no share changes when the mode is unknown)
+    m->err = "gsp_set_estimator: unknown mode";
+    return GSP_ERR_INVALID;
+  }
+  return for_each_share(m, [&](size_t r) { return gsp_set_estimator(m->ctx[r], mode); });
+}
+
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances) {
   if (!m) return GSP_ERR_INVALID;
   if (!instances && num_instances) {

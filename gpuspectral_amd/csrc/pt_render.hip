@@ -162,6 +162,9 @@ struct gsp_context {
   // light selection (gsp_set_light_sampling): context state like the lens.  GSP_LIGHTS_POWER selects the <LSEL> kernels and makes
   // pack_tables append the alias table behind the light records of every table image
   uint32_t light_mode = GSP_LIGHTS_UNIFORM;
+  // the estimator (gsp_set_estimator): context state like the light mode.  GSP_ESTIMATOR_TEXTBOOK selects the <EST> kernels and the
+  // any-hit sources whose occluded commit leaves P2.w alone; with GSP_LIGHTS_POWER, pack_tables appends 1 / sum(w) behind the alias table
+  uint32_t estimator = GSP_ESTIMATOR_REFERENCE;
   double bvh_build_ms = 0.0;
   // what gsp_upload_scene leaves resident for the per-frame edits (gsp_update_instances re-bakes from it, as the reference
   // keeps the BLAS of a mesh and rebuilds the TLAS, Renderer.cpp:122-131 / PathTracer.cpp:10-19): the object-space

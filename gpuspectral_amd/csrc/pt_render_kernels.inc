@@ -1,4 +1,6 @@
-// pt_render_kernels.inc -- part of the translation unit pt_render.hip (included there; not compiled on its own).
+// pt_render_kernels.inc -- part of the translation unit pt_render.hip (included there; not compiled on its own).  Also included by
+// pt_render_textbook.hip, the translation unit of the <EST = true> instantiations of k_shade / k_finish, with GSP_SHADE_KERNELS_ONLY
+// defined: everything behind k_finish is left out there.
 // The DEVICE side of the wavefront tracer: queue layouts, the ray sources / result sinks of k_trace (pt_wavetrace.h), k_generate,
 // k_shade, k_finish, k_resolve, the table / uv bake kernels, and DevBuf.  Host code: pt_render.hip (context, options),
 // pt_render_scene.inc (upload + per-frame edits), pt_render_pipeline.inc (the streaming pipeline + the rest of the C ABI),
@@ -265,6 +267,36 @@ typedef ExtendVerIOT<false> ExtendVerIO;
 typedef ConnectVerIOT<false> ConnectVerIO;
 typedef ExtendVerIOT<true> ExtendSplitIO;
 typedef ConnectVerIOT<true> ConnectSplitIO;
+// GSP_ESTIMATOR_TEXTBOOK (include/gpuspectral_pt.h, "Estimator"): P2.w of the continuing path is not the reference's directWeight
+// but lastPdf, the same for both verdicts -- the occluded commit leaves it alone.  Sources of their own (plain, versioned, split):
+// the any-hit kernels of a reference-mode context are the ones they were
+struct ConnectTextbookIO : ConnectIO {
+  __device__ __forceinline__ void store(uint32_t i, const HitRec& h, uint32_t, uint32_t nx) const {
+    if (h.slot < 0) return;
+    q4 res = sq.S3[i];
+    if (nx != 0xffffffffu) {
+      next_P3[nx] = res;
+    } else {
+      const uint32_t sid = fb(res.w);
+      res.w = 0.0f;
+      result[sid] = res;
+    }
+  }
+};
+template <bool SPLIT>
+struct ConnectTextbookVerIOT : ConnectTextbookIO {
+  static constexpr bool kVersioned = true, kSplit = SPLIT;
+  GeoRing g;
+  __device__ __forceinline__ uint32_t top_offset() const { return g.top_off; }
+  __device__ __forceinline__ uint32_t static_slots() const { return g.static_slots; }
+  __device__ __forceinline__ void geometry(uint32_t i, uint32_t pay, uint32_t& node_off, uint32_t& tri_base) const {
+    const uint32_t stamp = (pay & kNoNextBit) ? (pay & (kGeoVersions - 1u)) : geo_stamp(((const uint32_t*)&sq.S3[i])[3]);
+    g.offsets(stamp, node_off, tri_base);
+  }
+  __device__ __forceinline__ void store(uint32_t i, const HitRec& h, uint32_t aux, uint32_t pay) const {
+    ConnectTextbookIO::store(i, h, aux, (pay & kNoNextBit) ? 0xffffffffu : pay);
+  }
+};
 // the camera rays of the memo and the rays of gsp_trace on a split scene: every ray belongs to the newest version (`stamp`)
 struct MemoSplitIO : MemoIO {
   static constexpr bool kVersioned = true, kSplit = true;
@@ -344,7 +376,8 @@ constexpr int kShadeWaves = kShadeBlock / 64;
 // Only these instantiations take the larger view: the kernels of a context without media keep their argument layout
 // LSEL: the context picks its light by emitted power (gsp_set_light_sampling): shade_vertex<.., LSEL = true> reads the alias table
 // behind the light records -- part of the table image, so it is staged into LDS with it and has a copy in every version
-template <bool TEX, bool VER, bool MED, bool LSEL>
+// EST: the context runs the textbook estimator (gsp_set_estimator): shade_vertex<.., EST = true>; P2.w carries lastPdf
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST>
 __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
                                                         const q4* __restrict__ hits, PathQueue nxt, ShadowQueue sq,
                                                         q4* __restrict__ result, uint32_t* __restrict__ tails,
@@ -494,7 +527,7 @@ __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typen
         in.weight = mk3(p2.x, p2.y, p2.z);
         in.directWeight = p2.w;
         in.flags = fl;
-        shade_vertex<TEX, VER, MED, LSEL>(S, rc, in, h, out, view_media(S));
+        shade_vertex<TEX, VER, MED, LSEL, EST>(S, rc, in, h, out, view_media(S));
         alive = out.alive;
         has_shadow = out.has_shadow;
         ++shaded;
@@ -649,7 +682,7 @@ struct FinishStack {
   __device__ __forceinline__ uint32_t pop() { return col[(--top) * kBlock]; }
 };
 
-template <bool TEX, bool VER, bool MED, bool LSEL>
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST>
 __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
                                                     q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                     uint32_t* __restrict__ live,
@@ -707,7 +740,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED>::ty
         break;
       }
       ShadeOut out;
-      shade_vertex<TEX, VER, MED, LSEL>(S, rc, in, h, out, view_media(S));
+      shade_vertex<TEX, VER, MED, LSEL, EST>(S, rc, in, h, out, view_media(S));
       ++shaded;
       if (!out.has_shadow) {
         add_emitted(rc.clamp, out.emitted, res);
@@ -723,7 +756,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED>::ty
         }
         bool nee_done;
         connect_vertex(rc.clamp, out.shadow, occluded, res, nee_done);
-        if (nee_done && out.alive) out.next.directWeight = out.shadow.dw_nee;  // rayhit.rchit:785-787
+        if (!EST && nee_done && out.alive) out.next.directWeight = out.shadow.dw_nee;  // rayhit.rchit:785-787 (EST: lastPdf is in place)
       }
       if (!out.alive) break;
       in = out.next;
@@ -754,6 +787,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED>::ty
   }
 }
 
+#ifndef GSP_SHADE_KERNELS_ONLY
 // ---- resolve ----------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_resolve(uint32_t num_pixels, uint32_t K, uint32_t first_timestamp,
                                                      const q4* __restrict__ result, q4* __restrict__ accum,
@@ -1722,6 +1756,8 @@ struct DevBuf {
 
 std::mutex g_err_mutex;
 std::string g_create_error = "";
+
+#endif  // GSP_SHADE_KERNELS_ONLY
 
 }  // namespace
 

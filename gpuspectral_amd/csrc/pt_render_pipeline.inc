@@ -83,6 +83,7 @@ enum class Hit { kClosest, kAny, kAsked };
 template <class IO> struct TraceSource;
 template <> struct TraceSource<ExtendIO> { static constexpr Hit kHit = Hit::kClosest; typedef ExtendSplitIO Split; typedef ExtendVerIO Ver; };
 template <> struct TraceSource<ConnectIO> { static constexpr Hit kHit = Hit::kAny; typedef ConnectSplitIO Split; typedef ConnectVerIO Ver; };
+template <> struct TraceSource<ConnectTextbookIO> { static constexpr Hit kHit = Hit::kAny; typedef ConnectTextbookVerIOT<true> Split; typedef ConnectTextbookVerIOT<false> Ver; };
 template <> struct TraceSource<MemoIO> { static constexpr Hit kHit = Hit::kClosest; typedef MemoSplitIO Split; typedef void Ver; };
 template <> struct TraceSource<TestIO> { static constexpr Hit kHit = Hit::kAsked; typedef TestSplitIO Split; typedef void Ver; };
 
@@ -95,6 +96,14 @@ template <class IO>
 static void launch_trace(const gsp_context* ctx, hipStream_t st, const SceneView& view, const LiveVersions& V, bool stats, const IO& io,
                          const uint32_t* n_ptr, uint32_t n, uint32_t first, uint64_t bound, uint32_t chunk, uint32_t* work, uint32_t* spill,
                          const TraceStatsOut& so) {
+  // GSP_ESTIMATOR_TEXTBOOK: the shadow rays take the any-hit sources whose occluded commit leaves P2.w (lastPdf) alone
+  if constexpr (std::is_same<IO, ConnectIO>::value) {
+    if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK) {
+      ConnectTextbookIO tio;
+      static_cast<ConnectIO&>(tio) = io;
+      return launch_trace(ctx, st, view, V, stats, tio, n_ptr, n, first, bound, chunk, work, spill, so);
+    }
+  }
   typedef TraceSource<IO> S;
   constexpr bool in_flight = !std::is_void<typename S::Ver>::value;  // the rays are paths in flight: each carries its own stamp
   const auto launch = [&](auto ANY, auto STATS, const SceneView& v, const auto& record) {
@@ -117,7 +126,7 @@ static void launch_trace(const gsp_context* ctx, hipStream_t st, const SceneView
   with_hit_rule(std::false_type{}, view, io);
 }
 
-// k_shade / k_finish <TEX, VER, MED, LSEL>: TEX = the scene has textures or an environment map, VER = V.multi_version, MED = the context
+// k_shade / k_finish <TEX, VER, MED, LSEL, EST = false>: TEX = the scene has textures or an environment map, VER = V.multi_version, MED = the context
 // holds interior media (gsp_set_media), LSEL = it picks its light by emitted power (gsp_set_light_sampling); launch(TEX, VER, MED, LSEL, view)
 // gets them as std::integral_constant values (as atrous_level, pt_render_post.inc).  These kernels read V.vview -- the versioned view
 // exactly when VER -- and the <MED> ones the table behind it.
@@ -141,6 +150,27 @@ static void tex_ver_med_kernel(const gsp_context* ctx, const LiveVersions& V, La
   else if (V.multi_version) with_pick(std::false_type{}, std::true_type{});
   else if (ctx->textured) with_pick(std::true_type{}, std::false_type{});
   else with_pick(std::false_type{}, std::false_type{});
+}
+// ... and <.., EST = true>, the kernels of a context that runs the textbook estimator (gsp_set_estimator): the same four flags, handed to
+// the translation unit that holds those instantiations (pt_render_textbook.hip, launch_shade_textbook / launch_finish_textbook)
+static TextbookLaunch textbook_launch(const gsp_context* ctx, const LiveVersions& V, const RenderConstsBase& rc, hipStream_t st, uint32_t blocks,
+                                      const PathQueue& cur, q4* result, uint32_t* tails, uint32_t* live, uint32_t slot_paths) {
+  TextbookLaunch a{};
+  a.tex = ctx->textured;
+  a.ver = V.multi_version;
+  a.lsel = ctx->light_mode == GSP_LIGHTS_POWER;
+  a.media = ctx->num_media != 0 ? ctx->media.p : nullptr;
+  a.view = &V.vview;
+  a.rc = &rc;
+  a.stream = st;
+  a.blocks = blocks;
+  a.cur[0] = cur.P0, a.cur[1] = cur.P1, a.cur[2] = cur.P2, a.cur[3] = cur.P3;
+  a.result = result;
+  a.tails = tails;
+  a.live = live;
+  a.slot_paths = slot_paths;
+  a.stats = ctx->dstats.p;
+  return a;
 }
 }  // extern "C++"
 
@@ -244,8 +274,14 @@ static int finish_few_paths(gsp_context* ctx, gsp_context::Lane& L, const Render
   if (!(drain && L.queued == 0 && P.remaining == 0 && P.n > 0 && P.n <= ctx->finish_paths && ctx->pipe_params.collect_traversal_stats == 0 &&
         std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 <= kFinishLevels))
     return GSP_OK;
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK) {
+    TextbookLaunch a = textbook_launch(ctx, V, rcst, L.stream, (uint32_t)((P.n + kBlock - 1) / kBlock), lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq),
+                                       L.counters.p + C_LIVE, (uint32_t)P.batch_paths);
+    a.n = (uint32_t)P.n;
+    launch_finish_textbook(a);
+  } else
   tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
-    hipLaunchKernelGGL((k_finish<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value>), dim3((uint32_t)((P.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, sview, rcst,
+    hipLaunchKernelGGL((k_finish<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value, false>), dim3((uint32_t)((P.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, sview, rcst,
                        (uint32_t)P.n, lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq), L.counters.p + C_LIVE, (uint32_t)P.batch_paths, ctx->dstats.p);
   });
   CTX_TRY(ctx, hipGetLastError());
@@ -311,8 +347,17 @@ static int trace_shade_connect(gsp_context* ctx, gsp_context::Lane& L, const Ren
   CTX_TRY(ctx, hipGetLastError());
   if (ev) CTX_TRY(ctx, hipEventRecord(ev[1], st));
   const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + kShadeBlock - 1) / kShadeBlock, shade_resident_blocks(ctx))));
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK) {
+    TextbookLaunch a = textbook_launch(ctx, V, rcst, st, grid.x, cur, L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths);
+    a.n_ptr = n_ptr;
+    a.hits = hits;
+    a.next[0] = next.P0, a.next[1] = next.P1, a.next[2] = next.P2, a.next[3] = next.P3;
+    a.shadow[0] = sq.S0, a.shadow[1] = sq.S1, a.shadow[2] = sq.S3;
+    a.chunk = room_chunk;
+    launch_shade_textbook(a);
+  } else
   tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
-    hipLaunchKernelGGL((k_shade<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value>), grid, dim3(kShadeBlock), 0, st, sview, rcst, n_ptr, cur, hits, next, sq,
+    hipLaunchKernelGGL((k_shade<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value, false>), grid, dim3(kShadeBlock), 0, st, sview, rcst, n_ptr, cur, hits, next, sq,
                        L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths, room_chunk, ctx->dstats.p);
   });
   CTX_TRY(ctx, hipGetLastError());
@@ -1271,21 +1316,10 @@ int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media)
 
 // ---- light selection (include/gpuspectral_pt.h, "Light selection") ----
 static_assert(sizeof(gsp_light_pick) == 16 && sizeof(gsp_triangle_light) % 16 == 0, "the pick table starts straight behind the light records, on a 16-byte boundary");
-int gsp_set_light_sampling(gsp_context* ctx, uint32_t mode) {
-  if (!ctx) return GSP_ERR_INVALID;
-  if (mode != GSP_LIGHTS_UNIFORM && mode != GSP_LIGHTS_POWER) {
-    ctx->err = "gsp_set_light_sampling: unknown mode";
-    return GSP_ERR_INVALID;
-  }
-  CTX_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = drain_for_edit(ctx);  // the samples in flight were generated under the mode as it was
-  if (rc != GSP_OK) return rc;
-  if (mode == ctx->light_mode) return GSP_OK;
-  const uint32_t old_mode = ctx->light_mode;
-  ctx->light_mode = mode;
+// A resident scene under a drained pipeline: its tables are packed again from the context's host copy (the caller's records, as
+// they came) and uploaded, in the layout of the context's light mode and estimator as they are NOW.  No scene: nothing to do.
+static int repack_resident_tables(gsp_context* ctx) {
   if (!ctx->have_scene || ctx->h_tables.size() < TableImage::kHead) return GSP_OK;
-  // a resident scene: its tables are packed again from the context's host copy (the caller's records, as they came) and uploaded
-  // behind the drain, with or without the pick table
   gsp_scene_desc sc{};
   uint64_t counts[9];
   std::memcpy(counts, ctx->h_tables.data(), sizeof(counts));
@@ -1302,15 +1336,50 @@ int gsp_set_light_sampling(gsp_context* ctx, uint32_t mode) {
   sc.lights = (const gsp_triangle_light*)(tb + ctx->table_off[8]);
   sc.num_lights = (uint32_t)counts[8];
   TableImage img;
-  rc = pack_tables(ctx, &sc, img);  // (copies out of h_tables into the new image; upload_tables then swaps the two)
+  int rc = pack_tables(ctx, &sc, img);  // (copies out of h_tables into the new image; upload_tables then swaps the two)
   if (rc == GSP_OK) rc = upload_tables(ctx, &sc, img);
   if (rc != GSP_OK) {
-    ctx->light_mode = old_mode;
     ctx->have_scene = false;
     return rc;
   }
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return GSP_OK;
+}
+
+int gsp_set_light_sampling(gsp_context* ctx, uint32_t mode) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (mode != GSP_LIGHTS_UNIFORM && mode != GSP_LIGHTS_POWER) {
+    ctx->err = "gsp_set_light_sampling: unknown mode";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight were generated under the mode as it was
+  if (rc != GSP_OK) return rc;
+  if (mode == ctx->light_mode) return GSP_OK;
+  const uint32_t old_mode = ctx->light_mode;
+  ctx->light_mode = mode;
+  rc = repack_resident_tables(ctx);
+  if (rc != GSP_OK) ctx->light_mode = old_mode;
+  return rc;
+}
+
+// ---- estimator (include/gpuspectral_pt.h, "Estimator") ----
+int gsp_set_estimator(gsp_context* ctx, uint32_t mode) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (mode != GSP_ESTIMATOR_REFERENCE && mode != GSP_ESTIMATOR_TEXTBOOK) {
+    ctx->err = "gsp_set_estimator: unknown mode";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight carry the directWeight / lastPdf of the mode as it was
+  if (rc != GSP_OK) return rc;
+  if (mode == ctx->estimator) return GSP_OK;
+  const uint32_t old_mode = ctx->estimator;
+  ctx->estimator = mode;
+  if (ctx->light_mode != GSP_LIGHTS_POWER) return GSP_OK;  // (the tables of a uniform-pick context are the same in both modes)
+  rc = repack_resident_tables(ctx);  // with or without the trailing record behind the pick table
+  if (rc != GSP_OK) ctx->estimator = old_mode;
+  return rc;
 }
 
 int gsp_download_light_pick(gsp_context* ctx, gsp_light_pick* out, uint32_t capacity, uint32_t* count) {

@@ -91,14 +91,23 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
   // GSP_LIGHTS_POWER: a tenth sub-table, the alias table of the lights (pt_lightpick.h), straight behind the light records (64 B
   // each: no padding in between), so that (const gsp_light_pick*)(lights + num_lights) finds it.  Absent in uniform mode: such a
   // context keeps the image size, and so the LDS staging decision, it always had
-  const bool pick = ctx->light_mode == GSP_LIGHTS_POWER && sc->num_lights != 0;
+  const bool pick = light_pick_table_bytes(sc->num_lights, ctx->light_mode) != 0;
   img.pick_off = img.total;
-  if (pick) img.total += sizeof(gsp_light_pick) * (size_t)sc->num_lights;
+  img.total += light_pick_table_bytes(sc->num_lights, ctx->light_mode);
+  // ... and, with GSP_ESTIMATOR_TEXTBOOK on top, one trailing 16-byte record behind the table: {inv_sum_w, 0, 0, 0}, what
+  // shade_vertex<.., LSEL, EST> multiplies the weight of a light that was HIT with.  Absent in every other combination
+  const bool tail = light_pick_tail_bytes(sc->num_lights, ctx->light_mode, ctx->estimator) != 0;
+  const size_t tail_off = img.total;
+  img.total += light_pick_tail_bytes(sc->num_lights, ctx->light_mode, ctx->estimator);
   img.bytes.assign(TableImage::kHead + std::max<size_t>(img.total, 16), 0);
   std::memcpy(img.bytes.data(), counts, sizeof(counts));
   for (int k = 0; k < 9; ++k)
     if (bytes[k]) std::memcpy(img.bytes.data() + TableImage::kHead + img.off[k], src[k], bytes[k]);
   if (pick) build_light_pick(sc->lights, sc->num_lights, (gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off));
+  if (tail) {
+    const float inv_sum_w = light_pick_inv_sum(sc->lights, sc->num_lights);
+    std::memcpy(img.bytes.data() + TableImage::kHead + tail_off, &inv_sum_w, sizeof(float));
+  }
   return GSP_OK;
 }
 // image -> device, as the NEXT version of the tables (queued on the context's stream; the image becomes the context's host copy,

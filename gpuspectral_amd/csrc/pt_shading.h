@@ -545,6 +545,9 @@ GSP_HD void bsdf_sample(const BsdfTables& T, uint32_t handle, uint32_t& rng, f3 
 
 // evalBSDF, rayhit.rchit:643-654
 // cy: what bsdf_sample left for THIS vertex (same handle, same wo)
+// NOFLOOR (GSP_ESTIMATOR_TEXTBOOK, include/gpuspectral_pt.h "Estimator"): rough plastic's pdf is the one bsdf_sample reports (:541),
+// without the one-sided max(.., 0.01) of :577.  NOFLOOR = false is the reference, instruction for instruction.
+template <bool NOFLOOR = false>
 GSP_HD void bsdf_eval(const BsdfTables& T, uint32_t handle, f3 wo, f3 wi, BsdfResult& r, const BsdfCarry& cy, bool kd_on = false,
                       f3 kd = f3{}) {
   const uint32_t i = handle & 0xffffu;
@@ -603,8 +606,11 @@ GSP_HD void bsdf_eval(const BsdfTables& T, uint32_t handle, f3 wo, f3 wi, BsdfRe
       const gsp_rough_plastic_bsdf b = T.rough_plastic[i];
       f3 wh;
       rough_plastic_value(b, derived_of(T.rough_plastic, i), wo, wi, wh, r.f, kd_on, kd);
-      r.pdf = (0.5f * gmax(beckmann_d(wh, b.alpha) * gabs(wh.z), 0.01f)) / (4.0f * gabs(dot(wo, wh))) +
-              0.5f * cosine_pdf(wi);
+      if constexpr (NOFLOOR)
+        r.pdf = microfacet_pdf_half(wo, wh, b.alpha) + 0.5f * cosine_pdf(wi);
+      else
+        r.pdf = (0.5f * gmax(beckmann_d(wh, b.alpha) * gabs(wh.z), 0.01f)) / (4.0f * gabs(dot(wo, wh))) +
+                0.5f * cosine_pdf(wi);
       GSP_PROF_END_T(PR_EVAL_T0, PR_EVAL_T0, GSP_BSDF_ROUGH_PLASTIC);
     } break;
     default: break;
@@ -770,5 +776,19 @@ GSP_HD LightSample sample_light_power(const gsp_triangle_light* lights, const gs
   ls.pdf = ls.pdf * pmf;
   return ls;
 }
+
+// GSP_ESTIMATOR_TEXTBOOK under GSP_LIGHTS_POWER (include/gpuspectral_pt.h, "Estimator"): the probability with which the power pick
+// selects a light triangle that a ray HIT, from the hit's emission and area: its weight times inv_sum_w, the float32 rounding of
+// 1 / sum(w) that rides behind the alias table (pt_lightpick.h light_pick_inv_sum).  inv_sum_w == 0: the table fell back to the
+// uniform pick.  The pmf of the weights, not of the integer table (they differ by at most (1 + d_i) / (n 2^32))
+GSP_HD float light_hit_select_pmf(f3 emission, float A, float inv_sum_w, float inv_num_lights) {
+  float w_hit = gmax((0.2126f * emission.x + 0.7152f * emission.y) + 0.0722f * emission.z, 0.0f) * A;
+  if (!gisvalid(w_hit) || w_hit < 0.0f) w_hit = 0.0f;
+  return inv_sum_w != 0.0f ? w_hit * inv_sum_w : inv_num_lights;
+}
+// ... and the pdf (solid angle at the previous vertex) with which light sampling reaches the point that was hit: sample_light's
+// own formula with the hit triangle's area, times the selection probability
+GSP_HD float light_hit_area(f3 v0, f3 v1, f3 v2) { return 0.5f * gabs(length(cross(v2 - v0, v1 - v0))); }
+GSP_HD float light_hit_pdf(float t, f3 rayDir, f3 N, float A, float p_sel) { return ((t * t) / (gabs(dot(-rayDir, N)) * A)) * p_sel; }
 
 }  // namespace gsp

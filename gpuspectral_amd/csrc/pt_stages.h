@@ -315,7 +315,12 @@ struct ShadeOut {
 // LSEL: the context picks its light by emitted power (include/gpuspectral_pt.h, "Light selection"): sample_light_power reads the
 // alias table that sits straight behind the light records of this vertex's version of the tables (LDS or global, wherever the
 // lights are).  LSEL = false is the reference's uniform pick, instruction for instruction.
-template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false>
+// EST: the context runs the textbook estimator (include/gpuspectral_pt.h, "Estimator"): the NEE weight takes the BSDF's pdf of L
+// itself, rough plastic's eval pdf loses its floor, and an emitter met with NEE on, countEmitted == 0 and wasDelta == 0 is weighted
+// with power_heuristic(lastPdf, hitPdf), hitPdf = light sampling's pdf of reaching THIS point of THIS emitter.  The path's
+// directWeight field is dead in this mode and carries lastPdf, the bs.pdf of the vertex that sent the ray (the same for both
+// verdicts of its shadow ray).  EST = false is the reference's estimator, instruction for instruction.
+template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false>
 GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
                          ShadeOut& out, const gsp_medium* media = nullptr) {
   uint32_t rng = in.seed;                                                 // rchit:668
@@ -336,8 +341,8 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   const BsdfTables& T = VER ? Tv : S.bsdf;
   const gsp_triangle_light* lights = VER ? lights_v : S.lights;
   GSP_PROF_BEGIN(PR_PACKET);
-  const q4* sp = S.tri_shade + 4ll * ((long long)hit.slot +
-                                      (VER && (uint32_t)hit.slot >= S.static_slots ? (long long)geo_slot_offset(S.geo, geo_stamp(in.flags)) : 0ll));
+  const long long slot_v = (long long)hit.slot + (VER && (uint32_t)hit.slot >= S.static_slots ? (long long)geo_slot_offset(S.geo, geo_stamp(in.flags)) : 0ll);
+  const q4* sp = S.tri_shade + 4ll * slot_v;
   const q4 s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
   const uint32_t material = f2u(s0.w);                                    // :672 (instance record, baked per triangle)
   const uint32_t bsdf = material & (MED ? 0x0007ffffu : 0x7fffffffu);
@@ -403,7 +408,7 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   BsdfResult lb;
   GSP_PROF_END(PR_LIGHT);
   GSP_PROF_BEGIN(PR_EVAL);
-  bsdf_eval(T, bsdf, wo, wL, lb, cy, kd_on, kd);                     // :729
+  bsdf_eval<EST>(T, bsdf, wo, wL, lb, cy, kd_on, kd);                // :729
   GSP_PROF_END(PR_EVAL);
   GSP_PROF_BEGIN(PR_TAIL);
 
@@ -414,7 +419,7 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   const bool want_shadow = nee_on && !bs.delta && ((NdotV > 0.0f && dot(N, L) > 0.0f) || transmits) && (lightPdf != 0.0f);
   f3 nee = splat(0.0f);
   if (want_shadow) {
-    const float w = power_heuristic(lightPdf, bs.pdf);                    // :751
+    const float w = power_heuristic(lightPdf, EST ? lb.pdf : bs.pdf);     // :751 (EST: the pdf of L itself)
     nee = ((((w * NoL) * lb.f) * weight) * ls.emission) / lightPdf;       // :752
   }
   const uint32_t depth = in.flags & 0xffu;
@@ -422,7 +427,23 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   const uint32_t countEmitted = (in.flags >> 9) & 1u;
   const float lightFlag = NdotV > 0.0f ? 1.0f : 0.0f;                     // :760
   f3 emis = splat(0.0f);
-  if (nee_on && countEmitted == 0 && wasDelta == 0) emis = emis + ((in.directWeight * emission) * lightFlag) * weight;  // :763-765
+  float directWeight = in.directWeight;
+  if constexpr (EST) {
+    // the textbook weight: in.directWeight is lastPdf.  The hit triangle's world-space vertices (the intersection packet, at the
+    // slot the shading packet was read from) are fetched only for an emitter
+    directWeight = 1.0f;
+    if (nee_on && countEmitted == 0 && wasDelta == 0 && (emission.x != 0.0f || emission.y != 0.0f || emission.z != 0.0f)) {
+      const q4* ip = S.tri_isect + 3ll * slot_v;
+      const q4 i0 = ip[0], i1 = ip[1], i2 = ip[2];
+      const f3 v0 = mk3(i0.x, i0.y, i0.z), v1 = mk3(i1.x, i1.y, i1.z), v2 = mk3(i2.x, i2.y, i2.z);
+      const float A = light_hit_area(v0, v1, v2);
+      float p_sel = S.inv_num_lights;
+      // LSEL: the selection probability of the light that was HIT, through the trailing record behind the alias table (no lights: no table)
+      if (LSEL && S.num_lights != 0u) p_sel = light_hit_select_pmf(emission, A, *(const float*)((const gsp_light_pick*)(lights + S.num_lights) + S.num_lights), S.inv_num_lights);
+      directWeight = power_heuristic(in.directWeight, light_hit_pdf(hit.t, rayDir, N, A, p_sel));
+    }
+  }
+  if (nee_on && countEmitted == 0 && wasDelta == 0) emis = emis + ((directWeight * emission) * lightFlag) * weight;  // :763-765
   if (!nee_on || countEmitted == 1 || wasDelta == 1) emis = emis + (emission * lightFlag) * weight;                      // :766-768
 
   bool done = false;
@@ -435,7 +456,7 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   nx.seed = rng;                                                          // :759
   if (MED) nx.weight = weight;
   if (!done) {
-    nx.directWeight = 1.0f;                                               // :785-790 (connect overwrites when NEE happens)
+    nx.directWeight = EST ? bs.pdf : 1.0f;                                // :785-790 (connect overwrites when NEE happens); EST: lastPdf
     nx.o = position + 0.0001f * faceforward(N, -wi, N);                   // :793
     nx.d = wi;                                                            // :794
     nx.weight = weight * ((bs.f * NoW) / bs.pdf);                         // :795
@@ -473,7 +494,7 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
     out.shadow.tmax = Ldist - 0.01f;                                      // :747
     out.shadow.nee = nee;
     out.shadow.emis = emis;
-    out.shadow.dw_nee = power_heuristic(bs.pdf, lightPdf);                // :786
+    out.shadow.dw_nee = EST ? bs.pdf : power_heuristic(bs.pdf, lightPdf); // :786; EST: lastPdf, whatever the verdict
     out.shadow.sid = in.sid;
     out.shadow.next = -1;
   }

@@ -106,6 +106,7 @@ def load():
     L.gsph_pathtracer_download_temporal_svgf.argtypes = [vp, C.POINTER(abi.Denoise), C.POINTER(abi.Svgf), vp, u64]
     L.gsph_pathtracer_temporal_follow_instances.argtypes = [vp, C.c_int]
     L.gsph_pathtracer_set_light_sampling.argtypes = [vp, u32]
+    L.gsph_pathtracer_set_estimator.argtypes = [vp, u32]
     L.gsph_pathtracer_download_light_pick.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.gsph_pathtracer_download_temporal_motion.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_temporal_demodulate.argtypes = [vp, C.c_int]
@@ -446,6 +447,10 @@ class PathTracer:
                                                                    C.byref(svgf) if svgf is not None else None, out.ctypes.data, out.size),
                     "downloadTemporalSvgf")
         return out
+
+    def set_estimator(self, mode):
+        """PathTracer::setEstimator: "reference" (the default) or "textbook" (gpuspectral_pt.h "Estimator")."""
+        self._check(self._L.gsph_pathtracer_set_estimator(self._h, abi.estimator_mode(mode)), "setEstimator")
 
     def set_light_sampling(self, mode):
         """PathTracer::setLightSampling: "uniform" (the reference's pick) or "power" (gpuspectral_pt.h "Light selection")."""

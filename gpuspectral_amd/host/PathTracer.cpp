@@ -336,6 +336,8 @@ std::vector<float> PathTracer::downloadTemporalSvgf(const gsp_denoise* denoise, 
   return out;
 }
 
+void PathTracer::setEstimator(uint32_t mode) { check(gsp_set_estimator(ctx, mode), "gsp_set_estimator"); }
+
 void PathTracer::setLightSampling(uint32_t mode) { check(gsp_set_light_sampling(ctx, mode), "gsp_set_light_sampling"); }
 
 std::vector<gsp_light_pick> PathTracer::downloadLightPick() {
@@ -437,6 +439,8 @@ MultiGpuPathTracer::~MultiGpuPathTracer() { gsp_multi_destroy(multi); }
 void MultiGpuPathTracer::check(int rc, const char* what) {
   if (rc != GSP_OK) throw std::runtime_error(std::string(what) + ": " + gsp_multi_last_error(multi));
 }
+
+void MultiGpuPathTracer::setEstimator(uint32_t mode) { check(gsp_multi_set_estimator(multi, mode), "gsp_multi_set_estimator"); }
 
 void MultiGpuPathTracer::setLightSampling(uint32_t mode) { check(gsp_multi_set_light_sampling(multi, mode), "gsp_multi_set_light_sampling"); }
 

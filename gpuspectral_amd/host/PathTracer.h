@@ -86,6 +86,9 @@ class PathTracer : public RenderPassCreator {
   // (by emitted power).  Context state: it holds across scenes; reset() after a change starts a frame of one estimator.
   void setLightSampling(uint32_t mode);
   std::vector<gsp_light_pick> downloadLightPick();  // the resident alias table (GSP_LIGHTS_POWER with a scene uploaded)
+  // Estimator (gpuspectral_pt.h "Estimator"): GSP_ESTIMATOR_REFERENCE (the reference's weights, the default) or GSP_ESTIMATOR_TEXTBOOK
+  // (textbook multiple importance sampling: unbiased).  Context state: it holds across scenes; reset() after a change.
+  void setEstimator(uint32_t mode);
 
   // RGBA32F, row-major, width*height*4 floats (running mean, alpha 1)
   std::vector<float> download();
@@ -198,6 +201,7 @@ class MultiGpuPathTracer : public RenderPassCreator {
   void prepareScene(const Scene& scene);  // as PathTracer::prepareScene, on every share
   void invalidateScene() { tracker.forget(); }
   void setLightSampling(uint32_t mode);  // as PathTracer::setLightSampling, on every share
+  void setEstimator(uint32_t mode);      // as PathTracer::setEstimator, on every share
   std::vector<float> download();  // RGBA32F, row-major, width*height*4 floats
   std::vector<uint32_t> downloadDisplay();  // as PathTracer::downloadDisplay, on the gathered frame
   void renderFeatures(const Scene& scene, uint32_t spp);  // as PathTracer::renderFeatures, on every share

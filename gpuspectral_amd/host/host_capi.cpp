@@ -390,6 +390,9 @@ int gsph_pathtracer_download_temporal_svgf(void* pt, const gsp_denoise* denoise,
 int gsph_pathtracer_set_light_sampling(void* pt, uint32_t mode) {
   return guard([&] { ((PathTracer*)pt)->setLightSampling(mode); });
 }
+int gsph_pathtracer_set_estimator(void* pt, uint32_t mode) {  // PathTracer::setEstimator
+  return guard([&] { ((PathTracer*)pt)->setEstimator(mode); });
+}
 int gsph_pathtracer_download_light_pick(void* pt, gsp_light_pick* out, uint32_t capacity, uint32_t* count) {
   return guard([&] {
     auto t = ((PathTracer*)pt)->downloadLightPick();

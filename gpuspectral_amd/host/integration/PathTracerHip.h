@@ -66,6 +66,9 @@ class PathTracerHip : public RenderPassCreator {
   // light selection, opt-in (gpuspectral_pt.h "Light selection"): GSP_LIGHTS_POWER picks the NEE light by emitted power (an alias
   // table beside the lights).  Context state; restart() after a change.  The default is the reference's uniform pick
   void setLightSampling(uint32_t mode) { check(gsp_set_light_sampling(ctx, mode)); }
+  // estimator, opt-in (gpuspectral_pt.h "Estimator"): GSP_ESTIMATOR_TEXTBOOK weights NEE and emitter hits by textbook multiple
+  // importance sampling (unbiased).  Context state; restart() after a change.  The default is the reference's estimator
+  void setEstimator(uint32_t mode) { check(gsp_set_estimator(ctx, mode)); }
   float autofocus(float fx, float fy) {
     float d = 0.0f;
     check(gsp_focus_distance(ctx, width, height, fx, fy, &d));

@@ -12,6 +12,7 @@
 //   jitter drawn from the filter); --scene-filter: LoadOptions::readFilter (the film's <rfilter>; --filter other than none wins)
 //   --aperture R --focus-distance D | --focus-pixel X,Y [--blades N[:rot_deg]]: thin lens (gsp_set_lens; depth of field).
 //   --light-sampling uniform|power: gsp_set_light_sampling (uniform = the reference's pick, the default; power = by emitted power).
+//   --estimator reference|textbook: gsp_set_estimator (reference = the reference's weights, the default; textbook = unbiased).
 //   --scene-media: LoadOptions::readMedia (the shapes' <medium name="interior">: coloured glass, gsp_set_media).
 //   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
 //   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
@@ -68,6 +69,7 @@ int main(int argc, char** argv) {
   gsp_default_ctx_options(&ctxOptions);
   bool nee = true;
   uint32_t lightSampling = GSP_LIGHTS_UNIFORM;
+  uint32_t estimator = GSP_ESTIMATOR_REFERENCE;
   float adaptive = 0.0f;
   uint32_t adaptiveMin = 0, adaptiveStep = 0;
   uint32_t filter = GSP_FILTER_NONE;
@@ -123,6 +125,16 @@ int main(int argc, char** argv) {
       else if (v == "power") lightSampling = GSP_LIGHTS_POWER;
       else {
         std::fprintf(stderr, "--light-sampling: uniform or power, not '%s'\n", v.c_str());
+        return 2;
+      }
+      used = 2;
+    }
+    else if (flag == "--estimator" && argc > 2) {
+      const std::string v = argv[2];
+      if (v == "reference") estimator = GSP_ESTIMATOR_REFERENCE;
+      else if (v == "textbook") estimator = GSP_ESTIMATOR_TEXTBOOK;
+      else {
+        std::fprintf(stderr, "--estimator: reference or textbook, not '%s'\n", v.c_str());
         return 2;
       }
       used = 2;
@@ -424,7 +436,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -499,6 +511,7 @@ int main(int argc, char** argv) {
       PathTracer pt(width, height, devices[0], {}, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
       pt.setLightSampling(lightSampling);
+      pt.setEstimator(estimator);
       pt.params.adaptive_threshold = adaptive;
       pt.params.adaptive_min_spp = adaptiveMin;
       pt.params.adaptive_step = adaptiveStep;
@@ -581,6 +594,7 @@ int main(int argc, char** argv) {
       MultiGpuPathTracer pt(width, height, devices, &ctxOptions);
       pt.params.disable_nee = nee ? 0u : 1u;
       pt.setLightSampling(lightSampling);
+      pt.setEstimator(estimator);
       pt.params.adaptive_threshold = adaptive;  // (gsp_multi_render refuses adaptive sampling: reported as an error)
       pt.params.pixel_filter = filter;
       pt.params.pixel_filter_param = filterParam;

@@ -7,7 +7,7 @@ TILE x TILE pixels are dealt round-robin for load balance.  The only collective
 of a render is one gather of the ranks' compact RGBA32F buffers to rank 0
 (backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in the CPU tests).
 
-Context state that changes the estimator -- the lens, the media, the light selection mode (Context.set_light_sampling) -- is
+Context state that changes the estimator -- the lens, the media, the light selection mode (Context.set_light_sampling), the estimator mode (Context.set_estimator) -- is
 part of "the scene" here: every rank sets the same value on its context, or the tiles belong to different images.
 """
 import functools

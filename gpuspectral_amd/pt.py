@@ -31,6 +31,7 @@ EXPORTS = (
     "gsp_set_media",
     "gsp_set_light_sampling",
     "gsp_download_light_pick",
+    "gsp_set_estimator",
     "gsp_focus_distance",
     "gsp_frame_begin",
     "gsp_render",
@@ -95,6 +96,7 @@ EXPORTS = (
     "gsp_multi_set_lens",
     "gsp_multi_set_media",
     "gsp_multi_set_light_sampling",
+    "gsp_multi_set_estimator",
     "gsp_multi_update_instances",
     "gsp_multi_update_tables",
     "gsp_multi_frame_begin",
@@ -153,6 +155,8 @@ def load():
     L.gsp_set_light_sampling.argtypes = [vp, u32]
     L.gsp_download_light_pick.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.gsp_multi_set_light_sampling.argtypes = [vp, u32]
+    L.gsp_set_estimator.argtypes = [vp, u32]
+    L.gsp_multi_set_estimator.argtypes = [vp, u32]
     L.gsp_update_instances.argtypes = [vp, vp, u32]
     L.gsp_update_tables.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_ctx_destroy.argtypes = [vp]
@@ -259,7 +263,7 @@ def build_info():
 
 
 # the files csrc/Makefile hashes into the digest, in its order
-DIGEST_SOURCES = ("pt_render.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
+DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
                   "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
 
 
@@ -352,6 +356,10 @@ class Context:
         coefficients; medium number k of abi.bsdf_handle(.., medium=k) is sigmas[k - 1].  None or empty = no media."""
         arr = abi.media_array(sigmas)
         self._check(self._L.gsp_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_media")
+
+    def set_estimator(self, mode):
+        """gsp_set_estimator (gpuspectral_pt.h "Estimator"): "reference" / "textbook" or abi.ESTIMATOR_REFERENCE / ESTIMATOR_TEXTBOOK."""
+        self._check(self._L.gsp_set_estimator(self._h, abi.estimator_mode(mode)), "gsp_set_estimator")
 
     def set_light_sampling(self, mode):
         """gsp_set_light_sampling (gpuspectral_pt.h "Light selection"): "uniform" / "power" or abi.LIGHTS_UNIFORM / LIGHTS_POWER."""
@@ -816,6 +824,10 @@ class MultiContext:
         """gsp_multi_set_media: Context.set_media on every share."""
         arr = abi.media_array(sigmas)
         self._check(self._L.gsp_multi_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_media")
+
+    def set_estimator(self, mode):
+        """gsp_multi_set_estimator: Context.set_estimator on every share."""
+        self._check(self._L.gsp_multi_set_estimator(self._h, abi.estimator_mode(mode)), "gsp_multi_set_estimator")
 
     def set_light_sampling(self, mode):
         """gsp_multi_set_light_sampling: Context.set_light_sampling on every share."""

@@ -85,7 +85,7 @@ extern "C" {
                                 gsp_download_taa_display, gsp_taa_display_to_device (see "Temporal anti-aliasing");
                                 gsp_set_media, gsp_multi_set_media (see "Interior media");
                                 gsp_set_light_sampling, gsp_download_light_pick, gsp_multi_set_light_sampling (see "Light
-                                selection") */
+                                selection"); gsp_set_estimator, gsp_multi_set_estimator (see "Estimator") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -691,6 +691,59 @@ typedef struct gsp_light_pick {
 } gsp_light_pick; /* 16 B */
 int gsp_set_light_sampling(gsp_context* ctx, uint32_t mode);
 int gsp_download_light_pick(gsp_context* ctx, gsp_light_pick* out, uint32_t capacity, uint32_t* count);
+
+/*
+ * Estimator: opt-in textbook multiple importance sampling in place of the reference's weights.
+ *
+ * The reference's estimator departs from an unbiased path tracer with next-event estimation (NEE) in three places of the shading
+ * vertex: the NEE weight takes the BSDF's pdf of the SAMPLED direction, not of the direction L to the light (rayhit.rchit:751);
+ * an emitter that a BSDF-sampled ray hits is weighted with the pdf of the light the previous vertex sampled, or 1 when that
+ * shadow ray was occluded, not with the pdf of reaching the emitter that is hit (:763-765, :785-790); and rough plastic's eval
+ * pdf carries a one-sided floor max(D cos, 0.01) that its sample pdf does not (:577 against :541).  GSP_ESTIMATOR_REFERENCE (the
+ * default) is the reference, bit for bit, with the kernels a context ran before this section existed.  GSP_ESTIMATOR_TEXTBOOK
+ * replaces the three by the textbook forms below; its frames converge to what plain path tracing (disable_nee) converges to,
+ * under either light selection mode.  The firefly cut-off stays gsp_render_params.clamp in both modes.
+ *
+ * The mode is CONTEXT STATE, like the lens, the media and the light selection: gsp_set_estimator(ctx, mode) holds until changed
+ * and survives gsp_upload_scene.  It may be called with a scene resident: the samples in flight finish first (the wait of every
+ * scene edit); under GSP_LIGHTS_POWER the tables are then packed again and uploaded, as gsp_set_light_sampling does.  An unknown
+ * mode is GSP_ERR_INVALID and leaves the state unchanged.
+ *
+ * The rule, float32 in this order, with the vertex's quantities as rayhit.rchit names them (bs = the BSDF's sample, lb = the
+ * BSDF's value and pdf for L, power_heuristic(f, g) = (f * f) / (f * f + g * g)):
+ *   1. NEE weight:      w = power_heuristic(lightPdf, lb.pdf)                       (the reference: bs.pdf)
+ *   2. rough plastic:   the eval pdf is ((0.5 * D(wh)) * |wh.z|) / (4 * |dot(wo, wh)|) + 0.5 * cosine_pdf(wi), the form its
+ *                       sample reports, without the max(.., 0.01)
+ *   3. emitter hit, with NEE on, countEmitted == 0 and wasDelta == 0:
+ *          isLight = emission.r != 0 || emission.g != 0 || emission.b != 0
+ *          A       = 0.5 * |length(cross(v2 - v0, v1 - v0))|        v0, v1, v2: the hit triangle's world-space vertices
+ *          hitPdf  = ((t * t) / (|dot(-rayDir, N)| * A)) * p_sel    t: the hit distance, N: the geometric normal
+ *          weight  = isLight ? power_heuristic(lastPdf, hitPdf) : 1
+ *      lastPdf = bs.pdf of the vertex that sent the ray.  The triangle's vertices are read only when isLight.
+ *   4. p_sel, the probability with which light selection picks the triangle that was hit:
+ *          GSP_LIGHTS_UNIFORM:   p_sel = 1.0f / (float)num_lights
+ *          GSP_LIGHTS_POWER:     w_hit = max((0.2126f * r + 0.7152f * g) + 0.0722f * b, 0) * A   of the hit's emission and A above;
+ *                                a non-finite or negative w_hit counts as 0
+ *                                p_sel = w_hit * inv_sum_w
+ *      inv_sum_w = the float32 rounding of 1 / sum(w), the sum of "Light selection" (in double, ascending index, from the caller's
+ *      light records).  When every w was 0 the table fell back to uniform: inv_sum_w is then stored as 0 (as it is when the sum
+ *      or its reciprocal leaves the format) and p_sel = 1.0f / (float)num_lights.  inv_sum_w travels in ONE trailing 16-byte
+ *      record {inv_sum_w, 0, 0, 0} behind the alias table, present only when BOTH GSP_LIGHTS_POWER and GSP_ESTIMATOR_TEXTBOOK are
+ *      on: every other context keeps the table image it had, and gsp_download_light_pick its count.
+ *      p_sel is the pmf of the weights, not of the integer table: it equals the probability the table samples with only to
+ *      within (1 + d_i) / (n * 2^32) ("Light selection"), far below float32 rounding of the weights for any table that fits memory.
+ *      Like the reference's 1 / num_lights, it assumes that EVERY EMISSIVE TRIANGLE IS ONE LIGHT RECORD of the same radiance and
+ *      vertices: an emissive triangle without a record is weighted as if NEE could reach it.
+ *
+ * Path state does not grow: the path's directWeight field is dead in this mode and carries lastPdf; a shadow ray carries the same
+ * value for both of its verdicts, and the occluded commit leaves the field alone.
+ *
+ * What changes and what does not.  Extension rays, shaded vertices and shadow rays are those of the reference mode under the
+ * same light selection (the weights do not steer the path), and with disable_nee the two modes give the same frame bit for bit.
+ */
+#define GSP_ESTIMATOR_REFERENCE 0u /* the reference's weights, rayhit.rchit:751,763-765,785-790,577 */
+#define GSP_ESTIMATOR_TEXTBOOK 1u  /* power heuristic over the pdfs of the direction taken; unbiased */
+int gsp_set_estimator(gsp_context* ctx, uint32_t mode);
 
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
@@ -1368,6 +1421,7 @@ int gsp_multi_update_camera(gsp_multi* m, const gsp_camera* camera);
 int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens); /* gsp_set_lens on every share */
 int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_media); /* gsp_set_media on every share */
 int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode); /* gsp_set_light_sampling on every share */
+int gsp_multi_set_estimator(gsp_multi* m, uint32_t mode);      /* gsp_set_estimator on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);
 int gsp_multi_update_tables(gsp_multi* m, const gsp_scene_desc* scene);
 int gsp_multi_frame_begin(gsp_multi* m, uint32_t width, uint32_t height);

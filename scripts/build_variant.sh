@@ -16,10 +16,15 @@ F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectori
 hipcc $F -c pt_render.hip -o build/var_$1/pt_render.o &
 hipcc $F -c pt_bvh.hip -o build/var_$1/pt_bvh.o &
 hipcc $F -c pt_multi.hip -o build/var_$1/pt_multi.o &
+TB=""
+if [ -f pt_render_textbook.hip ]; then  # (revisions with the textbook estimator keep its kernels in a unit of their own)
+  hipcc $F -c pt_render_textbook.hip -o build/var_$1/pt_render_textbook.o &
+  TB="build/var_$1/pt_render_textbook.o"
+fi
 wait
 printf 'extern "C" const char gsp_build_info_string[] = "arch=gfx950 digest=variant-%s flags=%s";\n' "$1" "$F" > build/var_$1/pt_buildinfo.cpp
 g++ -O2 -fPIC -c build/var_$1/pt_buildinfo.cpp -o build/var_$1/pt_buildinfo.o
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/gpuspectral_amd/lib/variants/$1.so" build/var_$1/pt_render.o build/var_$1/pt_bvh.o build/var_$1/pt_multi.o build/var_$1/pt_buildinfo.o $( grep -q dlopen pt_multi.hip && echo -ldl || echo -L/opt/rocm/lib -lrccl )
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/gpuspectral_amd/lib/variants/$1.so" build/var_$1/pt_render.o $TB build/var_$1/pt_bvh.o build/var_$1/pt_multi.o build/var_$1/pt_buildinfo.o $( grep -q dlopen pt_multi.hip && echo -ldl || echo -L/opt/rocm/lib -lrccl )
 echo built $1
 rm -rf build/var_$1
 [ -n "$3" ] && rm -rf "$T" || true
