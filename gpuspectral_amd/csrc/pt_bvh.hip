@@ -29,6 +29,12 @@
 //   refit     (refit_bvh, gsp_update_instances) the reference rebuilds only its TLAS when an object moves
 //             (PathTracer.cpp:10-19); the flattened tree's counterpart: re-bake every packet into its slot, recompute all
 //             node boxes + child orders bottom-up in the existing topology, one launch per level
+//
+// Host side (the end of this file; DESIGN.md §4 "BVH build: phases and scratch lifetimes"): build_bvh is the list of its phases,
+// one function each -- 1 alloc_outputs, 2 bake_and_sort (bake, morton, sort, scatter), 3 ploc (hierarchy), 4 reinsert, 5 collapse,
+// 6 emit; a scene of 0 or 1 triangles ends in single_node_tree after phase 1 / 2.  Phases 3 and 5 meet the host (read_back) once per
+// round / level; 2, 4 and 6 queue only.  The scratch arrays that outlive a phase are BuildScratch's, allocated once each; a phase
+// gets a view with its own names for them, and the table at BuildScratch says who writes, who reads and from where an array is free.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -887,44 +893,106 @@ struct Scratch {
     }
     return e;
   }
+  template <class... T>
+  hipError_t alloc_each(size_t count, T**... p) {  // `count` elements for each array, requested in the order given
+    hipError_t e = hipSuccess;
+    (void)(((e = alloc(p, count)) == hipSuccess) && ...);
+    return e;
+  }
 };
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
-}  // namespace
+inline int fail(std::string& err, const std::string& what, int code = GSP_ERR_DEVICE) { return err = what, code; }
+#define GSP_RC_TRY(call) do { const int rc_ = (call); if (rc_ != GSP_OK) return rc_; } while (0)
 
-void free_bvh(DeviceBvh& b) {
-  if (!b.arrays_external) {
-    (void)hipFree(b.nodes);
-    (void)hipFree(b.tri_isect);
-    (void)hipFree(b.tri_shade);
+// ---- the views a phase of build_bvh gets of the build's scratch: the phase's own names for the arrays it may touch ------------
+struct SortView {  // phase 2: packets and padded boxes per global triangle (_g), then the same in Morton order (_m, leaf_*)
+  uint32_t n, *bounds, *vals_in, *vals_out, *arrive, *s2g_m;
+  uint64_t *keys_in, *keys_out;
+  q4 *isect_g, *shade_g, *lo_g, *hi_g, *isect_m, *shade_m, *leaf_lo, *leaf_hi;
+};
+struct PlocView {  // phase 3: the clusters ping-pong between (code_a, lo_a, hi_a) and (code_b, lo_b, hi_b)
+  uint32_t n, *keep, *isnew, *kpos, *npos;
+  int32_t *code_a, *code_b, *nn, *tail_result, *parent_int, *parent_leaf;
+  q4 *lo_a, *hi_a, *lo_b, *hi_b, *nodes2;
+};
+struct ReinsertView { uint32_t n, *arrive; int32_t *parent_int, *parent_leaf; q4* nodes2; };                // phase 4
+struct CollapseView { uint32_t n, *n_inner, *n_leaf; int32_t *items_a, *items_b; const q4* nodes2; };       // phase 5
+struct EmitView { uint32_t n; const uint32_t* s2g_m; const q4 *isect_m, *shade_m; };  // phase 6, single-node tree: Morton order
+
+// The scratch arrays that outlive one phase of build_bvh, each allocated ONCE (alloc, ploc) under the name of its first role.  This
+// table is the only place where an array has two names; a phase sees its view.  n = triangles; phases: 2 bake / Morton / sort /
+// scatter, 3 PLOC, 4 reinsertion, 5 collapse, 6 emit.  "free from": no later phase reads the contents, a new one may take the array.
+//
+//   array [elements]             written by                       read by                 later roles                                    free from
+//   isect_g, shade_g [3n, 4n]    2 k_bake                         2 k_scatter             --                                             3
+//   lo_g, hi_g [n]               2 k_bake                         2 k_morton, k_scatter   --                                             3
+//   bounds [8]                   2 host copy, k_bake              2 k_morton              --                                             3
+//   keys_*, vals_* [n]           2 k_morton, sort                 2 sort, k_scatter       --                                             3
+//   isect_m, shade_m, s2g_m      2 k_scatter                      6 k_permute_tris        (n == 1: copied to slot kFirstSlot)            end
+//   leaf_lo, leaf_hi [n]         2 k_scatter (n == 1: read back)  3 as lo_a, hi_a         3 ping-pong side a: every second round, looped  4
+//                                                                                         or in the tail, OVERWRITES the leaf boxes
+//   int_lo, int_hi [n]           3 as lo_b, hi_b                  3                       ping-pong side b                               4
+//   arrive [n]                   2 memset 0 (kept; not read)      --                      3 nn (as int32_t): k_ploc_nn -> flags, apply;   5
+//                                                                                         4 arrive: memset 0 + k_ri_refit, every round
+//   child_l, child_r [n]         3 as code_a, code_b              3                       5 items_a, items_b: a level's binary nodes      6
+//   parent_int, parent_leaf [n]  3 memset 0xff, ploc_emit         4 k_ri_*                --                                             5
+//   nodes2 [4n]                  3 ploc_emit; 4 k_ri_apply/refit  4; 5 k_wide_*           --                                             6
+//   flag, idx4 [n + 1]           3 as keep, isnew                 3 scans, k_ploc_apply   5 n_inner, n_leaf: k_wide_count -> scans        6
+//   kpos, npos [n + 1]           3 scans (requested by ploc())    3 k_ploc_apply, host    3 kpos[0..1] = tail_result of k_ploc_tail, once 4
+//                                                                                         the looped rounds are over
+// Arrays of one phase are locals of that phase: the sort's and the scans' temporaries; 4: mv_x, mv_xp, mv_gain, lock, applied and
+// ri_bad (the violation counter phase 5 reads back with its first level); 5: wide, tri_src (both read by 6), inner_off, leaf_off.
+struct BuildScratch {
+  uint32_t n, *s2g_m, *bounds, *vals_in, *vals_out, *arrive, *flag, *idx4, *kpos, *npos;
+  q4 *isect_g, *shade_g, *isect_m, *shade_m, *lo_g, *hi_g, *leaf_lo, *leaf_hi, *int_lo, *int_hi, *nodes2;
+  uint64_t *keys_in, *keys_out;
+  int32_t *child_l, *child_r, *parent_int, *parent_leaf;
+  int alloc(Scratch& S, uint32_t num_tris, std::string& err) {
+    n = num_tris;
+    GSP_HIP_TRY(S.alloc(&isect_g, (size_t)kIsectQuads * n));
+    GSP_HIP_TRY(S.alloc(&shade_g, (size_t)kShadeQuads * n));
+    GSP_HIP_TRY(S.alloc(&isect_m, (size_t)kIsectQuads * n));
+    GSP_HIP_TRY(S.alloc(&shade_m, (size_t)kShadeQuads * n));
+    GSP_HIP_TRY(S.alloc_each(n, &s2g_m, &lo_g, &hi_g, &leaf_lo, &leaf_hi, &int_lo, &int_hi));
+    GSP_HIP_TRY(S.alloc(&bounds, 8));
+    GSP_HIP_TRY(S.alloc_each(n, &keys_in, &keys_out, &vals_in, &vals_out, &arrive, &child_l, &child_r, &parent_int, &parent_leaf));
+    GSP_HIP_TRY(S.alloc(&nodes2, 4ull * n));
+    GSP_HIP_TRY(S.alloc_each(n + 1ull, &flag, &idx4));
+    return GSP_OK;
   }
-  (void)hipFree(b.slot_to_global);
-  (void)hipFree(b.rf_leaf_lo);
-  (void)hipFree(b.rf_leaf_hi);
-  (void)hipFree(b.rf_box_lo);
-  (void)hipFree(b.rf_box_hi);
-  (void)hipFree(b.rf_area);
-  (void)hipFree(b.rf_total);
-  (void)hipFree(b.rf_tmp);
-  (void)hipFree(b.rf_bounds);
-  b = DeviceBvh{};
+  SortView sort() const { return {n, bounds, vals_in, vals_out, arrive, s2g_m, keys_in, keys_out, isect_g, shade_g, lo_g, hi_g, isect_m, shade_m, leaf_lo, leaf_hi}; }
+  int ploc(Scratch& S, PlocView* v, std::string& err) {  // (with its scan arrays: the arena has them behind the sort's temporary)
+    GSP_HIP_TRY(S.alloc_each(n + 1ull, &kpos, &npos));
+    *v = {n, flag, idx4, kpos, npos, child_l, child_r, (int32_t*)arrive, (int32_t*)kpos, parent_int, parent_leaf, leaf_lo, leaf_hi, int_lo, int_hi, nodes2};
+    return GSP_OK;
+  }
+  ReinsertView reinsert() const { return {n, arrive, parent_int, parent_leaf, nodes2}; }
+  CollapseView collapse() const { return {n, flag, idx4, child_l, child_r, nodes2}; }
+  EmitView emit() const { return {n, s2g_m, isect_m, shade_m}; }
+};
+
+// Queues the copies of a few device words to the host and waits for the stream: the one way a phase meets the host.
+struct ReadBack { void* host; const void* dev; size_t bytes; };  // dev == nullptr: nothing to read
+int read_back(hipStream_t stream, std::initializer_list<ReadBack> words, std::string& err) {
+  for (const ReadBack& w : words)
+    if (w.dev) GSP_HIP_TRY(hipMemcpyAsync(w.host, w.dev, w.bytes, hipMemcpyDeviceToHost, stream));
+  GSP_HIP_TRY(hipStreamSynchronize(stream));
+  return GSP_OK;
 }
 
-int build_bvh(hipStream_t stream, const BuildInput& in, DeviceBvh& out, std::string& err) {
-  free_bvh(out);
-  const uint32_t n = in.num_tris;
-  // triangle slots are handed out from kFirstSlot on: a node's tri_base - ni (pt_trace.h) is then never negative and
-  // fits the 28 bits the traversal packs it into; the leading slots stay all-zero triangles (det == 0: never hit)
-  // ... and kWide - 1 all-zero slots FOLLOW the last triangle: an unused child position of a node is marked only by an inverted
-  // quantised box, and when a node's extent is below ~8 ulp of the ray's distance to it the 8-ulp slack of the box test lets
-  // such a position through as "leaf slot tri_base + p" -- a neighbouring triangle for most nodes (harmless: tested, and
-  // accepted only if really hit), the slots behind the array for the last one
-  const uint32_t slots = n + kFirstSlot + (kWide - 1);
+// Phase 1: the three per-slot output arrays, all-zero.  Triangle slots are handed out from kFirstSlot on: a node's tri_base - ni
+// (pt_trace.h) is then never negative and fits the 28 bits the traversal packs it into; the leading slots stay all-zero triangles
+// (det == 0: never hit) ... and kWide - 1 all-zero slots FOLLOW the last triangle (tree_slots): an unused child position of a node is
+// marked only by an inverted quantised box, and when a node's extent is below ~8 ulp of the ray's distance to it the 8-ulp slack of
+// the box test lets such a position through as "leaf slot tri_base + p" -- a neighbouring triangle for most nodes (harmless: tested,
+// and accepted only if really hit), the slots behind the array for the last one
+int alloc_outputs(hipStream_t stream, uint32_t n, DeviceBvh& out, std::string& err) {
+  const size_t slots = tree_slots(n, kFirstSlot);
   out.num_tris = n;
   out.first_slot = kFirstSlot;
-  out.num_nodes = 0;
-  size_t b_is = (size_t)slots * 48, b_sh = (size_t)slots * 64, b_map = (size_t)slots * 4;
+  size_t b_is = slots * kIsectQuads * sizeof(q4), b_sh = slots * kShadeQuads * sizeof(q4), b_map = slots * sizeof(uint32_t);
   GSP_HIP_TRY(hipMalloc((void**)&out.tri_isect, b_is));
   GSP_HIP_TRY(hipMalloc((void**)&out.tri_shade, b_sh));
   GSP_HIP_TRY(hipMalloc((void**)&out.slot_to_global, b_map));
@@ -934,257 +1002,231 @@ int build_bvh(hipStream_t stream, const BuildInput& in, DeviceBvh& out, std::str
   GSP_HIP_TRY(hipMemsetAsync(out.slot_to_global, 0, b_map, stream));
   out.root = 0;  // the root is always node 0 (a node exists even for an empty scene)
   out.depth = 1;
-  if (n == 0) {  // one node without children: every ray misses
-    q4 node[kNodeQuads];
-    encode_node_w4(node, nullptr, 0, 0, 0u, kFirstSlot);
-    GSP_HIP_TRY(hipMalloc((void**)&out.nodes, kNodeAllocMin));
-    GSP_HIP_TRY(hipMemcpyAsync(out.nodes, node, kNodeBytes, hipMemcpyHostToDevice, stream));
-    out.bytes += kNodeBytes;
-    out.num_nodes = 1;
-    out.level_first = {0u, 1u};
-    GSP_HIP_TRY(hipStreamSynchronize(stream));
-    return GSP_OK;
+  return GSP_OK;
+}
+
+// The tree of fewer than two triangles has no binary node: ONE wide node without children (child == nullptr: every ray misses) or
+// with the triangle as its only child, whose packets (tri) go to slot kFirstSlot.
+int single_node_tree(hipStream_t stream, const WideChild* child, const EmitView* tri, DeviceBvh& out, std::string& err) {
+  q4 node[kNodeQuads];
+  encode_node_w4(node, child, 0, child ? 1 : 0, 0u, kFirstSlot);
+  GSP_HIP_TRY(hipMalloc((void**)&out.nodes, kNodeAllocMin));
+  GSP_HIP_TRY(hipMemcpyAsync(out.nodes, node, kNodeBytes, hipMemcpyHostToDevice, stream));
+  if (tri) {
+    GSP_HIP_TRY(hipMemcpyAsync(out.tri_isect + kIsectQuads * kFirstSlot, tri->isect_m, kIsectQuads * sizeof(q4), hipMemcpyDeviceToDevice, stream));
+    GSP_HIP_TRY(hipMemcpyAsync(out.tri_shade + kShadeQuads * kFirstSlot, tri->shade_m, kShadeQuads * sizeof(q4), hipMemcpyDeviceToDevice, stream));
+    GSP_HIP_TRY(hipMemcpyAsync(out.slot_to_global + kFirstSlot, tri->s2g_m, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
   }
+  out.bytes += kNodeBytes;
+  out.num_nodes = 1;
+  out.level_first = {0u, 1u};
+  GSP_HIP_TRY(hipStreamSynchronize(stream));
+  return GSP_OK;
+}
 
-  Scratch S;
-  S.reserve(640ull * n + (1ull << 20));  // (the requests below sum to ~600 B per triangle + the sort's and scans' temporaries)
-  q4 *isect_g, *shade_g, *lo_g, *hi_g, *leaf_lo, *leaf_hi, *int_lo, *int_hi, *nodes2, *isect_m, *shade_m;
-  uint32_t *bounds, *vals_in, *vals_out, *arrive, *flag, *idx4, *s2g_m;
-  uint64_t *keys_in, *keys_out;
-  int32_t *child_l, *child_r, *parent_int, *parent_leaf;
-  GSP_HIP_TRY(S.alloc(&isect_g, 3ull * n));
-  GSP_HIP_TRY(S.alloc(&shade_g, 4ull * n));
-  GSP_HIP_TRY(S.alloc(&isect_m, 3ull * n));  // packets in Morton order (the collapse defines the final order)
-  GSP_HIP_TRY(S.alloc(&shade_m, 4ull * n));
-  GSP_HIP_TRY(S.alloc(&s2g_m, n));
-  GSP_HIP_TRY(S.alloc(&lo_g, n));
-  GSP_HIP_TRY(S.alloc(&hi_g, n));
-  GSP_HIP_TRY(S.alloc(&leaf_lo, n));
-  GSP_HIP_TRY(S.alloc(&leaf_hi, n));
-  GSP_HIP_TRY(S.alloc(&int_lo, n));
-  GSP_HIP_TRY(S.alloc(&int_hi, n));
-  GSP_HIP_TRY(S.alloc(&bounds, 8));
-  GSP_HIP_TRY(S.alloc(&keys_in, n));
-  GSP_HIP_TRY(S.alloc(&keys_out, n));
-  GSP_HIP_TRY(S.alloc(&vals_in, n));
-  GSP_HIP_TRY(S.alloc(&vals_out, n));
-  GSP_HIP_TRY(S.alloc(&arrive, n));
-  GSP_HIP_TRY(S.alloc(&child_l, n));
-  GSP_HIP_TRY(S.alloc(&child_r, n));
-  GSP_HIP_TRY(S.alloc(&parent_int, n));
-  GSP_HIP_TRY(S.alloc(&parent_leaf, n));
-  GSP_HIP_TRY(S.alloc(&nodes2, 4ull * n));
-  GSP_HIP_TRY(S.alloc(&flag, n + 1ull));
-  GSP_HIP_TRY(S.alloc(&idx4, n + 1ull));
-
+// Phase 2: world-space packets and boxes, Morton codes, sort, packets and boxes into Morton order.  No host round trip.
+int bake_and_sort(hipStream_t stream, const BuildInput& in, Scratch& S, const SortView& v, std::string& err) {
+  const uint32_t n = v.n;
   const uint32_t init_bounds[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
-  GSP_HIP_TRY(hipMemcpyAsync(bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
-  GSP_HIP_TRY(hipMemsetAsync(arrive, 0, sizeof(uint32_t) * n, stream));
-
-  hipLaunchKernelGGL(k_bake, dim3(blocks_for(n)), dim3(kBlock), 0, stream, in, isect_g, shade_g, lo_g, hi_g, bounds, (const uint32_t*)nullptr, 0u);
-  hipLaunchKernelGGL(k_morton, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, lo_g, hi_g, bounds, keys_in, vals_in);
+  GSP_HIP_TRY(hipMemcpyAsync(v.bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, stream));
+  GSP_HIP_TRY(hipMemsetAsync(v.arrive, 0, sizeof(uint32_t) * n, stream));
+  hipLaunchKernelGGL(k_bake, dim3(blocks_for(n)), dim3(kBlock), 0, stream, in, v.isect_g, v.shade_g, v.lo_g, v.hi_g, v.bounds, (const uint32_t*)nullptr, 0u);
+  hipLaunchKernelGGL(k_morton, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, v.lo_g, v.hi_g, v.bounds, v.keys_in, v.vals_in);
   GSP_HIP_TRY(hipGetLastError());
-
   size_t temp_bytes = 0;
-  GSP_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 63, stream));
+  GSP_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, v.keys_in, v.keys_out, v.vals_in, v.vals_out, n, 0, 63, stream));
   void* temp = nullptr;
   GSP_HIP_TRY(S.alloc((char**)&temp, temp_bytes));
-  GSP_HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 63, stream));
-
-  hipLaunchKernelGGL(k_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, vals_out, isect_g, shade_g, lo_g, hi_g,
-                     isect_m, shade_m, leaf_lo, leaf_hi, s2g_m);
+  GSP_HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, v.keys_in, v.keys_out, v.vals_in, v.vals_out, n, 0, 63, stream));
+  hipLaunchKernelGGL(k_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, v.vals_out, v.isect_g, v.shade_g, v.lo_g, v.hi_g,
+                     v.isect_m, v.shade_m, v.leaf_lo, v.leaf_hi, v.s2g_m);
   GSP_HIP_TRY(hipGetLastError());
-  if (n == 1) {  // no binary inner node: one wide node with the triangle as its only child
-    q4 box[2];
-    GSP_HIP_TRY(hipMemcpyAsync(&box[0], leaf_lo, sizeof(q4), hipMemcpyDeviceToHost, stream));
-    GSP_HIP_TRY(hipMemcpyAsync(&box[1], leaf_hi, sizeof(q4), hipMemcpyDeviceToHost, stream));
-    GSP_HIP_TRY(hipStreamSynchronize(stream));
-    q4 node[kNodeQuads];
-    WideChild c[8];
-    c[0].lo = box[0];
-    c[0].hi = box[1];
-    encode_node_w4(node, c, 0, 1, 0u, kFirstSlot);
-    GSP_HIP_TRY(hipMalloc((void**)&out.nodes, kNodeAllocMin));
-    GSP_HIP_TRY(hipMemcpyAsync(out.nodes, node, kNodeBytes, hipMemcpyHostToDevice, stream));
-    GSP_HIP_TRY(hipMemcpyAsync(out.tri_isect + 3ull * kFirstSlot, isect_m, 48, hipMemcpyDeviceToDevice, stream));
-    GSP_HIP_TRY(hipMemcpyAsync(out.tri_shade + 4ull * kFirstSlot, shade_m, 64, hipMemcpyDeviceToDevice, stream));
-    GSP_HIP_TRY(hipMemcpyAsync(out.slot_to_global + kFirstSlot, s2g_m, 4, hipMemcpyDeviceToDevice, stream));
-    out.bytes += kNodeBytes;
-    out.num_nodes = 1;
-    out.level_first = {0u, 1u};
-    GSP_HIP_TRY(hipStreamSynchronize(stream));
-    return GSP_OK;
-  }
+  return GSP_OK;
+}
 
-  int32_t root2 = 0;  // binary root
-  uint32_t* ri_bad = nullptr;  // violations k_ri_validate counted (read back with the first collapse level's totals)
-  {
-    {
-      // PLOC: cluster arrays ping-pong between (code_a, leaf_lo/hi) and (code_b, int_lo/hi)
-      int32_t *code_a = child_l, *code_b = child_r, *nn = (int32_t*)arrive;
-      uint32_t *keep = flag, *isnew = idx4, *kpos, *npos;
-      GSP_HIP_TRY(S.alloc(&kpos, n + 1ull));
-      GSP_HIP_TRY(S.alloc(&npos, n + 1ull));
-      size_t sb = 0;
-      GSP_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, keep, kpos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
-      void* stmp = nullptr;
-      GSP_HIP_TRY(S.alloc((char**)&stmp, sb));
-      GSP_HIP_TRY(hipMemsetAsync(parent_int, 0xff, sizeof(int32_t) * n, stream));
-      GSP_HIP_TRY(hipMemsetAsync(parent_leaf, 0xff, sizeof(int32_t) * n, stream));
-      hipLaunchKernelGGL(k_ploc_init, dim3(blocks_for(n)), dim3(kBlock), 0, stream, (int)n, code_a);
-      q4 *lo_a = leaf_lo, *hi_a = leaf_hi, *lo_b = int_lo, *hi_b = int_hi;
-      uint32_t m = n, node_base = 0;
-      while (m > (uint32_t)kPlocTail) {
-        hipLaunchKernelGGL(k_ploc_nn, dim3(blocks_for(m)), dim3(kBlock), 0, stream, (int)m, lo_a, hi_a, nn);
-        hipLaunchKernelGGL(k_ploc_flags, dim3(blocks_for(m)), dim3(kBlock), 0, stream, (int)m, nn, keep, isnew);
-        GSP_HIP_TRY(hipMemsetAsync(keep + m, 0, sizeof(uint32_t), stream));
-        GSP_HIP_TRY(hipMemsetAsync(isnew + m, 0, sizeof(uint32_t), stream));
-        GSP_HIP_TRY(rocprim::exclusive_scan(stmp, sb, keep, kpos, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
-        GSP_HIP_TRY(rocprim::exclusive_scan(stmp, sb, isnew, npos, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
-        hipLaunchKernelGGL(k_ploc_apply, dim3(blocks_for(m)), dim3(kBlock), 0, stream, (int)m, nn, keep, isnew, kpos, npos,
-                           node_base, code_a, lo_a, hi_a, code_b, lo_b, hi_b, nodes2, parent_int, parent_leaf);
-        uint32_t counts[2] = {0, 0};
-        GSP_HIP_TRY(hipMemcpyAsync(&counts[0], kpos + m, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        GSP_HIP_TRY(hipMemcpyAsync(&counts[1], npos + m, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        GSP_HIP_TRY(hipStreamSynchronize(stream));
-        if (counts[1] == 0 || counts[0] != m - counts[1]) {
-          err = "PLOC made no progress (internal error)";
-          return GSP_ERR_DEVICE;
-        }
-        node_base += counts[1];
-        m = counts[0];
-        std::swap(code_a, code_b);
-        std::swap(lo_a, lo_b);
-        std::swap(hi_a, hi_b);
-      }
-      if (m > 1) {  // the remaining rounds in one launch
-        int32_t* tail_result = (int32_t*)kpos;  // (two words of a scan array nobody reads any more)
-        hipLaunchKernelGGL(k_ploc_tail, dim3(1), dim3(kPlocTailThreads), 0, stream, (int)m, node_base, code_a, lo_a, hi_a, code_b, lo_b, hi_b,
-                           nodes2, parent_int, parent_leaf, tail_result);
-        GSP_HIP_TRY(hipGetLastError());
-        int32_t res[2] = {0, 0};
-        GSP_HIP_TRY(hipMemcpyAsync(res, tail_result, sizeof(res), hipMemcpyDeviceToHost, stream));
-        GSP_HIP_TRY(hipStreamSynchronize(stream));
-        if (res[1] != 1) {
-          err = "PLOC made no progress (internal error)";
-          return GSP_ERR_DEVICE;
-        }
-        root2 = res[0];
-      } else {
-        GSP_HIP_TRY(hipMemcpyAsync(&root2, code_a, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        GSP_HIP_TRY(hipStreamSynchronize(stream));
-      }
-      // leaf_lo/leaf_hi may have been overwritten by the ping-pong: nothing below reads them again
-      // ---- parallel reinsertion rounds (above): no host round trip inside
-      const int rounds = in.reinsert_rounds < 0 ? kReinsertRounds : std::min(in.reinsert_rounds, 64);
-      if (rounds > 0 && n >= 16) {
-        const size_t idx = 2ull * n;
-        int32_t *mv_x, *mv_xp;
-        float* mv_gain;
-        unsigned long long* lock;
-        uint32_t* applied;
-        GSP_HIP_TRY(S.alloc(&mv_x, idx));
-        GSP_HIP_TRY(S.alloc(&mv_xp, idx));
-        GSP_HIP_TRY(S.alloc(&mv_gain, idx));
-        GSP_HIP_TRY(S.alloc(&lock, idx));
-        GSP_HIP_TRY(S.alloc(&applied, 64));
-        GSP_HIP_TRY(hipMemsetAsync(applied, 0, 64 * sizeof(uint32_t), stream));
-        const uint32_t nb = blocks_for(2ull * n - 1);
-        for (int r = 0; r < rounds; ++r) {
-          GSP_HIP_TRY(hipMemsetAsync(lock, 0, idx * sizeof(unsigned long long), stream));
-          hipLaunchKernelGGL(k_ri_search, dim3(nb), dim3(kBlock), 0, stream, n, root2, nodes2, parent_int, parent_leaf, mv_x, mv_xp, mv_gain);
-          hipLaunchKernelGGL(k_ri_lock, dim3(nb), dim3(kBlock), 0, stream, n, nodes2, parent_int, parent_leaf, mv_x, mv_xp, mv_gain, lock);
-          hipLaunchKernelGGL(k_ri_apply, dim3(nb), dim3(kBlock), 0, stream, n, nodes2, parent_int, parent_leaf, mv_x, mv_xp, mv_gain, lock,
-                             applied + r);
-          GSP_HIP_TRY(hipMemsetAsync(arrive, 0, sizeof(uint32_t) * n, stream));
-          hipLaunchKernelGGL(k_ri_refit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, nodes2, parent_int, parent_leaf, arrive);
-          GSP_HIP_TRY(hipGetLastError());
-        }
-        GSP_HIP_TRY(S.alloc(&ri_bad, 1));
-        GSP_HIP_TRY(hipMemsetAsync(ri_bad, 0, sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(k_ri_validate, dim3(blocks_for(n - 1)), dim3(kBlock), 0, stream, n, root2, nodes2, parent_int, ri_bad);
-        GSP_HIP_TRY(hipGetLastError());
-      }
-    }
+// Phase 3, PLOC over the Morton-ordered leaves; *root2 = the binary root.  One host round trip per looped round (the cluster
+// counts) and one behind the tail launch.
+int ploc(hipStream_t stream, Scratch& S, PlocView v, int32_t* root2, std::string& err) {
+  const uint32_t n = v.n;
+  size_t sb = 0;
+  GSP_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, v.keep, v.kpos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
+  void* stmp = nullptr;
+  GSP_HIP_TRY(S.alloc((char**)&stmp, sb));
+  GSP_HIP_TRY(hipMemsetAsync(v.parent_int, 0xff, sizeof(int32_t) * n, stream));
+  GSP_HIP_TRY(hipMemsetAsync(v.parent_leaf, 0xff, sizeof(int32_t) * n, stream));
+  hipLaunchKernelGGL(k_ploc_init, dim3(blocks_for(n)), dim3(kBlock), 0, stream, (int)n, v.code_a);
+  uint32_t m = n, node_base = 0;
+  while (m > (uint32_t)kPlocTail) {
+    hipLaunchKernelGGL(k_ploc_nn, dim3(blocks_for(m)), dim3(kBlock), 0, stream, (int)m, v.lo_a, v.hi_a, v.nn);
+    hipLaunchKernelGGL(k_ploc_flags, dim3(blocks_for(m)), dim3(kBlock), 0, stream, (int)m, v.nn, v.keep, v.isnew);
+    GSP_HIP_TRY(hipMemsetAsync(v.keep + m, 0, sizeof(uint32_t), stream));
+    GSP_HIP_TRY(hipMemsetAsync(v.isnew + m, 0, sizeof(uint32_t), stream));
+    GSP_HIP_TRY(rocprim::exclusive_scan(stmp, sb, v.keep, v.kpos, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
+    GSP_HIP_TRY(rocprim::exclusive_scan(stmp, sb, v.isnew, v.npos, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), stream));
+    hipLaunchKernelGGL(k_ploc_apply, dim3(blocks_for(m)), dim3(kBlock), 0, stream, (int)m, v.nn, v.keep, v.isnew, v.kpos, v.npos,
+                       node_base, v.code_a, v.lo_a, v.hi_a, v.code_b, v.lo_b, v.hi_b, v.nodes2, v.parent_int, v.parent_leaf);
+    uint32_t counts[2] = {0, 0};  // clusters kept, nodes made
+    GSP_RC_TRY(read_back(stream, {{&counts[0], v.kpos + m, sizeof(uint32_t)}, {&counts[1], v.npos + m, sizeof(uint32_t)}}, err));
+    if (counts[1] == 0 || counts[0] != m - counts[1]) return fail(err, "PLOC made no progress (internal error)");
+    node_base += counts[1];
+    m = counts[0];
+    std::swap(v.code_a, v.code_b);
+    std::swap(v.lo_a, v.lo_b);
+    std::swap(v.hi_a, v.hi_b);
   }
-  // ---- collapse to the wide tree, level by level ----
-  const uint32_t n_int = n - 1;  // binary inner nodes: an upper bound of the wide nodes
+  // The remaining rounds in one launch.  m >= 2 here, so no "one cluster left" case: n >= 2, and a looped round starts from m > kPlocTail
+  // and merges disjoint pairs (at most m / 2; the check above holds it to kept == m - made), so it leaves more than kPlocTail / 2 clusters.
+  hipLaunchKernelGGL(k_ploc_tail, dim3(1), dim3(kPlocTailThreads), 0, stream, (int)m, node_base, v.code_a, v.lo_a, v.hi_a, v.code_b, v.lo_b, v.hi_b,
+                     v.nodes2, v.parent_int, v.parent_leaf, v.tail_result);
+  GSP_HIP_TRY(hipGetLastError());
+  int32_t res[2] = {0, 0};
+  GSP_RC_TRY(read_back(stream, {{res, v.tail_result, sizeof(res)}}, err));
+  if (res[1] != 1) return fail(err, "PLOC made no progress (internal error)");
+  *root2 = res[0];
+  return GSP_OK;
+}
+
+// Phase 4: parallel reinsertion rounds over the PLOC tree, then the validation of its boxes.  No host round trip: *ri_bad = the
+// device counter of the violations k_ri_validate found (phase 5 reads it back with its first level), left alone when no round runs.
+int reinsert(hipStream_t stream, int rounds, int32_t root2, Scratch& S, const ReinsertView& v, uint32_t** ri_bad, std::string& err) {
+  const uint32_t n = v.n;
+  if (rounds <= 0 || n < 16) return GSP_OK;
+  const size_t idx = 2ull * n;
+  int32_t *mv_x, *mv_xp;
+  float* mv_gain;
+  unsigned long long* lock;
+  uint32_t* applied;
+  GSP_HIP_TRY(S.alloc_each(idx, &mv_x, &mv_xp, &mv_gain, &lock));
+  GSP_HIP_TRY(S.alloc(&applied, 64));
+  GSP_HIP_TRY(hipMemsetAsync(applied, 0, 64 * sizeof(uint32_t), stream));
+  const uint32_t nb = blocks_for(2ull * n - 1);
+  for (int r = 0; r < rounds; ++r) {
+    GSP_HIP_TRY(hipMemsetAsync(lock, 0, idx * sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(k_ri_search, dim3(nb), dim3(kBlock), 0, stream, n, root2, v.nodes2, v.parent_int, v.parent_leaf, mv_x, mv_xp, mv_gain);
+    hipLaunchKernelGGL(k_ri_lock, dim3(nb), dim3(kBlock), 0, stream, n, v.nodes2, v.parent_int, v.parent_leaf, mv_x, mv_xp, mv_gain, lock);
+    hipLaunchKernelGGL(k_ri_apply, dim3(nb), dim3(kBlock), 0, stream, n, v.nodes2, v.parent_int, v.parent_leaf, mv_x, mv_xp, mv_gain, lock,
+                       applied + r);
+    GSP_HIP_TRY(hipMemsetAsync(v.arrive, 0, sizeof(uint32_t) * n, stream));
+    hipLaunchKernelGGL(k_ri_refit, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, v.nodes2, v.parent_int, v.parent_leaf, v.arrive);
+    GSP_HIP_TRY(hipGetLastError());
+  }
+  GSP_HIP_TRY(S.alloc(ri_bad, 1));
+  GSP_HIP_TRY(hipMemsetAsync(*ri_bad, 0, sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(k_ri_validate, dim3(blocks_for(n - 1)), dim3(kBlock), 0, stream, n, root2, v.nodes2, v.parent_int, *ri_bad);
+  GSP_HIP_TRY(hipGetLastError());
+  return GSP_OK;
+}
+
+struct WideTree { const q4* wide; const uint32_t* tri_src; uint32_t num_nodes, levels; };  // phase 5 -> 6: node records, per slot its triangle
+// Phase 5: binary tree -> wide tree, level by level; level_first as DeviceBvh keeps it.  One host round trip per level (the next
+// level's node count and the level's triangles; with the first, phase 4's violation counter).
+// 4-wide default: the parity collapse (children = grandchildren).  On PLOC trees it beats the greedy surface-area
+// collapse -- bench scene 14.7 vs 15.1 nodes per extension ray, 7.5 vs 9.2 per shadow ray (profiles/r03_collapse.txt;
+// the CPU probe agrees: 10.2 vs 10.4, 7.7 vs 8.3) -- while on top-down SAH trees it is the other way round.
+int collapse(hipStream_t stream, int32_t root2, const uint32_t* ri_bad, Scratch& S, CollapseView v, std::vector<uint32_t>& level_first, WideTree* w,
+             std::string& err) {
+  const uint32_t n = v.n, n_int = n - 1;  // binary inner nodes: an upper bound of the wide nodes
   q4* wide = nullptr;
   GSP_HIP_TRY(S.alloc(&wide, (size_t)kNodeQuads * n_int));
-  int32_t *items_a = child_l, *items_b = child_r;  // (free again after the hierarchy pass)
-  uint32_t *n_inner = flag, *n_leaf = idx4, *inner_off, *leaf_off, *tri_src;
+  uint32_t *inner_off, *leaf_off, *tri_src;
   GSP_HIP_TRY(S.alloc(&tri_src, (size_t)n + kFirstSlot));
-  GSP_HIP_TRY(S.alloc(&inner_off, n + 1ull));
-  GSP_HIP_TRY(S.alloc(&leaf_off, n + 1ull));
+  GSP_HIP_TRY(S.alloc_each(n + 1ull, &inner_off, &leaf_off));
   size_t scan_bytes = 0;
-  GSP_HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, n_inner, inner_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
+  GSP_HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, v.n_inner, inner_off, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), stream));
   void* scan_tmp = nullptr;
   GSP_HIP_TRY(S.alloc((char**)&scan_tmp, scan_bytes));
-  GSP_HIP_TRY(hipMemcpyAsync(items_a, &root2, sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  GSP_HIP_TRY(hipMemcpyAsync(v.items_a, &root2, sizeof(int32_t), hipMemcpyHostToDevice, stream));
   uint32_t count = 1, node_first = 0, tri_done = kFirstSlot, levels = 0;
-  out.level_first.clear();
-  // 4-wide default: the parity collapse (children = grandchildren).  On PLOC trees it beats the greedy surface-area
-  // collapse -- bench scene 14.7 vs 15.1 nodes per extension ray, 7.5 vs 9.2 per shadow ray (profiles/r03_collapse.txt;
-  // the CPU probe agrees: 10.2 vs 10.4, 7.7 vs 8.3) -- while on top-down SAH trees it is the other way round.
+  level_first.clear();
   while (count > 0) {
-    out.level_first.push_back(node_first);
-    hipLaunchKernelGGL(k_wide_count, dim3(blocks_for(count + 1ull)), dim3(kBlock), 0, stream, (int)count, items_a, nodes2, n_inner, n_leaf);
-    GSP_HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, n_inner, inner_off, 0u, (size_t)count + 1, rocprim::plus<uint32_t>(), stream));
-    GSP_HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, n_leaf, leaf_off, 0u, (size_t)count + 1, rocprim::plus<uint32_t>(), stream));
+    level_first.push_back(node_first);
+    hipLaunchKernelGGL(k_wide_count, dim3(blocks_for(count + 1ull)), dim3(kBlock), 0, stream, (int)count, v.items_a, v.nodes2, v.n_inner, v.n_leaf);
+    GSP_HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, v.n_inner, inner_off, 0u, (size_t)count + 1, rocprim::plus<uint32_t>(), stream));
+    GSP_HIP_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, v.n_leaf, leaf_off, 0u, (size_t)count + 1, rocprim::plus<uint32_t>(), stream));
     const uint32_t child_first = node_first + count;
-    hipLaunchKernelGGL(k_wide_emit, dim3(blocks_for(count)), dim3(kBlock), 0, stream, (int)count, items_a, nodes2, inner_off, leaf_off,
-                       node_first, child_first, tri_done, wide, items_b, tri_src);
-    uint32_t totals[2] = {0, 0}, bad = 0;
-    GSP_HIP_TRY(hipMemcpyAsync(&totals[0], inner_off + count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GSP_HIP_TRY(hipMemcpyAsync(&totals[1], leaf_off + count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (levels == 0 && ri_bad) GSP_HIP_TRY(hipMemcpyAsync(&bad, ri_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GSP_HIP_TRY(hipStreamSynchronize(stream));
+    hipLaunchKernelGGL(k_wide_emit, dim3(blocks_for(count)), dim3(kBlock), 0, stream, (int)count, v.items_a, v.nodes2, inner_off, leaf_off,
+                       node_first, child_first, tri_done, wide, v.items_b, tri_src);
+    uint32_t totals[2] = {0, 0}, bad = 0;  // inner and leaf children of the level
+    GSP_RC_TRY(read_back(stream, {{&totals[0], inner_off + count, sizeof(uint32_t)}, {&totals[1], leaf_off + count, sizeof(uint32_t)},
+                                  {&bad, levels == 0 ? ri_bad : nullptr, sizeof(uint32_t)}}, err));
     GSP_HIP_TRY(hipGetLastError());
-    if (bad) {
-      err = "BVH build: " + std::to_string(bad) + " node boxes of the reinserted tree do not bound their children (internal error: "
-            "the cross-XCD hand-over of k_ri_refit failed)";
-      return GSP_ERR_DEVICE;
-    }
+    if (bad)
+      return fail(err, "BVH build: " + std::to_string(bad) + " node boxes of the reinserted tree do not bound their children (internal error: "
+                       "the cross-XCD hand-over of k_ri_refit failed)");
     node_first = child_first;
     tri_done += totals[1];
     count = totals[0];
-    std::swap(items_a, items_b);
+    std::swap(v.items_a, v.items_b);
     ++levels;
-    if ((uint64_t)node_first + count > n_int || levels > 4096) {
-      err = "wide collapse overran its node bound (internal error)";
-      return GSP_ERR_DEVICE;
-    }
+    if ((uint64_t)node_first + count > n_int || levels > 4096) return fail(err, "wide collapse overran its node bound (internal error)");
   }
-  if (tri_done != n + kFirstSlot) {
-    err = "wide collapse lost triangles (internal error)";
-    return GSP_ERR_DEVICE;
-  }
-  const uint32_t num_nodes = node_first;
-  out.level_first.push_back(num_nodes);
-  if (num_nodes >= kMaxNodes) {
-    err = "scene too large: more BVH nodes than the traversal's node index holds (internal error: gsp_upload_scene bounds the triangle count)";
-    return GSP_ERR_INVALID;
-  }
-  out.num_nodes = num_nodes;
-  const size_t b_nodes = (size_t)num_nodes * kNodeBytes;
+  if (tri_done != n + kFirstSlot) return fail(err, "wide collapse lost triangles (internal error)");
+  level_first.push_back(node_first);
+  if (node_first >= kMaxNodes)
+    return fail(err, "scene too large: more BVH nodes than the traversal's node index holds (internal error: gsp_upload_scene bounds the triangle count)", GSP_ERR_INVALID);
+  *w = {wide, tri_src, node_first, levels};
+  return GSP_OK;
+}
+
+// Phase 6: the node array, and the triangles into the slots the collapse gave them.  Waits for the stream.
+int emit(hipStream_t stream, const WideTree& w, const EmitView& v, DeviceBvh& out, std::string& err) {
+  out.num_nodes = w.num_nodes;
+  const size_t b_nodes = (size_t)w.num_nodes * kNodeBytes;
   GSP_HIP_TRY(hipMalloc((void**)&out.nodes, std::max<size_t>(b_nodes, kNodeAllocMin)));  // k_trace stages the first kTopNodes records
   out.bytes += b_nodes;
-  GSP_HIP_TRY(hipMemcpyAsync(out.nodes, wide, b_nodes, hipMemcpyDeviceToDevice, stream));
-  hipLaunchKernelGGL(k_permute_tris, dim3(blocks_for(n)), dim3(kBlock), 0, stream, n, tri_src + kFirstSlot, isect_m, shade_m, s2g_m,
-                     out.tri_isect + 3ull * kFirstSlot, out.tri_shade + 4ull * kFirstSlot, out.slot_to_global + kFirstSlot);
+  GSP_HIP_TRY(hipMemcpyAsync(out.nodes, w.wide, b_nodes, hipMemcpyDeviceToDevice, stream));
+  hipLaunchKernelGGL(k_permute_tris, dim3(blocks_for(v.n)), dim3(kBlock), 0, stream, v.n, w.tri_src + kFirstSlot, v.isect_m, v.shade_m, v.s2g_m,
+                     out.tri_isect + kIsectQuads * kFirstSlot, out.tri_shade + kShadeQuads * kFirstSlot, out.slot_to_global + kFirstSlot);
   GSP_HIP_TRY(hipGetLastError());
   GSP_HIP_TRY(hipStreamSynchronize(stream));
-  out.depth = levels;  // levels of the wide tree: a traversal stacks at most one node group per level
+  out.depth = w.levels;  // levels of the wide tree: a traversal stacks at most one node group per level
   return GSP_OK;
+}
+
+}  // namespace
+
+void free_bvh(DeviceBvh& b) {
+  if (!b.arrays_external) b.free_tree_arrays();
+  (void)hipFree(b.slot_to_global);
+  b.rf.release();
+  b = DeviceBvh{};
+}
+
+int build_bvh(hipStream_t stream, const BuildInput& in, DeviceBvh& out, std::string& err) {
+  free_bvh(out);
+  const uint32_t n = in.num_tris;
+  GSP_RC_TRY(alloc_outputs(stream, n, out, err));
+  if (n == 0) return single_node_tree(stream, nullptr, nullptr, out, err);
+  Scratch S;
+  S.reserve(640ull * n + (1ull << 20));  // (the requests sum to ~600 B per triangle + the sort's and scans' temporaries)
+  BuildScratch B;
+  GSP_RC_TRY(B.alloc(S, n, err));
+  GSP_RC_TRY(bake_and_sort(stream, in, S, B.sort(), err));
+  if (n == 1) {
+    WideChild c;
+    const EmitView tri = B.emit();
+    GSP_RC_TRY(read_back(stream, {{&c.lo, B.leaf_lo, sizeof(q4)}, {&c.hi, B.leaf_hi, sizeof(q4)}}, err));
+    return single_node_tree(stream, &c, &tri, out, err);
+  }
+  PlocView clusters;
+  GSP_RC_TRY(B.ploc(S, &clusters, err));
+  int32_t root2 = 0;           // binary root
+  uint32_t* ri_bad = nullptr;  // violations k_ri_validate counted
+  GSP_RC_TRY(ploc(stream, S, clusters, &root2, err));
+  const int rounds = in.reinsert_rounds < 0 ? kReinsertRounds : std::min(in.reinsert_rounds, 64);
+  GSP_RC_TRY(reinsert(stream, rounds, root2, S, B.reinsert(), &ri_bad, err));
+  WideTree w;
+  GSP_RC_TRY(collapse(stream, root2, ri_bad, S, B.collapse(), out.level_first, &w, err));
+  return emit(stream, w, B.emit(), out, err);
 }
 
 namespace {
 int tree_area(hipStream_t stream, const DeviceBvh& bvh, double* sum, std::string& err) {
-  hipLaunchKernelGGL(k_wide_area, dim3(blocks_for(bvh.num_nodes)), dim3(kBlock), 0, stream, bvh.num_nodes, bvh.nodes, bvh.rf_area);
+  hipLaunchKernelGGL(k_wide_area, dim3(blocks_for(bvh.num_nodes)), dim3(kBlock), 0, stream, bvh.num_nodes, bvh.nodes, bvh.rf.area);
   GSP_HIP_TRY(hipGetLastError());
-  size_t tb = bvh.rf_tmp_bytes;  // (no atomics: the same sum every run)
-  GSP_HIP_TRY(rocprim::reduce(bvh.rf_tmp, tb, bvh.rf_area, bvh.rf_total, 0.0, (size_t)bvh.num_nodes, rocprim::plus<double>(), stream));
-  GSP_HIP_TRY(hipMemcpyAsync(sum, bvh.rf_total, sizeof(double), hipMemcpyDeviceToHost, stream));
+  size_t tb = bvh.rf.tmp_bytes;  // (no atomics: the same sum every run)
+  GSP_HIP_TRY(rocprim::reduce(bvh.rf.tmp, tb, bvh.rf.area, bvh.rf.total, 0.0, (size_t)bvh.num_nodes, rocprim::plus<double>(), stream));
+  GSP_HIP_TRY(hipMemcpyAsync(sum, bvh.rf.total, sizeof(double), hipMemcpyDeviceToHost, stream));
   GSP_HIP_TRY(hipStreamSynchronize(stream));
   return GSP_OK;
 }
@@ -1193,50 +1235,40 @@ int tree_area(hipStream_t stream, const DeviceBvh& bvh, double* sum, std::string
 int refit_bvh(hipStream_t stream, const BuildInput& in, DeviceBvh& bvh, double* growth, std::string& err) {
   *growth = 1.0;
   const uint32_t n = bvh.num_tris;
-  if (in.num_tris != n || bvh.level_first.size() < 2 || bvh.level_first.back() != bvh.num_nodes || !bvh.nodes) {
-    err = "refit_bvh: the tree does not belong to this triangle list (internal error)";
-    return GSP_ERR_DEVICE;
-  }
+  if (in.num_tris != n || bvh.level_first.size() < 2 || bvh.level_first.back() != bvh.num_nodes || !bvh.nodes)
+    return fail(err, "refit_bvh: the tree does not belong to this triangle list (internal error)");
   if (n == 0) return GSP_OK;
-  const uint32_t slots = n + kFirstSlot + (kWide - 1);
-  if (!bvh.rf_bounds) {  // first refit of this tree (or an earlier one ran out of memory half-way: start over)
-    for (void** q : {(void**)&bvh.rf_leaf_lo, (void**)&bvh.rf_leaf_hi, (void**)&bvh.rf_box_lo, (void**)&bvh.rf_box_hi, (void**)&bvh.rf_area,
-                     (void**)&bvh.rf_total, &bvh.rf_tmp}) {
-      (void)hipFree(*q);
-      *q = nullptr;
-    }
+  RefitScratch& rf = bvh.rf;
+  if (!rf.bounds) {  // first refit of this tree (or an earlier one ran out of memory half-way: start over)
+    rf.release();
+    const size_t slots = tree_slots(n, kFirstSlot);
     size_t tb = 0;
-    GSP_HIP_TRY(rocprim::reduce(nullptr, tb, bvh.rf_area, bvh.rf_total, 0.0, (size_t)bvh.num_nodes, rocprim::plus<double>(), stream));
+    GSP_HIP_TRY(rocprim::reduce(nullptr, tb, rf.area, rf.total, 0.0, (size_t)bvh.num_nodes, rocprim::plus<double>(), stream));
     tb = std::max<size_t>(tb, 16);
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_leaf_lo, sizeof(q4) * slots));
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_leaf_hi, sizeof(q4) * slots));
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_box_lo, sizeof(q4) * bvh.num_nodes));
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_box_hi, sizeof(q4) * bvh.num_nodes));
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_area, sizeof(double) * bvh.num_nodes));
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_total, sizeof(double)));
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_tmp, tb));
-    bvh.rf_tmp_bytes = tb;
-    GSP_HIP_TRY(hipMalloc((void**)&bvh.rf_bounds, 8 * sizeof(uint32_t)));  // (last: marks the set complete)
-    bvh.bytes += 2 * sizeof(q4) * ((size_t)slots + bvh.num_nodes) + sizeof(double) * (bvh.num_nodes + 1ull) + tb + 32;
+    GSP_HIP_TRY(hipMalloc((void**)&rf.leaf_lo, sizeof(q4) * slots));
+    GSP_HIP_TRY(hipMalloc((void**)&rf.leaf_hi, sizeof(q4) * slots));
+    GSP_HIP_TRY(hipMalloc((void**)&rf.box_lo, sizeof(q4) * bvh.num_nodes));
+    GSP_HIP_TRY(hipMalloc((void**)&rf.box_hi, sizeof(q4) * bvh.num_nodes));
+    GSP_HIP_TRY(hipMalloc((void**)&rf.area, sizeof(double) * bvh.num_nodes));
+    GSP_HIP_TRY(hipMalloc((void**)&rf.total, sizeof(double)));
+    GSP_HIP_TRY(hipMalloc((void**)&rf.tmp, tb));
+    rf.tmp_bytes = tb;
+    GSP_HIP_TRY(hipMalloc((void**)&rf.bounds, 8 * sizeof(uint32_t)));  // (last: marks the set complete)
+    bvh.bytes += 2 * sizeof(q4) * (slots + bvh.num_nodes) + sizeof(double) * (bvh.num_nodes + 1ull) + tb + 32;
   }
-  int rc;
-  if (bvh.area_built <= 0.0) {  // the tree is as built: its own measure first
-    rc = tree_area(stream, bvh, &bvh.area_built, err);
-    if (rc != GSP_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_bake, dim3(blocks_for(n)), dim3(kBlock), 0, stream, in, bvh.tri_isect, bvh.tri_shade, bvh.rf_leaf_lo, bvh.rf_leaf_hi,
+  if (bvh.area_built <= 0.0) GSP_RC_TRY(tree_area(stream, bvh, &bvh.area_built, err));  // the tree is as built: its own measure first
+  hipLaunchKernelGGL(k_bake, dim3(blocks_for(n)), dim3(kBlock), 0, stream, in, bvh.tri_isect, bvh.tri_shade, rf.leaf_lo, rf.leaf_hi,
                      (uint32_t*)nullptr, (const uint32_t*)bvh.slot_to_global, kFirstSlot);
   GSP_HIP_TRY(hipGetLastError());
   for (size_t l = bvh.level_first.size() - 1; l-- > 0;) {
     const uint32_t first = bvh.level_first[l], count = bvh.level_first[l + 1] - first;
     if (count == 0) continue;
-    hipLaunchKernelGGL(k_refit_level, dim3(blocks_for(count)), dim3(kBlock), 0, stream, first, count, bvh.nodes, bvh.rf_leaf_lo, bvh.rf_leaf_hi,
-                       bvh.rf_box_lo, bvh.rf_box_hi);
+    hipLaunchKernelGGL(k_refit_level, dim3(blocks_for(count)), dim3(kBlock), 0, stream, first, count, bvh.nodes, rf.leaf_lo, rf.leaf_hi, rf.box_lo,
+                       rf.box_hi);
   }
   GSP_HIP_TRY(hipGetLastError());
   double now = 0.0;
-  rc = tree_area(stream, bvh, &now, err);  // (synchronises: the caller's instance tables may go out of scope)
-  if (rc != GSP_OK) return rc;
+  GSP_RC_TRY(tree_area(stream, bvh, &now, err));  // (synchronises: the caller's instance tables may go out of scope)
   ++bvh.refits;
   *growth = bvh.area_built > 0.0 ? now / bvh.area_built : (now > 0.0 ? 1.0e30 : 1.0);
   return GSP_OK;

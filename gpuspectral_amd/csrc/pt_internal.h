@@ -54,11 +54,28 @@ void launch_finish_textbook(const TextbookLaunch& a);
     }                                                                                         \
   } while (0)
 
+// 16-byte quads per triangle slot of the intersection and the shading array (a node record: kNodeQuads, pt_trace.h)
+constexpr uint32_t kIsectQuads = 3u, kShadeQuads = 4u;
+
+// scratch of refit_bvh, allocated by the first refit of a tree and kept with it (a per-frame call: seven hipMalloc / hipFree
+// pairs cost more than the kernels): padded triangle boxes by slot, node boxes, per-node areas, reduction space
+struct RefitScratch {
+  q4 *leaf_lo = nullptr, *leaf_hi = nullptr, *box_lo = nullptr, *box_hi = nullptr;
+  double *area = nullptr, *total = nullptr;
+  void* tmp = nullptr;
+  size_t tmp_bytes = 0;
+  uint32_t* bounds = nullptr;  // allocated last: non-null marks the set complete
+  void release() {
+    for (void* p : {(void*)leaf_lo, (void*)leaf_hi, (void*)box_lo, (void*)box_hi, (void*)area, (void*)total, tmp, (void*)bounds}) (void)hipFree(p);
+    *this = RefitScratch{};
+  }
+};
+
 // Result of the device BVH build; all pointers are device memory owned by the caller's context.
 struct DeviceBvh {
   q4* nodes = nullptr;      // wide BVH, kNodeQuads quads per node (pt_trace.h); node 0 is the root
-  q4* tri_isect = nullptr;  // 3 quads per slot
-  q4* tri_shade = nullptr;  // 4 quads per slot
+  q4* tri_isect = nullptr;  // kIsectQuads quads per slot
+  q4* tri_shade = nullptr;  // kShadeQuads quads per slot
   uint32_t* slot_to_global = nullptr;
   bool arrays_external = false;  // nodes / tri_isect / tri_shade are a slot of the context's geometry ring (pt_render.hip): not free_bvh's
   int32_t root = 0;
@@ -72,14 +89,19 @@ struct DeviceBvh {
   std::vector<uint32_t> level_first;
   double area_built = 0.0;  // sum of the child-box surface areas right after the last full build (0 = not measured yet)
   uint32_t refits = 0;      // refits since that build
-  // scratch of refit_bvh, allocated by the first refit of a tree and kept with it (a per-frame call: seven hipMalloc / hipFree
-  // pairs cost more than the kernels): padded triangle boxes by slot, node boxes, per-node areas, reduction space
-  q4 *rf_leaf_lo = nullptr, *rf_leaf_hi = nullptr, *rf_box_lo = nullptr, *rf_box_hi = nullptr;
-  double *rf_area = nullptr, *rf_total = nullptr;
-  void* rf_tmp = nullptr;
-  size_t rf_tmp_bytes = 0;
-  uint32_t* rf_bounds = nullptr;
+  RefitScratch rf;
+  // the three arrays a tree owns go (free_bvh; pt_render_scene.inc when they move into the geometry ring): not for arrays_external
+  void free_tree_arrays() {
+    (void)hipFree(nodes);
+    (void)hipFree(tri_isect);
+    (void)hipFree(tri_shade);
+    nodes = tri_isect = tri_shade = nullptr;
+  }
 };
+// triangle slots a tree's intersection / shading arrays hold: first_slot leading all-zero slots (build_bvh), the triangles, and
+// the kWide - 1 all-zero slots behind them that a wide leaf may read
+inline uint64_t tree_slots(uint64_t num_tris, uint32_t first_slot) { return num_tris + first_slot + (kWide - 1); }
+inline uint64_t tree_slots(const DeviceBvh& t) { return tree_slots(t.num_tris, t.first_slot); }
 
 struct BuildInput {
   const gsp_instance* instances;  // device

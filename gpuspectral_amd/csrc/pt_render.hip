@@ -56,15 +56,12 @@
 
 using namespace gsp;
 
-// triangle slots a tree's intersection / shading arrays hold: leading all-zero slots, the triangles, the tail a wide leaf may read
-static uint64_t tree_slots(const DeviceBvh& t) { return (uint64_t)t.num_tris + t.first_slot + (kWide - 1); }
-
 // The three geometry arrays -- node records, intersection triangles, shading packets -- as ONE allocation unit addressed by
 // TRIANGLE SLOT: slot s starts at quad s * kPerSlot[k] of array k (a tree has at most one node per slot, so it fits where its
-// triangles do).  The context's geometry ring is one of these; nothing else spells the per-slot quad counts.
+// triangles do).  The context's geometry ring is one of these; the per-slot quad counts are pt_internal.h's (the builder's too).
 struct TreeArrays {
   DevBuf<q4> nodes, isect, shade;
-  static constexpr size_t kPerSlot[3] = {kNodeQuads, 3, 4};  // quads per triangle slot: nodes, isect, shade
+  static constexpr size_t kPerSlot[3] = {kNodeQuads, kIsectQuads, kShadeQuads};  // quads per triangle slot: nodes, isect, shade
   // bytes of the three arrays of a tree that owns them, as build_bvh counts them in DeviceBvh::bytes
   static size_t bytes_owned_by(const DeviceBvh& t) { return (size_t)t.num_nodes * kNodeBytes + tree_slots(t) * (kPerSlot[1] + kPerSlot[2]) * sizeof(q4); }
   size_t bytes() const { return (nodes.count + isect.count + shade.count) * sizeof(q4); }

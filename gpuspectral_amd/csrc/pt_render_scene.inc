@@ -178,10 +178,7 @@ static int grow_table_ring(gsp_context* ctx, uint32_t slots) {
 // the tree gives back the three arrays it owns (as build_bvh counted them in DeviceBvh::bytes, which the context's ledger holds)
 static void release_own_arrays(gsp_context* ctx, DeviceBvh& t) {
   const size_t freed = TreeArrays::bytes_owned_by(t);
-  (void)hipFree(t.nodes);
-  (void)hipFree(t.tri_isect);
-  (void)hipFree(t.tri_shade);
-  t.nodes = t.tri_isect = t.tri_shade = nullptr;
+  t.free_tree_arrays();
   t.bytes -= std::min(t.bytes, freed);
   ctx->bytes.sub(freed);
 }
@@ -431,7 +428,7 @@ static int build_whole_tree(gsp_context* ctx, const BuildInput& bi) {
   }
   ctx->bytes.add(ctx->bvh.bytes);
   if (ctx->num_textures) {  // the collapse defines the slot order: the per-slot uv follow it
-    CTX_TRY(ctx, ctx->tri_uv.ensure(8ull * (ctx->total_tris + ctx->bvh.first_slot + kWide), &ctx->bytes));
+    CTX_TRY(ctx, ctx->tri_uv.ensure(8ull * (tree_slots(ctx->bvh) + 1), &ctx->bytes));
     if (ctx->total_tris) {
       hipLaunchKernelGGL(k_gather_uv, dim3((uint32_t)((ctx->total_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (uint32_t)ctx->total_tris,
                          ctx->bvh.first_slot, ctx->bvh.slot_to_global, ctx->d_first.p, bi.num_instances, ctx->d_inst.p, ctx->d_uv.p, ctx->tri_uv.p);
