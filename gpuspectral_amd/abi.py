@@ -184,6 +184,22 @@ def media_array(sigmas):
     return (Medium * len(sigmas))(*[Medium((C.c_float * 3)(*s), 0.0) for s in sigmas])
 
 
+class MediumScatter(C.Structure):
+    """gsp_medium_scatter (include/gpuspectral_pt.h "Scattering media"): sigma_s per channel in 1 / length, Henyey-Greenstein g."""
+
+    _fields_ = [("sigma_s", C.c_float * 3), ("g", C.c_float)]
+
+
+def media_scatter_array(scatter):
+    """[(r, g, b) or ((r, g, b), g_hg), ...] -> (MediumScatter * n), or None for an empty list."""
+    out = []
+    for e in (scatter if scatter is not None else []):
+        e = tuple(e)
+        sig, g = (e[0], e[1]) if len(e) == 2 and hasattr(e[0], "__len__") else (e, 0.0)
+        out.append(MediumScatter((C.c_float * 3)(*[float(x) for x in sig]), float(g)))
+    return (MediumScatter * len(out))(*out) if out else None
+
+
 # Light selection (include/gpuspectral_pt.h "Light selection")
 LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1
 LIGHT_SAMPLING_NAMES = {"uniform": LIGHTS_UNIFORM, "power": LIGHTS_POWER}

@@ -36,6 +36,24 @@ inline const char* check_media(const gsp_medium* media, uint32_t num_media) {
       if (!(media[k].sigma_a[c] >= 0.0f) || std::isinf(media[k].sigma_a[c])) return "gsp_medium.sigma_a must be finite and >= 0";
   return nullptr;
 }
+// gsp_set_media_scattering: the table parallel to the context's `have` media (include/gpuspectral_pt.h, "Scattering media"; NULL or
+// 0 entries = none).  Returns nullptr or the text for gsp_last_error.
+inline const char* check_media_scattering(const gsp_medium_scatter* scatter, uint32_t n, uint32_t have) {
+  if (!scatter || n == 0u) return nullptr;
+  if (n != have) return "gsp_set_media_scattering: the count must be 0 or the context's media count (the table is parallel to gsp_set_media's)";
+  for (uint32_t k = 0; k < n; ++k) {
+    for (int c = 0; c < 3; ++c)
+      if (!(scatter[k].sigma_s[c] >= 0.0f) || std::isinf(scatter[k].sigma_s[c])) return "gsp_medium_scatter.sigma_s must be finite and >= 0";
+    if (!(std::fabs(scatter[k].g) < 1.0f)) return "gsp_medium_scatter.g must be finite with |g| < 1";
+  }
+  return nullptr;
+}
+// does any medium of the table scatter?  (selects the <SCT> kernels)
+inline bool any_scattering(const gsp_medium_scatter* scatter, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    if (scatter[k].sigma_s[0] != 0.0f || scatter[k].sigma_s[1] != 0.0f || scatter[k].sigma_s[2] != 0.0f) return true;
+  return false;
+}
 // the largest medium number the instances name (bits 19..30 of gsp_instance.bsdf)
 inline uint32_t max_medium_number(const gsp_instance* inst, size_t n) {
   uint32_t m = 0;

@@ -44,6 +44,14 @@ struct TextbookLaunch {
 };
 void launch_shade_textbook(const TextbookLaunch& a);
 void launch_finish_textbook(const TextbookLaunch& a);
+// Scattering media: the <MED = true, SCT = true> instantiations of both kernels, over TEX x VER x LSEL x EST, live in
+// pt_render_scatter.hip and take the same record + the scattering table and the estimator flag.  media and scatter are never null here.
+struct ScatterLaunch : TextbookLaunch {
+  const gsp_medium_scatter* scatter;
+  bool est;
+};
+void launch_shade_scatter(const ScatterLaunch& a);
+void launch_finish_scatter(const ScatterLaunch& a);
 
 #define GSP_HIP_TRY(expr)                                                                     \
   do {                                                                                        \

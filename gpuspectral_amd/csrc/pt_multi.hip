@@ -372,6 +372,11 @@ int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_medi
   return for_each_share(m, [&](size_t r) { return gsp_set_media(m->ctx[r], media, num_media); });
 }
 
+int gsp_multi_set_media_scattering(gsp_multi* m, const gsp_medium_scatter* scatter, uint32_t num_media) {  // (NULL or 0 = none)
+  if (!m) return GSP_ERR_INVALID;
+  return for_each_share(m, [&](size_t r) { return gsp_set_media_scattering(m->ctx[r], scatter, num_media); });
+}
+
 int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode) {
   if (!m) return GSP_ERR_INVALID;
   if (mode != GSP_LIGHTS_UNIFORM && mode != GSP_LIGHTS_POWER) {  // (checked first: no share changes when the mode is unknown)

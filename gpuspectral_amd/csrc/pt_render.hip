@@ -156,6 +156,11 @@ struct gsp_context {
   DevBuf<gsp_medium> media;
   std::vector<gsp_medium> h_media;
   uint32_t num_media = 0;
+  // ... and their scattering coefficients (gsp_set_media_scattering): a table parallel to `media`, empty = none.  scatter_on (some
+  // sigma_s != 0) selects the <SCT> kernels of pt_render_scatter.hip
+  DevBuf<gsp_medium_scatter> scatter;
+  std::vector<gsp_medium_scatter> h_scatter;
+  bool scatter_on = false;
   // light selection (gsp_set_light_sampling): context state like the lens.  GSP_LIGHTS_POWER selects the <LSEL> kernels and makes
   // pack_tables append the alias table behind the light records of every table image
   uint32_t light_mode = GSP_LIGHTS_UNIFORM;

@@ -172,6 +172,15 @@ static TextbookLaunch textbook_launch(const gsp_context* ctx, const LiveVersions
   a.stats = ctx->dstats.p;
   return a;
 }
+// ... and <.., MED = true, .., SCT = true>, the kernels of a context whose media scatter (gsp_set_media_scattering, some sigma_s != 0):
+// the same record + the scattering table and the estimator, handed to pt_render_scatter.hip
+static ScatterLaunch scatter_launch(const gsp_context* ctx, const TextbookLaunch& t) {
+  ScatterLaunch a{};
+  static_cast<TextbookLaunch&>(a) = t;
+  a.scatter = ctx->scatter.p;
+  a.est = ctx->estimator == GSP_ESTIMATOR_TEXTBOOK;
+  return a;
+}
 }  // extern "C++"
 
 // The blocks of k_shade a device holds at once: the largest grid (a block loops over tiles), each may leave one room chunk of fillers.
@@ -274,11 +283,12 @@ static int finish_few_paths(gsp_context* ctx, gsp_context::Lane& L, const Render
   if (!(drain && L.queued == 0 && P.remaining == 0 && P.n > 0 && P.n <= ctx->finish_paths && ctx->pipe_params.collect_traversal_stats == 0 &&
         std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 <= kFinishLevels))
     return GSP_OK;
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, L.stream, (uint32_t)((P.n + kBlock - 1) / kBlock), lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq),
                                        L.counters.p + C_LIVE, (uint32_t)P.batch_paths);
     a.n = (uint32_t)P.n;
-    launch_finish_textbook(a);
+    if (ctx->scatter_on) launch_finish_scatter(scatter_launch(ctx, a));
+    else launch_finish_textbook(a);
   } else
   tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
     hipLaunchKernelGGL((k_finish<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value, false>), dim3((uint32_t)((P.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, L.stream, sview, rcst,
@@ -347,14 +357,15 @@ static int trace_shade_connect(gsp_context* ctx, gsp_context::Lane& L, const Ren
   CTX_TRY(ctx, hipGetLastError());
   if (ev) CTX_TRY(ctx, hipEventRecord(ev[1], st));
   const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + kShadeBlock - 1) / kShadeBlock, shade_resident_blocks(ctx))));
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, st, grid.x, cur, L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths);
     a.n_ptr = n_ptr;
     a.hits = hits;
     a.next[0] = next.P0, a.next[1] = next.P1, a.next[2] = next.P2, a.next[3] = next.P3;
     a.shadow[0] = sq.S0, a.shadow[1] = sq.S1, a.shadow[2] = sq.S3;
     a.chunk = room_chunk;
-    launch_shade_textbook(a);
+    if (ctx->scatter_on) launch_shade_scatter(scatter_launch(ctx, a));
+    else launch_shade_textbook(a);
   } else
   tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
     hipLaunchKernelGGL((k_shade<decltype(TEX)::value, decltype(VER)::value, decltype(MED)::value, decltype(LSEL)::value, false>), grid, dim3(kShadeBlock), 0, st, sview, rcst, n_ptr, cur, hits, next, sq,
@@ -1310,7 +1321,31 @@ int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media)
     CTX_TRY(ctx, ctx->media.upload(ctx->h_media.data(), n, ctx->stream, &ctx->bytes));
     CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lanes' streams read it)
   }
+  if (n != ctx->num_media) {  // the scattering table is parallel to this one: another count drops it
+    ctx->h_scatter.clear();
+    ctx->scatter_on = false;
+  }
   ctx->num_media = n;
+  return GSP_OK;
+}
+
+// ---- scattering media (include/gpuspectral_pt.h, "Scattering media") ----
+int gsp_set_media_scattering(gsp_context* ctx, const gsp_medium_scatter* scatter, uint32_t num_media) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (const char* why = check_media_scattering(scatter, num_media, ctx->num_media)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  const uint32_t n = scatter ? num_media : 0u;
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight read the table as it was
+  if (rc != GSP_OK) return rc;
+  ctx->h_scatter.assign(scatter, scatter + n);
+  if (n != 0) {
+    CTX_TRY(ctx, ctx->scatter.upload(ctx->h_scatter.data(), n, ctx->stream, &ctx->bytes));
+    CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lanes' streams read it)
+  }
+  ctx->scatter_on = any_scattering(ctx->h_scatter.data(), n);
   return GSP_OK;
 }
 

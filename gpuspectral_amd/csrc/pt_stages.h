@@ -15,6 +15,7 @@
 // firefly test (raygen.rgen:60-63).  The NEE term needs the shadow ray, so the
 // shade pass hands both terms to the connect pass, which forms the same sum.
 #pragma once
+#include "pt_medium.h"
 #include "pt_shading.h"
 #include "pt_trace.h"
 
@@ -88,16 +89,26 @@ struct SceneView {
 struct SceneViewMed : SceneView {
   const gsp_medium* media = nullptr;
 };
-template <bool MED>
+// ... and the <MED = true, SCT = true> ones: + the table of scattering coefficients parallel to it (gsp_set_media_scattering)
+struct SceneViewSct : SceneViewMed {
+  const gsp_medium_scatter* scatter = nullptr;
+};
+template <bool MED, bool SCT = false>
 struct ShadeViewOf {
   using type = SceneView;
 };
 template <>
-struct ShadeViewOf<true> {
+struct ShadeViewOf<true, false> {
   using type = SceneViewMed;
+};
+template <>
+struct ShadeViewOf<true, true> {
+  using type = SceneViewSct;
 };
 GSP_HD const gsp_medium* view_media(const SceneView&) { return nullptr; }
 GSP_HD const gsp_medium* view_media(const SceneViewMed& v) { return v.media; }
+GSP_HD const gsp_medium_scatter* view_scatter(const SceneView&) { return nullptr; }
+GSP_HD const gsp_medium_scatter* view_scatter(const SceneViewSct& v) { return v.scatter; }
 
 // path flags word: depth [0,7] | wasDelta << 8 | countEmitted << 9 | table version << 10 [10,15] | geometry version << 16 [16,21]
 GSP_HD uint32_t pack_flags(uint32_t depth, uint32_t wasDelta, uint32_t countEmitted) {
@@ -320,9 +331,15 @@ struct ShadeOut {
 // with power_heuristic(lastPdf, hitPdf), hitPdf = light sampling's pdf of reaching THIS point of THIS emitter.  The path's
 // directWeight field is dead in this mode and carries lastPdf, the bs.pdf of the vertex that sent the ray (the same for both
 // verdicts of its shadow ray).  EST = false is the reference's estimator, instruction for instruction.
-template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false>
+// SCT (only with MED): some medium of the context scatters (include/gpuspectral_pt.h, "Scattering media"; `scatter` = the table
+// parallel to `media`).  A back-face vertex of a medium with any sigma_s != 0 draws the free path first: a medium event leaves
+// through the early return below -- no BSDF, no light sample, no shadow ray --, a surface event goes on as the ordinary vertex with
+// the weight of the decision.  A medium whose sigma_s is 0 takes the MED line and draws nothing.  SCT = false is the code of a
+// context whose media only absorb, instruction for instruction.
+template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false, bool SCT = false>
 GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
-                         ShadeOut& out, const gsp_medium* media = nullptr) {
+                         ShadeOut& out, const gsp_medium* media = nullptr, const gsp_medium_scatter* scatter = nullptr) {
+  static_assert(MED || !SCT, "the scattering table is parallel to the media table");
   uint32_t rng = in.seed;                                                 // rchit:668
   BsdfTables Tv;  // (VER only: this lane's version of the tables)
   const gsp_triangle_light* lights_v = nullptr;
@@ -361,7 +378,49 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   if (MED) {
     if (medium != 0u && dot(N, -rayDir) < 0.0f) {
       const gsp_medium* m = media + (medium - 1u);
-      weight = in.weight * mk3(det_expf(-(m->sigma_a[0] * hit.t)), det_expf(-(m->sigma_a[1] * hit.t)), det_expf(-(m->sigma_a[2] * hit.t)));
+      bool scatters = false;
+      if constexpr (SCT) {
+        const gsp_medium_scatter* sc = scatter + (medium - 1u);
+        const f3 sigma_s = mk3(sc->sigma_s[0], sc->sigma_s[1], sc->sigma_s[2]);
+        scatters = sigma_s.x != 0.0f || sigma_s.y != 0.0f || sigma_s.z != 0.0f;
+        if (scatters) {
+          const float u_c = rand_uniform(rng);
+          const float u_d = rand_uniform(rng);
+          const MediumEvent ev = medium_event(mk3(m->sigma_a[0], m->sigma_a[1], m->sigma_a[2]), sigma_s, hit.t, u_c, u_d, in.weight);
+          if (ev.scatter || !ev.valid) {
+            // a medium event (or an invalid density: the path ends): the vertex is a point inside the object.  It emits nothing,
+            // traces no shadow ray and continues along the phase function's sample; roulette and the depth test as at a surface
+            const uint32_t depth = in.flags & 0xffu;
+            PathState nx = in;
+            bool alive = ev.valid;
+            if (ev.valid) {
+              const float u1 = rand_uniform(rng);
+              const float u2 = rand_uniform(rng);
+              float pdf;
+              nx.d = sample_hg(rayDir, sc->g, u1, u2, pdf);
+              nx.o = in.o + rayDir * ev.s;
+              nx.weight = ev.w;
+              nx.directWeight = EST ? pdf : 1.0f;
+            }
+            nx.seed = rng;
+            if (depth > rc.rr_start_depth) {
+              const float q = gclamp(gmax(gmax(nx.weight.x, nx.weight.y), nx.weight.z), 0.05f, 1.0f);
+              uint32_t peek = nx.seed;
+              if (rand_uniform(peek) > q) alive = false;
+              nx.weight = nx.weight / q;
+            }
+            if (depth > rc.max_depth) alive = false;
+            nx.flags = pack_flags(depth + 1u, 0u, 0u) | (VER ? (in.flags & kStampMask) : 0u);
+            out.alive = alive;
+            out.next = nx;
+            out.has_shadow = false;
+            out.emitted = splat(0.0f);
+            return;
+          }
+          weight = ev.w;
+        }
+      }
+      if (!scatters) weight = in.weight * mk3(det_expf(-(m->sigma_a[0] * hit.t)), det_expf(-(m->sigma_a[1] * hit.t)), det_expf(-(m->sigma_a[2] * hit.t)));
     }
   }
   if (dot(N, -rayDir) < 0.0f) {                                           // :698-707

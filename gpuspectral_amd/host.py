@@ -65,6 +65,10 @@ def load():
     L.gsph_scene_set_lens.argtypes = [vp, C.c_float, C.c_float, u32, C.c_float]
     L.gsph_scene_media.restype = u32
     L.gsph_scene_media.argtypes = [vp, vp]
+    L.gsph_scene_media_scattering.restype = u32
+    L.gsph_scene_media_scattering.argtypes = [vp, vp]
+    L.gsph_scene_add_scattering_medium.restype = u32
+    L.gsph_scene_add_scattering_medium.argtypes = [vp, vp, vp, C.c_float]
     L.gsph_scene_object_medium.restype = u32
     L.gsph_scene_object_medium.argtypes = [vp, u32]
     L.gsph_scene_add_medium.restype = u32
@@ -141,20 +145,22 @@ class Scene:
     """A C++ GPUSpectral::Scene produced by loadScene (S/engine/Loader.cpp:253-349)."""
 
     def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False,
-                 read_lens=False, read_film=False, read_media=False):
+                 read_lens=False, read_film=False, read_media=False, read_scattering=False):
         """dormant_features: LoadOptions::dormantFeatures (textures / environment map, SURVEY 8(f).3); builtin_shapes:
         LoadOptions::builtinShapes (`disk` and `sphere` shapes are built instead of skipped, SURVEY 8(f).1); the defaults are
         the reference's behaviour.  read_filter: LoadOptions::readFilter (the film's <rfilter> becomes `pixel_filter`, which
         PathTracer.render applies unless its params name a filter of their own).  read_lens: LoadOptions::readLens (a `thinlens`
         sensor's aperture_radius / focus_distance become the camera's lens, which PathTracer hands to the device).  read_film:
         LoadOptions::readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn become `film`).  read_media:
-        LoadOptions::readMedia (the shapes' <medium name="interior"> become `media` and the objects' medium numbers: coloured glass)."""
+        LoadOptions::readMedia (the shapes' <medium name="interior"> become `media` and the objects' medium numbers: coloured glass).
+        read_scattering: LoadOptions::readScattering (implies read_media; sigmaS / albedo and the hg phase become `media_scattering`)."""
         self._L = load()
         ad = asset_dir.encode() if asset_dir else None
-        if builtin_shapes or read_filter or read_lens or read_film or read_media:
+        if builtin_shapes or read_filter or read_lens or read_film or read_media or read_scattering:
             self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) |
                                                    (4 if builtin_shapes else 0) | (8 if read_filter else 0) | (16 if read_lens else 0) |
-                                                   (32 if read_film else 0) | (64 if read_media else 0))
+                                                   (32 if read_film else 0) | (64 if read_media else 0) |
+                                                   (128 if read_scattering else 0))
         elif dormant_features:
             self._h = self._L.gsph_load_scene_ex(path.encode(), ad, 1, 1 if srgb_textures else 0)
         else:
@@ -206,6 +212,20 @@ class Scene:
         if n:
             self._L.gsph_scene_media(self._h, out.ctypes.data)
         return out
+
+    @property
+    def media_scattering(self):
+        """Scene::mediaScattering as an (n, 4) float32 array (sigma_s, g), parallel to `media`; empty while no medium scatters."""
+        n = self._L.gsph_scene_media_scattering(self._h, None)
+        out = np.zeros((n, 4), np.float32)
+        if n:
+            self._L.gsph_scene_media_scattering(self._h, out.ctypes.data)
+        return out
+
+    def add_scattering_medium(self, sigma_a, sigma_s, g=0.0):
+        """Scene::addMedium with scattering: the number of the (possibly shared) entry."""
+        a, s = np.ascontiguousarray(sigma_a, np.float32), np.ascontiguousarray(sigma_s, np.float32)
+        return int(self._L.gsph_scene_add_scattering_medium(self._h, a.ctypes.data, s.ctypes.data, float(g)))
 
     def object_medium(self, obj):
         """RenderObject::interiorMedium: 0 = none, k = media[k - 1]."""

@@ -303,7 +303,7 @@ std::shared_ptr<Object> parseObject(const XmlNode& el, ParseState& ps) {
         ps.pending.push_back(PendingRef{o, o->children.size(), ch.get("id")});
         o->children.push_back(nullptr);
       }
-    } else if (isObjectTag(ch.tag)) {
+    } else if (isObjectTag(ch.tag) || (ch.tag == "phase" && el.tag == "medium")) {  // (a medium's phase function: LoadOptions::readScattering)
       auto child = parseObject(ch, ps);
       if (ch.attr("id")) ids[ch.get("id")] = child;
       if (ch.attr("name")) o->named.emplace_back(nm, child);
@@ -642,7 +642,7 @@ MeshPtr loadMesh(const std::string& path, uint32_t id) {
 // LoadOptions::readMedia: the interior medium of a shape (include/gpuspectral_pt.h "Interior media"), inline or as a <ref> to a
 // top-level <medium id=..>, as its number in Scene::media; 0 = none.  sigma_a = sigmaA, or sigmaT * (1 - albedo); an optional float
 // `scale` multiplies.  What is not a pure homogeneous absorber inside the shape is skipped with one warning, as `disk` shapes are.
-static uint32_t shapeInteriorMedium(Scene& scene, const Object& shape, const ParseState& ps) {
+static uint32_t shapeInteriorMedium(Scene& scene, const Object& shape, const ParseState& ps, bool readScattering) {
   std::vector<std::pair<std::string, std::shared_ptr<Object>>> found;
   for (auto& nc : shape.named)
     if (nc.second && nc.second->kind == "medium") found.push_back(nc);
@@ -674,7 +674,8 @@ static uint32_t shapeInteriorMedium(Scene& scene, const Object& shape, const Par
     const bool hasA = triple("sigma_a", 0.0f, sa), hasT = triple("sigma_t", 0.0f, st);
     triple("sigma_s", 0.0f, ss);
     triple("albedo", 0.0f, al);
-    if (ss[0] != 0.0f || ss[1] != 0.0f || ss[2] != 0.0f || al[0] != 0.0f || al[1] != 0.0f || al[2] != 0.0f) {
+    const bool scatters = ss[0] != 0.0f || ss[1] != 0.0f || ss[2] != 0.0f || al[0] != 0.0f || al[1] != 0.0f || al[2] != 0.0f;
+    if (scatters && !readScattering) {
       scene.warnings.push_back("scattering medium skipped (sigmaS / albedo != 0: only pure absorbers are supported)");
       continue;
     }
@@ -683,7 +684,21 @@ static uint32_t shapeInteriorMedium(Scene& scene, const Object& shape, const Par
     const float scale = m.number("scale", 1.0f);
     gsp_medium rec{};
     for (int c = 0; c < 3; ++c) rec.sigma_a[c] = sa[c] * scale;
-    number = scene.addMedium(rec);
+    if (!readScattering) {
+      number = scene.addMedium(rec);
+      continue;
+    }
+    // LoadOptions::readScattering: sigma_s = sigmaS, or sigmaT * albedo; the phase function's g
+    if (m.props.find("sigma_s") == m.props.end() && hasT)
+      for (int c = 0; c < 3; ++c) ss[c] = st[c] * al[c];
+    gsp_medium_scatter sc{};
+    for (int c = 0; c < 3; ++c) sc.sigma_s[c] = ss[c] * scale;
+    for (auto& ch : m.children) {
+      if (!ch || ch->kind != "phase") continue;
+      if (ch->plugin == "hg") sc.g = ch->number("g", 0.0f);
+      else if (ch->plugin != "isotropic") scene.warnings.push_back("unsupported phase function '" + ch->plugin + "' replaced by isotropic");
+    }
+    number = scene.addMedium(rec, sc);
   }
   return number;
 }
@@ -771,7 +786,8 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
           emitting = true;
         }
       }
-      if (options.readMedia) renderObject.interiorMedium = shapeInteriorMedium(outScene, *obj, ps);
+      if (options.readMedia || options.readScattering)
+        renderObject.interiorMedium = shapeInteriorMedium(outScene, *obj, ps, options.readScattering);
       renderObject.mesh = mesh;
       renderObject.transform = matrix;
       renderObject.material = outScene.addMaterial(material);

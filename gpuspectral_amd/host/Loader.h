@@ -51,6 +51,11 @@ struct LoadOptions {
   // Scene::media; RenderObject::interiorMedium names it.  A medium with sigmaS != 0 or albedo != 0, a name="exterior" medium and a
   // type other than homogeneous are skipped with one warning each, as `disk` shapes are.
   bool readMedia = false;
+  // readScattering = true (implies readMedia) also reads what makes a medium scatter (include/gpuspectral_pt.h "Scattering media"):
+  // `sigmaS`, or `sigmaT` with `albedo` (sigma_s = sigmaT * albedo, sigma_a = sigmaT * (1 - albedo)), times `scale`; and a
+  // <phase type="hg"><float name="g" ../></phase> child (`isotropic` or no child: g = 0; any other phase type: one warning, g = 0).
+  // Scene::mediaScattering then runs parallel to Scene::media.  false: a scattering medium is skipped with its warning, as above.
+  bool readScattering = false;
 };
 
 // assetDir: where rect.obj / box.obj / disk.obj live (Engine::assetPath); "" = the

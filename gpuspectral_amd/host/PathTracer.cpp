@@ -75,7 +75,19 @@ bool SceneTracker::lensChanged(const Scene& scene, gsp_lens& out) const {
 
 bool SceneTracker::mediaChanged(const Scene& scene) const {
   return scene.media.size() != media.size() ||
-         (!media.empty() && std::memcmp(scene.media.data(), media.data(), media.size() * sizeof(gsp_medium)) != 0);
+         (!media.empty() && std::memcmp(scene.media.data(), media.data(), media.size() * sizeof(gsp_medium)) != 0) ||
+         scene.mediaScattering.size() != mediaScattering.size() ||
+         (!mediaScattering.empty() &&
+          std::memcmp(scene.mediaScattering.data(), mediaScattering.data(), mediaScattering.size() * sizeof(gsp_medium_scatter)) != 0);
+}
+
+// the media table, and behind it the scattering table parallel to it (gsp_set_media with another count drops the device's).  Returns
+// gsp_set_media's code (it may refuse to shrink the table under the resident scene: the caller tries again behind the scene)
+template <class SetMedia, class SetScattering>
+static int sendMedia(const Scene& scene, SetMedia&& setMedia, SetScattering&& setScattering) {
+  const int rc = setMedia(scene.media.data(), (uint32_t)scene.media.size());
+  if (rc != GSP_OK) return rc;
+  return setScattering(scene.mediaScattering.data(), (uint32_t)scene.mediaScattering.size());
 }
 
 unsigned SceneTracker::diff(const Scene& scene, std::vector<gsp_instance>& inst) const {
@@ -156,15 +168,23 @@ void PathTracer::prepareScene(const Scene& scene) {
   }
   // the media table goes BEFORE a scene that names more entries than the device holds and AFTER one that names fewer than the
   // resident scene does (gsp_set_media refuses to shrink the table under it): tried first, and again behind the scene if refused
+  const auto sendBoth = [&] {
+    return sendMedia(
+        scene, [&](const gsp_medium* m, uint32_t n) { return gsp_set_media(ctx, m, n); },
+        [&](const gsp_medium_scatter* sc, uint32_t n) { return gsp_set_media_scattering(ctx, sc, n); });
+  };
   bool mediaPending = tracker.mediaChanged(scene);
-  if (mediaPending && gsp_set_media(ctx, scene.media.data(), (uint32_t)scene.media.size()) == GSP_OK) {
+  if (mediaPending && sendBoth() == GSP_OK) {
     tracker.rememberMedia(scene);
     mediaPending = false;
   }
   std::vector<gsp_instance> inst;
   const unsigned change = tracker.diff(scene, inst);
   if (change == SceneTracker::None) {
-    if (mediaPending) check(gsp_set_media(ctx, scene.media.data(), (uint32_t)scene.media.size()), "gsp_set_media");
+    if (mediaPending) {
+      check(sendBoth(), "gsp_set_media / gsp_set_media_scattering");
+      tracker.rememberMedia(scene);
+    }
     return;
   }
   tracker.forget();  // (a failed call below leaves nothing remembered: the next pass uploads everything)
@@ -195,7 +215,7 @@ void PathTracer::prepareScene(const Scene& scene) {
     if (change & SceneTracker::CameraChanged) check(gsp_update_camera(ctx, &d.camera), "gsp_update_camera");
   }
   if (mediaPending) {
-    check(gsp_set_media(ctx, scene.media.data(), (uint32_t)scene.media.size()), "gsp_set_media");
+    check(sendBoth(), "gsp_set_media / gsp_set_media_scattering");
     tracker.rememberMedia(scene);
   }
   tracker.remember(scene, inst);
@@ -457,8 +477,13 @@ void MultiGpuPathTracer::prepareScene(const Scene& scene) {
     tracker.rememberLens(lens);
   }
   // (the media table: as PathTracer::prepareScene; a change that has to follow the scene takes the full upload here)
+  const auto sendBoth = [&] {
+    return sendMedia(
+        scene, [&](const gsp_medium* m, uint32_t n) { return gsp_multi_set_media(multi, m, n); },
+        [&](const gsp_medium_scatter* sc, uint32_t n) { return gsp_multi_set_media_scattering(multi, sc, n); });
+  };
   bool mediaPending = tracker.mediaChanged(scene);
-  if (mediaPending && gsp_multi_set_media(multi, scene.media.data(), (uint32_t)scene.media.size()) == GSP_OK) {
+  if (mediaPending && sendBoth() == GSP_OK) {
     tracker.rememberMedia(scene);
     mediaPending = false;
   }
@@ -484,7 +509,7 @@ void MultiGpuPathTracer::prepareScene(const Scene& scene) {
     check(gsp_multi_upload_scene(multi, &flat.desc), "gsp_multi_upload_scene");
   }
   if (mediaPending) {
-    check(gsp_multi_set_media(multi, scene.media.data(), (uint32_t)scene.media.size()), "gsp_multi_set_media");
+    check(sendBoth(), "gsp_multi_set_media / gsp_multi_set_media_scattering");
     tracker.rememberMedia(scene);
   }
   tracker.remember(scene, inst);

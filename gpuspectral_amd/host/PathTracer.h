@@ -40,7 +40,10 @@ struct SceneTracker {
   void rememberLens(const gsp_lens& l) { lens = l; }
   // the scene's interior media (Scene::media) against the table last sent; context state of its own too (gsp_set_media)
   bool mediaChanged(const Scene& scene) const;
-  void rememberMedia(const Scene& scene) { media = scene.media; }
+  void rememberMedia(const Scene& scene) {
+    media = scene.media;
+    mediaScattering = scene.mediaScattering;
+  }
 
  private:
   bool valid = false;
@@ -50,6 +53,7 @@ struct SceneTracker {
   gsp_camera camera{};
   gsp_lens lens{};                      // (zeroed = pinhole = a fresh context's state)
   std::vector<gsp_medium> media;        // (empty = none = a fresh context's state)
+  std::vector<gsp_medium_scatter> mediaScattering;  // ... and the scattering table parallel to it (gsp_set_media_scattering)
   std::vector<uint64_t> assets;         // dormant features: texture / environment-map sizes, flags, envmap transform
 };
 

@@ -203,13 +203,28 @@ struct Scene {
   std::vector<RoughPlasticBSDF> roughPlasticBSDFs;
   // interior media: filled only by loadScene(..., LoadOptions{.readMedia = true}) or by the host itself; equal coefficients share
   // one entry.  PathTracer sends the table (gsp_set_media) when its value changed
-  uint32_t addMedium(const gsp_medium& m) {
-    for (size_t k = 0; k < media.size(); ++k)
-      if (media[k].sigma_a[0] == m.sigma_a[0] && media[k].sigma_a[1] == m.sigma_a[1] && media[k].sigma_a[2] == m.sigma_a[2]) return (uint32_t)k + 1;
+  uint32_t addMedium(const gsp_medium& m) { return addMedium(m, gsp_medium_scatter{{0.0f, 0.0f, 0.0f}, 0.0f}); }
+  // ... with scattering (gpuspectral_pt.h "Scattering media"; LoadOptions::readScattering): equal (absorber, scatterer) pairs share
+  // one entry.  mediaScattering is empty while no medium of the scene scatters, else parallel to media.  PathTracer sends it
+  // (gsp_set_media_scattering) behind the media table
+  uint32_t addMedium(const gsp_medium& m, const gsp_medium_scatter& sc) {
+    const bool scatters = sc.sigma_s[0] != 0.0f || sc.sigma_s[1] != 0.0f || sc.sigma_s[2] != 0.0f;
+    const gsp_medium_scatter want = scatters ? sc : gsp_medium_scatter{{0.0f, 0.0f, 0.0f}, 0.0f};  // (g of a medium that does not scatter says nothing)
+    for (size_t k = 0; k < media.size(); ++k) {
+      const gsp_medium_scatter have = k < mediaScattering.size() ? mediaScattering[k] : gsp_medium_scatter{{0.0f, 0.0f, 0.0f}, 0.0f};
+      if (media[k].sigma_a[0] == m.sigma_a[0] && media[k].sigma_a[1] == m.sigma_a[1] && media[k].sigma_a[2] == m.sigma_a[2] &&
+          have.sigma_s[0] == want.sigma_s[0] && have.sigma_s[1] == want.sigma_s[1] && have.sigma_s[2] == want.sigma_s[2] && have.g == want.g)
+        return (uint32_t)k + 1;
+    }
     media.push_back(gsp_medium{{m.sigma_a[0], m.sigma_a[1], m.sigma_a[2]}, 0.0f});
+    if (scatters || !mediaScattering.empty()) {
+      mediaScattering.resize(media.size(), gsp_medium_scatter{{0.0f, 0.0f, 0.0f}, 0.0f});
+      mediaScattering.back() = want;
+    }
     return (uint32_t)media.size();
   }
   std::vector<gsp_medium> media;
+  std::vector<gsp_medium_scatter> mediaScattering;
   std::vector<std::string> warnings;  // what the loader skipped (the reference printed these to stdout)
   // the film's <rfilter>, read only with LoadOptions::readFilter: GSP_FILTER_* and its parameter (0 = the filter's default).
   // 0 = none: the renderer's own params decide.  PathTracer::render uses these when its params.pixel_filter is GSP_FILTER_NONE

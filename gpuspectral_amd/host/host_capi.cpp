@@ -65,7 +65,8 @@ void* gsph_load_scene_ex(const char* path, const char* asset_dir, int dormant, i
 }
 // flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere),
 // 8 = readFilter (the film's <rfilter>), 16 = readLens (a thinlens sensor's aperture_radius / focus_distance),
-// 32 = readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn), 64 = readMedia (the shapes' interior media)
+// 32 = readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn), 64 = readMedia (the shapes' interior media),
+// 128 = readScattering (their sigmaS / albedo and hg phase; implies 64)
 void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned flags) {
   SceneBox* b = nullptr;
   int rc = guard([&] {
@@ -78,6 +79,7 @@ void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned fla
     opt.readLens = (flags & 16u) != 0;
     opt.readFilm = (flags & 32u) != 0;
     opt.readMedia = (flags & 64u) != 0;
+    opt.readScattering = (flags & 128u) != 0;
     b->scene = loadScene(path, asset_dir ? asset_dir : "", opt);
     flattenScene(b->scene, b->flat);
   });
@@ -133,6 +135,21 @@ uint32_t gsph_scene_media(void* s, float* out) {
     for (size_t k = 0; k < m.size(); ++k)
       for (int c = 0; c < 3; ++c) out[3 * k + c] = m[k].sigma_a[c];
   return (uint32_t)m.size();
+}
+// ... and their scattering coefficients (LoadOptions::readScattering / Scene::mediaScattering): the count, 0 or that of the media;
+// out = 4 floats (sigma_s, g) per medium, may be NULL
+uint32_t gsph_scene_media_scattering(void* s, float* out) {
+  const std::vector<gsp_medium_scatter>& m = ((SceneBox*)s)->scene.mediaScattering;
+  if (out)
+    for (size_t k = 0; k < m.size(); ++k) {
+      for (int c = 0; c < 3; ++c) out[4 * k + c] = m[k].sigma_s[c];
+      out[4 * k + 3] = m[k].g;
+    }
+  return (uint32_t)m.size();
+}
+// Scene::addMedium with scattering: sigma_a (3 floats), sigma_s (3 floats), g
+uint32_t gsph_scene_add_scattering_medium(void* s, const float* sigma_a3, const float* sigma_s3, float g) {
+  return ((SceneBox*)s)->scene.addMedium(gsp_medium{{sigma_a3[0], sigma_a3[1], sigma_a3[2]}, 0.0f}, gsp_medium_scatter{{sigma_s3[0], sigma_s3[1], sigma_s3[2]}, g});
 }
 // RenderObject::interiorMedium of an object (0 = none); set: the number of an entry of the scene's media, which
 // gsph_scene_add_medium appends (equal coefficients share one entry).  gsph_scene_reflatten rebuilds the flattened handles.

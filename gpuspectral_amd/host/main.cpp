@@ -14,6 +14,7 @@
 //   --light-sampling uniform|power: gsp_set_light_sampling (uniform = the reference's pick, the default; power = by emitted power).
 //   --estimator reference|textbook: gsp_set_estimator (reference = the reference's weights, the default; textbook = unbiased).
 //   --scene-media: LoadOptions::readMedia (the shapes' <medium name="interior">: coloured glass, gsp_set_media).
+//   --scene-scattering: LoadOptions::readScattering (implies --scene-media; sigmaS / albedo and the hg phase: gsp_set_media_scattering).
 //   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
 //   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
 //   --features PREFIX [--feature-spp N]: also render the feature buffers (gpuspectral_pt.h "Feature buffers"; N samples per pixel,
@@ -148,6 +149,7 @@ int main(int argc, char** argv) {
     else if (flag == "--scene-lens") options.readLens = true;
     else if (flag == "--scene-film") options.readFilm = true;
     else if (flag == "--scene-media") options.readMedia = true;
+    else if (flag == "--scene-scattering") options.readScattering = true;
     else if (flag == "--ldr" && argc > 2) ldrPath = argv[2], used = 2;
     else if (flag == "--features" && argc > 2) featuresPrefix = argv[2], used = 2;
     else if (flag == "--feature-spp" && argc > 2) {
@@ -436,7 +438,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--scene-scattering] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window

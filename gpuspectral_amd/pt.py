@@ -29,6 +29,7 @@ EXPORTS = (
     "gsp_update_tables",
     "gsp_set_lens",
     "gsp_set_media",
+    "gsp_set_media_scattering",
     "gsp_set_light_sampling",
     "gsp_download_light_pick",
     "gsp_set_estimator",
@@ -95,6 +96,7 @@ EXPORTS = (
     "gsp_multi_update_camera",
     "gsp_multi_set_lens",
     "gsp_multi_set_media",
+    "gsp_multi_set_media_scattering",
     "gsp_multi_set_light_sampling",
     "gsp_multi_set_estimator",
     "gsp_multi_update_instances",
@@ -152,6 +154,8 @@ def load():
     L.gsp_multi_set_lens.argtypes = [vp, C.POINTER(abi.Lens)]
     L.gsp_set_media.argtypes = [vp, C.POINTER(abi.Medium), u32]
     L.gsp_multi_set_media.argtypes = [vp, C.POINTER(abi.Medium), u32]
+    L.gsp_set_media_scattering.argtypes = [vp, C.POINTER(abi.MediumScatter), u32]
+    L.gsp_multi_set_media_scattering.argtypes = [vp, C.POINTER(abi.MediumScatter), u32]
     L.gsp_set_light_sampling.argtypes = [vp, u32]
     L.gsp_download_light_pick.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.gsp_multi_set_light_sampling.argtypes = [vp, u32]
@@ -263,8 +267,8 @@ def build_info():
 
 
 # the files csrc/Makefile hashes into the digest, in its order
-DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
-                  "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
+DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_render_scatter.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
+                  "pt_medium.h", "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -356,6 +360,12 @@ class Context:
         coefficients; medium number k of abi.bsdf_handle(.., medium=k) is sigmas[k - 1].  None or empty = no media."""
         arr = abi.media_array(sigmas)
         self._check(self._L.gsp_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_media")
+
+    def set_media_scattering(self, scatter=None):
+        """gsp_set_media_scattering: the table parallel to set_media's (gpuspectral_pt.h "Scattering media"), one entry per medium:
+        (r, g, b) scattering coefficients, or ((r, g, b), g) with the Henyey-Greenstein asymmetry.  None or empty = no scattering."""
+        arr = abi.media_scatter_array(scatter)
+        self._check(self._L.gsp_set_media_scattering(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_media_scattering")
 
     def set_estimator(self, mode):
         """gsp_set_estimator (gpuspectral_pt.h "Estimator"): "reference" / "textbook" or abi.ESTIMATOR_REFERENCE / ESTIMATOR_TEXTBOOK."""
@@ -824,6 +834,11 @@ class MultiContext:
         """gsp_multi_set_media: Context.set_media on every share."""
         arr = abi.media_array(sigmas)
         self._check(self._L.gsp_multi_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_media")
+
+    def set_media_scattering(self, scatter=None):
+        """gsp_multi_set_media_scattering: Context.set_media_scattering on every share."""
+        arr = abi.media_scatter_array(scatter)
+        self._check(self._L.gsp_multi_set_media_scattering(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_media_scattering")
 
     def set_estimator(self, mode):
         """gsp_multi_set_estimator: Context.set_estimator on every share."""

@@ -85,7 +85,8 @@ extern "C" {
                                 gsp_download_taa_display, gsp_taa_display_to_device (see "Temporal anti-aliasing");
                                 gsp_set_media, gsp_multi_set_media (see "Interior media");
                                 gsp_set_light_sampling, gsp_download_light_pick, gsp_multi_set_light_sampling (see "Light
-                                selection"); gsp_set_estimator, gsp_multi_set_estimator (see "Estimator") */
+                                selection"); gsp_set_estimator, gsp_multi_set_estimator (see "Estimator");
+                                gsp_set_media_scattering, gsp_multi_set_media_scattering (see "Scattering media") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -628,6 +629,54 @@ typedef struct gsp_medium {
   float reserved;   /* 0 */
 } gsp_medium;
 int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media); /* NULL or 0 = none */
+
+/*
+ * Scattering media: opt-in volumetric scattering inside the closed shapes that carry an interior medium (milk, wax, jade, smoke
+ * in a glass box).  Free-path sampling and a Henyey-Greenstein phase function, in the shading vertex.
+ *
+ * gsp_set_media_scattering(ctx, scatter, n) gives the context a table PARALLEL to the one of gsp_set_media: entry k - 1 belongs
+ * to medium k.  n is 0 (or scatter NULL: no scattering) or equal to the context's media count.  sigma_s is in units of 1 /
+ * world-space length, finite and >= 0; g is the Henyey-Greenstein asymmetry, finite, |g| < 1 (> 0 scatters forward).
+ * GSP_ERR_INVALID for a coefficient or g outside that and for a count that is neither 0 nor the media count; the table is then
+ * unchanged.  Context state like the media: the samples in flight finish first, it holds until changed and survives
+ * gsp_upload_scene.  gsp_set_media with a DIFFERENT count drops the scattering table (the same count keeps it).  A context
+ * whose table is absent or all sigma_s == 0 runs the kernels and computes the bits it did before this call existed.
+ *
+ * Where: a vertex whose medium k != 0, on a back face (dot(N, -rayDir) < 0 on the geometric normal, before the two-sided flip),
+ * and sigma_s[k-1] has a nonzero channel.  The line w = weight * exp(-(sigma_a * t)) of "Interior media" is replaced by the
+ * following, float32 in this order, sigma_t = sigma_a + sigma_s per channel, log / exp / sin / cos the library's deterministic ones:
+ *   1. two draws from the path's stream, BEFORE any other draw of the vertex: u_c, then u_d.
+ *        c* = min((uint)(u_c * 3), 2);   s = -log(1 - u_d) / sigma_t[c*]     (sigma_t[c*] == 0: s = +inf, the surface)
+ *   2. surface event, !(s < t):   Tr_c = exp(-(sigma_t_c * t));   p = ((Tr_r + Tr_g) + Tr_b) / 3;   w = (weight * Tr) / p
+ *      and the ordinary vertex goes on with w and the stream as it stands.
+ *   3. medium event, s < t:   Tr_c = exp(-(sigma_t_c * s));   p = ((sigma_t_r * Tr_r + sigma_t_g * Tr_g) + sigma_t_b * Tr_b) / 3;
+ *        w = ((weight * sigma_s) * Tr) / p
+ *      two more draws u1, u2 sample Henyey-Greenstein about rayDir:
+ *        |g| < 1e-3:  cos = 1 - 2 * u1;   pdf_hg = 1 / (4 * pi)
+ *        else:        sq = (1 - g * g) / ((1 - g) + (2 * g) * u1);   cos = clamp(((1 + g * g) - sq * sq) / (2 * g), -1, 1)
+ *                     d = (1 + g * g) - (2 * g) * cos;   pdf_hg = (1 - g * g) / ((4 * pi) * (d * sqrt(d)))
+ *        sin = sqrt(max(0, 1 - cos * cos));   phi = (2 * pi) * u2;   dir = frame(rayDir) * (sin * cos(phi), sin * sin(phi), cos)
+ *      with the frame of the shading vertex's make_frame.  The phase value equals its pdf and cancels.  The vertex emits nothing
+ *      and traces NO shadow ray.  Its next state: o = in.o + rayDir * s (no offset), d = dir, weight = w, depth + 1, wasDelta = 0,
+ *      countEmitted = 0, the version stamps as a surface vertex carries them, directWeight = pdf_hg under GSP_ESTIMATOR_TEXTBOOK
+ *      and 1 otherwise.  Russian roulette (on w, peeking the next draw) and the max_depth test run as for a surface vertex.
+ *   4. p == 0 or not finite (every channel's transmittance underflowed): the path ends and adds nothing.
+ *   5. The entry piece of "Interior media" keeps its line, with sigma_a: absorption over the 1e-4 offset is kept, scattering
+ *      inside it is neglected -- the path is merely not scattered over 1e-4 / |c|, which loses no energy.
+ *   6. A medium whose sigma_s is all 0 takes the deterministic line of "Interior media" and draws nothing, also in a context
+ *      where other media scatter.
+ *
+ * Limits.  No next-event estimation from inside a medium: a shadow ray would be stopped by the object's own surface, so nothing
+ * is lost for closed shapes; an index-matched boundary stays opaque to shadow rays as it is without scattering.  No emitters
+ * inside a medium.  A scatter event counts as a bounce and max_depth is at most 250: dense, high-albedo media are truncated
+ * (the mean number of events grows like the square of the optical thickness).  The stateless rule of "Interior media" carries
+ * over: a path that scatters inside a closed shape meets a back face of the same shape next.
+ */
+typedef struct gsp_medium_scatter {
+  float sigma_s[3]; /* scattering coefficient per channel, 1 / length; finite, >= 0 */
+  float g;          /* Henyey-Greenstein asymmetry, |g| < 1; 0 = isotropic */
+} gsp_medium_scatter;
+int gsp_set_media_scattering(gsp_context* ctx, const gsp_medium_scatter* scatter, uint32_t num_media); /* NULL or 0 = none */
 
 /*
  * Light selection: opt-in choice of the light for next-event estimation in proportion to its emitted power.
@@ -1420,6 +1469,7 @@ int gsp_multi_upload_scene(gsp_multi* m, const gsp_scene_desc* scene);
 int gsp_multi_update_camera(gsp_multi* m, const gsp_camera* camera);
 int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens); /* gsp_set_lens on every share */
 int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_media); /* gsp_set_media on every share */
+int gsp_multi_set_media_scattering(gsp_multi* m, const gsp_medium_scatter* scatter, uint32_t num_media); /* gsp_set_media_scattering on every share */
 int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode); /* gsp_set_light_sampling on every share */
 int gsp_multi_set_estimator(gsp_multi* m, uint32_t mode);      /* gsp_set_estimator on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);

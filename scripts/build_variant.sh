@@ -21,6 +21,10 @@ if [ -f pt_render_textbook.hip ]; then  # (revisions with the textbook estimator
   hipcc $F -c pt_render_textbook.hip -o build/var_$1/pt_render_textbook.o &
   TB="build/var_$1/pt_render_textbook.o"
 fi
+if [ -f pt_render_scatter.hip ]; then  # (... and those with scattering media the <MED, SCT> kernels)
+  hipcc $F -c pt_render_scatter.hip -o build/var_$1/pt_render_scatter.o &
+  TB="$TB build/var_$1/pt_render_scatter.o"
+fi
 wait
 printf 'extern "C" const char gsp_build_info_string[] = "arch=gfx950 digest=variant-%s flags=%s";\n' "$1" "$F" > build/var_$1/pt_buildinfo.cpp
 g++ -O2 -fPIC -c build/var_$1/pt_buildinfo.cpp -o build/var_$1/pt_buildinfo.o
