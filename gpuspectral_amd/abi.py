@@ -200,6 +200,39 @@ def media_scatter_array(scatter):
     return (MediumScatter * len(out))(*out) if out else None
 
 
+# Delta lights (include/gpuspectral_pt.h "Delta lights")
+LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 1, 2, 3
+
+
+class DeltaLight(C.Structure):
+    """gsp_delta_light, 64 B: a point, spot or directional emitter."""
+
+    _fields_ = [("position", C.c_float * 3), ("kind", C.c_uint32), ("direction", C.c_float * 3), ("cos_cutoff", C.c_float),
+                ("intensity", C.c_float * 3), ("cos_beam", C.c_float), ("extent", C.c_float), ("reserved", C.c_float * 3)]
+
+
+def point_light(position, intensity):
+    return DeltaLight((C.c_float * 3)(*position), LIGHT_POINT, (C.c_float * 3)(0, 0, 0), 0.0, (C.c_float * 3)(*intensity), 0.0, 0.0, (C.c_float * 3)(0, 0, 0))
+
+
+def spot_light(position, direction, intensity, cos_cutoff, cos_beam):
+    """direction: unit, the spot's axis (the way the light travels); the cosines of the cutoff angle and of the beam width."""
+    return DeltaLight((C.c_float * 3)(*position), LIGHT_SPOT, (C.c_float * 3)(*direction), cos_cutoff, (C.c_float * 3)(*intensity), cos_beam, 0.0,
+                      (C.c_float * 3)(0, 0, 0))
+
+
+def directional_light(direction, irradiance, extent):
+    """direction: unit, the way the light travels; extent: the radius of the scene as the power pick is to see it."""
+    return DeltaLight((C.c_float * 3)(0, 0, 0), LIGHT_DIRECTIONAL, (C.c_float * 3)(*direction), 0.0, (C.c_float * 3)(*irradiance), 0.0, extent,
+                      (C.c_float * 3)(0, 0, 0))
+
+
+def delta_light_array(lights):
+    """[DeltaLight, ...] -> (DeltaLight * n), or None for an empty list."""
+    lights = list(lights) if lights is not None else []
+    return (DeltaLight * len(lights))(*lights) if lights else None
+
+
 # Light selection (include/gpuspectral_pt.h "Light selection")
 LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1
 LIGHT_SAMPLING_NAMES = {"uniform": LIGHTS_UNIFORM, "power": LIGHTS_POWER}

@@ -52,6 +52,14 @@ struct ScatterLaunch : TextbookLaunch {
 };
 void launch_shade_scatter(const ScatterLaunch& a);
 void launch_finish_scatter(const ScatterLaunch& a);
+// Delta lights: the <DLT = true> instantiations, over TEX x VER x LSEL x EST with MED = SCT = true, live in pt_render_delta.hip.  A
+// context without media hands null tables (no handle carries a medium number then: the media lines never run), one whose media
+// only absorb a scattering table of zeros (such a medium takes the deterministic line).  The view's num_lights counts both kinds.
+struct DeltaLaunch : ScatterLaunch {
+  uint32_t num_tri_lights;
+};
+void launch_shade_delta(const DeltaLaunch& a);
+void launch_finish_delta(const DeltaLaunch& a);
 
 #define GSP_HIP_TRY(expr)                                                                     \
   do {                                                                                        \

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/gpuspectral_pt.h"
+#include "pt_deltalight.h"
 
 namespace gsp {
 
@@ -21,6 +22,19 @@ inline double light_pick_weight(const gsp_triangle_light& L) {
   }
   const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
   const double w = (y > 0.0 ? y : 0.0) * (0.5 * std::sqrt(cx * cx + cy * cy + cz * cz));
+  return std::isfinite(w) ? w : 0.0;
+}
+
+// ... and of an accepted delta record: the power it emits into the scene, with Y of its intensity (a directional light: through the
+// disc of radius `extent` that faces it)
+inline double light_pick_weight(const gsp_delta_light& L) {
+  const double pi = 3.14159265358979323846;
+  const double y0 = 0.2126 * (double)L.intensity[0] + 0.7152 * (double)L.intensity[1] + 0.0722 * (double)L.intensity[2];
+  const double y = y0 > 0.0 ? y0 : 0.0;
+  double w = 0.0;
+  if (L.kind == GSP_LIGHT_POINT) w = 4.0 * pi * y;
+  else if (L.kind == GSP_LIGHT_SPOT) w = 2.0 * pi * (1.0 - ((double)L.cos_beam + (double)L.cos_cutoff) / 2.0) * y;
+  else if (L.kind == GSP_LIGHT_DIRECTIONAL) w = pi * ((double)L.extent * (double)L.extent) * y;
   return std::isfinite(w) ? w : 0.0;
 }
 
@@ -109,16 +123,22 @@ inline float light_pick_inv_sum_from_weights(const double* w_in, uint32_t n) {
   const float r = (float)(1.0 / sum);
   return std::isfinite(r) ? r : 0.0f;
 }
-inline float light_pick_inv_sum(const gsp_triangle_light* lights, uint32_t n) {
-  std::vector<double> w(n);
+// the weights of a light table: the n triangle lights, then the nd delta lights behind them (include/gpuspectral_pt.h, "Delta lights")
+inline std::vector<double> light_pick_weights(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta, uint32_t nd) {
+  std::vector<double> w((size_t)n + nd);
   for (uint32_t i = 0; i < n; ++i) w[i] = light_pick_weight(lights[i]);
-  return light_pick_inv_sum_from_weights(w.data(), n);
+  for (uint32_t i = 0; i < nd; ++i) w[(size_t)n + i] = light_pick_weight(delta[i]);
+  return w;
+}
+inline float light_pick_inv_sum(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta = nullptr, uint32_t nd = 0) {
+  const std::vector<double> w = light_pick_weights(lights, n, delta, nd);
+  return light_pick_inv_sum_from_weights(w.data(), n + nd);
 }
 
-inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, gsp_light_pick* out) {
-  std::vector<double> w(n);
-  for (uint32_t i = 0; i < n; ++i) w[i] = light_pick_weight(lights[i]);
-  build_light_pick_from_weights(w.data(), n, out);
+inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta, uint32_t nd, gsp_light_pick* out) {
+  const std::vector<double> w = light_pick_weights(lights, n, delta, nd);
+  build_light_pick_from_weights(w.data(), n + nd, out);
 }
+inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, gsp_light_pick* out) { build_light_pick(lights, n, nullptr, 0, out); }
 
 }  // namespace gsp

@@ -124,7 +124,8 @@ struct gsp_context {
   size_t table_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // byte offsets inside a slot: BSDF types 0..7, then the lights
   size_t tables_bytes = 0;
   TableRing tab;  // slots, slot size, current version, rotation (pt_versions.h: pure bookkeeping, model-tested on the CPU)
-  uint32_t num_lights = 0;
+  uint32_t num_lights = 0;      // records of the resident light table: the scene's triangle lights + the delta lights behind them
+  uint32_t num_tri_lights = 0;  // ... the triangle lights among them
   // r05: the GEOMETRY ring (pt_stages.h): 2^geo.log2 <= kGeoVersions slots of geo.stride triangle slots each -- node records, intersection
   // triangles, shading packets -- so that gsp_update_instances need not wait for the samples in flight either: the refit goes
   // into the next slot, new samples are stamped with it, the old ones finish in theirs.  Made by the first gsp_update_instances
@@ -161,6 +162,9 @@ struct gsp_context {
   DevBuf<gsp_medium_scatter> scatter;
   std::vector<gsp_medium_scatter> h_scatter;
   bool scatter_on = false;
+  // delta lights (gsp_set_delta_lights): context state like the media, as accepted (directions renormalised).  Not empty selects the
+  // <DLT> kernels of pt_render_delta.hip and makes pack_tables append the records behind the triangle lights of every table image
+  std::vector<gsp_delta_light> h_delta;
   // light selection (gsp_set_light_sampling): context state like the lens.  GSP_LIGHTS_POWER selects the <LSEL> kernels and makes
   // pack_tables append the alias table behind the light records of every table image
   uint32_t light_mode = GSP_LIGHTS_UNIFORM;

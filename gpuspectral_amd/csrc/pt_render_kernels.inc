@@ -379,8 +379,10 @@ constexpr int kShadeWaves = kShadeBlock / 64;
 // EST: the context runs the textbook estimator (gsp_set_estimator): shade_vertex<.., EST = true>; P2.w carries lastPdf
 // SCT (with MED): some medium scatters (gsp_set_media_scattering): shade_vertex<.., SCT = true> and the table behind
 // SceneViewSct::scatter, read like the media table.  These instantiations live in pt_render_scatter.hip
-template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false>
-__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED, SCT>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
+// DLT: the context holds delta lights (gsp_set_delta_lights): shade_vertex<.., DLT = true> and SceneViewDlt::num_tri_lights; the
+// records sit behind the triangle lights in the table image.  These instantiations live in pt_render_delta.hip
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false>
+__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED, SCT, DLT>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
                                                         const q4* __restrict__ hits, PathQueue nxt, ShadowQueue sq,
                                                         q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                         uint32_t* __restrict__ live,
@@ -529,7 +531,7 @@ __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typen
         in.weight = mk3(p2.x, p2.y, p2.z);
         in.directWeight = p2.w;
         in.flags = fl;
-        shade_vertex<TEX, VER, MED, LSEL, EST, SCT>(S, rc, in, h, out, view_media(S), view_scatter(S));
+        shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S));
         alive = out.alive;
         has_shadow = out.has_shadow;
         ++shaded;
@@ -684,8 +686,8 @@ struct FinishStack {
   __device__ __forceinline__ uint32_t pop() { return col[(--top) * kBlock]; }
 };
 
-template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false>
-__global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false>
+__global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT, DLT>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
                                                     q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                     uint32_t* __restrict__ live,
                                                     uint32_t slot_paths, DevStats* __restrict__ stats) {
@@ -742,7 +744,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT
         break;
       }
       ShadeOut out;
-      shade_vertex<TEX, VER, MED, LSEL, EST, SCT>(S, rc, in, h, out, view_media(S), view_scatter(S));
+      shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S));
       ++shaded;
       if (!out.has_shadow) {
         add_emitted(rc.clamp, out.emitted, res);

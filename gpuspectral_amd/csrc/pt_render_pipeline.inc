@@ -181,6 +181,16 @@ static ScatterLaunch scatter_launch(const gsp_context* ctx, const TextbookLaunch
   a.est = ctx->estimator == GSP_ESTIMATOR_TEXTBOOK;
   return a;
 }
+// ... and <.., DLT = true>, the kernels of a context that holds delta lights (gsp_set_delta_lights), handed to pt_render_delta.hip: the
+// scattering record (the media tables null without media, the scattering table zeros where the media only absorb:
+// sync_absorbing_scatter_table) + the number of triangle lights in front of the delta records
+static DeltaLaunch delta_launch(const gsp_context* ctx, const TextbookLaunch& t) {
+  DeltaLaunch a{};
+  static_cast<ScatterLaunch&>(a) = scatter_launch(ctx, t);
+  if (ctx->num_media == 0) a.scatter = nullptr;
+  a.num_tri_lights = ctx->num_tri_lights;
+  return a;
+}
 }  // extern "C++"
 
 // The blocks of k_shade a device holds at once: the largest grid (a block loops over tiles), each may leave one room chunk of fillers.
@@ -283,11 +293,12 @@ static int finish_few_paths(gsp_context* ctx, gsp_context::Lane& L, const Render
   if (!(drain && L.queued == 0 && P.remaining == 0 && P.n > 0 && P.n <= ctx->finish_paths && ctx->pipe_params.collect_traversal_stats == 0 &&
         std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 <= kFinishLevels))
     return GSP_OK;
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty()) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, L.stream, (uint32_t)((P.n + kBlock - 1) / kBlock), lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq),
                                        L.counters.p + C_LIVE, (uint32_t)P.batch_paths);
     a.n = (uint32_t)P.n;
-    if (ctx->scatter_on) launch_finish_scatter(scatter_launch(ctx, a));
+    if (!ctx->h_delta.empty()) launch_finish_delta(delta_launch(ctx, a));
+    else if (ctx->scatter_on) launch_finish_scatter(scatter_launch(ctx, a));
     else launch_finish_textbook(a);
   } else
   tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
@@ -357,14 +368,15 @@ static int trace_shade_connect(gsp_context* ctx, gsp_context::Lane& L, const Ren
   CTX_TRY(ctx, hipGetLastError());
   if (ev) CTX_TRY(ctx, hipEventRecord(ev[1], st));
   const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + kShadeBlock - 1) / kShadeBlock, shade_resident_blocks(ctx))));
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty()) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, st, grid.x, cur, L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths);
     a.n_ptr = n_ptr;
     a.hits = hits;
     a.next[0] = next.P0, a.next[1] = next.P1, a.next[2] = next.P2, a.next[3] = next.P3;
     a.shadow[0] = sq.S0, a.shadow[1] = sq.S1, a.shadow[2] = sq.S3;
     a.chunk = room_chunk;
-    if (ctx->scatter_on) launch_shade_scatter(scatter_launch(ctx, a));
+    if (!ctx->h_delta.empty()) launch_shade_delta(delta_launch(ctx, a));
+    else if (ctx->scatter_on) launch_shade_scatter(scatter_launch(ctx, a));
     else launch_shade_textbook(a);
   } else
   tex_ver_med_kernel(ctx, V, [&](auto TEX, auto VER, auto MED, auto LSEL, const auto& sview) {
@@ -1300,6 +1312,17 @@ int gsp_set_lens(gsp_context* ctx, const gsp_lens* lens_host) {
   return GSP_OK;
 }
 
+// A context with delta lights runs the <MED, SCT, DLT> kernels whatever its media (pt_render_delta.hip).  Where it holds media but
+// no scattering table, those kernels read one of zeros from the table's device buffer: every medium then takes the deterministic
+// line of the absorbing kernels.  Called behind every change of the three tables, under a drained pipeline.
+static int sync_absorbing_scatter_table(gsp_context* ctx) {
+  if (ctx->h_delta.empty() || ctx->num_media == 0 || !ctx->h_scatter.empty()) return GSP_OK;
+  const std::vector<gsp_medium_scatter> zeros(ctx->num_media, gsp_medium_scatter{{0.0f, 0.0f, 0.0f}, 0.0f});
+  CTX_TRY(ctx, ctx->scatter.upload(zeros.data(), zeros.size(), ctx->stream, &ctx->bytes));
+  CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (`zeros` goes out of scope; the lanes' streams read the table)
+  return GSP_OK;
+}
+
 // ---- interior media (include/gpuspectral_pt.h, "Interior media") ----
 int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media) {
   if (!ctx) return GSP_ERR_INVALID;
@@ -1326,7 +1349,7 @@ int gsp_set_media(gsp_context* ctx, const gsp_medium* media, uint32_t num_media)
     ctx->scatter_on = false;
   }
   ctx->num_media = n;
-  return GSP_OK;
+  return sync_absorbing_scatter_table(ctx);
 }
 
 // ---- scattering media (include/gpuspectral_pt.h, "Scattering media") ----
@@ -1346,7 +1369,7 @@ int gsp_set_media_scattering(gsp_context* ctx, const gsp_medium_scatter* scatter
     CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the lanes' streams read it)
   }
   ctx->scatter_on = any_scattering(ctx->h_scatter.data(), n);
-  return GSP_OK;
+  return sync_absorbing_scatter_table(ctx);
 }
 
 // ---- light selection (include/gpuspectral_pt.h, "Light selection") ----
@@ -1415,6 +1438,33 @@ int gsp_set_estimator(gsp_context* ctx, uint32_t mode) {
   rc = repack_resident_tables(ctx);  // with or without the trailing record behind the pick table
   if (rc != GSP_OK) ctx->estimator = old_mode;
   return rc;
+}
+
+// ---- delta lights (include/gpuspectral_pt.h, "Delta lights") ----
+int gsp_set_delta_lights(gsp_context* ctx, const gsp_delta_light* lights, uint32_t count) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (const char* why = check_delta_lights(lights, count)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  std::vector<gsp_delta_light> accepted(lights ? count : 0u);
+  for (size_t k = 0; k < accepted.size(); ++k) accepted[k] = accept_delta_light(lights[k]);
+  if ((uint64_t)ctx->num_tri_lights + accepted.size() > 0xffffffffull) {
+    ctx->err = "gsp_set_delta_lights: too many lights";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight read the light table as it was
+  if (rc != GSP_OK) return rc;
+  if (accepted.size() == ctx->h_delta.size() && (accepted.empty() || std::memcmp(accepted.data(), ctx->h_delta.data(), sizeof(gsp_delta_light) * accepted.size()) == 0))
+    return GSP_OK;
+  ctx->h_delta.swap(accepted);
+  rc = repack_resident_tables(ctx);  // the records ride behind the triangle lights of the table image
+  if (rc != GSP_OK) {
+    ctx->h_delta.swap(accepted);
+    return rc;
+  }
+  return sync_absorbing_scatter_table(ctx);
 }
 
 int gsp_download_light_pick(gsp_context* ctx, gsp_light_pick* out, uint32_t capacity, uint32_t* count) {

@@ -62,7 +62,9 @@ static constexpr size_t kRecordBytes[9] = {sizeof(gsp_diffuse_bsdf), sizeof(gsp_
                                            sizeof(gsp_smooth_plastic_bsdf), sizeof(gsp_rough_conductor_bsdf), sizeof(gsp_smooth_floor_bsdf),
                                            sizeof(gsp_rough_floor_bsdf), sizeof(gsp_rough_plastic_bsdf), sizeof(gsp_triangle_light)};
 // The eight BSDF arrays + the lights (+ in GSP_LIGHTS_POWER mode their alias table) of `sc`, packed back to back (16-B aligned each) as they sit in the context's one table
-// allocation; the counts ride in front of the image so that "equal images" means equal tables.
+// allocation; the counts ride in front of the image so that "equal images" means equal tables.  The context's delta lights
+// (gsp_set_delta_lights) sit straight behind the triangle lights, 64 B each like them; count 8 stays the TRIANGLE lights, so an image
+// unpacks into the scene it was packed from (repack_resident_tables) and a context without delta lights keeps its bytes.
 struct TableImage {
   std::vector<uint8_t> bytes;  // [9 x uint64 count][tables ...]: the device holds bytes.data() + kHead onwards
   size_t off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, total = 0;
@@ -74,6 +76,12 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
                         sc->rough_conductor_bsdfs, sc->smooth_floor_bsdfs, sc->rough_floor_bsdfs, sc->rough_plastic_bsdfs, sc->lights};
   size_t bytes[9];
   uint64_t counts[9];
+  const uint32_t num_delta = (uint32_t)ctx->h_delta.size(), all_lights = sc->num_lights + num_delta;
+  if (all_lights < num_delta) {
+    ctx->err = "too many lights";
+    return GSP_ERR_SCENE;
+  }
+  const size_t delta_bytes = sizeof(gsp_delta_light) * (size_t)num_delta;
   img.total = 0;
   for (int k = 0; k < 9; ++k) {
     counts[k] = k < 8 ? sc->num_bsdfs[k] : sc->num_lights;
@@ -88,24 +96,26 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
     img.off[k] = img.total;
     img.total += (bytes[k] + 15) & ~(size_t)15;
   }
+  img.total += delta_bytes;  // (behind the triangle lights, the last of the nine: 64-B records, no padding)
   // GSP_LIGHTS_POWER: a tenth sub-table, the alias table of the lights (pt_lightpick.h), straight behind the light records (64 B
   // each: no padding in between), so that (const gsp_light_pick*)(lights + num_lights) finds it.  Absent in uniform mode: such a
   // context keeps the image size, and so the LDS staging decision, it always had
-  const bool pick = light_pick_table_bytes(sc->num_lights, ctx->light_mode) != 0;
+  const bool pick = light_pick_table_bytes(all_lights, ctx->light_mode) != 0;
   img.pick_off = img.total;
-  img.total += light_pick_table_bytes(sc->num_lights, ctx->light_mode);
+  img.total += light_pick_table_bytes(all_lights, ctx->light_mode);
   // ... and, with GSP_ESTIMATOR_TEXTBOOK on top, one trailing 16-byte record behind the table: {inv_sum_w, 0, 0, 0}, what
   // shade_vertex<.., LSEL, EST> multiplies the weight of a light that was HIT with.  Absent in every other combination
-  const bool tail = light_pick_tail_bytes(sc->num_lights, ctx->light_mode, ctx->estimator) != 0;
+  const bool tail = light_pick_tail_bytes(all_lights, ctx->light_mode, ctx->estimator) != 0;
   const size_t tail_off = img.total;
-  img.total += light_pick_tail_bytes(sc->num_lights, ctx->light_mode, ctx->estimator);
+  img.total += light_pick_tail_bytes(all_lights, ctx->light_mode, ctx->estimator);
   img.bytes.assign(TableImage::kHead + std::max<size_t>(img.total, 16), 0);
   std::memcpy(img.bytes.data(), counts, sizeof(counts));
   for (int k = 0; k < 9; ++k)
     if (bytes[k]) std::memcpy(img.bytes.data() + TableImage::kHead + img.off[k], src[k], bytes[k]);
-  if (pick) build_light_pick(sc->lights, sc->num_lights, (gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off));
+  if (delta_bytes) std::memcpy(img.bytes.data() + TableImage::kHead + img.off[8] + bytes[8], ctx->h_delta.data(), delta_bytes);
+  if (pick) build_light_pick(sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta, (gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off));
   if (tail) {
-    const float inv_sum_w = light_pick_inv_sum(sc->lights, sc->num_lights);
+    const float inv_sum_w = light_pick_inv_sum(sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta);
     std::memcpy(img.bytes.data() + TableImage::kHead + tail_off, &inv_sum_w, sizeof(float));
   }
   return GSP_OK;
@@ -133,7 +143,8 @@ static int upload_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage&
   CTX_TRY(ctx, hipMemcpyAsync(base, ctx->h_tables.data() + TableImage::kHead, std::max<size_t>(img.total, 16), hipMemcpyHostToDevice, ctx->stream));
   for (int k = 0; k < 9; ++k) ctx->table_off[k] = img.off[k];
   ctx->tables_bytes = img.total;
-  ctx->num_lights = sc->num_lights;
+  ctx->num_tri_lights = sc->num_lights;
+  ctx->num_lights = sc->num_lights + (uint32_t)ctx->h_delta.size();  // (the delta records need no bake: they are resident as accepted)
   for (int k = 0; k < GSP_BSDF_TYPE_COUNT; ++k) ctx->num_bsdfs[k] = sc->num_bsdfs[k];
   // the resident light and diffuse records carry what a vertex would compute from them alone (pt_shading.h bake_light / bake_diffuse)
   uint32_t nb = sc->num_lights;
@@ -794,7 +805,7 @@ int gsp_update_tables(gsp_context* ctx, const gsp_scene_desc* sc) {
   // re-reads the tables every frame; a host that edits a material every frame keeps the path pool full now,
   // profiles/r05_update_latency.txt.)  Otherwise -- another layout, or kTableVersions edits within the life of one sample --
   // the queued samples finish first, as until r04.
-  bool same_layout = ctx->pipe_active && sc->num_lights == ctx->num_lights && img.total == ctx->tables_bytes && ctx->tables.p != nullptr;
+  bool same_layout = ctx->pipe_active && sc->num_lights == ctx->num_tri_lights && sc->num_lights + ctx->h_delta.size() == ctx->num_lights && img.total == ctx->tables_bytes && ctx->tables.p != nullptr;
   for (int k = 0; k < GSP_BSDF_TYPE_COUNT && same_layout; ++k) same_layout = sc->num_bsdfs[k] == ctx->num_bsdfs[k];
   size_t free_b = 0, total_b = 0;
   if (same_layout && ctx->tab.slots == 1) CTX_TRY(ctx, hipMemGetInfo(&free_b, &total_b));  // (only the decision to grow asks)

@@ -690,20 +690,9 @@ struct LightSample {
   f3 emission;
   float pdf;
 };
-// Draws R (index), U (e1), U (e2) -- always three draws (SURVEY Appendix B).  `lights` = BAKED records (bake_light);
-// inv_num_lights = 1.0f / (float)num_lights (:151), formed once on the host.
-GSP_HD LightSample sample_light(const gsp_triangle_light* lights, uint32_t num_lights, float inv_num_lights, uint32_t& rng, f3 pos) {
+// the point on triangle light L of the variates (e1, e2) and its solid-angle pdf at pos (:136-151), pmf = the probability of the pick
+GSP_HD LightSample sample_light_triangle(const gsp_triangle_light* L, float e1, float e2, f3 pos, float pmf) {
   LightSample ls;
-  uint32_t r = pcg_next(rng);
-  float e1 = rand_uniform(rng);
-  float e2 = rand_uniform(rng);
-  if (num_lights == 0) {  // modulo by zero in the reference (:148): no light, zero pdf
-    ls.position = pos;
-    ls.emission = splat(0.0f);
-    ls.pdf = 0.0f;
-    return ls;
-  }
-  const gsp_triangle_light* L = lights + (r % num_lights);
   float se1 = gsqrt(e1);
   float u = 1.0f - se1;
   float v = e2 * se1;
@@ -721,8 +710,23 @@ GSP_HD LightSample sample_light(const gsp_triangle_light* lights, uint32_t num_l
   ls.position = lightPos;
   ls.emission = ld3(L->radiance) * (c > 0.0f ? 1.0f : 0.0f);
   ls.pdf = (ldist * ldist) / (gabs(c) * A);
-  ls.pdf = ls.pdf * inv_num_lights;
+  ls.pdf = ls.pdf * pmf;
   return ls;
+}
+// Draws R (index), U (e1), U (e2) -- always three draws (SURVEY Appendix B).  `lights` = BAKED records (bake_light);
+// inv_num_lights = 1.0f / (float)num_lights (:151), formed once on the host.
+GSP_HD LightSample sample_light(const gsp_triangle_light* lights, uint32_t num_lights, float inv_num_lights, uint32_t& rng, f3 pos) {
+  LightSample ls;
+  uint32_t r = pcg_next(rng);
+  float e1 = rand_uniform(rng);
+  float e2 = rand_uniform(rng);
+  if (num_lights == 0) {  // modulo by zero in the reference (:148): no light, zero pdf
+    ls.position = pos;
+    ls.emission = splat(0.0f);
+    ls.pdf = 0.0f;
+    return ls;
+  }
+  return sample_light_triangle(lights + (r % num_lights), e1, e2, pos, inv_num_lights);
 }
 
 // GSP_LIGHTS_POWER (include/gpuspectral_pt.h, "Light selection"): the light is drawn in proportion to Y(radiance) * area through
@@ -755,26 +759,8 @@ GSP_HD LightSample sample_light_power(const gsp_triangle_light* lights, const gs
     return ls;
   }
   float pmf;
-  const gsp_triangle_light* L = lights + light_pick_index(pick, num_lights, r, pmf);
-  float se1 = gsqrt(e1);
-  float u = 1.0f - se1;
-  float v = e2 * se1;
-  float w = (1.0f - u) - v;
-  f3 v0 = ld3(L->positions[0]);
-  f3 v1 = ld3(L->positions[1]);
-  f3 v2 = ld3(L->positions[2]);
-  float A = L->radiance[3];
-  f3 normal = mk3(L->positions[0][3], L->positions[1][3], L->positions[2][3]);
-  f3 lightPos = (u * v0 + v * v1) + w * v2;
-  f3 toL = lightPos - pos;
-  float ldist = length(toL);
-  f3 l = normalize(toL);
-  float c = dot(-l, normal);
-  ls.position = lightPos;
-  ls.emission = ld3(L->radiance) * (c > 0.0f ? 1.0f : 0.0f);
-  ls.pdf = (ldist * ldist) / (gabs(c) * A);
-  ls.pdf = ls.pdf * pmf;
-  return ls;
+  const uint32_t k = light_pick_index(pick, num_lights, r, pmf);
+  return sample_light_triangle(lights + k, e1, e2, pos, pmf);
 }
 
 // GSP_ESTIMATOR_TEXTBOOK under GSP_LIGHTS_POWER (include/gpuspectral_pt.h, "Estimator"): the probability with which the power pick

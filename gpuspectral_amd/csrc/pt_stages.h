@@ -15,6 +15,7 @@
 // firefly test (raygen.rgen:60-63).  The NEE term needs the shadow ray, so the
 // shade pass hands both terms to the connect pass, which forms the same sum.
 #pragma once
+#include "pt_deltalight.h"
 #include "pt_medium.h"
 #include "pt_shading.h"
 #include "pt_trace.h"
@@ -93,9 +94,18 @@ struct SceneViewMed : SceneView {
 struct SceneViewSct : SceneViewMed {
   const gsp_medium_scatter* scatter = nullptr;
 };
-template <bool MED, bool SCT = false>
+// ... and the <DLT = true> ones (gsp_set_delta_lights): + the number of TRIANGLE lights in front of the delta records of the light
+// table (num_lights counts both).  They are built for MED = SCT = false and MED = SCT = true only and take this one view
+struct SceneViewDlt : SceneViewSct {
+  uint32_t num_tri_lights = 0;
+};
+template <bool MED, bool SCT = false, bool DLT = false>
 struct ShadeViewOf {
   using type = SceneView;
+};
+template <bool MED, bool SCT>
+struct ShadeViewOf<MED, SCT, true> {
+  using type = SceneViewDlt;
 };
 template <>
 struct ShadeViewOf<true, false> {
@@ -109,6 +119,8 @@ GSP_HD const gsp_medium* view_media(const SceneView&) { return nullptr; }
 GSP_HD const gsp_medium* view_media(const SceneViewMed& v) { return v.media; }
 GSP_HD const gsp_medium_scatter* view_scatter(const SceneView&) { return nullptr; }
 GSP_HD const gsp_medium_scatter* view_scatter(const SceneViewSct& v) { return v.scatter; }
+GSP_HD uint32_t view_tri_lights(const SceneView&) { return 0u; }
+GSP_HD uint32_t view_tri_lights(const SceneViewDlt& v) { return v.num_tri_lights; }
 
 // path flags word: depth [0,7] | wasDelta << 8 | countEmitted << 9 | table version << 10 [10,15] | geometry version << 16 [16,21]
 GSP_HD uint32_t pack_flags(uint32_t depth, uint32_t wasDelta, uint32_t countEmitted) {
@@ -336,9 +348,15 @@ struct ShadeOut {
 // through the early return below -- no BSDF, no light sample, no shadow ray --, a surface event goes on as the ordinary vertex with
 // the weight of the decision.  A medium whose sigma_s is 0 takes the MED line and draws nothing.  SCT = false is the code of a
 // context whose media only absorb, instruction for instruction.
-template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false, bool SCT = false>
+// DLT: the context holds delta lights (include/gpuspectral_pt.h, "Delta lights"): the light table has S.num_lights records, the first
+// num_tri_lights of them triangles, the rest gsp_delta_light (never empty here: num_lights != 0).  The same three draws and the same
+// pick; an index >= num_tri_lights takes sample_delta_light (pt_deltalight.h) and an NEE term without the power heuristic, a
+// smaller one the triangle's operations as they stand.  DLT = false is the code of a context without delta lights, instruction for
+// instruction.
+template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false, bool SCT = false, bool DLT = false>
 GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
-                         ShadeOut& out, const gsp_medium* media = nullptr, const gsp_medium_scatter* scatter = nullptr) {
+                         ShadeOut& out, const gsp_medium* media = nullptr, const gsp_medium_scatter* scatter = nullptr,
+                         uint32_t num_tri_lights = 0u) {
   static_assert(MED || !SCT, "the scattering table is parallel to the media table");
   uint32_t rng = in.seed;                                                 // rchit:668
   BsdfTables Tv;  // (VER only: this lane's version of the tables)
@@ -456,12 +474,37 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   const float NoW = gabs(wi_l.z);                                         // :717
   const f3 wi = to_world(onb, wi_l);                                      // :718
 
-  const LightSample ls = LSEL ? sample_light_power(lights, (const gsp_light_pick*)(lights + S.num_lights), S.num_lights, rng, position)
-                              : sample_light(lights, S.num_lights, S.inv_num_lights, rng, position);  // :720
-  const f3 toL = ls.position - position;
-  const f3 L = normalize(toL);                                            // :722
+  LightSample ls;
+  f3 L;
+  float Ldist;
+  bool delta_light = false;  // (DLT only) the pick landed on a delta record
+  if constexpr (DLT) {
+    const uint32_t r = pcg_next(rng);
+    const float e1 = rand_uniform(rng);
+    const float e2 = rand_uniform(rng);
+    float pmf = S.inv_num_lights;
+    const uint32_t k = LSEL ? light_pick_index((const gsp_light_pick*)(lights + S.num_lights), S.num_lights, r, pmf) : r % S.num_lights;
+    delta_light = k >= num_tri_lights;
+    if (delta_light) {  // (e1, e2: drawn and unused)
+      const DeltaSample ds = sample_delta_light(*(const gsp_delta_light*)(lights + k), position, pmf);
+      L = ds.L;
+      Ldist = ds.Ldist;
+      ls.emission = ds.emission;
+      ls.pdf = ds.pdf;
+    } else {
+      ls = sample_light_triangle(lights + k, e1, e2, position, pmf);
+      const f3 toL = ls.position - position;
+      L = normalize(toL);
+      Ldist = length(toL);
+    }
+  } else {
+    ls = LSEL ? sample_light_power(lights, (const gsp_light_pick*)(lights + S.num_lights), S.num_lights, rng, position)
+              : sample_light(lights, S.num_lights, S.inv_num_lights, rng, position);  // :720
+    const f3 toL = ls.position - position;
+    L = normalize(toL);                                                   // :722
+    Ldist = length(toL);                                                  // :724
+  }
   const f3 wL = to_local(onb, L);                                         // :723
-  const float Ldist = length(toL);                                        // :724
   const float NoL = gabs(dot(SN, L));                                     // :725
   const float lightPdf = ls.pdf;
   BsdfResult lb;
@@ -478,8 +521,12 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   const bool want_shadow = nee_on && !bs.delta && ((NdotV > 0.0f && dot(N, L) > 0.0f) || transmits) && (lightPdf != 0.0f);
   f3 nee = splat(0.0f);
   if (want_shadow) {
-    const float w = power_heuristic(lightPdf, EST ? lb.pdf : bs.pdf);     // :751 (EST: the pdf of L itself)
-    nee = ((((w * NoL) * lb.f) * weight) * ls.emission) / lightPdf;       // :752
+    if (DLT && delta_light) {  // no BSDF sample reaches a delta light: weight 1
+      nee = (((NoL * lb.f) * weight) * ls.emission) / lightPdf;
+    } else {
+      const float w = power_heuristic(lightPdf, EST ? lb.pdf : bs.pdf);   // :751 (EST: the pdf of L itself)
+      nee = ((((w * NoL) * lb.f) * weight) * ls.emission) / lightPdf;     // :752
+    }
   }
   const uint32_t depth = in.flags & 0xffu;
   const uint32_t wasDelta = (in.flags >> 8) & 1u;
@@ -554,6 +601,7 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
     out.shadow.nee = nee;
     out.shadow.emis = emis;
     out.shadow.dw_nee = EST ? bs.pdf : power_heuristic(bs.pdf, lightPdf); // :786; EST: lastPdf, whatever the verdict
+    if (DLT && !EST && delta_light) out.shadow.dw_nee = 1.0f;              // what a vertex without a shadow ray hands on
     out.shadow.sid = in.sid;
     out.shadow.next = -1;
   }

@@ -67,6 +67,10 @@ def load():
     L.gsph_scene_media.argtypes = [vp, vp]
     L.gsph_scene_media_scattering.restype = u32
     L.gsph_scene_media_scattering.argtypes = [vp, vp]
+    L.gsph_scene_delta_lights.restype = u32
+    L.gsph_scene_delta_lights.argtypes = [vp, vp]
+    L.gsph_scene_set_delta_lights.restype = None
+    L.gsph_scene_set_delta_lights.argtypes = [vp, C.POINTER(abi.DeltaLight), u32]
     L.gsph_scene_add_scattering_medium.restype = u32
     L.gsph_scene_add_scattering_medium.argtypes = [vp, vp, vp, C.c_float]
     L.gsph_scene_object_medium.restype = u32
@@ -145,7 +149,7 @@ class Scene:
     """A C++ GPUSpectral::Scene produced by loadScene (S/engine/Loader.cpp:253-349)."""
 
     def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False,
-                 read_lens=False, read_film=False, read_media=False, read_scattering=False):
+                 read_lens=False, read_film=False, read_media=False, read_scattering=False, read_emitters=False):
         """dormant_features: LoadOptions::dormantFeatures (textures / environment map, SURVEY 8(f).3); builtin_shapes:
         LoadOptions::builtinShapes (`disk` and `sphere` shapes are built instead of skipped, SURVEY 8(f).1); the defaults are
         the reference's behaviour.  read_filter: LoadOptions::readFilter (the film's <rfilter> becomes `pixel_filter`, which
@@ -153,14 +157,15 @@ class Scene:
         sensor's aperture_radius / focus_distance become the camera's lens, which PathTracer hands to the device).  read_film:
         LoadOptions::readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn become `film`).  read_media:
         LoadOptions::readMedia (the shapes' <medium name="interior"> become `media` and the objects' medium numbers: coloured glass).
-        read_scattering: LoadOptions::readScattering (implies read_media; sigmaS / albedo and the hg phase become `media_scattering`)."""
+        read_scattering: LoadOptions::readScattering (implies read_media; sigmaS / albedo and the hg phase become `media_scattering`).
+        read_emitters: LoadOptions::readEmitters (top-level point / spot / directional emitters become `delta_lights`)."""
         self._L = load()
         ad = asset_dir.encode() if asset_dir else None
-        if builtin_shapes or read_filter or read_lens or read_film or read_media or read_scattering:
+        if builtin_shapes or read_filter or read_lens or read_film or read_media or read_scattering or read_emitters:
             self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) |
                                                    (4 if builtin_shapes else 0) | (8 if read_filter else 0) | (16 if read_lens else 0) |
                                                    (32 if read_film else 0) | (64 if read_media else 0) |
-                                                   (128 if read_scattering else 0))
+                                                   (128 if read_scattering else 0) | (256 if read_emitters else 0))
         elif dormant_features:
             self._h = self._L.gsph_load_scene_ex(path.encode(), ad, 1, 1 if srgb_textures else 0)
         else:
@@ -221,6 +226,20 @@ class Scene:
         if n:
             self._L.gsph_scene_media_scattering(self._h, out.ctypes.data)
         return out
+
+    @property
+    def delta_lights(self):
+        """Scene::deltaLights as a list of abi.DeltaLight; empty without read_emitters / set_delta_lights."""
+        n = self._L.gsph_scene_delta_lights(self._h, None)
+        out = (abi.DeltaLight * max(n, 1))()
+        if n:
+            self._L.gsph_scene_delta_lights(self._h, out)
+        return list(out)[:n]
+
+    def set_delta_lights(self, lights):
+        """Scene::deltaLights = the abi.DeltaLight records of `lights` (PathTracer sends the table when its value changed)."""
+        arr = abi.delta_light_array(lights)
+        self._L.gsph_scene_set_delta_lights(self._h, arr, len(arr) if arr is not None else 0)
 
     def add_scattering_medium(self, sigma_a, sigma_s, g=0.0):
         """Scene::addMedium with scattering: the number of the (possibly shared) entry."""

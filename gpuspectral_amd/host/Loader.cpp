@@ -703,6 +703,74 @@ static uint32_t shapeInteriorMedium(Scene& scene, const Object& shape, const Par
   return number;
 }
 
+// LoadOptions::readEmitters: one top-level <emitter type="point" | "spot" | "directional"> -> its record (a directional light's extent
+// is filled in behind the shapes)
+static gsp_delta_light loadDeltaEmitter(const Object& e) {
+  gsp_delta_light l{};
+  double rowMajor[16];
+  for (int k = 0; k < 16; ++k) rowMajor[k] = (k % 5 == 0) ? 1.0 : 0.0;
+  auto tw = e.props.find("to_world");
+  const bool hasTransform = tw != e.props.end() && tw->second.type == PT_TRANSFORM;
+  if (hasTransform)
+    for (int k = 0; k < 16; ++k) rowMajor[k] = tw->second.matrix[k];
+  // the image of +z (third column), unit, in double; the translation (fourth column)
+  double axis[3] = {rowMajor[2], rowMajor[6], rowMajor[10]};
+  const double translation[3] = {rowMajor[3], rowMajor[7], rowMajor[11]};
+  const auto vectorProp = [&](const char* name, double* out) {
+    auto it = e.props.find(name);
+    if (it == e.props.end() || it->second.type != PT_VECTOR) return false;
+    for (int c = 0; c < 3; ++c) out[c] = it->second.v[c];
+    return true;
+  };
+  const float scale = e.number("scale", 1.0f);
+  const vec3 power = e.color(e.plugin == "directional" ? "irradiance" : "intensity");
+  l.intensity[0] = power.x * scale, l.intensity[1] = power.y * scale, l.intensity[2] = power.z * scale;
+  if (e.plugin == "directional") {
+    l.kind = GSP_LIGHT_DIRECTIONAL;
+    vectorProp("direction", axis);
+    l.extent = 1.0f;
+  } else {
+    double pos[3] = {translation[0], translation[1], translation[2]};
+    if (e.plugin == "point") vectorProp("position", pos);
+    for (int c = 0; c < 3; ++c) l.position[c] = (float)pos[c];
+    l.kind = e.plugin == "point" ? GSP_LIGHT_POINT : GSP_LIGHT_SPOT;
+  }
+  if (l.kind != GSP_LIGHT_POINT) {
+    const double len = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (!(len > 0.0)) throw std::runtime_error("emitter type '" + e.plugin + "': the direction has no length");
+    for (int c = 0; c < 3; ++c) l.direction[c] = (float)(axis[c] / len);
+  }
+  if (l.kind == GSP_LIGHT_SPOT) {
+    const double kPi = 3.14159265358979323846;
+    const double cutoff = e.has("cutoff_angle") ? (double)e.number("cutoff_angle") : 20.0;
+    const double beam = e.has("beam_width") ? (double)e.number("beam_width") : cutoff * 3.0 / 4.0;
+    l.cos_cutoff = (float)std::cos(cutoff * kPi / 180.0);
+    l.cos_beam = (float)std::cos(beam * kPi / 180.0);
+  }
+  return l;
+}
+
+// half the diagonal of the world-space bounding box of every render object's vertices; 1 for a scene without any
+static float sceneExtent(const Scene& scene) {
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+  bool any = false;
+  for (const RenderObject& o : scene.renderObjects) {
+    if (!o.mesh) continue;
+    for (const Mesh::Vertex& v : o.mesh->getVertices()) {
+      const vec4 p = o.transform * vec4{v.pos.x, v.pos.y, v.pos.z, 1.0f};
+      const double q[3] = {p.x, p.y, p.z};
+      for (int c = 0; c < 3; ++c) {
+        lo[c] = std::min(lo[c], q[c]);
+        hi[c] = std::max(hi[c], q[c]);
+      }
+      any = true;
+    }
+  }
+  if (!any) return 1.0f;
+  const double d = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+  return d > 0.0 ? (float)(0.5 * d) : 1.0f;
+}
+
 Scene loadScene(const std::string& path, const std::string& assetDirArg, const LoadOptions& options) {
   std::ifstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("cannot open scene file: " + path);
@@ -878,6 +946,8 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
           });
         });
       }
+    } else if (obj->kind == "emitter" && options.readEmitters && (obj->plugin == "point" || obj->plugin == "spot" || obj->plugin == "directional")) {
+      outScene.deltaLights.push_back(loadDeltaEmitter(*obj));
     } else if (obj->kind == "emitter") {
       if (!options.dormantFeatures || obj->plugin != "envmap") {
         outScene.warnings.push_back("top-level emitter (envmap) ignored, as in the reference (Loader.cpp:338-346)");
@@ -896,6 +966,11 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
         outScene.hasEnvMap = true;
       }
     }
+  }
+  if (!outScene.deltaLights.empty()) {  // a directional light's extent: half the diagonal of the scene's world-space bounding box
+    const float extent = sceneExtent(outScene);
+    for (gsp_delta_light& l : outScene.deltaLights)
+      if (l.kind == GSP_LIGHT_DIRECTIONAL) l.extent = extent;
   }
   return outScene;
 }

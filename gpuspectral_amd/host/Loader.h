@@ -56,6 +56,16 @@ struct LoadOptions {
   // <phase type="hg"><float name="g" ../></phase> child (`isotropic` or no child: g = 0; any other phase type: one warning, g = 0).
   // Scene::mediaScattering then runs parallel to Scene::media.  false: a scattering medium is skipped with its warning, as above.
   bool readScattering = false;
+  // readEmitters = true reads the top-level delta emitters (include/gpuspectral_pt.h "Delta lights") into Scene::deltaLights:
+  //   <emitter type="point">: `position`, or the translation of `toWorld`; `intensity`
+  //   <emitter type="spot">: `toWorld` (position = its translation, axis = the image of +z); `intensity`; `cutoffAngle` (default 20
+  //     degrees) and `beamWidth` (default 3 / 4 of the cutoff); the cosines are formed in double.  The falloff between them is the
+  //     library's smoothstep of the cosine, not Mitsuba's ramp in the angle
+  //   <emitter type="directional">: `direction`, or the image of +z under `toWorld`; `irradiance`; extent = half the diagonal of the
+  //     world-space bounding box of the scene's vertices (1 for a scene without any)
+  // A `scale` multiplies the intensity / irradiance.  Every other emitter type keeps its warning.  false: the scene and its warnings are
+  // what they were before this option existed.
+  bool readEmitters = false;
 };
 
 // assetDir: where rect.obj / box.obj / disk.obj live (Engine::assetPath); "" = the

@@ -81,6 +81,11 @@ bool SceneTracker::mediaChanged(const Scene& scene) const {
           std::memcmp(scene.mediaScattering.data(), mediaScattering.data(), mediaScattering.size() * sizeof(gsp_medium_scatter)) != 0);
 }
 
+bool SceneTracker::deltaLightsChanged(const Scene& scene) const {
+  return scene.deltaLights.size() != deltaLights.size() ||
+         (!deltaLights.empty() && std::memcmp(scene.deltaLights.data(), deltaLights.data(), deltaLights.size() * sizeof(gsp_delta_light)) != 0);
+}
+
 // the media table, and behind it the scattering table parallel to it (gsp_set_media with another count drops the device's).  Returns
 // gsp_set_media's code (it may refuse to shrink the table under the resident scene: the caller tries again behind the scene)
 template <class SetMedia, class SetScattering>
@@ -165,6 +170,10 @@ void PathTracer::prepareScene(const Scene& scene) {
   if (tracker.lensChanged(scene, lens)) {  // (context state: no scene needed, no drain)
     check(gsp_set_lens(ctx, &lens), "gsp_set_lens");
     tracker.rememberLens(lens);
+  }
+  if (tracker.deltaLightsChanged(scene)) {  // (context state too: it waits for the samples in flight and repacks the resident tables)
+    check(gsp_set_delta_lights(ctx, scene.deltaLights.data(), (uint32_t)scene.deltaLights.size()), "gsp_set_delta_lights");
+    tracker.rememberDeltaLights(scene);
   }
   // the media table goes BEFORE a scene that names more entries than the device holds and AFTER one that names fewer than the
   // resident scene does (gsp_set_media refuses to shrink the table under it): tried first, and again behind the scene if refused
@@ -475,6 +484,10 @@ void MultiGpuPathTracer::prepareScene(const Scene& scene) {
   if (tracker.lensChanged(scene, lens)) {
     check(gsp_multi_set_lens(multi, &lens), "gsp_multi_set_lens");
     tracker.rememberLens(lens);
+  }
+  if (tracker.deltaLightsChanged(scene)) {
+    check(gsp_multi_set_delta_lights(multi, scene.deltaLights.data(), (uint32_t)scene.deltaLights.size()), "gsp_multi_set_delta_lights");
+    tracker.rememberDeltaLights(scene);
   }
   // (the media table: as PathTracer::prepareScene; a change that has to follow the scene takes the full upload here)
   const auto sendBoth = [&] {

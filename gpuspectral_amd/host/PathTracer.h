@@ -40,6 +40,9 @@ struct SceneTracker {
   void rememberLens(const gsp_lens& l) { lens = l; }
   // the scene's interior media (Scene::media) against the table last sent; context state of its own too (gsp_set_media)
   bool mediaChanged(const Scene& scene) const;
+  // ... and its delta lights (Scene::deltaLights) against the table last sent (gsp_set_delta_lights)
+  bool deltaLightsChanged(const Scene& scene) const;
+  void rememberDeltaLights(const Scene& scene) { deltaLights = scene.deltaLights; }
   void rememberMedia(const Scene& scene) {
     media = scene.media;
     mediaScattering = scene.mediaScattering;
@@ -54,6 +57,7 @@ struct SceneTracker {
   gsp_lens lens{};                      // (zeroed = pinhole = a fresh context's state)
   std::vector<gsp_medium> media;        // (empty = none = a fresh context's state)
   std::vector<gsp_medium_scatter> mediaScattering;  // ... and the scattering table parallel to it (gsp_set_media_scattering)
+  std::vector<gsp_delta_light> deltaLights;         // (empty = none = a fresh context's state)
   std::vector<uint64_t> assets;         // dormant features: texture / environment-map sizes, flags, envmap transform
 };
 

@@ -225,6 +225,9 @@ struct Scene {
   }
   std::vector<gsp_medium> media;
   std::vector<gsp_medium_scatter> mediaScattering;
+  // delta lights (gpuspectral_pt.h "Delta lights"): filled only by loadScene(..., LoadOptions{.readEmitters = true}) or by the host
+  // itself.  PathTracer sends the table (gsp_set_delta_lights) when its value changed
+  std::vector<gsp_delta_light> deltaLights;
   std::vector<std::string> warnings;  // what the loader skipped (the reference printed these to stdout)
   // the film's <rfilter>, read only with LoadOptions::readFilter: GSP_FILTER_* and its parameter (0 = the filter's default).
   // 0 = none: the renderer's own params decide.  PathTracer::render uses these when its params.pixel_filter is GSP_FILTER_NONE

@@ -66,7 +66,7 @@ void* gsph_load_scene_ex(const char* path, const char* asset_dir, int dormant, i
 // flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere),
 // 8 = readFilter (the film's <rfilter>), 16 = readLens (a thinlens sensor's aperture_radius / focus_distance),
 // 32 = readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn), 64 = readMedia (the shapes' interior media),
-// 128 = readScattering (their sigmaS / albedo and hg phase; implies 64)
+// 128 = readScattering (their sigmaS / albedo and hg phase; implies 64), 256 = readEmitters (top-level point / spot / directional emitters)
 void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned flags) {
   SceneBox* b = nullptr;
   int rc = guard([&] {
@@ -80,6 +80,7 @@ void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned fla
     opt.readFilm = (flags & 32u) != 0;
     opt.readMedia = (flags & 64u) != 0;
     opt.readScattering = (flags & 128u) != 0;
+    opt.readEmitters = (flags & 256u) != 0;
     b->scene = loadScene(path, asset_dir ? asset_dir : "", opt);
     flattenScene(b->scene, b->flat);
   });
@@ -146,6 +147,16 @@ uint32_t gsph_scene_media_scattering(void* s, float* out) {
       out[4 * k + 3] = m[k].g;
     }
   return (uint32_t)m.size();
+}
+// the scene's delta lights (LoadOptions::readEmitters / Scene::deltaLights): the count; out = one gsp_delta_light (64 B) each, may be NULL
+uint32_t gsph_scene_delta_lights(void* s, gsp_delta_light* out) {
+  const std::vector<gsp_delta_light>& l = ((SceneBox*)s)->scene.deltaLights;
+  if (out && !l.empty()) std::memcpy(out, l.data(), l.size() * sizeof(gsp_delta_light));
+  return (uint32_t)l.size();
+}
+// Scene::deltaLights = the n records at `lights` (n = 0: none)
+void gsph_scene_set_delta_lights(void* s, const gsp_delta_light* lights, uint32_t n) {
+  ((SceneBox*)s)->scene.deltaLights.assign(lights, lights + (lights ? n : 0u));
 }
 // Scene::addMedium with scattering: sigma_a (3 floats), sigma_s (3 floats), g
 uint32_t gsph_scene_add_scattering_medium(void* s, const float* sigma_a3, const float* sigma_s3, float g) {

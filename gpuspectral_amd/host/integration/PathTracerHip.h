@@ -64,6 +64,8 @@ class PathTracerHip : public RenderPassCreator {
   // name (GSP_BSDF_HANDLE_MEDIUM; 0 = none).  Context state; set it BEFORE the scene that names its entries, restart() after a change
   void setMedia(const std::vector<gsp_medium>& media) { check(gsp_set_media(ctx, media.data(), (uint32_t)media.size())); }
   // ... and their scattering coefficients (gpuspectral_pt.h "Scattering media"): a table parallel to the media, or empty = none
+  // delta lights (gpuspectral_pt.h "Delta lights"): point, spot and directional emitters beside the triangle lights; empty = none
+  void setDeltaLights(const std::vector<gsp_delta_light>& lights) { check(gsp_set_delta_lights(ctx, lights.data(), (uint32_t)lights.size())); }
   void setMediaScattering(const std::vector<gsp_medium_scatter>& scatter) { check(gsp_set_media_scattering(ctx, scatter.data(), (uint32_t)scatter.size())); }
   // light selection, opt-in (gpuspectral_pt.h "Light selection"): GSP_LIGHTS_POWER picks the NEE light by emitted power (an alias
   // table beside the lights).  Context state; restart() after a change.  The default is the reference's uniform pick

@@ -15,6 +15,8 @@
 //   --estimator reference|textbook: gsp_set_estimator (reference = the reference's weights, the default; textbook = unbiased).
 //   --scene-media: LoadOptions::readMedia (the shapes' <medium name="interior">: coloured glass, gsp_set_media).
 //   --scene-scattering: LoadOptions::readScattering (implies --scene-media; sigmaS / albedo and the hg phase: gsp_set_media_scattering).
+//   --scene-emitters: LoadOptions::readEmitters (top-level point / spot / directional emitters: gsp_set_delta_lights).
+//   --point-light X,Y,Z,R,G,B (repeatable): one more point light of that position and radiant intensity, for a scene file without an emitter element.
 //   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
 //   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
 //   --features PREFIX [--feature-spp N]: also render the feature buffers (gpuspectral_pt.h "Feature buffers"; N samples per pixel,
@@ -79,6 +81,7 @@ int main(int argc, char** argv) {
   bool focusPixel = false;
   int blades = -1;
   std::string ldrPath;
+  std::vector<gsp_delta_light> pointLights;  // --point-light, behind the scene's own (--scene-emitters)
   std::string featuresPrefix;
   int featureSpp = -1;  // (-1 = not given: the frame's spp)
   std::string denoisePath;
@@ -150,6 +153,20 @@ int main(int argc, char** argv) {
     else if (flag == "--scene-film") options.readFilm = true;
     else if (flag == "--scene-media") options.readMedia = true;
     else if (flag == "--scene-scattering") options.readScattering = true;
+    else if (flag == "--scene-emitters") options.readEmitters = true;
+    else if (flag == "--point-light" && argc > 2) {
+      float v[6];
+      int end = 0;
+      if (std::sscanf(argv[2], "%f,%f,%f,%f,%f,%f%n", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &end) != 6 || argv[2][end] != 0) {
+        std::fprintf(stderr, "gsp_render: --point-light X,Y,Z,R,G,B: a position and a radiant intensity\n");
+        return 2;
+      }
+      gsp_delta_light l{};
+      l.kind = GSP_LIGHT_POINT;
+      for (int c = 0; c < 3; ++c) l.position[c] = v[c], l.intensity[c] = v[3 + c];
+      pointLights.push_back(l);
+      used = 2;
+    }
     else if (flag == "--ldr" && argc > 2) ldrPath = argv[2], used = 2;
     else if (flag == "--features" && argc > 2) featuresPrefix = argv[2], used = 2;
     else if (flag == "--feature-spp" && argc > 2) {
@@ -438,7 +455,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--scene-scattering] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--scene-scattering] [--scene-emitters] [--point-light X,Y,Z,R,G,B]... [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -479,6 +496,7 @@ int main(int argc, char** argv) {
     if (svgfFeedback && svgfPath.empty()) throw std::runtime_error("--svgf-feedback needs --svgf out.pfm (it feeds the filter's first levels back into the history)");
     Scene scene = loadScene(argv[1], "", options);
     for (auto& w : scene.warnings) std::fprintf(stderr, "WARN: %s\n", w.c_str());
+    scene.deltaLights.insert(scene.deltaLights.end(), pointLights.begin(), pointLights.end());
     // thin lens: the scene's (--scene-lens), overridden flag by flag
     if (aperture >= 0.0f || focusDistance > 0.0f || blades >= 0 || focusPixel) {
       float fd = focusDistance > 0.0f ? focusDistance : scene.camera.getFocusDistance();

@@ -33,6 +33,7 @@ EXPORTS = (
     "gsp_set_light_sampling",
     "gsp_download_light_pick",
     "gsp_set_estimator",
+    "gsp_set_delta_lights",
     "gsp_focus_distance",
     "gsp_frame_begin",
     "gsp_render",
@@ -99,6 +100,7 @@ EXPORTS = (
     "gsp_multi_set_media_scattering",
     "gsp_multi_set_light_sampling",
     "gsp_multi_set_estimator",
+    "gsp_multi_set_delta_lights",
     "gsp_multi_update_instances",
     "gsp_multi_update_tables",
     "gsp_multi_frame_begin",
@@ -161,6 +163,8 @@ def load():
     L.gsp_multi_set_light_sampling.argtypes = [vp, u32]
     L.gsp_set_estimator.argtypes = [vp, u32]
     L.gsp_multi_set_estimator.argtypes = [vp, u32]
+    L.gsp_set_delta_lights.argtypes = [vp, C.POINTER(abi.DeltaLight), u32]
+    L.gsp_multi_set_delta_lights.argtypes = [vp, C.POINTER(abi.DeltaLight), u32]
     L.gsp_update_instances.argtypes = [vp, vp, u32]
     L.gsp_update_tables.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_ctx_destroy.argtypes = [vp]
@@ -267,8 +271,8 @@ def build_info():
 
 
 # the files csrc/Makefile hashes into the digest, in its order
-DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_render_scatter.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
-                  "pt_medium.h", "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
+DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_render_scatter.hip", "pt_render_delta.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
+                  "pt_medium.h", "pt_deltalight.h", "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -366,6 +370,12 @@ class Context:
         (r, g, b) scattering coefficients, or ((r, g, b), g) with the Henyey-Greenstein asymmetry.  None or empty = no scattering."""
         arr = abi.media_scatter_array(scatter)
         self._check(self._L.gsp_set_media_scattering(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_media_scattering")
+
+    def set_delta_lights(self, lights=None):
+        """gsp_set_delta_lights (gpuspectral_pt.h "Delta lights"): a list of abi.DeltaLight (abi.point_light, spot_light,
+        directional_light).  None or empty = no delta lights."""
+        arr = abi.delta_light_array(lights)
+        self._check(self._L.gsp_set_delta_lights(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_delta_lights")
 
     def set_estimator(self, mode):
         """gsp_set_estimator (gpuspectral_pt.h "Estimator"): "reference" / "textbook" or abi.ESTIMATOR_REFERENCE / ESTIMATOR_TEXTBOOK."""
@@ -834,6 +844,11 @@ class MultiContext:
         """gsp_multi_set_media: Context.set_media on every share."""
         arr = abi.media_array(sigmas)
         self._check(self._L.gsp_multi_set_media(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_media")
+
+    def set_delta_lights(self, lights=None):
+        """gsp_multi_set_delta_lights: Context.set_delta_lights on every share."""
+        arr = abi.delta_light_array(lights)
+        self._check(self._L.gsp_multi_set_delta_lights(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_delta_lights")
 
     def set_media_scattering(self, scatter=None):
         """gsp_multi_set_media_scattering: Context.set_media_scattering on every share."""

@@ -86,7 +86,8 @@ extern "C" {
                                 gsp_set_media, gsp_multi_set_media (see "Interior media");
                                 gsp_set_light_sampling, gsp_download_light_pick, gsp_multi_set_light_sampling (see "Light
                                 selection"); gsp_set_estimator, gsp_multi_set_estimator (see "Estimator");
-                                gsp_set_media_scattering, gsp_multi_set_media_scattering (see "Scattering media") */
+                                gsp_set_media_scattering, gsp_multi_set_media_scattering (see "Scattering media");
+                                gsp_set_delta_lights, gsp_multi_set_delta_lights (see "Delta lights") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -794,6 +795,91 @@ int gsp_download_light_pick(gsp_context* ctx, gsp_light_pick* out, uint32_t capa
 #define GSP_ESTIMATOR_TEXTBOOK 1u  /* power heuristic over the pdfs of the direction taken; unbiased */
 int gsp_set_estimator(gsp_context* ctx, uint32_t mode);
 
+/*
+ * Delta lights: opt-in point, spot and directional emitters beside the emissive triangles.
+ *
+ * Every light of the reference is an emissive triangle.  gsp_set_delta_lights(ctx, lights, count) gives the context a table of
+ * emitters WITHOUT AREA: a point light (a bulb), a spot light (a bulb behind a smooth-edged cone) and a directional light (the
+ * sun).  Only next-event estimation reaches them: no ray ever hits one, and a BSDF sample never finds one.
+ *
+ * The table is CONTEXT STATE like the media table: it holds until changed and survives gsp_upload_scene and gsp_update_tables.
+ * It may be set with a scene resident: the samples in flight finish first (the wait of every scene edit), then the tables are
+ * packed again from the context's host copy and uploaded, as gsp_set_light_sampling does.  count == 0 (or lights NULL) drops the
+ * table.  A context without delta lights runs the kernels, holds the table bytes and returns the frame it did before this section
+ * existed, bit for bit.
+ *
+ * Validation.  GSP_ERR_INVALID, and the state unchanged, when: kind is not one of the three; any field is not finite; a channel
+ * of intensity is negative; the direction of a spot or directional light is not unit within 1e-3 (|length - 1| <= 1e-3 in double;
+ * an accepted direction is renormalised in double and rounded to float32, and that is what the device reads); a spot has
+ * cos_beam <= cos_cutoff; a directional light has extent <= 0; a word of reserved is not 0.  The direction of a point light and
+ * the position of a directional light are finite and otherwise ignored.
+ *
+ * Where the records live.  The delta records (64 bytes, the size of gsp_triangle_light) sit in the light table straight behind
+ * the triangle lights, in every table version.  num_lights and 1.0f / (float)num_lights of the shading vertex count BOTH kinds,
+ * so under GSP_LIGHTS_POWER the alias table still starts at (lights + num_lights), and the records ride into LDS with the lights
+ * when the image is at most 8192 bytes.  gsp_download_light_pick reports triangles + delta records, in that order.
+ *
+ * The pick.  The shading vertex makes the three draws of the reference (r, e1, e2) and the same pick: r % num_lights, or the
+ * alias table.  An index >= the number of TRIANGLE lights names delta record (index - triangles).  e1 and e2 are then drawn and
+ * unused: the random stream of a path does not depend on the kind of light it picked.  pmf = 1.0f / (float)num_lights, or the
+ * stored pmf of the alias table.
+ *
+ * The sample, float32 in this order (p = the shading point, dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z, sqrt and the
+ * divisions IEEE):
+ *   point:        toL = position - p;   d2 = dot(toL, toL);   Ldist = sqrt(d2);   L = toL / Ldist  (per component)
+ *                 emission = intensity;   lightPdf = d2 * pmf
+ *                 d2 == 0: lightPdf = 0 (no shadow ray), L = (0, 0, 1), Ldist = 0
+ *   spot:         as point, then   c = dot(direction, -L);   t = clamp((c - cos_cutoff) / (cos_beam - cos_cutoff), 0, 1)
+ *                 s = (t * t) * (3 - 2 * t);   emission = intensity * s
+ *                 The smoothstep of the COSINE between the cutoff and the beam: no inverse trigonometric function runs on the
+ *                 device.  This is NOT Mitsuba's ramp, which is linear in the angle; inside the beam and outside the cutoff the two agree.
+ *   directional:  L = -direction;   Ldist = 1e30f;   emission = intensity (the irradiance on a plane facing the light);   lightPdf = pmf
+ * (toL points from the shading point to the light; with it the NEE term below is intensity * cos / d2.)
+ *
+ * NEE for a delta sample.  The gate is the reference's: NEE on, the BSDF sample not delta, the side tests on the geometric
+ * normal (or a transmitting BSDF), lightPdf != 0.  NoL = |dot(SN, L)|, lb = the BSDF's value for L.  The weight is 1 -- no BSDF
+ * sample can reach a delta light, so there is no second strategy to weigh against:
+ *     nee = (((NoL * lb.f) * weight) * emission) / lightPdf            (weight = the path weight of the vertex)
+ * The shadow ray runs from p along L with tmin 0.01 and tmax = Ldist - 0.01f (1e30f for a directional light: float32 absorbs the
+ * 0.01).  The directWeight that the continuing path carries to its next emitter hit when the shadow ray is unoccluded is
+ * 1.0f (GSP_ESTIMATOR_TEXTBOOK: bs.pdf, as always): what a vertex without a shadow ray hands on.  A pick that lands on a
+ * TRIANGLE light in a context with delta lights computes, operation for operation, what the vertex computed before.
+ *
+ * Emitter hits.  Delta lights are never hit.  Under GSP_ESTIMATOR_TEXTBOOK the weight of a TRIANGLE emitter that is hit uses the
+ * p_sel of the table that includes the delta records: 1.0f / (float)num_lights over both kinds, or w_hit * inv_sum_w with the sum
+ * over both kinds.
+ *
+ * Power pick weights ("Light selection"), in double, from the accepted records, BEHIND the triangle weights in the same
+ * ascending sum; Y(c) = max(0.2126 R + 0.7152 G + 0.0722 B, 0):
+ *     point:        4 pi Y(intensity)
+ *     spot:         2 pi (1 - (cos_beam + cos_cutoff) / 2) Y(intensity)
+ *     directional:  pi extent^2 Y(intensity)          extent = the radius of the scene as the power pick is to see it
+ *
+ * Media.  A medium event of "Scattering media" still takes no light sample.  A context that holds delta lights and media runs
+ * the kernels of scattering media whatever its sigma_s: a medium whose sigma_s is 0 takes the deterministic line there and draws
+ * nothing, so the frame is that of the absorbing kernels.
+ *
+ * disable_nee.  Delta lights are DARK under it: nothing but next-event estimation reaches them.  The sentence of "Estimator"
+ * that textbook frames converge to what plain path tracing converges to therefore holds for the triangle lights only.
+ *
+ * Limits.  A delta light behind a refracting or index-matched boundary stays hidden (shadow rays stop at every surface); no
+ * light sample from a medium event; no textured or goniometric emitters.
+ */
+#define GSP_LIGHT_POINT 1u
+#define GSP_LIGHT_SPOT 2u
+#define GSP_LIGHT_DIRECTIONAL 3u
+typedef struct gsp_delta_light { /* 64 B, the size of gsp_triangle_light */
+  float position[3];  /* point, spot: world position */
+  uint32_t kind;      /* GSP_LIGHT_* */
+  float direction[3]; /* spot, directional: unit, the way the light TRAVELS (the spot's axis) */
+  float cos_cutoff;   /* spot: cosine of the cutoff angle (no light outside it) */
+  float intensity[3]; /* point, spot: radiant intensity per channel; directional: irradiance on a plane facing the light */
+  float cos_beam;     /* spot: cosine of the beam width (full intensity inside it); > cos_cutoff */
+  float extent;       /* directional: radius R of the scene as the power pick sees it; > 0 */
+  float reserved[3];  /* 0 */
+} gsp_delta_light;
+int gsp_set_delta_lights(gsp_context* ctx, const gsp_delta_light* lights, uint32_t count); /* NULL or 0 = none */
+
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
 
@@ -1470,6 +1556,7 @@ int gsp_multi_update_camera(gsp_multi* m, const gsp_camera* camera);
 int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens); /* gsp_set_lens on every share */
 int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_media); /* gsp_set_media on every share */
 int gsp_multi_set_media_scattering(gsp_multi* m, const gsp_medium_scatter* scatter, uint32_t num_media); /* gsp_set_media_scattering on every share */
+int gsp_multi_set_delta_lights(gsp_multi* m, const gsp_delta_light* lights, uint32_t count); /* gsp_set_delta_lights on every share */
 int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode); /* gsp_set_light_sampling on every share */
 int gsp_multi_set_estimator(gsp_multi* m, uint32_t mode);      /* gsp_set_estimator on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);
