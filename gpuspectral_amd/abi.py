@@ -233,6 +233,16 @@ def delta_light_array(lights):
     return (DeltaLight * len(lights))(*lights) if lights else None
 
 
+# Environment light (include/gpuspectral_pt.h "Environment light")
+LIGHT_ENVIRONMENT = 4  # internal: the kind word of the environment record
+
+
+class EnvmapSampling(C.Structure):
+    """gsp_envmap_sampling, 16 B"""
+
+    _fields_ = [("enabled", C.c_uint32), ("extent", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 # Light selection (include/gpuspectral_pt.h "Light selection")
 LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1
 LIGHT_SAMPLING_NAMES = {"uniform": LIGHTS_UNIFORM, "power": LIGHTS_POWER}

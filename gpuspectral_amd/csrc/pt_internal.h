@@ -60,6 +60,14 @@ struct DeltaLaunch : ScatterLaunch {
 };
 void launch_shade_delta(const DeltaLaunch& a);
 void launch_finish_delta(const DeltaLaunch& a);
+// Environment light: the <ENV = true> instantiations, over VER x LSEL with TEX = MED = EST = SCT = DLT = true, live in
+// pt_render_envlight.hip.  The delta record as it stands (a context without textures still holds an envmap: TEX; no delta lights:
+// num_tri_lights == the records in front of the environment record) + the cell table
+struct EnvLaunch : DeltaLaunch {
+  const gsp_light_pick* env_cells;
+};
+void launch_shade_envlight(const EnvLaunch& a);
+void launch_finish_envlight(const EnvLaunch& a);
 
 #define GSP_HIP_TRY(expr)                                                                     \
   do {                                                                                        \

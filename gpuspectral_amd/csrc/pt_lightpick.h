@@ -123,21 +123,23 @@ inline float light_pick_inv_sum_from_weights(const double* w_in, uint32_t n) {
   const float r = (float)(1.0 / sum);
   return std::isfinite(r) ? r : 0.0f;
 }
-// the weights of a light table: the n triangle lights, then the nd delta lights behind them (include/gpuspectral_pt.h, "Delta lights")
-inline std::vector<double> light_pick_weights(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta, uint32_t nd) {
-  std::vector<double> w((size_t)n + nd);
+// the weights of a light table: the n triangle lights, then the nd delta lights behind them (include/gpuspectral_pt.h, "Delta lights"),
+// then the environment record's (env_w, "Environment light"; null = the table has none)
+inline std::vector<double> light_pick_weights(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta, uint32_t nd, const double* env_w = nullptr) {
+  std::vector<double> w((size_t)n + nd + (env_w ? 1u : 0u));
   for (uint32_t i = 0; i < n; ++i) w[i] = light_pick_weight(lights[i]);
   for (uint32_t i = 0; i < nd; ++i) w[(size_t)n + i] = light_pick_weight(delta[i]);
+  if (env_w) w[(size_t)n + nd] = *env_w;
   return w;
 }
-inline float light_pick_inv_sum(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta = nullptr, uint32_t nd = 0) {
-  const std::vector<double> w = light_pick_weights(lights, n, delta, nd);
-  return light_pick_inv_sum_from_weights(w.data(), n + nd);
+inline float light_pick_inv_sum(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta = nullptr, uint32_t nd = 0, const double* env_w = nullptr) {
+  const std::vector<double> w = light_pick_weights(lights, n, delta, nd, env_w);
+  return light_pick_inv_sum_from_weights(w.data(), (uint32_t)w.size());
 }
 
-inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta, uint32_t nd, gsp_light_pick* out) {
-  const std::vector<double> w = light_pick_weights(lights, n, delta, nd);
-  build_light_pick_from_weights(w.data(), n + nd, out);
+inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, const gsp_delta_light* delta, uint32_t nd, gsp_light_pick* out, const double* env_w = nullptr) {
+  const std::vector<double> w = light_pick_weights(lights, n, delta, nd, env_w);
+  build_light_pick_from_weights(w.data(), (uint32_t)w.size(), out);
 }
 inline void build_light_pick(const gsp_triangle_light* lights, uint32_t n, gsp_light_pick* out) { build_light_pick(lights, n, nullptr, 0, out); }
 

@@ -165,6 +165,17 @@ struct gsp_context {
   // delta lights (gsp_set_delta_lights): context state like the media, as accepted (directions renormalised).  Not empty selects the
   // <DLT> kernels of pt_render_delta.hip and makes pack_tables append the records behind the triangle lights of every table image
   std::vector<gsp_delta_light> h_delta;
+  // the environment light (gsp_set_envmap_sampling): the switch is context state like the delta lights.  env_light = it is on AND the
+  // resident scene has an envmap: selects the <ENV> kernels of pt_render_envlight.hip and makes pack_tables append the record behind
+  // the delta records of every table image.  The cell table and the radiant sum are scene state (made at upload, or when the switch
+  // is first turned on under a resident scene), one copy beside the table versions
+  gsp_envmap_sampling env_sampling{};
+  bool env_light = false;
+  std::vector<gsp_light_pick> h_env_cells;
+  DevBuf<gsp_light_pick> env_cells;
+  uint32_t env_cw = 0, env_ch = 0;
+  double env_radiant = 0.0;         // sum over texels of Y * solid angle
+  float env_light_to_local[16] = {};  // the frame the record's inverse is formed from (the scene's, known before upload_textures runs)
   // light selection (gsp_set_light_sampling): context state like the lens.  GSP_LIGHTS_POWER selects the <LSEL> kernels and makes
   // pack_tables append the alias table behind the light records of every table image
   uint32_t light_mode = GSP_LIGHTS_UNIFORM;

@@ -381,8 +381,10 @@ constexpr int kShadeWaves = kShadeBlock / 64;
 // SceneViewSct::scatter, read like the media table.  These instantiations live in pt_render_scatter.hip
 // DLT: the context holds delta lights (gsp_set_delta_lights): shade_vertex<.., DLT = true> and SceneViewDlt::num_tri_lights; the
 // records sit behind the triangle lights in the table image.  These instantiations live in pt_render_delta.hip
-template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false>
-__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED, SCT, DLT>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
+// ENV: the context samples its environment map as a light (gsp_set_envmap_sampling): shade_vertex<.., ENV = true>, miss_emitted_env
+// and SceneViewEnv::env_cells; the record is the last of the light table.  These instantiations live in pt_render_envlight.hip
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false, bool ENV = false>
+__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED, SCT, DLT, ENV>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
                                                         const q4* __restrict__ hits, PathQueue nxt, ShadowQueue sq,
                                                         q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                         uint32_t* __restrict__ live,
@@ -531,7 +533,7 @@ __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typen
         in.weight = mk3(p2.x, p2.y, p2.z);
         in.directWeight = p2.w;
         in.flags = fl;
-        shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S));
+        shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT, ENV>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S), view_env_cells(S));
         alive = out.alive;
         has_shadow = out.has_shadow;
         ++shaded;
@@ -541,6 +543,11 @@ __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typen
         PathState in;
         in.d = mk3(p0.w, p1.x, p1.y);
         in.weight = mk3(p2.x, p2.y, p2.z);
+        if constexpr (ENV) {
+          in.directWeight = p2.w;
+          in.flags = fl;
+          add_emitted(rc.clamp, miss_emitted_env<VER>(S, rc, in, view_env_cells(S)), sum);
+        } else
         add_emitted(rc.clamp, miss_emitted(S, in), sum);
       }
       // the path ends here and no shadow ray is pending: its sum is the sample
@@ -686,8 +693,8 @@ struct FinishStack {
   __device__ __forceinline__ uint32_t pop() { return col[(--top) * kBlock]; }
 };
 
-template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false>
-__global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT, DLT>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false, bool ENV = false>
+__global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT, DLT, ENV>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
                                                     q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                     uint32_t* __restrict__ live,
                                                     uint32_t slot_paths, DevStats* __restrict__ stats) {
@@ -740,11 +747,12 @@ __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT
         }
       }
       if (!hit) {  // miss.rmiss:15-18
-        if (TEX && S.tex.env_texels != nullptr) add_emitted(rc.clamp, miss_emitted(S, in), res);
+        if constexpr (ENV) add_emitted(rc.clamp, miss_emitted_env<VER>(S, rc, in, view_env_cells(S)), res);
+        else if (TEX && S.tex.env_texels != nullptr) add_emitted(rc.clamp, miss_emitted(S, in), res);
         break;
       }
       ShadeOut out;
-      shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S));
+      shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT, ENV>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S), view_env_cells(S));
       ++shaded;
       if (!out.has_shadow) {
         add_emitted(rc.clamp, out.emitted, res);

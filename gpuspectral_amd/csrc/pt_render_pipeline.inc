@@ -191,6 +191,14 @@ static DeltaLaunch delta_launch(const gsp_context* ctx, const TextbookLaunch& t)
   a.num_tri_lights = ctx->num_tri_lights;
   return a;
 }
+// ... and <.., ENV = true>, the kernels of a context that samples its environment map as a light (gsp_set_envmap_sampling with an envmap
+// resident; always textured, always the textbook estimator), handed to pt_render_envlight.hip: the delta record + the cell table
+static EnvLaunch env_launch(const gsp_context* ctx, const TextbookLaunch& t) {
+  EnvLaunch a{};
+  static_cast<DeltaLaunch&>(a) = delta_launch(ctx, t);
+  a.env_cells = ctx->env_cells.p;
+  return a;
+}
 }  // extern "C++"
 
 // The blocks of k_shade a device holds at once: the largest grid (a block loops over tiles), each may leave one room chunk of fillers.
@@ -293,11 +301,12 @@ static int finish_few_paths(gsp_context* ctx, gsp_context::Lane& L, const Render
   if (!(drain && L.queued == 0 && P.remaining == 0 && P.n > 0 && P.n <= ctx->finish_paths && ctx->pipe_params.collect_traversal_stats == 0 &&
         std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 <= kFinishLevels))
     return GSP_OK;
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty()) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty() || ctx->env_light) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, L.stream, (uint32_t)((P.n + kBlock - 1) / kBlock), lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq),
                                        L.counters.p + C_LIVE, (uint32_t)P.batch_paths);
     a.n = (uint32_t)P.n;
-    if (!ctx->h_delta.empty()) launch_finish_delta(delta_launch(ctx, a));
+    if (ctx->env_light) launch_finish_envlight(env_launch(ctx, a));
+    else if (!ctx->h_delta.empty()) launch_finish_delta(delta_launch(ctx, a));
     else if (ctx->scatter_on) launch_finish_scatter(scatter_launch(ctx, a));
     else launch_finish_textbook(a);
   } else
@@ -368,14 +377,15 @@ static int trace_shade_connect(gsp_context* ctx, gsp_context::Lane& L, const Ren
   CTX_TRY(ctx, hipGetLastError());
   if (ev) CTX_TRY(ctx, hipEventRecord(ev[1], st));
   const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + kShadeBlock - 1) / kShadeBlock, shade_resident_blocks(ctx))));
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty()) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty() || ctx->env_light) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, st, grid.x, cur, L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths);
     a.n_ptr = n_ptr;
     a.hits = hits;
     a.next[0] = next.P0, a.next[1] = next.P1, a.next[2] = next.P2, a.next[3] = next.P3;
     a.shadow[0] = sq.S0, a.shadow[1] = sq.S1, a.shadow[2] = sq.S3;
     a.chunk = room_chunk;
-    if (!ctx->h_delta.empty()) launch_shade_delta(delta_launch(ctx, a));
+    if (ctx->env_light) launch_shade_envlight(env_launch(ctx, a));
+    else if (!ctx->h_delta.empty()) launch_shade_delta(delta_launch(ctx, a));
     else if (ctx->scatter_on) launch_shade_scatter(scatter_launch(ctx, a));
     else launch_shade_textbook(a);
   } else
@@ -1312,11 +1322,11 @@ int gsp_set_lens(gsp_context* ctx, const gsp_lens* lens_host) {
   return GSP_OK;
 }
 
-// A context with delta lights runs the <MED, SCT, DLT> kernels whatever its media (pt_render_delta.hip).  Where it holds media but
+// A context with delta lights (or the environment light switched on) runs the <MED, SCT, DLT> kernels whatever its media (pt_render_delta.hip, pt_render_envlight.hip).  Where it holds media but
 // no scattering table, those kernels read one of zeros from the table's device buffer: every medium then takes the deterministic
 // line of the absorbing kernels.  Called behind every change of the three tables, under a drained pipeline.
 static int sync_absorbing_scatter_table(gsp_context* ctx) {
-  if (ctx->h_delta.empty() || ctx->num_media == 0 || !ctx->h_scatter.empty()) return GSP_OK;
+  if ((ctx->h_delta.empty() && ctx->env_sampling.enabled == 0u) || ctx->num_media == 0 || !ctx->h_scatter.empty()) return GSP_OK;
   const std::vector<gsp_medium_scatter> zeros(ctx->num_media, gsp_medium_scatter{{0.0f, 0.0f, 0.0f}, 0.0f});
   CTX_TRY(ctx, ctx->scatter.upload(zeros.data(), zeros.size(), ctx->stream, &ctx->bytes));
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (`zeros` goes out of scope; the lanes' streams read the table)
@@ -1432,6 +1442,10 @@ int gsp_set_estimator(gsp_context* ctx, uint32_t mode) {
   int rc = drain_for_edit(ctx);  // the samples in flight carry the directWeight / lastPdf of the mode as it was
   if (rc != GSP_OK) return rc;
   if (mode == ctx->estimator) return GSP_OK;
+  if (mode == GSP_ESTIMATOR_REFERENCE && ctx->env_sampling.enabled != 0u) {
+    ctx->err = "gsp_set_estimator: envmap sampling is on, and the environment light exists under GSP_ESTIMATOR_TEXTBOOK only";
+    return GSP_ERR_INVALID;
+  }
   const uint32_t old_mode = ctx->estimator;
   ctx->estimator = mode;
   if (ctx->light_mode != GSP_LIGHTS_POWER) return GSP_OK;  // (the tables of a uniform-pick context are the same in both modes)
@@ -1463,6 +1477,52 @@ int gsp_set_delta_lights(gsp_context* ctx, const gsp_delta_light* lights, uint32
   if (rc != GSP_OK) {
     ctx->h_delta.swap(accepted);
     return rc;
+  }
+  return sync_absorbing_scatter_table(ctx);
+}
+
+// ---- environment light (include/gpuspectral_pt.h, "Environment light") ----
+int gsp_set_envmap_sampling(gsp_context* ctx, const gsp_envmap_sampling* sampling) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (const char* why = check_envmap_sampling(sampling)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  gsp_envmap_sampling want{};
+  if (sampling && sampling->enabled != 0u) want.enabled = 1u, want.extent = sampling->extent;
+  if (want.enabled != 0u && ctx->estimator != GSP_ESTIMATOR_TEXTBOOK) {
+    ctx->err = "gsp_set_envmap_sampling: the environment light exists under GSP_ESTIMATOR_TEXTBOOK only (gsp_set_estimator first)";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight read the light table as it was
+  if (rc != GSP_OK) return rc;
+  if (std::memcmp(&want, &ctx->env_sampling, sizeof(want)) == 0) return GSP_OK;
+  const bool with_map = ctx->have_scene && ctx->env_width != 0u;
+  const bool on = want.enabled != 0u && with_map;
+  if (on && !env_frame_is_rotation(ctx->env_to_local)) {
+    ctx->err = "gsp_set_envmap_sampling: the upper 3x3 of the resident envmap's to_local is not orthonormal within 1e-4";
+    return GSP_ERR_INVALID;
+  }
+  if (on && ctx->h_env_cells.empty()) {  // the scene came before the switch: its texels come back from the device once
+    std::vector<float> texels(4ull * ctx->env_width * ctx->env_height);
+    CTX_TRY(ctx, hipMemcpyAsync(texels.data(), ctx->env_texels.p, texels.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    rc = build_env_light(ctx, texels.data(), ctx->env_width, ctx->env_height, ctx->env_to_local);
+    if (rc != GSP_OK) return rc;
+    CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  const gsp_envmap_sampling old = ctx->env_sampling;
+  const bool old_on = ctx->env_light;
+  ctx->env_sampling = want;
+  ctx->env_light = on;
+  if (on || old_on) {
+    rc = repack_resident_tables(ctx);  // with or without the record behind the delta records
+    if (rc != GSP_OK) {
+      ctx->env_sampling = old;
+      ctx->env_light = old_on;
+      return rc;
+    }
   }
   return sync_absorbing_scatter_table(ctx);
 }

@@ -76,12 +76,15 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
                         sc->rough_conductor_bsdfs, sc->smooth_floor_bsdfs, sc->rough_floor_bsdfs, sc->rough_plastic_bsdfs, sc->lights};
   size_t bytes[9];
   uint64_t counts[9];
-  const uint32_t num_delta = (uint32_t)ctx->h_delta.size(), all_lights = sc->num_lights + num_delta;
-  if (all_lights < num_delta) {
+  // ... and the environment record (gsp_set_envmap_sampling with an envmap resident) behind those, the last of the light table
+  const uint32_t num_delta = (uint32_t)ctx->h_delta.size(), num_env = ctx->env_light ? 1u : 0u, all_lights = sc->num_lights + num_delta + num_env;
+  if (all_lights < num_delta + num_env || sc->num_lights + num_delta < num_delta) {
     ctx->err = "too many lights";
     return GSP_ERR_SCENE;
   }
-  const size_t delta_bytes = sizeof(gsp_delta_light) * (size_t)num_delta;
+  const size_t delta_bytes = sizeof(gsp_delta_light) * (size_t)num_delta, env_bytes = sizeof(EnvLightRecord) * (size_t)num_env;
+  const double env_w = num_env ? env_power_weight(ctx->env_radiant, ctx->env_sampling.extent) : 0.0;
+  const double* env_wp = num_env ? &env_w : nullptr;
   img.total = 0;
   for (int k = 0; k < 9; ++k) {
     counts[k] = k < 8 ? sc->num_bsdfs[k] : sc->num_lights;
@@ -96,7 +99,7 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
     img.off[k] = img.total;
     img.total += (bytes[k] + 15) & ~(size_t)15;
   }
-  img.total += delta_bytes;  // (behind the triangle lights, the last of the nine: 64-B records, no padding)
+  img.total += delta_bytes + env_bytes;  // (behind the triangle lights, the last of the nine: 64-B records, no padding)
   // GSP_LIGHTS_POWER: a tenth sub-table, the alias table of the lights (pt_lightpick.h), straight behind the light records (64 B
   // each: no padding in between), so that (const gsp_light_pick*)(lights + num_lights) finds it.  Absent in uniform mode: such a
   // context keeps the image size, and so the LDS staging decision, it always had
@@ -113,10 +116,16 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
   for (int k = 0; k < 9; ++k)
     if (bytes[k]) std::memcpy(img.bytes.data() + TableImage::kHead + img.off[k], src[k], bytes[k]);
   if (delta_bytes) std::memcpy(img.bytes.data() + TableImage::kHead + img.off[8] + bytes[8], ctx->h_delta.data(), delta_bytes);
-  if (pick) build_light_pick(sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta, (gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off));
+  if (pick) build_light_pick(sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta, (gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off), env_wp);
   if (tail) {
-    const float inv_sum_w = light_pick_inv_sum(sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta);
+    const float inv_sum_w = light_pick_inv_sum(sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta, env_wp);
     std::memcpy(img.bytes.data() + TableImage::kHead + tail_off, &inv_sum_w, sizeof(float));
+  }
+  if (num_env) {  // p_sel: what the table of the context's mode implies for the record -- 1 / n, or the mass of its entry of the alias table
+    float p_sel = 1.0f / (float)all_lights;
+    if (pick) p_sel = ((const gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off))[all_lights - 1u].pmf_self;
+    const EnvLightRecord rec = make_env_record(ctx->env_light_to_local, ctx->env_cw, ctx->env_ch, p_sel);
+    std::memcpy(img.bytes.data() + TableImage::kHead + img.off[8] + bytes[8] + delta_bytes, &rec, sizeof(rec));
   }
   return GSP_OK;
 }
@@ -144,7 +153,7 @@ static int upload_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage&
   for (int k = 0; k < 9; ++k) ctx->table_off[k] = img.off[k];
   ctx->tables_bytes = img.total;
   ctx->num_tri_lights = sc->num_lights;
-  ctx->num_lights = sc->num_lights + (uint32_t)ctx->h_delta.size();  // (the delta records need no bake: they are resident as accepted)
+  ctx->num_lights = sc->num_lights + (uint32_t)ctx->h_delta.size() + (ctx->env_light ? 1u : 0u);  // (the delta and environment records need no bake: they are resident as packed)
   for (int k = 0; k < GSP_BSDF_TYPE_COUNT; ++k) ctx->num_bsdfs[k] = sc->num_bsdfs[k];
   // the resident light and diffuse records carry what a vertex would compute from them alone (pt_shading.h bake_light / bake_diffuse)
   uint32_t nb = sc->num_lights;
@@ -518,6 +527,18 @@ static int upload_textures(gsp_context* ctx, const gsp_scene_desc* sc) {
   return GSP_OK;
 }
 
+// The environment light's scene state (include/gpuspectral_pt.h, "Environment light") from the map's texels on the host: the cell
+// table (host copy and device), the radiant sum of the power weight, the frame.  The caller has checked the frame
+static int build_env_light(gsp_context* ctx, const float* texels, uint32_t width, uint32_t height, const float* to_local) {
+  const std::vector<double> w = env_cell_weights(texels, width, height, ctx->env_cw, ctx->env_ch);
+  ctx->h_env_cells.assign(w.size(), gsp_light_pick{});
+  build_light_pick_from_weights(w.data(), (uint32_t)w.size(), ctx->h_env_cells.data());
+  ctx->env_radiant = env_radiant_sum(texels, width, height);
+  for (int k = 0; k < 16; ++k) ctx->env_light_to_local[k] = to_local[k];
+  CTX_TRY(ctx, ctx->env_cells.upload(ctx->h_env_cells.data(), ctx->h_env_cells.size(), ctx->stream, &ctx->bytes));  // (h_env_cells stays alive)
+  return GSP_OK;
+}
+
 int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
   if (!ctx || !sc) return GSP_ERR_INVALID;
   CTX_TRY(ctx, hipSetDevice(ctx->device));
@@ -534,6 +555,18 @@ int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
   rc = check_scene(ctx, sc, &total_tris);
   if (rc != GSP_OK) return rc;
   auto t0 = std::chrono::steady_clock::now();
+  // the environment light: on for this scene when the switch is and the scene has a map; its record goes into the tables below
+  ctx->env_light = false;
+  ctx->h_env_cells.clear();
+  if (ctx->env_sampling.enabled != 0u && sc->envmap.texels != nullptr) {
+    if (!env_frame_is_rotation(sc->envmap.to_local)) {
+      ctx->err = "environment map: envmap sampling is on and the upper 3x3 of to_local is not orthonormal within 1e-4";
+      return GSP_ERR_SCENE;
+    }
+    rc = build_env_light(ctx, sc->envmap.texels, sc->envmap.width, sc->envmap.height, sc->envmap.to_local);
+    if (rc != GSP_OK) return rc;
+    ctx->env_light = true;
+  }
   {
     TableImage img;
     rc = pack_tables(ctx, sc, img);
@@ -805,7 +838,7 @@ int gsp_update_tables(gsp_context* ctx, const gsp_scene_desc* sc) {
   // re-reads the tables every frame; a host that edits a material every frame keeps the path pool full now,
   // profiles/r05_update_latency.txt.)  Otherwise -- another layout, or kTableVersions edits within the life of one sample --
   // the queued samples finish first, as until r04.
-  bool same_layout = ctx->pipe_active && sc->num_lights == ctx->num_tri_lights && sc->num_lights + ctx->h_delta.size() == ctx->num_lights && img.total == ctx->tables_bytes && ctx->tables.p != nullptr;
+  bool same_layout = ctx->pipe_active && sc->num_lights == ctx->num_tri_lights && sc->num_lights + ctx->h_delta.size() + (ctx->env_light ? 1u : 0u) == ctx->num_lights && img.total == ctx->tables_bytes && ctx->tables.p != nullptr;
   for (int k = 0; k < GSP_BSDF_TYPE_COUNT && same_layout; ++k) same_layout = sc->num_bsdfs[k] == ctx->num_bsdfs[k];
   size_t free_b = 0, total_b = 0;
   if (same_layout && ctx->tab.slots == 1) CTX_TRY(ctx, hipMemGetInfo(&free_b, &total_b));  // (only the decision to grow asks)

@@ -16,6 +16,7 @@
 // shade pass hands both terms to the connect pass, which forms the same sum.
 #pragma once
 #include "pt_deltalight.h"
+#include "pt_envlight.h"
 #include "pt_medium.h"
 #include "pt_shading.h"
 #include "pt_trace.h"
@@ -99,20 +100,29 @@ struct SceneViewSct : SceneViewMed {
 struct SceneViewDlt : SceneViewSct {
   uint32_t num_tri_lights = 0;
 };
-template <bool MED, bool SCT = false, bool DLT = false>
+// ... and the <ENV = true> ones (gsp_set_envmap_sampling with an envmap resident): + the cell table of the environment light
+// (pt_envlight.h), scene state beside the table versions.  The record that names its size is the LAST of the light table
+struct SceneViewEnv : SceneViewDlt {
+  const gsp_light_pick* env_cells = nullptr;
+};
+template <bool MED, bool SCT = false, bool DLT = false, bool ENV = false>
 struct ShadeViewOf {
   using type = SceneView;
 };
 template <bool MED, bool SCT>
-struct ShadeViewOf<MED, SCT, true> {
+struct ShadeViewOf<MED, SCT, true, false> {
   using type = SceneViewDlt;
 };
+template <bool MED, bool SCT>
+struct ShadeViewOf<MED, SCT, true, true> {
+  using type = SceneViewEnv;
+};
 template <>
-struct ShadeViewOf<true, false> {
+struct ShadeViewOf<true, false, false, false> {
   using type = SceneViewMed;
 };
 template <>
-struct ShadeViewOf<true, true> {
+struct ShadeViewOf<true, true, false, false> {
   using type = SceneViewSct;
 };
 GSP_HD const gsp_medium* view_media(const SceneView&) { return nullptr; }
@@ -121,6 +131,8 @@ GSP_HD const gsp_medium_scatter* view_scatter(const SceneView&) { return nullptr
 GSP_HD const gsp_medium_scatter* view_scatter(const SceneViewSct& v) { return v.scatter; }
 GSP_HD uint32_t view_tri_lights(const SceneView&) { return 0u; }
 GSP_HD uint32_t view_tri_lights(const SceneViewDlt& v) { return v.num_tri_lights; }
+GSP_HD const gsp_light_pick* view_env_cells(const SceneView&) { return nullptr; }
+GSP_HD const gsp_light_pick* view_env_cells(const SceneViewEnv& v) { return v.env_cells; }
 
 // path flags word: depth [0,7] | wasDelta << 8 | countEmitted << 9 | table version << 10 [10,15] | geometry version << 16 [16,21]
 GSP_HD uint32_t pack_flags(uint32_t depth, uint32_t wasDelta, uint32_t countEmitted) {
@@ -353,11 +365,17 @@ struct ShadeOut {
 // pick; an index >= num_tri_lights takes sample_delta_light (pt_deltalight.h) and an NEE term without the power heuristic, a
 // smaller one the triangle's operations as they stand.  DLT = false is the code of a context without delta lights, instruction for
 // instruction.
-template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false, bool SCT = false, bool DLT = false>
+// ENV (only with TEX, EST and DLT): the context samples its environment map as a light (include/gpuspectral_pt.h, "Environment
+// light"): the LAST record of the light table is the EnvLightRecord, `env_cells` its cell table.  The same three draws and the same
+// pick; a pick that lands on the record draws one further word, picks a cell and takes sample_env_light (pt_envlight.h) and the
+// triangle's textbook NEE term with Ldist = 1e30f.  ENV = false is the code of a context without the switch, instruction for
+// instruction.
+template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false, bool SCT = false, bool DLT = false, bool ENV = false>
 GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
                          ShadeOut& out, const gsp_medium* media = nullptr, const gsp_medium_scatter* scatter = nullptr,
-                         uint32_t num_tri_lights = 0u) {
+                         uint32_t num_tri_lights = 0u, const gsp_light_pick* env_cells = nullptr) {
   static_assert(MED || !SCT, "the scattering table is parallel to the media table");
+  static_assert(!ENV || (TEX && EST && DLT), "the environment light lives in the textbook estimator, behind the delta records");
   uint32_t rng = in.seed;                                                 // rchit:668
   BsdfTables Tv;  // (VER only: this lane's version of the tables)
   const gsp_triangle_light* lights_v = nullptr;
@@ -484,8 +502,25 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
     const float e2 = rand_uniform(rng);
     float pmf = S.inv_num_lights;
     const uint32_t k = LSEL ? light_pick_index((const gsp_light_pick*)(lights + S.num_lights), S.num_lights, r, pmf) : r % S.num_lights;
-    delta_light = k >= num_tri_lights;
-    if (delta_light) {  // (e1, e2: drawn and unused)
+    const bool env_light = ENV && k == S.num_lights - 1u;  // (ENV only) the pick landed on the environment record, the last one
+    delta_light = !env_light && k >= num_tri_lights;
+    if constexpr (ENV) {
+      if (env_light && rc.nee != 0u) {  // one further draw picks the cell; (e1, e2) place the direction inside it
+        const uint32_t r2 = pcg_next(rng);
+        const EnvSample es = sample_env_light(S.tex, env_cells, *(const EnvLightRecord*)(lights + k), r2, e1, e2);
+        L = es.L;
+        Ldist = 1e30f;
+        ls.emission = es.emission;
+        ls.pdf = es.pdf;
+      } else if (env_light) {  // disable_nee: no light sample is used, so none is made and the random stream is that of the switch off
+        L = mk3(0.0f, 0.0f, 1.0f);
+        Ldist = 1e30f;
+        ls.emission = splat(0.0f);
+        ls.pdf = 0.0f;
+      }
+    }
+    if (env_light) {
+    } else if (delta_light) {  // (e1, e2: drawn and unused)
       const DeltaSample ds = sample_delta_light(*(const gsp_delta_light*)(lights + k), position, pmf);
       L = ds.L;
       Ldist = ds.Ldist;
@@ -612,6 +647,20 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
 // map along its direction.  MIS: sampleLight never draws the environment, so the weight is the one an emitter met after a
 // delta bounce gets (rayhit.rchit:766-768): the full path weight.
 GSP_HD f3 miss_emitted(const SceneView& S, const PathState& in) { return sample_envmap(S.tex, in.d) * in.weight; }
+// ... in a context that samples the environment as a light (include/gpuspectral_pt.h, "Environment light"; `in` complete: flags and
+// directWeight = lastPdf too): an escape that next-event estimation could have produced -- NEE on, countEmitted == 0, wasDelta == 0
+// -- is weighted against the density of its own direction, from the function the sampling side called; every other escape adds the
+// full weight as above.  The record is read from the path's version of the tables
+template <bool VER>
+GSP_HD f3 miss_emitted_env(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const gsp_light_pick* env_cells) {
+  const gsp_triangle_light* lights = VER ? (const gsp_triangle_light*)((const char*)S.lights + (size_t)((in.flags & kVerMask) >> kVerShift) * S.ver_stride) : S.lights;
+  const EnvLightRecord& rec = *(const EnvLightRecord*)(lights + (S.num_lights - 1u));
+  const EnvEval ev = env_eval(S.tex, env_cells, rec.cw, rec.ch, in.d);
+  const uint32_t wasDelta = (in.flags >> 8) & 1u;
+  const uint32_t countEmitted = (in.flags >> 9) & 1u;
+  if (rc.nee != 0u && countEmitted == 0u && wasDelta == 0u) return (ev.radiance * power_heuristic(in.directWeight, ev.density * rec.p_sel)) * in.weight;
+  return ev.radiance * in.weight;
+}
 
 // rayhit.rchit:750-754 + raygen.rgen:60-63 for a vertex that traced a shadow ray
 GSP_HD void connect_vertex(float clampv, const ShadowRay& s, bool occluded, q4& result, bool& nee_done) {

@@ -71,6 +71,10 @@ def load():
     L.gsph_scene_delta_lights.argtypes = [vp, vp]
     L.gsph_scene_set_delta_lights.restype = None
     L.gsph_scene_set_delta_lights.argtypes = [vp, C.POINTER(abi.DeltaLight), u32]
+    L.gsph_scene_envmap_sampling.restype = u32
+    L.gsph_scene_envmap_sampling.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gsph_scene_set_envmap_sampling.restype = None
+    L.gsph_scene_set_envmap_sampling.argtypes = [vp, u32, C.c_float]
     L.gsph_scene_add_scattering_medium.restype = u32
     L.gsph_scene_add_scattering_medium.argtypes = [vp, vp, vp, C.c_float]
     L.gsph_scene_object_medium.restype = u32
@@ -149,7 +153,7 @@ class Scene:
     """A C++ GPUSpectral::Scene produced by loadScene (S/engine/Loader.cpp:253-349)."""
 
     def __init__(self, path, asset_dir=None, dormant_features=False, srgb_textures=True, builtin_shapes=False, read_filter=False,
-                 read_lens=False, read_film=False, read_media=False, read_scattering=False, read_emitters=False):
+                 read_lens=False, read_film=False, read_media=False, read_scattering=False, read_emitters=False, sample_envmap=False):
         """dormant_features: LoadOptions::dormantFeatures (textures / environment map, SURVEY 8(f).3); builtin_shapes:
         LoadOptions::builtinShapes (`disk` and `sphere` shapes are built instead of skipped, SURVEY 8(f).1); the defaults are
         the reference's behaviour.  read_filter: LoadOptions::readFilter (the film's <rfilter> becomes `pixel_filter`, which
@@ -158,14 +162,15 @@ class Scene:
         LoadOptions::readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn become `film`).  read_media:
         LoadOptions::readMedia (the shapes' <medium name="interior"> become `media` and the objects' medium numbers: coloured glass).
         read_scattering: LoadOptions::readScattering (implies read_media; sigmaS / albedo and the hg phase become `media_scattering`).
-        read_emitters: LoadOptions::readEmitters (top-level point / spot / directional emitters become `delta_lights`)."""
+        read_emitters: LoadOptions::readEmitters (top-level point / spot / directional emitters become `delta_lights`).
+        sample_envmap: LoadOptions::sampleEnvmap (`envmap_sampling` = on, with the radius of the scene's bounds as its extent)."""
         self._L = load()
         ad = asset_dir.encode() if asset_dir else None
-        if builtin_shapes or read_filter or read_lens or read_film or read_media or read_scattering or read_emitters:
+        if builtin_shapes or read_filter or read_lens or read_film or read_media or read_scattering or read_emitters or sample_envmap:
             self._h = self._L.gsph_load_scene_opts(path.encode(), ad, (1 if dormant_features else 0) | (2 if srgb_textures else 0) |
                                                    (4 if builtin_shapes else 0) | (8 if read_filter else 0) | (16 if read_lens else 0) |
                                                    (32 if read_film else 0) | (64 if read_media else 0) |
-                                                   (128 if read_scattering else 0) | (256 if read_emitters else 0))
+                                                   (128 if read_scattering else 0) | (256 if read_emitters else 0) | (512 if sample_envmap else 0))
         elif dormant_features:
             self._h = self._L.gsph_load_scene_ex(path.encode(), ad, 1, 1 if srgb_textures else 0)
         else:
@@ -235,6 +240,17 @@ class Scene:
         if n:
             self._L.gsph_scene_delta_lights(self._h, out)
         return list(out)[:n]
+
+    @property
+    def envmap_sampling(self):
+        """Scene::envmapSampling as (enabled, extent); (False, 0.0) without sample_envmap / set_envmap_sampling."""
+        extent = C.c_float(0.0)
+        on = self._L.gsph_scene_envmap_sampling(self._h, C.byref(extent))
+        return bool(on), float(extent.value)
+
+    def set_envmap_sampling(self, enabled=True, extent=1.0):
+        """Scene::envmapSampling (PathTracer sends the switch when its value changed; the tracer must run the textbook estimator)."""
+        self._L.gsph_scene_set_envmap_sampling(self._h, 1 if enabled else 0, extent)
 
     def set_delta_lights(self, lights):
         """Scene::deltaLights = the abi.DeltaLight records of `lights` (PathTracer sends the table when its value changed)."""

@@ -972,6 +972,10 @@ Scene loadScene(const std::string& path, const std::string& assetDirArg, const L
     for (gsp_delta_light& l : outScene.deltaLights)
       if (l.kind == GSP_LIGHT_DIRECTIONAL) l.extent = extent;
   }
+  if (options.sampleEnvmap) {  // the environment light: the switch, with the radius of the scene's bounds as the power pick is to see it
+    outScene.envmapSampling.enabled = 1u;
+    outScene.envmapSampling.extent = sceneExtent(outScene);
+  }
   return outScene;
 }
 

@@ -66,6 +66,11 @@ struct LoadOptions {
   // A `scale` multiplies the intensity / irradiance.  Every other emitter type keeps its warning.  false: the scene and its warnings are
   // what they were before this option existed.
   bool readEmitters = false;
+  // sampleEnvmap = true switches the environment light on (include/gpuspectral_pt.h "Environment light"): Scene::envmapSampling =
+  // {enabled, extent = half the diagonal of the world-space bounding box of the scene's vertices (1 for a scene without any)}.  It
+  // takes effect only for a scene that carries an environment map (dormantFeatures) and needs GSP_ESTIMATOR_TEXTBOOK.  false: the
+  // scene is what it was before this option existed.
+  bool sampleEnvmap = false;
 };
 
 // assetDir: where rect.obj / box.obj / disk.obj live (Engine::assetPath); "" = the

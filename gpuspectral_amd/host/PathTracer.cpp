@@ -86,6 +86,11 @@ bool SceneTracker::deltaLightsChanged(const Scene& scene) const {
          (!deltaLights.empty() && std::memcmp(scene.deltaLights.data(), deltaLights.data(), deltaLights.size() * sizeof(gsp_delta_light)) != 0);
 }
 
+bool SceneTracker::envmapSamplingChanged(const Scene& scene) const {
+  if (scene.envmapSampling.enabled == 0u && envmapSampling.enabled == 0u) return false;  // (off is off, whatever the other words hold)
+  return std::memcmp(&scene.envmapSampling, &envmapSampling, sizeof(gsp_envmap_sampling)) != 0;
+}
+
 // the media table, and behind it the scattering table parallel to it (gsp_set_media with another count drops the device's).  Returns
 // gsp_set_media's code (it may refuse to shrink the table under the resident scene: the caller tries again behind the scene)
 template <class SetMedia, class SetScattering>
@@ -174,6 +179,10 @@ void PathTracer::prepareScene(const Scene& scene) {
   if (tracker.deltaLightsChanged(scene)) {  // (context state too: it waits for the samples in flight and repacks the resident tables)
     check(gsp_set_delta_lights(ctx, scene.deltaLights.data(), (uint32_t)scene.deltaLights.size()), "gsp_set_delta_lights");
     tracker.rememberDeltaLights(scene);
+  }
+  if (tracker.envmapSamplingChanged(scene)) {  // (the environment light: context state as well; refused under the reference estimator)
+    check(gsp_set_envmap_sampling(ctx, &scene.envmapSampling), "gsp_set_envmap_sampling");
+    tracker.rememberEnvmapSampling(scene);
   }
   // the media table goes BEFORE a scene that names more entries than the device holds and AFTER one that names fewer than the
   // resident scene does (gsp_set_media refuses to shrink the table under it): tried first, and again behind the scene if refused
@@ -488,6 +497,10 @@ void MultiGpuPathTracer::prepareScene(const Scene& scene) {
   if (tracker.deltaLightsChanged(scene)) {
     check(gsp_multi_set_delta_lights(multi, scene.deltaLights.data(), (uint32_t)scene.deltaLights.size()), "gsp_multi_set_delta_lights");
     tracker.rememberDeltaLights(scene);
+  }
+  if (tracker.envmapSamplingChanged(scene)) {
+    check(gsp_multi_set_envmap_sampling(multi, &scene.envmapSampling), "gsp_multi_set_envmap_sampling");
+    tracker.rememberEnvmapSampling(scene);
   }
   // (the media table: as PathTracer::prepareScene; a change that has to follow the scene takes the full upload here)
   const auto sendBoth = [&] {

@@ -43,6 +43,9 @@ struct SceneTracker {
   // ... and its delta lights (Scene::deltaLights) against the table last sent (gsp_set_delta_lights)
   bool deltaLightsChanged(const Scene& scene) const;
   void rememberDeltaLights(const Scene& scene) { deltaLights = scene.deltaLights; }
+  // ... and its environment-light switch (Scene::envmapSampling) against the one last sent (gsp_set_envmap_sampling)
+  bool envmapSamplingChanged(const Scene& scene) const;
+  void rememberEnvmapSampling(const Scene& scene) { envmapSampling = scene.envmapSampling; }
   void rememberMedia(const Scene& scene) {
     media = scene.media;
     mediaScattering = scene.mediaScattering;
@@ -58,6 +61,7 @@ struct SceneTracker {
   std::vector<gsp_medium> media;        // (empty = none = a fresh context's state)
   std::vector<gsp_medium_scatter> mediaScattering;  // ... and the scattering table parallel to it (gsp_set_media_scattering)
   std::vector<gsp_delta_light> deltaLights;         // (empty = none = a fresh context's state)
+  gsp_envmap_sampling envmapSampling{};             // (zeroed = off = a fresh context's state)
   std::vector<uint64_t> assets;         // dormant features: texture / environment-map sizes, flags, envmap transform
 };
 

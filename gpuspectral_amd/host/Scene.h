@@ -228,6 +228,9 @@ struct Scene {
   // delta lights (gpuspectral_pt.h "Delta lights"): filled only by loadScene(..., LoadOptions{.readEmitters = true}) or by the host
   // itself.  PathTracer sends the table (gsp_set_delta_lights) when its value changed
   std::vector<gsp_delta_light> deltaLights;
+  // the environment light (gpuspectral_pt.h "Environment light"): filled only by loadScene(..., LoadOptions{.sampleEnvmap = true}) or by
+  // the host itself.  PathTracer sends the switch (gsp_set_envmap_sampling) when its value changed; the tracer must run GSP_ESTIMATOR_TEXTBOOK
+  gsp_envmap_sampling envmapSampling{};
   std::vector<std::string> warnings;  // what the loader skipped (the reference printed these to stdout)
   // the film's <rfilter>, read only with LoadOptions::readFilter: GSP_FILTER_* and its parameter (0 = the filter's default).
   // 0 = none: the renderer's own params decide.  PathTracer::render uses these when its params.pixel_filter is GSP_FILTER_NONE

@@ -66,7 +66,8 @@ void* gsph_load_scene_ex(const char* path, const char* asset_dir, int dormant, i
 // flags: 1 = LoadOptions::dormantFeatures, 2 = srgbTextures, 4 = builtinShapes (disk / sphere),
 // 8 = readFilter (the film's <rfilter>), 16 = readLens (a thinlens sensor's aperture_radius / focus_distance),
 // 32 = readFilm (an ldrfilm's gamma / exposure / tonemapMethod / key / burn), 64 = readMedia (the shapes' interior media),
-// 128 = readScattering (their sigmaS / albedo and hg phase; implies 64), 256 = readEmitters (top-level point / spot / directional emitters)
+// 128 = readScattering (their sigmaS / albedo and hg phase; implies 64), 256 = readEmitters (top-level point / spot / directional emitters),
+// 512 = sampleEnvmap (the environment-light switch, extent = the radius of the scene's bounds)
 void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned flags) {
   SceneBox* b = nullptr;
   int rc = guard([&] {
@@ -81,6 +82,7 @@ void* gsph_load_scene_opts(const char* path, const char* asset_dir, unsigned fla
     opt.readMedia = (flags & 64u) != 0;
     opt.readScattering = (flags & 128u) != 0;
     opt.readEmitters = (flags & 256u) != 0;
+    opt.sampleEnvmap = (flags & 512u) != 0;
     b->scene = loadScene(path, asset_dir ? asset_dir : "", opt);
     flattenScene(b->scene, b->flat);
   });
@@ -153,6 +155,15 @@ uint32_t gsph_scene_delta_lights(void* s, gsp_delta_light* out) {
   const std::vector<gsp_delta_light>& l = ((SceneBox*)s)->scene.deltaLights;
   if (out && !l.empty()) std::memcpy(out, l.data(), l.size() * sizeof(gsp_delta_light));
   return (uint32_t)l.size();
+}
+// Scene::envmapSampling: the switch (return value) and its extent; and its setter
+uint32_t gsph_scene_envmap_sampling(void* s, float* extent) {
+  const gsp_envmap_sampling& e = ((SceneBox*)s)->scene.envmapSampling;
+  if (extent) *extent = e.extent;
+  return e.enabled;
+}
+void gsph_scene_set_envmap_sampling(void* s, uint32_t enabled, float extent) {
+  ((SceneBox*)s)->scene.envmapSampling = gsp_envmap_sampling{enabled ? 1u : 0u, extent, {0u, 0u}};
 }
 // Scene::deltaLights = the n records at `lights` (n = 0: none)
 void gsph_scene_set_delta_lights(void* s, const gsp_delta_light* lights, uint32_t n) {

@@ -66,6 +66,12 @@ class PathTracerHip : public RenderPassCreator {
   // ... and their scattering coefficients (gpuspectral_pt.h "Scattering media"): a table parallel to the media, or empty = none
   // delta lights (gpuspectral_pt.h "Delta lights"): point, spot and directional emitters beside the triangle lights; empty = none
   void setDeltaLights(const std::vector<gsp_delta_light>& lights) { check(gsp_set_delta_lights(ctx, lights.data(), (uint32_t)lights.size())); }
+  // the environment light (gpuspectral_pt.h "Environment light"): sample the scene's environment map as a light, with MIS; extent = the
+  // radius of the scene as the power pick is to see it.  Needs setEstimator(GSP_ESTIMATOR_TEXTBOOK) first; restart() after a change
+  void setEnvmapSampling(bool enabled, float extent = 1.0f) {
+    const gsp_envmap_sampling s{enabled ? 1u : 0u, extent, {0u, 0u}};
+    check(gsp_set_envmap_sampling(ctx, &s));
+  }
   void setMediaScattering(const std::vector<gsp_medium_scatter>& scatter) { check(gsp_set_media_scattering(ctx, scatter.data(), (uint32_t)scatter.size())); }
   // light selection, opt-in (gpuspectral_pt.h "Light selection"): GSP_LIGHTS_POWER picks the NEE light by emitted power (an alias
   // table beside the lights).  Context state; restart() after a change.  The default is the reference's uniform pick

@@ -16,6 +16,9 @@
 //   --scene-media: LoadOptions::readMedia (the shapes' <medium name="interior">: coloured glass, gsp_set_media).
 //   --scene-scattering: LoadOptions::readScattering (implies --scene-media; sigmaS / albedo and the hg phase: gsp_set_media_scattering).
 //   --scene-emitters: LoadOptions::readEmitters (top-level point / spot / directional emitters: gsp_set_delta_lights).
+//   --env-sampling [--env-extent R]: sample the scene's environment map as a light (gsp_set_envmap_sampling; with --dormant-features, which
+//     loads the map).  R = the radius of the scene as the power pick is to see it, default: the radius of the scene's bounds.  Implies
+//     --estimator textbook; an error beside an explicit --estimator reference.
 //   --point-light X,Y,Z,R,G,B (repeatable): one more point light of that position and radiant intensity, for a scene file without an emitter element.
 //   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
 //   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
@@ -73,6 +76,8 @@ int main(int argc, char** argv) {
   bool nee = true;
   uint32_t lightSampling = GSP_LIGHTS_UNIFORM;
   uint32_t estimator = GSP_ESTIMATOR_REFERENCE;
+  bool estimatorGiven = false, envSampling = false;
+  float envExtent = -1.0f;  // (-1 = not given: the radius of the scene's bounds)
   float adaptive = 0.0f;
   uint32_t adaptiveMin = 0, adaptiveStep = 0;
   uint32_t filter = GSP_FILTER_NONE;
@@ -139,6 +144,16 @@ int main(int argc, char** argv) {
       else if (v == "textbook") estimator = GSP_ESTIMATOR_TEXTBOOK;
       else {
         std::fprintf(stderr, "--estimator: reference or textbook, not '%s'\n", v.c_str());
+        return 2;
+      }
+      estimatorGiven = true;
+      used = 2;
+    }
+    else if (flag == "--env-sampling") envSampling = true;
+    else if (flag == "--env-extent" && argc > 2) {
+      envExtent = (float)std::atof(argv[2]);
+      if (!(envExtent > 0.0f)) {
+        std::fprintf(stderr, "gsp_render: --env-extent R: a radius > 0\n");
         return 2;
       }
       used = 2;
@@ -455,7 +470,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--scene-scattering] [--scene-emitters] [--point-light X,Y,Z,R,G,B]... [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--scene-scattering] [--scene-emitters] [--point-light X,Y,Z,R,G,B]... [--env-sampling [--env-extent R]] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -494,9 +509,18 @@ int main(int argc, char** argv) {
   }
   try {
     if (svgfFeedback && svgfPath.empty()) throw std::runtime_error("--svgf-feedback needs --svgf out.pfm (it feeds the filter's first levels back into the history)");
+    if (envSampling) {
+      if (estimatorGiven && estimator == GSP_ESTIMATOR_REFERENCE)
+        throw std::runtime_error("--env-sampling needs the textbook estimator: drop --estimator reference (the option implies --estimator textbook)");
+      estimator = GSP_ESTIMATOR_TEXTBOOK;
+      options.sampleEnvmap = true;
+    } else if (envExtent > 0.0f) {
+      throw std::runtime_error("--env-extent needs --env-sampling");
+    }
     Scene scene = loadScene(argv[1], "", options);
     for (auto& w : scene.warnings) std::fprintf(stderr, "WARN: %s\n", w.c_str());
     scene.deltaLights.insert(scene.deltaLights.end(), pointLights.begin(), pointLights.end());
+    if (envSampling && envExtent > 0.0f) scene.envmapSampling.extent = envExtent;  // (LoadOptions::sampleEnvmap has set the switch and the bounds' radius)
     // thin lens: the scene's (--scene-lens), overridden flag by flag
     if (aperture >= 0.0f || focusDistance > 0.0f || blades >= 0 || focusPixel) {
       float fd = focusDistance > 0.0f ? focusDistance : scene.camera.getFocusDistance();

@@ -34,6 +34,7 @@ EXPORTS = (
     "gsp_download_light_pick",
     "gsp_set_estimator",
     "gsp_set_delta_lights",
+    "gsp_set_envmap_sampling",
     "gsp_focus_distance",
     "gsp_frame_begin",
     "gsp_render",
@@ -101,6 +102,7 @@ EXPORTS = (
     "gsp_multi_set_light_sampling",
     "gsp_multi_set_estimator",
     "gsp_multi_set_delta_lights",
+    "gsp_multi_set_envmap_sampling",
     "gsp_multi_update_instances",
     "gsp_multi_update_tables",
     "gsp_multi_frame_begin",
@@ -165,6 +167,8 @@ def load():
     L.gsp_multi_set_estimator.argtypes = [vp, u32]
     L.gsp_set_delta_lights.argtypes = [vp, C.POINTER(abi.DeltaLight), u32]
     L.gsp_multi_set_delta_lights.argtypes = [vp, C.POINTER(abi.DeltaLight), u32]
+    L.gsp_set_envmap_sampling.argtypes = [vp, C.POINTER(abi.EnvmapSampling)]
+    L.gsp_multi_set_envmap_sampling.argtypes = [vp, C.POINTER(abi.EnvmapSampling)]
     L.gsp_update_instances.argtypes = [vp, vp, u32]
     L.gsp_update_tables.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_ctx_destroy.argtypes = [vp]
@@ -271,8 +275,8 @@ def build_info():
 
 
 # the files csrc/Makefile hashes into the digest, in its order
-DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_render_scatter.hip", "pt_render_delta.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
-                  "pt_medium.h", "pt_deltalight.h", "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
+DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_render_scatter.hip", "pt_render_delta.hip", "pt_render_envlight.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
+                  "pt_medium.h", "pt_deltalight.h", "pt_envlight.h", "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -376,6 +380,12 @@ class Context:
         directional_light).  None or empty = no delta lights."""
         arr = abi.delta_light_array(lights)
         self._check(self._L.gsp_set_delta_lights(self._h, arr, len(arr) if arr is not None else 0), "gsp_set_delta_lights")
+
+    def set_envmap_sampling(self, enabled=True, extent=1.0):
+        """gsp_set_envmap_sampling (gpuspectral_pt.h "Environment light"): sample the scene's environment map as a light (textbook
+        estimator only).  extent: the radius of the scene as the power pick is to see it.  enabled=False drops the sampling."""
+        s = abi.EnvmapSampling(1, extent, (C.c_uint32 * 2)(0, 0)) if enabled else None
+        self._check(self._L.gsp_set_envmap_sampling(self._h, C.byref(s) if s is not None else None), "gsp_set_envmap_sampling")
 
     def set_estimator(self, mode):
         """gsp_set_estimator (gpuspectral_pt.h "Estimator"): "reference" / "textbook" or abi.ESTIMATOR_REFERENCE / ESTIMATOR_TEXTBOOK."""
@@ -849,6 +859,11 @@ class MultiContext:
         """gsp_multi_set_delta_lights: Context.set_delta_lights on every share."""
         arr = abi.delta_light_array(lights)
         self._check(self._L.gsp_multi_set_delta_lights(self._h, arr, len(arr) if arr is not None else 0), "gsp_multi_set_delta_lights")
+
+    def set_envmap_sampling(self, enabled=True, extent=1.0):
+        """gsp_multi_set_envmap_sampling: Context.set_envmap_sampling on every share."""
+        s = abi.EnvmapSampling(1, extent, (C.c_uint32 * 2)(0, 0)) if enabled else None
+        self._check(self._L.gsp_multi_set_envmap_sampling(self._h, C.byref(s) if s is not None else None), "gsp_multi_set_envmap_sampling")
 
     def set_media_scattering(self, scatter=None):
         """gsp_multi_set_media_scattering: Context.set_media_scattering on every share."""

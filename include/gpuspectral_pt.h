@@ -87,7 +87,8 @@ extern "C" {
                                 gsp_set_light_sampling, gsp_download_light_pick, gsp_multi_set_light_sampling (see "Light
                                 selection"); gsp_set_estimator, gsp_multi_set_estimator (see "Estimator");
                                 gsp_set_media_scattering, gsp_multi_set_media_scattering (see "Scattering media");
-                                gsp_set_delta_lights, gsp_multi_set_delta_lights (see "Delta lights") */
+                                gsp_set_delta_lights, gsp_multi_set_delta_lights (see "Delta lights");
+                                gsp_set_envmap_sampling, gsp_multi_set_envmap_sampling (see "Environment light") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -880,6 +881,91 @@ typedef struct gsp_delta_light { /* 64 B, the size of gsp_triangle_light */
 } gsp_delta_light;
 int gsp_set_delta_lights(gsp_context* ctx, const gsp_delta_light* lights, uint32_t count); /* NULL or 0 = none */
 
+/*
+ * Environment light: opt-in next-event estimation towards the environment map, with MIS.
+ *
+ * gsp_scene_desc.envmap lights only the paths that leave the scene by chance ("light sampling does not see it", above).
+ * gsp_set_envmap_sampling(ctx, &{enabled = 1, extent}) makes the map ONE MORE RECORD of the light table: the light pick may land on
+ * it, the vertex then samples a direction from a piecewise-constant density over the map and traces a shadow ray of length 1e30f,
+ * and a path that escapes along a BSDF sample weighs the map's radiance against that density.  Path state, queues and the traversal
+ * kernel are what they were.
+ *
+ * The switch is CONTEXT STATE like the delta-light table: it survives gsp_upload_scene and gsp_update_tables and may be set with a
+ * scene resident (the samples in flight finish first, then the tables are packed again and uploaded, as gsp_set_delta_lights
+ * does).  NULL or enabled == 0 drops the sampling.  It takes effect only while the resident scene has an envmap; without one it is
+ * inert.  A context that never enables it, or has disabled it again, runs the kernels, holds the table bytes and returns the frame
+ * of before, bit for bit.
+ *
+ * Validation (the state stays unchanged on every failure).  GSP_ERR_INVALID when enabled != 0 and: extent is not finite or not > 0;
+ * a word of reserved is not 0; the context runs GSP_ESTIMATOR_REFERENCE -- the environment light exists under
+ * GSP_ESTIMATOR_TEXTBOOK only (the reference has no environment sampling to restate), so gsp_set_estimator(.., TEXTBOOK) comes
+ * first, and gsp_set_estimator(.., REFERENCE) with the switch on is GSP_ERR_INVALID as well.  ROTATION: sampling needs the inverse
+ * of envmap.to_local, and the density below has no Jacobian term, so the upper 3x3 A of to_local must be orthonormal: every entry
+ * of A^T A - I at most 1e-4 in magnitude, in double.  gsp_set_envmap_sampling on a resident scene that fails this is
+ * GSP_ERR_INVALID; gsp_upload_scene of such a scene with the switch on is GSP_ERR_SCENE.  The library forms local -> world = A^-1
+ * (cofactors over the determinant, in double, rounded to float32 once) when it packs the record.
+ *
+ * The sampling distribution: piecewise constant over a grid of Cw x Ch cells in the map's own (u, v), Cw = min(width, 512),
+ * Ch = min(height, 256) (at most 131 072 entries of 16 B = 2 MiB: resident in one L2, where a table per texel of a 2k x 1k map
+ * would be 32 MiB of random access).  Cell (i, j), i < Cw, j < Ch, has number j * Cw + i and covers u in [i / Cw, (i + 1) / Cw),
+ * v in [j / Ch, (j + 1) / Ch).  Its weight, in double on the host at upload:
+ *     w = sin(pi * (j + 0.5) / Ch) * max Y(texel)            Y(c) = max(0.2126 R + 0.7152 G + 0.0722 B, 0), not finite: 0
+ * the maximum over EVERY texel the bilinear lookup above can read for a (u, v) inside the cell: columns floor(i * width / Cw - 0.5
+ * - eps) .. floor((i + 1) * width / Cw - 0.5 + eps) + 1, wrapped; rows likewise with height and Ch, clamped; eps = width (height)
+ * * 2^-21 covers the float32 rounding of the lookup's coordinate.  Taking the maximum over the filter's footprint makes the density
+ * positive wherever the looked-up radiance is not 0: the condition for an unbiased estimator.  The weights go through the alias
+ * construction of "Light selection" as they stand; pmf(cell) is the mass the integer table implies (pmf_self of the cell's entry).
+ * The table is scene state, made by gsp_upload_scene (or, when the switch is first set under a resident scene, from the resident
+ * texels), one copy beside the table versions: gsp_update_tables does not touch it.
+ *
+ * The light record: ONE 64-byte record behind the delta records in every table version, counted by num_lights and
+ * 1.0f / (float)num_lights and reported LAST by gsp_download_light_pick.  Its kind is GSP_LIGHT_ENVIRONMENT, for internal use:
+ * gsp_set_delta_lights keeps rejecting it.  Under GSP_LIGHTS_POWER its weight is, in double, behind the delta weights in the same
+ * ascending sum,
+ *     pi * extent^2 * sum over texels of Y(texel) * (2 pi / width) * (pi / height) * sin(pi * (row + 0.5) / height)
+ * (rows in ascending order, columns ascending inside a row) -- extent = the radius of the scene as the power pick is to see it,
+ * as gsp_delta_light.extent.  The record carries p_sel, the selection probability the table of the context's mode implies for
+ * it: 1.0f / (float)num_lights, or pmf_self of its entry of the alias table.  Both sides below read THIS word.
+ *
+ * radiance and density of a world direction d -- ONE function, called by both sides (float32 in this order):
+ *     e = to_local * d;   s = sqrt(e.x * e.x + e.z * e.z);   u = atan2(e.x, -e.z) * (1 / 2pi) + 0.5;   v = 1 - atan2(s, e.y) * (1 / pi)
+ *     radiance = the bilinear lookup at (u, v), operation for operation the one of the escape above
+ *     ci = (uint32)clamp(u * (float)Cw, 0, Cw - 1) with NaN -> 0;   cj likewise from v and Ch
+ *     density = s > 0 ? ((pmf(cj * Cw + ci) * (float)Cw) * (float)Ch) / ((2 pi^2) * s) : 0        (2 pi^2 = 19.739208802178716f)
+ * (s is sin(theta) of a unit direction: taken from the direction, not from v.)
+ *
+ * Pick and sample.  The vertex makes the same three draws (r, e1, e2) and the same pick.  A pick that lands on the environment
+ * record draws ONE FURTHER 32-bit word r2 and picks the cell c through the cell table as "Light selection" picks a light.  This
+ * is the one kind of light whose pick lengthens the path's random stream by one draw.  (Under disable_nee no light sample is
+ * used: the word is not drawn, lightPdf = 0, and the stream is that of a context without the switch.)  Then
+ *     u = ((float)(c % Cw) + e1) / (float)Cw;   v = ((float)(c / Cw) + e2) / (float)Ch
+ *     theta = (1 - v) * pi;   phi = (u - 0.5) * (2 pi);   (st, ct) = sincos(theta);   (sp, cp) = sincos(phi)
+ *     e = (st * sp, ct, -(st * cp));   L = local_to_world * e   (row r: (m[r][0] * e.x + m[r][1] * e.y) + m[r][2] * e.z)
+ * and the function above is called on L: emission = its radiance, lightPdf = its density * p_sel, Ldist = 1e30f.
+ *
+ * NEE.  The gate is the existing one (lightPdf != 0 included).  weight = power_heuristic(lightPdf, lb.pdf), the triangle's
+ * textbook form;  nee = ((((w * NoL) * lb.f) * weight) * emission) / lightPdf, behind the firefly test like every emitted term.
+ *
+ * Escapes.  With NEE on, countEmitted == 0 and wasDelta == 0 an escaping path adds
+ *     (radiance * power_heuristic(lastPdf, density * p_sel)) * weight
+ * and otherwise radiance * weight as before: camera rays, rays after a delta bounce, disable_nee.  With disable_nee the frame is
+ * therefore that of a context without the switch.  A medium event of "Scattering media" still takes no light sample (the ray it
+ * sends meets a back face of its own closed shape next, not the environment).
+ *
+ * Media: as "Delta lights" -- a context with the switch on and an envmap resident runs the kernels of scattering media whatever
+ * its media.
+ *
+ * Limits.  Shadow rays stop at every surface, so the sky behind a window pane is still found by BSDF sampling only.  The density
+ * is per cell, not per texel, above 512 x 256.
+ */
+#define GSP_LIGHT_ENVIRONMENT 4u /* internal: the kind word of the environment record; gsp_set_delta_lights rejects it */
+typedef struct gsp_envmap_sampling {
+  uint32_t enabled;     /* 0 = off */
+  float extent;         /* radius of the scene as the power pick is to see it; > 0 and finite when enabled */
+  uint32_t reserved[2]; /* 0 */
+} gsp_envmap_sampling;  /* 16 B */
+int gsp_set_envmap_sampling(gsp_context* ctx, const gsp_envmap_sampling* sampling); /* NULL = off */
+
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
 
@@ -1557,6 +1643,7 @@ int gsp_multi_set_lens(gsp_multi* m, const gsp_lens* lens); /* gsp_set_lens on e
 int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_media); /* gsp_set_media on every share */
 int gsp_multi_set_media_scattering(gsp_multi* m, const gsp_medium_scatter* scatter, uint32_t num_media); /* gsp_set_media_scattering on every share */
 int gsp_multi_set_delta_lights(gsp_multi* m, const gsp_delta_light* lights, uint32_t count); /* gsp_set_delta_lights on every share */
+int gsp_multi_set_envmap_sampling(gsp_multi* m, const gsp_envmap_sampling* sampling); /* gsp_set_envmap_sampling on every share */
 int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode); /* gsp_set_light_sampling on every share */
 int gsp_multi_set_estimator(gsp_multi* m, uint32_t mode);      /* gsp_set_estimator on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);

@@ -29,6 +29,10 @@ if [ -f pt_render_delta.hip ]; then  # (... and those with delta lights the <DLT
   hipcc $F -c pt_render_delta.hip -o build/var_$1/pt_render_delta.o &
   TB="$TB build/var_$1/pt_render_delta.o"
 fi
+if [ -f pt_render_envlight.hip ]; then  # (... and those that sample the environment map as a light the <ENV> kernels)
+  hipcc $F -c pt_render_envlight.hip -o build/var_$1/pt_render_envlight.o &
+  TB="$TB build/var_$1/pt_render_envlight.o"
+fi
 wait
 printf 'extern "C" const char gsp_build_info_string[] = "arch=gfx950 digest=variant-%s flags=%s";\n' "$1" "$F" > build/var_$1/pt_buildinfo.cpp
 g++ -O2 -fPIC -c build/var_$1/pt_buildinfo.cpp -o build/var_$1/pt_buildinfo.o
