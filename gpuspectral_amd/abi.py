@@ -243,6 +243,19 @@ class EnvmapSampling(C.Structure):
     _fields_ = [("enabled", C.c_uint32), ("extent", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+# Light grid (include/gpuspectral_pt.h "Light grid")
+class LightGrid(C.Structure):
+    """gsp_light_grid, 32 B"""
+
+    _fields_ = [("enabled", C.c_uint32), ("resolution", C.c_uint32 * 3), ("reserved", C.c_uint32 * 4)]
+
+
+def light_grid(resolution=None):
+    """An enabled gsp_light_grid: resolution (nx, ny, nz), or None = auto"""
+    nx, ny, nz = (0, 0, 0) if resolution is None else resolution
+    return LightGrid(1, (C.c_uint32 * 3)(nx, ny, nz), (C.c_uint32 * 4)(0, 0, 0, 0))
+
+
 # Light selection (include/gpuspectral_pt.h "Light selection")
 LIGHTS_UNIFORM, LIGHTS_POWER = 0, 1
 LIGHT_SAMPLING_NAMES = {"uniform": LIGHTS_UNIFORM, "power": LIGHTS_POWER}

@@ -68,6 +68,14 @@ struct EnvLaunch : DeltaLaunch {
 };
 void launch_shade_envlight(const EnvLaunch& a);
 void launch_finish_envlight(const EnvLaunch& a);
+// Light grid: the <GRD = true> instantiations, over VER with TEX = MED = LSEL = EST = SCT = DLT = true and ENV = false, live in
+// pt_render_lightgrid.hip.  The delta record as it stands (no textures: an empty texture view; no delta lights: num_tri_lights ==
+// num_lights) + where the grid sits inside a table version.  The view's tables_bytes ends in front of the grid
+struct GridLaunch : DeltaLaunch {
+  uint32_t grid_off;
+};
+void launch_shade_lightgrid(const GridLaunch& a);
+void launch_finish_lightgrid(const GridLaunch& a);
 
 #define GSP_HIP_TRY(expr)                                                                     \
   do {                                                                                        \

@@ -387,6 +387,11 @@ int gsp_multi_set_envmap_sampling(gsp_multi* m, const gsp_envmap_sampling* sampl
   return for_each_share(m, [&](size_t r) { return gsp_set_envmap_sampling(m->ctx[r], sampling); });
 }
 
+int gsp_multi_set_light_grid(gsp_multi* m, const gsp_light_grid* grid) {  // (NULL = off)
+  if (!m) return GSP_ERR_INVALID;
+  return for_each_share(m, [&](size_t r) { return gsp_set_light_grid(m->ctx[r], grid); });
+}
+
 int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode) {
   if (!m) return GSP_ERR_INVALID;
   if (mode != GSP_LIGHTS_UNIFORM && mode != GSP_LIGHTS_POWER) {  // (checked first: no share changes when the mode is unknown)

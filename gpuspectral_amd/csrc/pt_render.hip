@@ -176,6 +176,17 @@ struct gsp_context {
   uint32_t env_cw = 0, env_ch = 0;
   double env_radiant = 0.0;         // sum over texels of Y * solid angle
   float env_light_to_local[16] = {};  // the frame the record's inverse is formed from (the scene's, known before upload_textures runs)
+  // the light grid (gsp_set_light_grid): the switch is context state beside the light mode and the estimator.  grid_resident = the
+  // resident table versions carry a grid (the switch on, GSP_LIGHTS_POWER and GSP_ESTIMATOR_TEXTBOOK, a scene with lights and
+  // vertices): selects the <GRD> kernels of pt_render_lightgrid.hip.  pack_tables appends the grid behind the pick table's trailing
+  // record of every table image; grid_off = where, tables_stage_bytes = the bytes in front of it (what LDS staging sees; ==
+  // tables_bytes without a grid).  scene_lo / scene_hi: the bounds of the geometry as uploaded (gsp_upload_scene)
+  gsp_light_grid light_grid{};
+  bool grid_resident = false;
+  uint32_t grid_res[3] = {0, 0, 0};
+  size_t grid_off = 0, tables_stage_bytes = 0;
+  bool scene_has_bounds = false;
+  float scene_lo[3] = {0, 0, 0}, scene_hi[3] = {0, 0, 0};
   // light selection (gsp_set_light_sampling): context state like the lens.  GSP_LIGHTS_POWER selects the <LSEL> kernels and makes
   // pack_tables append the alias table behind the light records of every table image
   uint32_t light_mode = GSP_LIGHTS_UNIFORM;
@@ -428,7 +439,7 @@ struct gsp_context {
     v.bsdf.rough_plastic = (const gsp_rough_plastic_bsdf*)(tb + table_off[7]);
     v.lights = (const gsp_triangle_light*)(tb + table_off[8]);
     v.tables = tb;
-    v.tables_bytes = (uint32_t)tables_bytes;
+    v.tables_bytes = (uint32_t)tables_stage_bytes;  // (a light grid behind the tables is never staged)
     v.num_lights = num_lights;
     v.inv_num_lights = num_lights ? 1.0f / (float)num_lights : 0.0f;
     if (textured) {

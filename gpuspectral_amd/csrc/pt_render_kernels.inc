@@ -383,8 +383,11 @@ constexpr int kShadeWaves = kShadeBlock / 64;
 // records sit behind the triangle lights in the table image.  These instantiations live in pt_render_delta.hip
 // ENV: the context samples its environment map as a light (gsp_set_envmap_sampling): shade_vertex<.., ENV = true>, miss_emitted_env
 // and SceneViewEnv::env_cells; the record is the last of the light table.  These instantiations live in pt_render_envlight.hip
-template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false, bool ENV = false>
-__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED, SCT, DLT, ENV>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
+// GRD: the context selects its light through the light grid (gsp_set_light_grid): shade_vertex<.., GRD = true> and
+// SceneViewGrd::grid_off; the grid sits behind the pick table of every table version and is read from global memory (tables_bytes
+// of the view, and so the staged copy, ends in front of it).  These instantiations live in pt_render_lightgrid.hip
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false, bool ENV = false, bool GRD = false>
+__global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typename ShadeViewOf<MED, SCT, DLT, ENV, GRD>::type S, RenderConstsBase rc, const uint32_t* __restrict__ n_ptr, PathQueue cur,
                                                         const q4* __restrict__ hits, PathQueue nxt, ShadowQueue sq,
                                                         q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                         uint32_t* __restrict__ live,
@@ -533,7 +536,7 @@ __global__ __launch_bounds__(kShadeBlock, GSP_SHADE_MINWAVES) void k_shade(typen
         in.weight = mk3(p2.x, p2.y, p2.z);
         in.directWeight = p2.w;
         in.flags = fl;
-        shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT, ENV>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S), view_env_cells(S));
+        shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT, ENV, GRD>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S), view_env_cells(S), view_grid_off(S));
         alive = out.alive;
         has_shadow = out.has_shadow;
         ++shaded;
@@ -693,8 +696,8 @@ struct FinishStack {
   __device__ __forceinline__ uint32_t pop() { return col[(--top) * kBlock]; }
 };
 
-template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false, bool ENV = false>
-__global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT, DLT, ENV>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
+template <bool TEX, bool VER, bool MED, bool LSEL, bool EST, bool SCT = false, bool DLT = false, bool ENV = false, bool GRD = false>
+__global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT, DLT, ENV, GRD>::type S, RenderConstsBase rc, uint32_t n, PathQueue q,
                                                     q4* __restrict__ result, uint32_t* __restrict__ tails,
                                                     uint32_t* __restrict__ live,
                                                     uint32_t slot_paths, DevStats* __restrict__ stats) {
@@ -752,7 +755,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(typename ShadeViewOf<MED, SCT
         break;
       }
       ShadeOut out;
-      shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT, ENV>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S), view_env_cells(S));
+      shade_vertex<TEX, VER, MED, LSEL, EST, SCT, DLT, ENV, GRD>(S, rc, in, h, out, view_media(S), view_scatter(S), view_tri_lights(S), view_env_cells(S), view_grid_off(S));
       ++shaded;
       if (!out.has_shadow) {
         add_emitted(rc.clamp, out.emitted, res);

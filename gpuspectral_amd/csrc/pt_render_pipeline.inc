@@ -199,6 +199,14 @@ static EnvLaunch env_launch(const gsp_context* ctx, const TextbookLaunch& t) {
   a.env_cells = ctx->env_cells.p;
   return a;
 }
+// ... and <.., GRD = true>, the kernels of a context with a light grid resident (gsp_set_light_grid under the power pick and the textbook
+// estimator, a scene with lights), handed to pt_render_lightgrid.hip: the delta record + where the grid sits inside a table version
+static GridLaunch grid_launch(const gsp_context* ctx, const TextbookLaunch& t) {
+  GridLaunch a{};
+  static_cast<DeltaLaunch&>(a) = delta_launch(ctx, t);
+  a.grid_off = (uint32_t)ctx->grid_off;
+  return a;
+}
 }  // extern "C++"
 
 // The blocks of k_shade a device holds at once: the largest grid (a block loops over tiles), each may leave one room chunk of fillers.
@@ -301,11 +309,12 @@ static int finish_few_paths(gsp_context* ctx, gsp_context::Lane& L, const Render
   if (!(drain && L.queued == 0 && P.remaining == 0 && P.n > 0 && P.n <= ctx->finish_paths && ctx->pipe_params.collect_traversal_stats == 0 &&
         std::max(ctx->bvh.depth, ctx->split ? ctx->dyn.depth : 0u) + 2 <= kFinishLevels))
     return GSP_OK;
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty() || ctx->env_light) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty() || ctx->env_light || ctx->grid_resident) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, L.stream, (uint32_t)((P.n + kBlock - 1) / kBlock), lane_queue(L, P.cur), L.result.p, lane_tails(L, L.enq),
                                        L.counters.p + C_LIVE, (uint32_t)P.batch_paths);
     a.n = (uint32_t)P.n;
-    if (ctx->env_light) launch_finish_envlight(env_launch(ctx, a));
+    if (ctx->grid_resident) launch_finish_lightgrid(grid_launch(ctx, a));
+    else if (ctx->env_light) launch_finish_envlight(env_launch(ctx, a));
     else if (!ctx->h_delta.empty()) launch_finish_delta(delta_launch(ctx, a));
     else if (ctx->scatter_on) launch_finish_scatter(scatter_launch(ctx, a));
     else launch_finish_textbook(a);
@@ -377,14 +386,15 @@ static int trace_shade_connect(gsp_context* ctx, gsp_context::Lane& L, const Ren
   CTX_TRY(ctx, hipGetLastError());
   if (ev) CTX_TRY(ctx, hipEventRecord(ev[1], st));
   const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + kShadeBlock - 1) / kShadeBlock, shade_resident_blocks(ctx))));
-  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty() || ctx->env_light) {
+  if (ctx->estimator == GSP_ESTIMATOR_TEXTBOOK || ctx->scatter_on || !ctx->h_delta.empty() || ctx->env_light || ctx->grid_resident) {
     TextbookLaunch a = textbook_launch(ctx, V, rcst, st, grid.x, cur, L.result.p, tails_out, L.counters.p + C_LIVE, (uint32_t)L.pipe.batch_paths);
     a.n_ptr = n_ptr;
     a.hits = hits;
     a.next[0] = next.P0, a.next[1] = next.P1, a.next[2] = next.P2, a.next[3] = next.P3;
     a.shadow[0] = sq.S0, a.shadow[1] = sq.S1, a.shadow[2] = sq.S3;
     a.chunk = room_chunk;
-    if (ctx->env_light) launch_shade_envlight(env_launch(ctx, a));
+    if (ctx->grid_resident) launch_shade_lightgrid(grid_launch(ctx, a));
+    else if (ctx->env_light) launch_shade_envlight(env_launch(ctx, a));
     else if (!ctx->h_delta.empty()) launch_shade_delta(delta_launch(ctx, a));
     else if (ctx->scatter_on) launch_shade_scatter(scatter_launch(ctx, a));
     else launch_shade_textbook(a);
@@ -1322,11 +1332,11 @@ int gsp_set_lens(gsp_context* ctx, const gsp_lens* lens_host) {
   return GSP_OK;
 }
 
-// A context with delta lights (or the environment light switched on) runs the <MED, SCT, DLT> kernels whatever its media (pt_render_delta.hip, pt_render_envlight.hip).  Where it holds media but
+// A context with delta lights (or the environment light or the light grid switched on) runs the <MED, SCT, DLT> kernels whatever its media (pt_render_delta.hip, pt_render_envlight.hip).  Where it holds media but
 // no scattering table, those kernels read one of zeros from the table's device buffer: every medium then takes the deterministic
 // line of the absorbing kernels.  Called behind every change of the three tables, under a drained pipeline.
 static int sync_absorbing_scatter_table(gsp_context* ctx) {
-  if ((ctx->h_delta.empty() && ctx->env_sampling.enabled == 0u) || ctx->num_media == 0 || !ctx->h_scatter.empty()) return GSP_OK;
+  if ((ctx->h_delta.empty() && ctx->env_sampling.enabled == 0u && ctx->light_grid.enabled == 0u) || ctx->num_media == 0 || !ctx->h_scatter.empty()) return GSP_OK;
   const std::vector<gsp_medium_scatter> zeros(ctx->num_media, gsp_medium_scatter{{0.0f, 0.0f, 0.0f}, 0.0f});
   CTX_TRY(ctx, ctx->scatter.upload(zeros.data(), zeros.size(), ctx->stream, &ctx->bytes));
   CTX_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (`zeros` goes out of scope; the lanes' streams read the table)
@@ -1424,6 +1434,10 @@ int gsp_set_light_sampling(gsp_context* ctx, uint32_t mode) {
   int rc = drain_for_edit(ctx);  // the samples in flight were generated under the mode as it was
   if (rc != GSP_OK) return rc;
   if (mode == ctx->light_mode) return GSP_OK;
+  if (mode != GSP_LIGHTS_POWER && ctx->light_grid.enabled != 0u) {
+    ctx->err = "gsp_set_light_sampling: the light grid is on, and it exists under GSP_LIGHTS_POWER only";
+    return GSP_ERR_INVALID;
+  }
   const uint32_t old_mode = ctx->light_mode;
   ctx->light_mode = mode;
   rc = repack_resident_tables(ctx);
@@ -1444,6 +1458,10 @@ int gsp_set_estimator(gsp_context* ctx, uint32_t mode) {
   if (mode == ctx->estimator) return GSP_OK;
   if (mode == GSP_ESTIMATOR_REFERENCE && ctx->env_sampling.enabled != 0u) {
     ctx->err = "gsp_set_estimator: envmap sampling is on, and the environment light exists under GSP_ESTIMATOR_TEXTBOOK only";
+    return GSP_ERR_INVALID;
+  }
+  if (mode == GSP_ESTIMATOR_REFERENCE && ctx->light_grid.enabled != 0u) {
+    ctx->err = "gsp_set_estimator: the light grid is on, and it exists under GSP_ESTIMATOR_TEXTBOOK only";
     return GSP_ERR_INVALID;
   }
   const uint32_t old_mode = ctx->estimator;
@@ -1494,6 +1512,10 @@ int gsp_set_envmap_sampling(gsp_context* ctx, const gsp_envmap_sampling* samplin
     ctx->err = "gsp_set_envmap_sampling: the environment light exists under GSP_ESTIMATOR_TEXTBOOK only (gsp_set_estimator first)";
     return GSP_ERR_INVALID;
   }
+  if (want.enabled != 0u && ctx->light_grid.enabled != 0u) {
+    ctx->err = "gsp_set_envmap_sampling: the light grid is on, and the environment record has no selection probability per cell (gsp_set_light_grid(NULL) first)";
+    return GSP_ERR_INVALID;
+  }
   CTX_TRY(ctx, hipSetDevice(ctx->device));
   int rc = drain_for_edit(ctx);  // the samples in flight read the light table as it was
   if (rc != GSP_OK) return rc;
@@ -1525,6 +1547,66 @@ int gsp_set_envmap_sampling(gsp_context* ctx, const gsp_envmap_sampling* samplin
     }
   }
   return sync_absorbing_scatter_table(ctx);
+}
+
+// ---- light grid (include/gpuspectral_pt.h, "Light grid") ----
+int gsp_set_light_grid(gsp_context* ctx, const gsp_light_grid* grid) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (const char* why = check_light_grid(grid)) {
+    ctx->err = why;
+    return GSP_ERR_INVALID;
+  }
+  gsp_light_grid want{};
+  if (grid && grid->enabled != 0u) {
+    want.enabled = 1u;
+    for (int c = 0; c < 3; ++c) want.resolution[c] = grid->resolution[c];
+  }
+  if (want.enabled != 0u && ctx->light_mode != GSP_LIGHTS_POWER) {
+    ctx->err = "gsp_set_light_grid: the light grid exists under GSP_LIGHTS_POWER only (gsp_set_light_sampling first)";
+    return GSP_ERR_INVALID;
+  }
+  if (want.enabled != 0u && ctx->estimator != GSP_ESTIMATOR_TEXTBOOK) {
+    ctx->err = "gsp_set_light_grid: the light grid exists under GSP_ESTIMATOR_TEXTBOOK only (gsp_set_estimator first)";
+    return GSP_ERR_INVALID;
+  }
+  if (want.enabled != 0u && ctx->env_sampling.enabled != 0u) {
+    ctx->err = "gsp_set_light_grid: envmap sampling is on, and the environment record has no selection probability per cell (gsp_set_envmap_sampling(NULL) first)";
+    return GSP_ERR_INVALID;
+  }
+  CTX_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = drain_for_edit(ctx);  // the samples in flight read the light table as it was
+  if (rc != GSP_OK) return rc;
+  if (std::memcmp(&want, &ctx->light_grid, sizeof(want)) == 0) return GSP_OK;
+  if (want.enabled != 0u && ctx->have_scene) {  // (checked before anything changes: a refused resolution leaves the resident tables alone)
+    uint32_t res[3];
+    if (light_grid_applies(ctx, ctx->num_lights) && lightgrid_resolve(want, ctx->scene_lo, ctx->scene_hi, ctx->num_lights, res) != 0) {
+      ctx->err = "gsp_set_light_grid: cells * lights is beyond 2^20 entries (a 16 MB table image)";
+      return GSP_ERR_NOMEM;
+    }
+  }
+  const gsp_light_grid old = ctx->light_grid;
+  ctx->light_grid = want;
+  rc = repack_resident_tables(ctx);  // with or without the grid behind the pick table
+  if (rc != GSP_OK) {
+    ctx->light_grid = old;
+    return rc;
+  }
+  return sync_absorbing_scatter_table(ctx);
+}
+
+int gsp_get_light_grid(gsp_context* ctx, gsp_light_grid* resolved, float bounds[6]) {
+  if (!ctx) return GSP_ERR_INVALID;
+  if (resolved) {
+    *resolved = gsp_light_grid{};
+    resolved->enabled = ctx->grid_resident ? 1u : 0u;
+    for (int c = 0; c < 3; ++c) resolved->resolution[c] = ctx->grid_resident ? ctx->grid_res[c] : 0u;
+  }
+  if (bounds)
+    for (int c = 0; c < 3; ++c) {
+      bounds[c] = ctx->grid_resident ? ctx->scene_lo[c] : 0.0f;
+      bounds[3 + c] = ctx->grid_resident ? ctx->scene_hi[c] : 0.0f;
+    }
+  return GSP_OK;
 }
 
 int gsp_download_light_pick(gsp_context* ctx, gsp_light_pick* out, uint32_t capacity, uint32_t* count) {

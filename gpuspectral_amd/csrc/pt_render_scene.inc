@@ -69,8 +69,15 @@ struct TableImage {
   std::vector<uint8_t> bytes;  // [9 x uint64 count][tables ...]: the device holds bytes.data() + kHead onwards
   size_t off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, total = 0;
   size_t pick_off = 0;         // the light pick table (GSP_LIGHTS_POWER only): == off[8] + 64 * num_lights
+  size_t grid_off = 0;         // the light grid (gsp_set_light_grid; 0 = none): behind the pick table's trailing record
+  size_t stage_total = 0;      // the bytes in front of the grid (== total without one): what LDS staging sees
+  uint32_t grid_res[3] = {0, 0, 0};
   static constexpr size_t kHead = 9 * sizeof(uint64_t);
 };
+// the light grid is built for a table of n lights: the switch, both modes, lights, and a scene with vertices
+static bool light_grid_applies(const gsp_context* ctx, uint32_t n) {
+  return ctx->light_grid.enabled != 0u && ctx->light_mode == GSP_LIGHTS_POWER && ctx->estimator == GSP_ESTIMATOR_TEXTBOOK && n != 0u && ctx->scene_has_bounds;
+}
 static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& img) {
   const void* src[9] = {sc->diffuse_bsdfs, sc->smooth_dielectric_bsdfs, sc->smooth_conductor_bsdfs, sc->smooth_plastic_bsdfs,
                         sc->rough_conductor_bsdfs, sc->smooth_floor_bsdfs, sc->rough_floor_bsdfs, sc->rough_plastic_bsdfs, sc->lights};
@@ -111,6 +118,20 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
   const bool tail = light_pick_tail_bytes(all_lights, ctx->light_mode, ctx->estimator) != 0;
   const size_t tail_off = img.total;
   img.total += light_pick_tail_bytes(all_lights, ctx->light_mode, ctx->estimator);
+  // the light grid (pt_lightgrid.h): behind everything a context without it holds, so that those bytes -- and the LDS staging
+  // decision, which reads stage_total -- are what they were
+  img.stage_total = img.total;
+  img.grid_off = 0;
+  LightGridHeader grid_head{};
+  if (light_grid_applies(ctx, all_lights)) {
+    if (lightgrid_resolve(ctx->light_grid, ctx->scene_lo, ctx->scene_hi, all_lights, img.grid_res) != 0) {
+      ctx->err = "light grid: cells * lights is beyond 2^20 entries (a 16 MB table image)";
+      return GSP_ERR_NOMEM;
+    }
+    grid_head = make_lightgrid_header(ctx->scene_lo, ctx->scene_hi, img.grid_res);
+    img.grid_off = img.total;
+    img.total += lightgrid_bytes(grid_head.nx, grid_head.ny, grid_head.nz, all_lights);
+  }
   img.bytes.assign(TableImage::kHead + std::max<size_t>(img.total, 16), 0);
   std::memcpy(img.bytes.data(), counts, sizeof(counts));
   for (int k = 0; k < 9; ++k)
@@ -121,6 +142,9 @@ static int pack_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage& i
     const float inv_sum_w = light_pick_inv_sum(sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta, env_wp);
     std::memcpy(img.bytes.data() + TableImage::kHead + tail_off, &inv_sum_w, sizeof(float));
   }
+  if (img.grid_off)
+    build_light_grid(grid_head, sc->lights, sc->num_lights, ctx->h_delta.data(), num_delta, (const gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off),
+                     img.bytes.data() + TableImage::kHead + img.grid_off);
   if (num_env) {  // p_sel: what the table of the context's mode implies for the record -- 1 / n, or the mass of its entry of the alias table
     float p_sel = 1.0f / (float)all_lights;
     if (pick) p_sel = ((const gsp_light_pick*)(img.bytes.data() + TableImage::kHead + img.pick_off))[all_lights - 1u].pmf_self;
@@ -152,6 +176,10 @@ static int upload_tables(gsp_context* ctx, const gsp_scene_desc* sc, TableImage&
   CTX_TRY(ctx, hipMemcpyAsync(base, ctx->h_tables.data() + TableImage::kHead, std::max<size_t>(img.total, 16), hipMemcpyHostToDevice, ctx->stream));
   for (int k = 0; k < 9; ++k) ctx->table_off[k] = img.off[k];
   ctx->tables_bytes = img.total;
+  ctx->tables_stage_bytes = img.stage_total;
+  ctx->grid_off = img.grid_off;
+  ctx->grid_resident = img.grid_off != 0;
+  for (int c = 0; c < 3; ++c) ctx->grid_res[c] = img.grid_res[c];
   ctx->num_tri_lights = sc->num_lights;
   ctx->num_lights = sc->num_lights + (uint32_t)ctx->h_delta.size() + (ctx->env_light ? 1u : 0u);  // (the delta and environment records need no bake: they are resident as packed)
   for (int k = 0; k < GSP_BSDF_TYPE_COUNT; ++k) ctx->num_bsdfs[k] = sc->num_bsdfs[k];
@@ -555,6 +583,9 @@ int gsp_upload_scene(gsp_context* ctx, const gsp_scene_desc* sc) {
   rc = check_scene(ctx, sc, &total_tris);
   if (rc != GSP_OK) return rc;
   auto t0 = std::chrono::steady_clock::now();
+  // the bounds the light grid covers: the geometry as uploaded.  Formed at every upload (one pass over the vertices on the host,
+  // small against the BVH build): gsp_set_light_grid may come later, when the positions are resident on the device only
+  ctx->scene_has_bounds = lightgrid_scene_bounds(sc, ctx->scene_lo, ctx->scene_hi);
   // the environment light: on for this scene when the switch is and the scene has a map; its record goes into the tables below
   ctx->env_light = false;
   ctx->h_env_cells.clear();

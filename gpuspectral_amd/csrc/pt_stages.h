@@ -17,6 +17,7 @@
 #pragma once
 #include "pt_deltalight.h"
 #include "pt_envlight.h"
+#include "pt_lightgrid.h"
 #include "pt_medium.h"
 #include "pt_shading.h"
 #include "pt_trace.h"
@@ -105,24 +106,34 @@ struct SceneViewDlt : SceneViewSct {
 struct SceneViewEnv : SceneViewDlt {
   const gsp_light_pick* env_cells = nullptr;
 };
-template <bool MED, bool SCT = false, bool DLT = false, bool ENV = false>
+// ... and the <GRD = true> ones (gsp_set_light_grid with a grid resident): + the byte offset of the light grid (pt_lightgrid.h)
+// inside a table version, counted from SceneView::tables.  The grid is read from there, NEVER from the LDS copy: tables_bytes of
+// such a view names only the bytes in front of the grid
+struct SceneViewGrd : SceneViewDlt {
+  uint32_t grid_off = 0;
+};
+template <bool MED, bool SCT = false, bool DLT = false, bool ENV = false, bool GRD = false>
 struct ShadeViewOf {
   using type = SceneView;
 };
 template <bool MED, bool SCT>
-struct ShadeViewOf<MED, SCT, true, false> {
+struct ShadeViewOf<MED, SCT, true, false, false> {
   using type = SceneViewDlt;
 };
 template <bool MED, bool SCT>
-struct ShadeViewOf<MED, SCT, true, true> {
+struct ShadeViewOf<MED, SCT, true, true, false> {
   using type = SceneViewEnv;
 };
+template <bool MED, bool SCT>
+struct ShadeViewOf<MED, SCT, true, false, true> {
+  using type = SceneViewGrd;
+};
 template <>
-struct ShadeViewOf<true, false, false, false> {
+struct ShadeViewOf<true, false, false, false, false> {
   using type = SceneViewMed;
 };
 template <>
-struct ShadeViewOf<true, true, false, false> {
+struct ShadeViewOf<true, true, false, false, false> {
   using type = SceneViewSct;
 };
 GSP_HD const gsp_medium* view_media(const SceneView&) { return nullptr; }
@@ -133,6 +144,8 @@ GSP_HD uint32_t view_tri_lights(const SceneView&) { return 0u; }
 GSP_HD uint32_t view_tri_lights(const SceneViewDlt& v) { return v.num_tri_lights; }
 GSP_HD const gsp_light_pick* view_env_cells(const SceneView&) { return nullptr; }
 GSP_HD const gsp_light_pick* view_env_cells(const SceneViewEnv& v) { return v.env_cells; }
+GSP_HD uint32_t view_grid_off(const SceneView&) { return 0u; }
+GSP_HD uint32_t view_grid_off(const SceneViewGrd& v) { return v.grid_off; }
 
 // path flags word: depth [0,7] | wasDelta << 8 | countEmitted << 9 | table version << 10 [10,15] | geometry version << 16 [16,21]
 GSP_HD uint32_t pack_flags(uint32_t depth, uint32_t wasDelta, uint32_t countEmitted) {
@@ -370,12 +383,20 @@ struct ShadeOut {
 // pick; a pick that lands on the record draws one further word, picks a cell and takes sample_env_light (pt_envlight.h) and the
 // triangle's textbook NEE term with Ldist = 1e30f.  ENV = false is the code of a context without the switch, instruction for
 // instruction.
-template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false, bool SCT = false, bool DLT = false, bool ENV = false>
+// GRD (only with LSEL, EST and DLT, never with ENV): the context selects its light through the light grid (include/gpuspectral_pt.h,
+// "Light grid"): `grid_off` = the byte offset of the grid inside this vertex's version of the tables, from S.tables (global memory
+// also where the tables in front of it were staged into LDS).  The same three draws; the pick reads the alias table of the cell of
+// q = the origin this vertex gives its continuation ray, and an emitter that is hit takes p_sel from the cell of in.o -- the q of
+// the vertex that sent the ray, the same three floats (nx.o below).  GRD = false is the code of a context without the grid,
+// instruction for instruction.
+template <bool TEX = false, bool VER = false, bool MED = false, bool LSEL = false, bool EST = false, bool SCT = false, bool DLT = false, bool ENV = false,
+          bool GRD = false>
 GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const PathState& in, const HitRec& hit,
                          ShadeOut& out, const gsp_medium* media = nullptr, const gsp_medium_scatter* scatter = nullptr,
-                         uint32_t num_tri_lights = 0u, const gsp_light_pick* env_cells = nullptr) {
+                         uint32_t num_tri_lights = 0u, const gsp_light_pick* env_cells = nullptr, uint32_t grid_off = 0u) {
   static_assert(MED || !SCT, "the scattering table is parallel to the media table");
   static_assert(!ENV || (TEX && EST && DLT), "the environment light lives in the textbook estimator, behind the delta records");
+  static_assert(!GRD || (LSEL && EST && DLT && !ENV), "the light grid lives under the power pick and the textbook estimator, without the environment record");
   uint32_t rng = in.seed;                                                 // rchit:668
   BsdfTables Tv;  // (VER only: this lane's version of the tables)
   const gsp_triangle_light* lights_v = nullptr;
@@ -393,6 +414,8 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
   }
   const BsdfTables& T = VER ? Tv : S.bsdf;
   const gsp_triangle_light* lights = VER ? lights_v : S.lights;
+  // (GRD only) the grid of this vertex's version of the tables, in global memory
+  const uint8_t* grid = GRD ? S.tables + ((VER ? (size_t)((in.flags & kVerMask) >> kVerShift) * S.ver_stride : (size_t)0) + grid_off) : nullptr;
   GSP_PROF_BEGIN(PR_PACKET);
   const long long slot_v = (long long)hit.slot + (VER && (uint32_t)hit.slot >= S.static_slots ? (long long)geo_slot_offset(S.geo, geo_stamp(in.flags)) : 0ll);
   const q4* sp = S.tri_shade + 4ll * slot_v;
@@ -501,7 +524,12 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
     const float e1 = rand_uniform(rng);
     const float e2 = rand_uniform(rng);
     float pmf = S.inv_num_lights;
-    const uint32_t k = LSEL ? light_pick_index((const gsp_light_pick*)(lights + S.num_lights), S.num_lights, r, pmf) : r % S.num_lights;
+    uint32_t k;
+    if constexpr (GRD) {  // the table of the cell of q, the origin of the continuation ray (nx.o below: the same expression)
+      k = lightgrid_pick(grid, (const gsp_light_pick*)(lights + S.num_lights), S.num_lights, position + 0.0001f * faceforward(N, -wi, N), r, pmf);
+    } else {
+      k = LSEL ? light_pick_index((const gsp_light_pick*)(lights + S.num_lights), S.num_lights, r, pmf) : r % S.num_lights;
+    }
     const bool env_light = ENV && k == S.num_lights - 1u;  // (ENV only) the pick landed on the environment record, the last one
     delta_light = !env_light && k >= num_tri_lights;
     if constexpr (ENV) {
@@ -580,6 +608,9 @@ GSP_HD void shade_vertex(const SceneView& S, const RenderConstsBase& rc, const P
       const float A = light_hit_area(v0, v1, v2);
       float p_sel = S.inv_num_lights;
       // LSEL: the selection probability of the light that was HIT, through the trailing record behind the alias table (no lights: no table)
+      if constexpr (GRD) {  // ... positional: the cell of the ray's origin, the weight from the hit's own data (pt_lightgrid.h)
+        p_sel = lightgrid_hit_select_pmf(grid, (const gsp_light_pick*)(lights + S.num_lights), S.num_lights, S.inv_num_lights, in.o, v0, v1, v2, emission, A);
+      } else
       if (LSEL && S.num_lights != 0u) p_sel = light_hit_select_pmf(emission, A, *(const float*)((const gsp_light_pick*)(lights + S.num_lights) + S.num_lights), S.inv_num_lights);
       directWeight = power_heuristic(in.directWeight, light_hit_pdf(hit.t, rayDir, N, A, p_sel));
     }

@@ -119,6 +119,7 @@ def load():
     L.gsph_pathtracer_temporal_follow_instances.argtypes = [vp, C.c_int]
     L.gsph_pathtracer_set_light_sampling.argtypes = [vp, u32]
     L.gsph_pathtracer_set_estimator.argtypes = [vp, u32]
+    L.gsph_pathtracer_set_light_grid.argtypes = [vp, u32, u32, u32, u32]
     L.gsph_pathtracer_download_light_pick.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.gsph_pathtracer_download_temporal_motion.argtypes = [vp, vp, u64]
     L.gsph_pathtracer_temporal_demodulate.argtypes = [vp, C.c_int]
@@ -506,6 +507,12 @@ class PathTracer:
     def set_estimator(self, mode):
         """PathTracer::setEstimator: "reference" (the default) or "textbook" (gpuspectral_pt.h "Estimator")."""
         self._check(self._L.gsph_pathtracer_set_estimator(self._h, abi.estimator_mode(mode)), "setEstimator")
+
+    def set_light_grid(self, enabled=True, resolution=None):
+        """PathTracer::setLightGrid (gpuspectral_pt.h "Light grid"): resolution (nx, ny, nz), None = the library chooses.  Needs
+        set_light_sampling("power") and set_estimator("textbook") first."""
+        nx, ny, nz = (0, 0, 0) if resolution is None else resolution
+        self._check(self._L.gsph_pathtracer_set_light_grid(self._h, 1 if enabled else 0, nx, ny, nz), "setLightGrid")
 
     def set_light_sampling(self, mode):
         """PathTracer::setLightSampling: "uniform" (the reference's pick) or "power" (gpuspectral_pt.h "Light selection")."""

@@ -378,6 +378,11 @@ void PathTracer::setEstimator(uint32_t mode) { check(gsp_set_estimator(ctx, mode
 
 void PathTracer::setLightSampling(uint32_t mode) { check(gsp_set_light_sampling(ctx, mode), "gsp_set_light_sampling"); }
 
+void PathTracer::setLightGrid(bool enabled, uint32_t nx, uint32_t ny, uint32_t nz) {
+  const gsp_light_grid g{enabled ? 1u : 0u, {nx, ny, nz}, {0u, 0u, 0u, 0u}};
+  check(gsp_set_light_grid(ctx, &g), "gsp_set_light_grid");
+}
+
 std::vector<gsp_light_pick> PathTracer::downloadLightPick() {
   uint32_t n = 0;
   (void)gsp_download_light_pick(ctx, nullptr, 0, &n);  // (the count; the call below reports what is wrong)
@@ -481,6 +486,11 @@ void MultiGpuPathTracer::check(int rc, const char* what) {
 void MultiGpuPathTracer::setEstimator(uint32_t mode) { check(gsp_multi_set_estimator(multi, mode), "gsp_multi_set_estimator"); }
 
 void MultiGpuPathTracer::setLightSampling(uint32_t mode) { check(gsp_multi_set_light_sampling(multi, mode), "gsp_multi_set_light_sampling"); }
+
+void MultiGpuPathTracer::setLightGrid(bool enabled, uint32_t nx, uint32_t ny, uint32_t nz) {
+  const gsp_light_grid g{enabled ? 1u : 0u, {nx, ny, nz}, {0u, 0u, 0u, 0u}};
+  check(gsp_multi_set_light_grid(multi, &g), "gsp_multi_set_light_grid");
+}
 
 void MultiGpuPathTracer::reset() {
   timestamp = 0;

@@ -101,6 +101,10 @@ class PathTracer : public RenderPassCreator {
   // Estimator (gpuspectral_pt.h "Estimator"): GSP_ESTIMATOR_REFERENCE (the reference's weights, the default) or GSP_ESTIMATOR_TEXTBOOK
   // (textbook multiple importance sampling: unbiased).  Context state: it holds across scenes; reset() after a change.
   void setEstimator(uint32_t mode);
+  // Light grid (gpuspectral_pt.h "Light grid"): spatial light selection, one alias table per cell of a grid over the scene.  Needs
+  // setLightSampling(GSP_LIGHTS_POWER) and setEstimator(GSP_ESTIMATOR_TEXTBOOK) first (the library's error otherwise).  nx = ny = nz
+  // = 0: the library chooses the resolution.  Context state: it holds across scenes; reset() after a change.
+  void setLightGrid(bool enabled, uint32_t nx = 0, uint32_t ny = 0, uint32_t nz = 0);
 
   // RGBA32F, row-major, width*height*4 floats (running mean, alpha 1)
   std::vector<float> download();
@@ -214,6 +218,7 @@ class MultiGpuPathTracer : public RenderPassCreator {
   void invalidateScene() { tracker.forget(); }
   void setLightSampling(uint32_t mode);  // as PathTracer::setLightSampling, on every share
   void setEstimator(uint32_t mode);      // as PathTracer::setEstimator, on every share
+  void setLightGrid(bool enabled, uint32_t nx = 0, uint32_t ny = 0, uint32_t nz = 0);  // as PathTracer::setLightGrid, on every share
   std::vector<float> download();  // RGBA32F, row-major, width*height*4 floats
   std::vector<uint32_t> downloadDisplay();  // as PathTracer::downloadDisplay, on the gathered frame
   void renderFeatures(const Scene& scene, uint32_t spp);  // as PathTracer::renderFeatures, on every share

@@ -432,6 +432,9 @@ int gsph_pathtracer_set_light_sampling(void* pt, uint32_t mode) {
 int gsph_pathtracer_set_estimator(void* pt, uint32_t mode) {  // PathTracer::setEstimator
   return guard([&] { ((PathTracer*)pt)->setEstimator(mode); });
 }
+int gsph_pathtracer_set_light_grid(void* pt, uint32_t enabled, uint32_t nx, uint32_t ny, uint32_t nz) {  // PathTracer::setLightGrid
+  return guard([&] { ((PathTracer*)pt)->setLightGrid(enabled != 0u, nx, ny, nz); });
+}
 int gsph_pathtracer_download_light_pick(void* pt, gsp_light_pick* out, uint32_t capacity, uint32_t* count) {
   return guard([&] {
     auto t = ((PathTracer*)pt)->downloadLightPick();

@@ -79,6 +79,12 @@ class PathTracerHip : public RenderPassCreator {
   // estimator, opt-in (gpuspectral_pt.h "Estimator"): GSP_ESTIMATOR_TEXTBOOK weights NEE and emitter hits by textbook multiple
   // importance sampling (unbiased).  Context state; restart() after a change.  The default is the reference's estimator
   void setEstimator(uint32_t mode) { check(gsp_set_estimator(ctx, mode)); }
+  // light grid, opt-in (gpuspectral_pt.h "Light grid"): one alias table per cell of a grid over the scene; needs GSP_LIGHTS_POWER and
+  // GSP_ESTIMATOR_TEXTBOOK first.  nx = ny = nz = 0: the library chooses the resolution.  Context state; restart() after a change
+  void setLightGrid(bool enabled, uint32_t nx = 0, uint32_t ny = 0, uint32_t nz = 0) {
+    const gsp_light_grid g{enabled ? 1u : 0u, {nx, ny, nz}, {0u, 0u, 0u, 0u}};
+    check(gsp_set_light_grid(ctx, &g));
+  }
   float autofocus(float fx, float fy) {
     float d = 0.0f;
     check(gsp_focus_distance(ctx, width, height, fx, fy, &d));

@@ -19,6 +19,9 @@
 //   --env-sampling [--env-extent R]: sample the scene's environment map as a light (gsp_set_envmap_sampling; with --dormant-features, which
 //     loads the map).  R = the radius of the scene as the power pick is to see it, default: the radius of the scene's bounds.  Implies
 //     --estimator textbook; an error beside an explicit --estimator reference.
+//   --light-grid [NX,NY,NZ]: spatial light selection (gsp_set_light_grid), one alias table per cell of a grid over the scene; without a
+//     resolution the library chooses one.  It implies nothing else: without --light-sampling power --estimator textbook the run ends
+//     with the library's error text and exit code 2.
 //   --point-light X,Y,Z,R,G,B (repeatable): one more point light of that position and radiant intensity, for a scene file without an emitter element.
 //   --focus-pixel runs the autofocus (gsp_focus_distance) on that fragCoord before rendering; --scene-lens: LoadOptions::readLens
 //   (a thinlens sensor's aperture_radius / focus_distance; the flags above override the scene's values one by one)
@@ -77,6 +80,8 @@ int main(int argc, char** argv) {
   uint32_t lightSampling = GSP_LIGHTS_UNIFORM;
   uint32_t estimator = GSP_ESTIMATOR_REFERENCE;
   bool estimatorGiven = false, envSampling = false;
+  bool lightGrid = false;
+  uint32_t lightGridRes[3] = {0, 0, 0};  // (0, 0, 0 = the library chooses)
   float envExtent = -1.0f;  // (-1 = not given: the radius of the scene's bounds)
   float adaptive = 0.0f;
   uint32_t adaptiveMin = 0, adaptiveStep = 0;
@@ -148,6 +153,15 @@ int main(int argc, char** argv) {
       }
       estimatorGiven = true;
       used = 2;
+    }
+    else if (flag == "--light-grid") {  // (the resolution is optional: NX,NY,NZ right behind the flag)
+      lightGrid = true;
+      unsigned a = 0, b = 0, c = 0;
+      char tail = 0;
+      if (argc > 2 && std::sscanf(argv[2], "%u,%u,%u%c", &a, &b, &c, &tail) == 3) {
+        lightGridRes[0] = a, lightGridRes[1] = b, lightGridRes[2] = c;
+        used = 2;
+      }
     }
     else if (flag == "--env-sampling") envSampling = true;
     else if (flag == "--env-extent" && argc > 2) {
@@ -470,7 +484,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (argc < 3) {
-    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--scene-scattering] [--scene-emitters] [--point-light X,Y,Z,R,G,B]... [--env-sampling [--env-extent R]] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
+    std::fprintf(stderr, "usage: gsp_render [--dormant-features] [--builtin-shapes] [--no-nee] [--light-sampling uniform|power] [--estimator reference|textbook] [--memory-share F] [--pool-paths N] [--adaptive T [--adaptive-min N] [--adaptive-step N]] [--filter none|box|tent[:r]|gaussian[:s]] [--scene-filter] [--aperture R] [--focus-distance D] [--focus-pixel X,Y] [--blades N[:rot_deg]] [--scene-lens] [--scene-media] [--scene-scattering] [--scene-emitters] [--point-light X,Y,Z,R,G,B]... [--env-sampling [--env-extent R]] [--light-grid [NX,NY,NZ]] [--features PREFIX [--feature-spp N]] [--denoise out.pfm [--denoise-iterations N] [--denoise-sigma c,n,z,a]] [--temporal out.pfm --temporal-frames N [--temporal-orbit DEG]] [--temporal-follow [--temporal-move INST,DX,DY,DZ] [--motion out.pfm]] [--svgf out.pfm [--svgf-sigma S] [--svgf-min-history N]] [--temporal-demodulate] [--svgf-feedback LEVELS] [--temporal-antilag [--antilag-fast N] [--antilag-radius R] [--antilag-sigma S]] [--taa out.png [--taa-alpha A] [--taa-sigma S]] [--ldr out.png [--tonemap clamp|aces|reinhard[:key[:burn]]] [--exposure E] [--gamma G|srgb] [--scene-film]] scene.xml out.pfm [width height spp [device | d0,d1,...]]\n");
     return 2;
   }
   const uint32_t width = argc > 3 ? (uint32_t)std::atoi(argv[3]) : 500;  // S/main.cpp:17: 500x500 window
@@ -556,6 +570,14 @@ int main(int argc, char** argv) {
       pt.params.disable_nee = nee ? 0u : 1u;
       pt.setLightSampling(lightSampling);
       pt.setEstimator(estimator);
+      if (lightGrid) {
+        try {
+          pt.setLightGrid(true, lightGridRes[0], lightGridRes[1], lightGridRes[2]);
+        } catch (const std::exception& e) {  // (a missing prerequisite, a resolution out of range: the library's own words)
+          std::fprintf(stderr, "gsp_render: --light-grid: %s\n", e.what());
+          return 2;
+        }
+      }
       pt.params.adaptive_threshold = adaptive;
       pt.params.adaptive_min_spp = adaptiveMin;
       pt.params.adaptive_step = adaptiveStep;
@@ -639,6 +661,14 @@ int main(int argc, char** argv) {
       pt.params.disable_nee = nee ? 0u : 1u;
       pt.setLightSampling(lightSampling);
       pt.setEstimator(estimator);
+      if (lightGrid) {
+        try {
+          pt.setLightGrid(true, lightGridRes[0], lightGridRes[1], lightGridRes[2]);
+        } catch (const std::exception& e) {  // (a missing prerequisite, a resolution out of range: the library's own words)
+          std::fprintf(stderr, "gsp_render: --light-grid: %s\n", e.what());
+          return 2;
+        }
+      }
       pt.params.adaptive_threshold = adaptive;  // (gsp_multi_render refuses adaptive sampling: reported as an error)
       pt.params.pixel_filter = filter;
       pt.params.pixel_filter_param = filterParam;

@@ -35,6 +35,8 @@ EXPORTS = (
     "gsp_set_estimator",
     "gsp_set_delta_lights",
     "gsp_set_envmap_sampling",
+    "gsp_set_light_grid",
+    "gsp_get_light_grid",
     "gsp_focus_distance",
     "gsp_frame_begin",
     "gsp_render",
@@ -103,6 +105,7 @@ EXPORTS = (
     "gsp_multi_set_estimator",
     "gsp_multi_set_delta_lights",
     "gsp_multi_set_envmap_sampling",
+    "gsp_multi_set_light_grid",
     "gsp_multi_update_instances",
     "gsp_multi_update_tables",
     "gsp_multi_frame_begin",
@@ -169,6 +172,9 @@ def load():
     L.gsp_multi_set_delta_lights.argtypes = [vp, C.POINTER(abi.DeltaLight), u32]
     L.gsp_set_envmap_sampling.argtypes = [vp, C.POINTER(abi.EnvmapSampling)]
     L.gsp_multi_set_envmap_sampling.argtypes = [vp, C.POINTER(abi.EnvmapSampling)]
+    L.gsp_set_light_grid.argtypes = [vp, C.POINTER(abi.LightGrid)]
+    L.gsp_get_light_grid.argtypes = [vp, C.POINTER(abi.LightGrid), C.POINTER(C.c_float)]
+    L.gsp_multi_set_light_grid.argtypes = [vp, C.POINTER(abi.LightGrid)]
     L.gsp_update_instances.argtypes = [vp, vp, u32]
     L.gsp_update_tables.argtypes = [vp, C.POINTER(abi.SceneDesc)]
     L.gsp_ctx_destroy.argtypes = [vp]
@@ -275,8 +281,8 @@ def build_info():
 
 
 # the files csrc/Makefile hashes into the digest, in its order
-DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_render_scatter.hip", "pt_render_delta.hip", "pt_render_envlight.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
-                  "pt_medium.h", "pt_deltalight.h", "pt_envlight.h", "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
+DIGEST_SOURCES = ("pt_render.hip", "pt_render_textbook.hip", "pt_render_scatter.hip", "pt_render_delta.hip", "pt_render_envlight.hip", "pt_render_lightgrid.hip", "pt_bvh.hip", "pt_multi.hip", "pt_render_kernels.inc", "pt_render_scene.inc", "pt_render_pipeline.inc", "pt_render_post.inc", "pt_wavetrace.h", "pt_versions.h", "pt_hostmath.h", "pt_lightpick.h", "pt_math.h", "pt_shading.h",
+                  "pt_medium.h", "pt_deltalight.h", "pt_envlight.h", "pt_lightgrid.h", "pt_trace.h", "pt_stages.h", "pt_internal.h", "pt_display.h", "pt_features.h", "pt_denoise.h", "pt_temporal.h", "pt_svgf.h", "pt_motion.h", "pt_illum.h", "pt_antilag.h", "pt_taa.h", "../../include/gpuspectral_pt.h")
 
 
 def source_digest():
@@ -386,6 +392,19 @@ class Context:
         estimator only).  extent: the radius of the scene as the power pick is to see it.  enabled=False drops the sampling."""
         s = abi.EnvmapSampling(1, extent, (C.c_uint32 * 2)(0, 0)) if enabled else None
         self._check(self._L.gsp_set_envmap_sampling(self._h, C.byref(s) if s is not None else None), "gsp_set_envmap_sampling")
+
+    def set_light_grid(self, enabled=True, resolution=None):
+        """gsp_set_light_grid (gpuspectral_pt.h "Light grid"): spatial light selection, one alias table per cell of a grid over the
+        scene (needs set_light_sampling("power") and set_estimator("textbook") first).  resolution: (nx, ny, nz), None = auto.
+        enabled=False drops the grid."""
+        s = abi.light_grid(resolution) if enabled else None
+        self._check(self._L.gsp_set_light_grid(self._h, C.byref(s) if s is not None else None), "gsp_set_light_grid")
+
+    def light_grid(self):
+        """gsp_get_light_grid: (enabled, (nx, ny, nz), (lo, hi)) of the grid the resident tables were built with."""
+        s, b = abi.LightGrid(), (C.c_float * 6)()
+        self._check(self._L.gsp_get_light_grid(self._h, C.byref(s), b), "gsp_get_light_grid")
+        return bool(s.enabled), tuple(s.resolution), (tuple(b[:3]), tuple(b[3:]))
 
     def set_estimator(self, mode):
         """gsp_set_estimator (gpuspectral_pt.h "Estimator"): "reference" / "textbook" or abi.ESTIMATOR_REFERENCE / ESTIMATOR_TEXTBOOK."""
@@ -864,6 +883,11 @@ class MultiContext:
         """gsp_multi_set_envmap_sampling: Context.set_envmap_sampling on every share."""
         s = abi.EnvmapSampling(1, extent, (C.c_uint32 * 2)(0, 0)) if enabled else None
         self._check(self._L.gsp_multi_set_envmap_sampling(self._h, C.byref(s) if s is not None else None), "gsp_multi_set_envmap_sampling")
+
+    def set_light_grid(self, enabled=True, resolution=None):
+        """gsp_multi_set_light_grid: Context.set_light_grid on every share."""
+        s = abi.light_grid(resolution) if enabled else None
+        self._check(self._L.gsp_multi_set_light_grid(self._h, C.byref(s) if s is not None else None), "gsp_multi_set_light_grid")
 
     def set_media_scattering(self, scatter=None):
         """gsp_multi_set_media_scattering: Context.set_media_scattering on every share."""

@@ -88,7 +88,8 @@ extern "C" {
                                 selection"); gsp_set_estimator, gsp_multi_set_estimator (see "Estimator");
                                 gsp_set_media_scattering, gsp_multi_set_media_scattering (see "Scattering media");
                                 gsp_set_delta_lights, gsp_multi_set_delta_lights (see "Delta lights");
-                                gsp_set_envmap_sampling, gsp_multi_set_envmap_sampling (see "Environment light") */
+                                gsp_set_envmap_sampling, gsp_multi_set_envmap_sampling (see "Environment light");
+                                gsp_set_light_grid, gsp_get_light_grid, gsp_multi_set_light_grid (see "Light grid") */
 
 /* ---- status codes (0 = ok); the message is at gsp_last_error(ctx) ---- */
 #define GSP_OK 0
@@ -966,6 +967,90 @@ typedef struct gsp_envmap_sampling {
 } gsp_envmap_sampling;  /* 16 B */
 int gsp_set_envmap_sampling(gsp_context* ctx, const gsp_envmap_sampling* sampling); /* NULL = off */
 
+/*
+ * Light grid: opt-in SPATIAL light selection -- one alias table per cell of a regular grid over the scene.
+ *
+ * GSP_LIGHTS_POWER stores one selection probability per light for the whole scene: a wall point next to a small lamp sends that
+ * lamp one shadow ray in a thousand when a large panel elsewhere holds the power.  gsp_set_light_grid(ctx, &{enabled = 1,
+ * resolution}) makes the table a function of position: a grid over the bounding box of the scene's geometry, one alias table per
+ * cell, each light weighted by power / distance^2 to that cell.  The pick makes the same three draws and reads ONE 16-byte entry,
+ * of the table of the shading point's cell; traversal, the queues and the path state are what they were.
+ *
+ * A switch of its own, CONTEXT STATE beside the light mode and the estimator: it survives gsp_upload_scene and gsp_update_tables
+ * and may be set with a scene resident (the samples in flight finish first, then the tables are packed again from the context's
+ * host copy and uploaded, as gsp_set_light_sampling does).  NULL or enabled == 0 drops the grid.  A context that never enables it,
+ * or has disabled it again, runs the kernels, holds the table bytes and returns the frame of before, bit for bit.
+ *
+ * Prerequisites and validation (the state stays unchanged on every failure).  GSP_ERR_INVALID when enabled != 0 and: a word of
+ * reserved is not 0; a component of resolution is above 64; resolution mixes zero and non-zero components (0, 0, 0 = auto); the
+ * context does not run GSP_LIGHTS_POWER together with GSP_ESTIMATOR_TEXTBOOK -- the reference estimator's weights read the pdf of
+ * ANOTHER light, which a position-dependent pick would only compound, so gsp_set_light_sampling(.., POWER) and
+ * gsp_set_estimator(.., TEXTBOOK) come first, and leaving either mode with the grid on is GSP_ERR_INVALID as well; the context
+ * samples its environment map as a light (gsp_set_envmap_sampling) -- and gsp_set_envmap_sampling(enabled) with the grid on is
+ * GSP_ERR_INVALID in turn.  The environment record stores one p_sel per table; a p_sel per cell is a follow-up.  Delta lights are
+ * in scope.
+ *
+ * Bounds.  The box [lo, hi] of every vertex of every instance as gsp_upload_scene received it (object -> world as the BVH forms
+ * it, float32).  gsp_update_instances does not move it.  A scene without lights, or without a vertex, has no grid.
+ *
+ * Resolution.  Explicit: nx, ny, nz as given.  Auto: the largest m <= 32 with n_axis = clamp(round(extent_axis / (longest / m)),
+ * 1, m) (cells as near cubic as the rounding allows) whose cells * num_lights is at most 2^20 entries (a 16 MB image).  An axis
+ * without extent has 1 cell either way.  An explicit resolution beyond that cap -- or a light table beyond it at 1 x 1 x 1 -- is
+ * GSP_ERR_NOMEM from the call that would build the grid (the setter under a resident scene, else gsp_upload_scene).
+ * gsp_get_light_grid reports what the RESIDENT tables were built with: enabled (0 when there is no grid resident), the resolved
+ * resolution, and bounds = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z}; either pointer may be NULL.
+ *
+ * Cell of a point p, float32 per axis:  cell = (hi - lo) / (float)n;  inv_cell = (float)n / (hi - lo)  (both 0 on an axis without
+ * extent);  f = floor((p - lo) * inv_cell);  the axis index is f when 0 <= f < n.  A point that fails the test on any axis -- outside
+ * the box, on its upper face when the product reaches n, or not finite -- takes the FALLBACK: the power alias table of "Light
+ * selection" with its trailing inv_sum_w, which stays in front of the grid.  Moved instances and escaped positions are therefore
+ * always defined and unbiased.  Cell number = (iz * ny + iy) * nx + ix.
+ *
+ * The weight of light i for the cell of centre c = lo + (index + 0.5f) * cell -- ONE function (csrc/pt_lightgrid.h), float32, called by
+ * the builder and by the emitter-hit pdf below.  Rcell = 0.5f * sqrt((cell.x^2 + cell.y^2) + cell.z^2);  Y as in "Light selection":
+ *     triangle:     cen = ((v0 + v1) + v2) * (1 / 3.f);  Rtri = sqrt(max over vertices of |v - cen|^2);  n = cross(v1 - v0, v2 - v0)
+ *                   d = c - cen;  R = Rcell + Rtri;   w = (Y(radiance) * A) / max(dot(d, d), R * R)
+ *                   w = 0 when EVERY corner of the cell lies behind the emitting side by more than a margin:
+ *                       smax = dot(n, d) + ((|n.x| * (0.5f * cell.x) + |n.y| * (0.5f * cell.y)) + |n.z| * (0.5f * cell.z))
+ *                       S = ((|c.x| + |c.y|) + |c.z|) + ((|cen.x| + |cen.y|) + |cen.z|)) + (Rcell + Rtri);   smax < -((1e-4f * S) * |n|)
+ *                   (the margin is fifty times the float32 error of smax, so a cell never loses a light that a point in it sees
+ *                   from the front; a cell the light's plane cuts has smax >= 0)
+ *     point, spot:  d = position - c;   w = Y(intensity) / max(dot(d, d), Rcell * Rcell)
+ *     directional:  w = Y(intensity)
+ * All three are luminous-irradiance scales, so the kinds stay comparable inside a cell.  A weight that is not finite or not
+ * positive counts as 0.  The weights of a cell go, widened to double, through the alias construction of "Light selection" as
+ * they stand (sums in double, ascending index) and give the cell's table of num_lights entries and one 16-byte tail
+ * {inv_sum_w, 0, 0, 0}, inv_sum_w = float32(1 / sum).  A cell whose weights are ALL 0 holds a copy of the fallback table and tail
+ * 0: its picks and its hit pdf are the fallback's.  It never becomes a uniform table, which the hit pdf could not restate.
+ *
+ * Layout.  Behind the power pick table and its trailing record in EVERY table version (gsp_update_tables rebuilds it with the
+ * tables; nothing new to call):  a 64-byte header {lo, nx | inv_cell, ny | cell, nz | hi, Rcell}, then the cells in number order,
+ * (num_lights + 1) * 16 bytes each.  The LDS staging decision and the staged copy see only the bytes IN FRONT of the grid: a small
+ * scene keeps its BSDF tables, lights and fallback table in LDS, the grid is read from L2 / HBM.
+ *
+ * The pick.  r, e1, e2 as always; the table is that of the cell of q (below), the slot and coin the r * num_lights split of "Light
+ * selection"; no further draw, so the random streams of all modes coincide behind the light sample.  The point on the light and
+ * the solid-angle pdf are formed at the shading point p as before.
+ *
+ * The emitter-hit pdf (rule 4 of "Estimator", made positional):  p_sel = weight(cell of the ray's origin o, the hit triangle's
+ * vertices from the intersection packet, the hit's emission, A) * inv_sum_w[cell];  a cell with tail 0 or an origin without a
+ * cell:  the rule of GSP_LIGHTS_POWER on the fallback's tail.
+ *
+ * WHICH POINT NAMES THE CELL.  The two ends of MIS must name the same cell, and the ray's origin is not the shading point: it is
+ * q = p + 0.0001f * faceforward(N, -wi, N), the origin the vertex gives its continuation ray (rayhit.rchit:793).  So the PICK
+ * uses the cell of q -- formed before the light sample from the BSDF sample's direction, the very expression the continuation
+ * stores -- and the hit end reads the origin its path record carries, the same three floats.  (A vertex whose BSDF sample is
+ * invalid forms q from that sample all the same; a NaN takes the fallback, and such a path ends there.)  Camera rays and rays
+ * behind a delta bounce take the full weight as before and read no cell.
+ */
+typedef struct gsp_light_grid {
+  uint32_t enabled;       /* 0 = off */
+  uint32_t resolution[3]; /* cells along x, y, z: each 1..64, or 0, 0, 0 = auto */
+  uint32_t reserved[4];   /* 0 */
+} gsp_light_grid;         /* 32 B */
+int gsp_set_light_grid(gsp_context* ctx, const gsp_light_grid* grid); /* NULL or enabled == 0: off */
+int gsp_get_light_grid(gsp_context* ctx, gsp_light_grid* resolved, float bounds[6]); /* what the resident tables were built with */
+
 /* Block until all queued work of the context has finished. */
 int gsp_sync(gsp_context* ctx);
 
@@ -1644,6 +1729,7 @@ int gsp_multi_set_media(gsp_multi* m, const gsp_medium* media, uint32_t num_medi
 int gsp_multi_set_media_scattering(gsp_multi* m, const gsp_medium_scatter* scatter, uint32_t num_media); /* gsp_set_media_scattering on every share */
 int gsp_multi_set_delta_lights(gsp_multi* m, const gsp_delta_light* lights, uint32_t count); /* gsp_set_delta_lights on every share */
 int gsp_multi_set_envmap_sampling(gsp_multi* m, const gsp_envmap_sampling* sampling); /* gsp_set_envmap_sampling on every share */
+int gsp_multi_set_light_grid(gsp_multi* m, const gsp_light_grid* grid); /* gsp_set_light_grid on every share */
 int gsp_multi_set_light_sampling(gsp_multi* m, uint32_t mode); /* gsp_set_light_sampling on every share */
 int gsp_multi_set_estimator(gsp_multi* m, uint32_t mode);      /* gsp_set_estimator on every share */
 int gsp_multi_update_instances(gsp_multi* m, const gsp_instance* instances, uint32_t num_instances);

@@ -33,6 +33,10 @@ if [ -f pt_render_envlight.hip ]; then  # (... and those that sample the environ
   hipcc $F -c pt_render_envlight.hip -o build/var_$1/pt_render_envlight.o &
   TB="$TB build/var_$1/pt_render_envlight.o"
 fi
+if [ -f pt_render_lightgrid.hip ]; then  # (... and those with a light grid the <GRD> kernels)
+  hipcc $F -c pt_render_lightgrid.hip -o build/var_$1/pt_render_lightgrid.o &
+  TB="$TB build/var_$1/pt_render_lightgrid.o"
+fi
 wait
 printf 'extern "C" const char gsp_build_info_string[] = "arch=gfx950 digest=variant-%s flags=%s";\n' "$1" "$F" > build/var_$1/pt_buildinfo.cpp
 g++ -O2 -fPIC -c build/var_$1/pt_buildinfo.cpp -o build/var_$1/pt_buildinfo.o
